@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- particle-steps/s of the synchronous stepper on BASELINE config 2.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps once, writes the final state if --dump-outputs is given and prints the
+line.  --full adds what takes runs of its own: the median of --repeats (default 5) timed repeats, the copy-kernel
+ceiling, per-kernel timings and the roofline object, the final-state check and the CPU baselines.
+--dump-outputs DIR writes the state the timed steps leave (what aps_get_state hands a caller: positions, spins, bound
+and alive flags; one row per ensemble) as float64 DIR/<name>.npy, a fixed seeded sample if it exceeds 64 MB in all.
 
 A step = one pass of the hot path (mean field + occupancy at every particle -> rates -> Philox draw -> commit)
 over all N particles, in the formulation --method selects: "tiles" (= "auto", the default: the reference's histogram ->
@@ -132,6 +138,29 @@ def cpu_reference_loop(w, budget_s=12.0):
             "sample": f"{n} Gillespie events (compute_local_m_field + step_gillespie restated in NumPy), {el:.1f} s"}
 
 
+DUMP_BYTES_MAX = 64_000_000
+
+
+def final_state(h, n_ens):
+    """What a caller of the stepper receives after the timed steps: aps_get_state of every ensemble, as float64."""
+    states = [h.get_state(ensemble=e) for e in range(n_ens)]
+    out = {name: np.stack([st[i] for st in states]).astype(np.float64) for i, name in enumerate(("positions", "spins", "bound", "alive"))}
+    return {k: v[0] for k, v in out.items()} if n_ens == 1 else out
+
+
+def dump_outputs(arrays, outdir):
+    """Write each array as outdir/<name>.npy; above DUMP_BYTES_MAX in all, the same fixed seeded sample of flat indices
+    is taken from every array (written as sample_index.npy)."""
+    os.makedirs(outdir, exist_ok=True)
+    size = next(iter(arrays.values())).size
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES_MAX:
+        keep = DUMP_BYTES_MAX // (8 * (len(arrays) + 1))
+        idx = np.sort(np.random.default_rng(12345).choice(size, size=keep, replace=False))
+        arrays = dict({k: v.reshape(-1)[idx] for k, v in arrays.items()}, sample_index=idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 class stdout_to_stderr:
     """RCCL prints a banner to fd 1 while a communicator is created; the contract is ONE JSON line on stdout."""
 
@@ -166,7 +195,7 @@ def bench_pde(args):
            "config": {"workload": "IMEX_PDE_solver_run_sweep.py shape: L=1000, dt=5e-4, periodic, bidirectional, ring-wide "
                                   "Gaussian kernel (1001 taps), 1000 tracers, 256 beta values in one launch",
                       "per_system_steps_per_s": (nsteps + 1) / (ms * 1e-3)}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle.pde_numpy import PdeOracle
         n_cpu = 300
         orc = PdeOracle(T=n_cpu * kw["dt"], beta=2.0, **kw)
@@ -202,7 +231,7 @@ def bench_gillespie(args):
            "config": {"workload": "L=1000, N=500, K=1, sigma=0.005, rate_active=5, rate_diffusion=0.02, T=20, obs_dt=0.1; 32 beta x 32 runs "
                                   "as 1024 persistent workgroups", "events_per_system": float(r["n_events"].mean()),
                       "per_system_events_per_s": float(r["n_events"].max()) / (ms * 1e-3), "kernel_ms": ms}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle.gillespie_numpy import GillespieOracle
         orc = GillespieOracle(L=L, xlim=1.0, rate_diffusion=0.02, rate_active=5.0, beta=0.7, N=N, scale_rates=False,
                               local_kernel_sigma=0.005, site_capacity=1, rng=np.random.default_rng(0))
@@ -285,10 +314,18 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--workload", default="config2", choices=["config2", "pde", "gillespie"] + sorted(EXTRA))
     ap.add_argument("--method", default="auto", choices=["auto", "lattice", "pairs", "tiles"])
-    ap.add_argument("--repeats", type=int, default=5, help="timed repeats of the K steps; the line reports their median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repeats of the K steps; the line reports their median (default 1, with --full 5)")
     ap.add_argument("--fp32", action="store_true", help="32-bit integer field (aps_params.fp32); default only for --workload config5")
     ap.add_argument("--f64", action="store_true", help="force the exact binary64 field")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the state after the timed steps as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the repeats, roofline and per-kernel timings, the final-state check and the CPU baselines")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.dump_outputs and (args.workload in ("pde", "gillespie") or args.gpus > 1 or os.environ.get("APS_BENCH_FORCE_SHARDED") == "1"):
+        raise SystemExit("bench.py: --dump-outputs covers the particle stepper on one GPU (--gpus 1, workloads config2 / config4 / config5 / hbm)")
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
     if "WORLD_SIZE" not in os.environ:
@@ -528,14 +565,14 @@ def main():
             times.append(float(el.item()))
         elapsed = float(np.median(times))
         extra = {"repeats": len(times), "repeats_ms_per_step": [t / args.steps * 1e3 for t in times], "graph_replay": False}
-        # consistency across ranks: site shards -> every particle is owned by exactly one rank; index shards -> same state everywhere
+        # consistency across ranks (--full): site shards -> every particle is owned by exactly one rank; index shards -> same state everywhere
         p, s, b, a = h.get_state()
         dist.barrier()                                       # (peer stores: no rank frees its landing buffers before all are done)
-        if site_shards:
+        if args.full and site_shards:
             owned = torch.tensor([int((a != 2).sum()), int(p[a == 1].astype(np.int64).sum())], dtype=torch.int64)
             dist.all_reduce(owned, op=dist.ReduceOp.SUM)
             assert int(owned[0]) == w["N"], f"ranks own {int(owned[0])} particles of {w['N']}"
-        else:
+        elif args.full:
             chk = torch.tensor([int(p.astype(np.int64).sum()), int((s > 0).sum())], dtype=torch.int64)
             lo, hi = chk.clone(), chk.clone()
             dist.all_reduce(lo, op=dist.ReduceOp.MIN)
@@ -555,7 +592,7 @@ def main():
             h.set_state(pos, spin, ensemble=e)
         h.step(args.warmup)                       # aps_step synchronises its stream before returning
         times = []
-        for _ in range(max(1, args.repeats)):     # median of >= 5 repeats of the K timed steps
+        for _ in range(max(1, args.repeats)):     # --full: median of >= 5 repeats of the K timed steps
             t0 = time.perf_counter()
             h.step(args.steps)
             times.append(time.perf_counter() - t0)
@@ -566,109 +603,112 @@ def main():
                  "graph_replay": single_steps == 0 and loop_steps == 0, "steps_from_graphs": graph_steps, "steps_launched_singly": single_steps,
                  # resident loop (csrc/tile_loop.hpp): steps of a timed call taken inside ONE launch, every tile resident
                  "steps_in_resident_loop": loop_steps, "resident_loop": {1: "used", 0: "not eligible: " + loop_why, -1: "gave up: " + loop_why}.get(loop_state, "not tried")}
-        hbm_copy = h.copy_bandwidth(1 << 30, 5)   # this box's streaming ceiling (read + written bytes of a 1 GiB copy)
-        # per-kernel durations, timed live with HIP events on the stream the kernels are launched on
-        reps = max(10, min(args.steps, 50))
-        if h.method == "pairs":
-            ms, launches, pairs = h.step_timed(reps)
-            avg_s = ms / launches * 1e-3
-            achieved = ALGO_BYTES_PER_PARTICLE_STEP * w["N"] * n_ens / avg_s / 1e9
-            pairs_per_s = pairs / (ms * 1e-3)
-            lds_peak_pairs = 256 * 2.4e9 / LDS_CYCLES_PER_64_PAIRS * 64      # one LDS pipe per CU
-            roof = {"bound": "hbm", "bound_measured": "lds (table gather; PMC in profiles/r01_pmc_traffic.json)",
-                    "kernel": "pair_accumulate", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic_bytes(args.workload, "pair_accumulate"),
-                    "avg_launch_us": avg_s * 1e6, "algorithmic_bytes_per_launch": ALGO_BYTES_PER_PARTICLE_STEP * w["N"] * n_ens,
-                    "note": "the contract's HBM figure; this kernel is bound by the LDS table gather (the 0.4 MB state "
-                            "lives in L2), see on_chip",
-                    "on_chip": {"pairs_per_launch": pairs / launches, "pairs_per_s": pairs_per_s,
-                                "lds_bound_pairs_per_s": lds_peak_pairs, "lds_frac": pairs_per_s / lds_peak_pairs,
-                                "lds_cycles_per_64_pairs": LDS_CYCLES_PER_64_PAIRS,
-                                "valu_issue_slots_per_pair": 4, "valu_frac": pairs_per_s * 4 / VALU_LANE_OPS_PER_S}}
-        else:
-            ms_fu, n_fu, deposits = h.step_timed(reps)            # deposits = field changes of the sampled steps (device counters)
-            prof = h.step_profile(reps)
-            # seconds per launch: start/stop events attached to each kernel's own dispatch (hipExtLaunchKernel), i.e.
-            # the begin -> end interval rocprofv3 --kernel-trace reports.  APS_PROF_BRACKET=1 switches to events recorded
-            # around the launch instead, which read ~2 us more per kernel (the event packets' own cost).
-            kern = {k: v[0] / v[1] * 1e-3 for k, v in prof.items() if v[1]}
-            ntt = h.ntt_info()
-            if ntt["on"] and "tile_step" in kern:      # convolution handles step by tile_dense (csrc/tile_dense.hpp): no sweep, no lists
-                kern["tile_dense"] = kern.pop("tile_step")
-            if ntt["on"] and ntt["prof_launches"]:     # the field update as an exact convolution (csrc/ntt_conv.hpp): three (five) launches per step
-                kern["ntt_conv"] = ntt["prof_ms"] / ntt["prof_launches"] * 1e-3
-            bracketed = os.environ.get("APS_PROF_BRACKET") is not None
-            dep_per_step = deposits / max(n_fu, 1)
-            N_all, L_all = w["N"] * n_ens, w["L"] * n_ens
-            changed = None
-            if "apply" in kern:                          # accepted events of one step, counted: the states before and after compared
-                before = [h.get_state(ensemble=e) for e in range(n_ens)]
-                h.step(1)
-                changed = float(sum(int(((x[0] != y[0]) | (x[1] != y[1]) | (x[2] != y[2]) | (x[3] != y[3])).sum())
-                                    for x, y in zip(before, [h.get_state(ensemble=e) for e in range(n_ens)])))
-                del before
-            algo = {k: step_algo_bytes(k, N_all, L_all, w["K"], dep_per_step, bool(w.get("fp32")), changed) for k in kern}
-            if "tile_dense" in algo:                   # cell words read and written, {W, S} (int2 / double2) at the particles' sites; the coefficient atomics left out
-                algo["tile_dense"] = 8.0 * w["K"] * L_all + (8.0 if w.get("fp32") else 16.0) * N_all
-            launches_per_step = {k: 1 for k in kern}
-            if "ntt_conv" in kern:
-                # per launch and prime: both signals of 2^m residues read and written (4 B each) -- the first sweep reads the deposit
-                # signals instead (once for all primes), the last one reads residues and reads + writes {W, S} of the sites (int2 / double2);
-                # per step on top: the table's spectrum, read by the middle launch
-                M_ntt = float(1 << ntt["log2_m"]) * n_ens
-                n_pr = 1 if w.get("fp32") else 2                       # binary64 field: two primes
-                lps = ntt["prof_launches"] / reps
-                launches_per_step["ntt_conv"] = lps
-                algo["ntt_conv"] = (lps * 16.0 * M_ntt * n_pr - (n_pr - 1) * 8.0 * M_ntt - 8.0 * M_ntt * n_pr      # (the last sweep writes no residues)
-                                    + 4.0 * M_ntt * n_pr + (16.0 if w.get("fp32") else 32.0) * L_all) / lps
-            step_bytes = sum(algo[k] * launches_per_step[k] for k in kern)
-            if loop_steps > 0:
-                # the timed steps ran inside tile_loop: ONE launch = loop_steps steps; its duration from events attached to
-                # that dispatch; algorithmic bytes per launch = the per-step figure x the steps the launch takes (the state
-                # a streaming step would read and write stays on chip between the steps: that is the point of the kernel)
-                lt = [h.step_loop_timed(args.steps) for _ in range(5)]
-                assert all(n == loop_steps for _, n in lt)
-                kern["tile_loop"] = float(np.median([ms for ms, _ in lt])) * 1e-3
-                algo["tile_loop"] = algo["tile_step"] * loop_steps
-            dom = "tile_loop" if loop_steps > 0 else max(kern, key=lambda k: kern[k] * launches_per_step[k])
-            achieved = algo[dom] / kern[dom] / 1e9
-            us_step = elapsed / args.steps * 1e6
-            # what limits the kernel: HBM only if the algorithmic bytes move at a sizeable fraction of the measured copy rate
-            if loop_steps > 0:
-                limiter = ("latency of the per-step chain inside the resident loop (wait for the neighbours' records -> deposit sweep -> "
-                           "proposals -> exclusion -> publish); the state never leaves the chip between steps")
-            elif dom == "ntt_conv":
-                limiter = ("f64 issue of the modular butterflies (%d launches of an exact number-theoretic transform, 2 x 2^%d residues each) and the "
-                           "memory passes between them" % (ntt["launches"], ntt["log2_m"]))
-            elif achieved >= 0.5 * hbm_copy:
-                limiter = "hbm"
-            elif L_all * (32 + 8 * w["K"]) < 200e6:
-                limiter = "latency (cache-resident working set: dependent load -> compute -> store chain of a ~10 us launch)"
+        outputs = final_state(h, n_ens) if args.dump_outputs else None   # before the --full legs step the handle further
+        if args.full:
+            hbm_copy = h.copy_bandwidth(1 << 30, 5)   # this box's streaming ceiling (read + written bytes of a 1 GiB copy)
+            # per-kernel durations, timed live with HIP events on the stream the kernels are launched on
+            reps = max(10, min(args.steps, 50))
+            if h.method == "pairs":
+                ms, launches, pairs = h.step_timed(reps)
+                avg_s = ms / launches * 1e-3
+                achieved = ALGO_BYTES_PER_PARTICLE_STEP * w["N"] * n_ens / avg_s / 1e9
+                pairs_per_s = pairs / (ms * 1e-3)
+                lds_peak_pairs = 256 * 2.4e9 / LDS_CYCLES_PER_64_PAIRS * 64      # one LDS pipe per CU
+                roof = {"bound": "hbm", "bound_measured": "lds (table gather; PMC in profiles/r01_pmc_traffic.json)",
+                        "kernel": "pair_accumulate", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic_bytes(args.workload, "pair_accumulate"),
+                        "avg_launch_us": avg_s * 1e6, "algorithmic_bytes_per_launch": ALGO_BYTES_PER_PARTICLE_STEP * w["N"] * n_ens,
+                        "note": "the contract's HBM figure; this kernel is bound by the LDS table gather (the 0.4 MB state "
+                                "lives in L2), see on_chip",
+                        "on_chip": {"pairs_per_launch": pairs / launches, "pairs_per_s": pairs_per_s,
+                                    "lds_bound_pairs_per_s": lds_peak_pairs, "lds_frac": pairs_per_s / lds_peak_pairs,
+                                    "lds_cycles_per_64_pairs": LDS_CYCLES_PER_64_PAIRS,
+                                    "valu_issue_slots_per_pair": 4, "valu_frac": pairs_per_s * 4 / VALU_LANE_OPS_PER_S}}
             else:
-                limiter = "valu/lds issue of the deposit sweep (f64 fma + LDS table gather per deposit x 64-site row)"
-            roof = {"bound": "hbm", "bound_measured": limiter, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic_bytes(args.workload, dom, max(loop_steps, 1)),
-                    "hbm_copy_GBps": hbm_copy, "frac_of_copy": achieved / hbm_copy,
-                    "avg_launch_us": kern[dom] * 1e6, "algorithmic_bytes_per_launch": algo[dom],
-                    "timing": "HIP events around each launch" if bracketed else "HIP start/stop events attached to each dispatch",
-                    "per_kernel": {k: {"avg_launch_us": kern[k] * 1e6, "algorithmic_bytes_per_launch": algo[k],
-                                       "achieved_GBps": algo[k] / kern[k] / 1e9,
-                                       "traffic": measured_traffic_bytes(args.workload, k, loop_steps if k == "tile_loop" else 1)} for k in kern},
-                    "whole_step": {"algorithmic_bytes": step_bytes, "us_per_step": us_step,
-                                   "achieved_GBps": step_bytes / (us_step * 1e-6) / 1e9,
-                                   "frac": step_bytes / (us_step * 1e-6) / 1e9 / HBM_PEAK_GBS},
-                    "note": ("algorithmic bytes = what a step must read and write when the state streams through HBM ((32 + 8K) B per site + the deposits); "
-                             "inside the resident loop the state stays in LDS between steps and only the records travel (counter traffic about a tenth, "
-                             "profiles/r02_loop_config2_pmc.json): the fraction says how fast the steps go, not how busy HBM is") if loop_steps > 0 else
-                            "algorithmic bytes = (32 + 8K) B per site + the deposits, per step",
-                    "deposits_per_step": dep_per_step, "changed_particles_per_step": changed, "kernels_per_step": sum(launches_per_step.values()) if loop_steps == 0 else 1.0 / loop_steps,
-                    "launches_per_step": launches_per_step,
-                    "steps_per_launch": loop_steps if loop_steps > 0 else 1}
-        roof = dict(roof or {}, **{"hbm_copy_GBps": hbm_copy})
+                ms_fu, n_fu, deposits = h.step_timed(reps)            # deposits = field changes of the sampled steps (device counters)
+                prof = h.step_profile(reps)
+                # seconds per launch: start/stop events attached to each kernel's own dispatch (hipExtLaunchKernel), i.e.
+                # the begin -> end interval rocprofv3 --kernel-trace reports.  APS_PROF_BRACKET=1 switches to events recorded
+                # around the launch instead, which read ~2 us more per kernel (the event packets' own cost).
+                kern = {k: v[0] / v[1] * 1e-3 for k, v in prof.items() if v[1]}
+                ntt = h.ntt_info()
+                if ntt["on"] and "tile_step" in kern:      # convolution handles step by tile_dense (csrc/tile_dense.hpp): no sweep, no lists
+                    kern["tile_dense"] = kern.pop("tile_step")
+                if ntt["on"] and ntt["prof_launches"]:     # the field update as an exact convolution (csrc/ntt_conv.hpp): three (five) launches per step
+                    kern["ntt_conv"] = ntt["prof_ms"] / ntt["prof_launches"] * 1e-3
+                bracketed = os.environ.get("APS_PROF_BRACKET") is not None
+                dep_per_step = deposits / max(n_fu, 1)
+                N_all, L_all = w["N"] * n_ens, w["L"] * n_ens
+                changed = None
+                if "apply" in kern:                          # accepted events of one step, counted: the states before and after compared
+                    before = [h.get_state(ensemble=e) for e in range(n_ens)]
+                    h.step(1)
+                    changed = float(sum(int(((x[0] != y[0]) | (x[1] != y[1]) | (x[2] != y[2]) | (x[3] != y[3])).sum())
+                                        for x, y in zip(before, [h.get_state(ensemble=e) for e in range(n_ens)])))
+                    del before
+                algo = {k: step_algo_bytes(k, N_all, L_all, w["K"], dep_per_step, bool(w.get("fp32")), changed) for k in kern}
+                if "tile_dense" in algo:                   # cell words read and written, {W, S} (int2 / double2) at the particles' sites; the coefficient atomics left out
+                    algo["tile_dense"] = 8.0 * w["K"] * L_all + (8.0 if w.get("fp32") else 16.0) * N_all
+                launches_per_step = {k: 1 for k in kern}
+                if "ntt_conv" in kern:
+                    # per launch and prime: both signals of 2^m residues read and written (4 B each) -- the first sweep reads the deposit
+                    # signals instead (once for all primes), the last one reads residues and reads + writes {W, S} of the sites (int2 / double2);
+                    # per step on top: the table's spectrum, read by the middle launch
+                    M_ntt = float(1 << ntt["log2_m"]) * n_ens
+                    n_pr = 1 if w.get("fp32") else 2                       # binary64 field: two primes
+                    lps = ntt["prof_launches"] / reps
+                    launches_per_step["ntt_conv"] = lps
+                    algo["ntt_conv"] = (lps * 16.0 * M_ntt * n_pr - (n_pr - 1) * 8.0 * M_ntt - 8.0 * M_ntt * n_pr      # (the last sweep writes no residues)
+                                        + 4.0 * M_ntt * n_pr + (16.0 if w.get("fp32") else 32.0) * L_all) / lps
+                step_bytes = sum(algo[k] * launches_per_step[k] for k in kern)
+                if loop_steps > 0:
+                    # the timed steps ran inside tile_loop: ONE launch = loop_steps steps; its duration from events attached to
+                    # that dispatch; algorithmic bytes per launch = the per-step figure x the steps the launch takes (the state
+                    # a streaming step would read and write stays on chip between the steps: that is the point of the kernel)
+                    lt = [h.step_loop_timed(args.steps) for _ in range(5)]
+                    assert all(n == loop_steps for _, n in lt)
+                    kern["tile_loop"] = float(np.median([ms for ms, _ in lt])) * 1e-3
+                    algo["tile_loop"] = algo["tile_step"] * loop_steps
+                dom = "tile_loop" if loop_steps > 0 else max(kern, key=lambda k: kern[k] * launches_per_step[k])
+                achieved = algo[dom] / kern[dom] / 1e9
+                us_step = elapsed / args.steps * 1e6
+                # what limits the kernel: HBM only if the algorithmic bytes move at a sizeable fraction of the measured copy rate
+                if loop_steps > 0:
+                    limiter = ("latency of the per-step chain inside the resident loop (wait for the neighbours' records -> deposit sweep -> "
+                               "proposals -> exclusion -> publish); the state never leaves the chip between steps")
+                elif dom == "ntt_conv":
+                    limiter = ("f64 issue of the modular butterflies (%d launches of an exact number-theoretic transform, 2 x 2^%d residues each) and the "
+                               "memory passes between them" % (ntt["launches"], ntt["log2_m"]))
+                elif achieved >= 0.5 * hbm_copy:
+                    limiter = "hbm"
+                elif L_all * (32 + 8 * w["K"]) < 200e6:
+                    limiter = "latency (cache-resident working set: dependent load -> compute -> store chain of a ~10 us launch)"
+                else:
+                    limiter = "valu/lds issue of the deposit sweep (f64 fma + LDS table gather per deposit x 64-site row)"
+                roof = {"bound": "hbm", "bound_measured": limiter, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic_bytes(args.workload, dom, max(loop_steps, 1)),
+                        "hbm_copy_GBps": hbm_copy, "frac_of_copy": achieved / hbm_copy,
+                        "avg_launch_us": kern[dom] * 1e6, "algorithmic_bytes_per_launch": algo[dom],
+                        "timing": "HIP events around each launch" if bracketed else "HIP start/stop events attached to each dispatch",
+                        "per_kernel": {k: {"avg_launch_us": kern[k] * 1e6, "algorithmic_bytes_per_launch": algo[k],
+                                           "achieved_GBps": algo[k] / kern[k] / 1e9,
+                                           "traffic": measured_traffic_bytes(args.workload, k, loop_steps if k == "tile_loop" else 1)} for k in kern},
+                        "whole_step": {"algorithmic_bytes": step_bytes, "us_per_step": us_step,
+                                       "achieved_GBps": step_bytes / (us_step * 1e-6) / 1e9,
+                                       "frac": step_bytes / (us_step * 1e-6) / 1e9 / HBM_PEAK_GBS},
+                        "note": ("algorithmic bytes = what a step must read and write when the state streams through HBM ((32 + 8K) B per site + the deposits); "
+                                 "inside the resident loop the state stays in LDS between steps and only the records travel (counter traffic about a tenth, "
+                                 "profiles/r02_loop_config2_pmc.json): the fraction says how fast the steps go, not how busy HBM is") if loop_steps > 0 else
+                                "algorithmic bytes = (32 + 8K) B per site + the deposits, per step",
+                        "deposits_per_step": dep_per_step, "changed_particles_per_step": changed, "kernels_per_step": sum(launches_per_step.values()) if loop_steps == 0 else 1.0 / loop_steps,
+                        "launches_per_step": launches_per_step,
+                        "steps_per_launch": loop_steps if loop_steps > 0 else 1}
+            roof = dict(roof or {}, **{"hbm_copy_GBps": hbm_copy})
     if not sharded_path:
         n_ens_total, sharding_note = n_ens, "one GPU"
-    p, s, b, a = h.get_state()
-    assert (a != 0).all() and np.bincount(p[a == 1], minlength=w["L"]).max() <= w["K"]
+    if args.full:
+        p, s, b, a = h.get_state()
+        assert (a != 0).all() and np.bincount(p[a == 1], minlength=w["L"]).max() <= w["K"]
     h_method = h.method
     h.close()
     if rank != 0:
@@ -689,9 +729,11 @@ def main():
     out.update(extra)
     if roof:
         out["roofline"] = roof
-    if world == 1 and not args.no_cpu_baseline and args.workload == "config2":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "config2":
         out["cpu_baseline"] = cpu_baseline(w)
         out["cpu_reference_loop"] = cpu_reference_loop(w)
+    if args.dump_outputs:
+        dump_outputs(outputs, args.dump_outputs)
     print(json.dumps(out))
 
 

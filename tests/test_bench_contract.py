@@ -1,9 +1,12 @@
-"""CPU checks of the measurement contract: the committed bench line carries every field the driver reads, and
-bench.py refuses to run without a GPU instead of timing anything on the CPU (the product has no CPU fallback)."""
+"""Checks of the measurement contract: the committed bench line carries every field the driver reads, bench.py refuses to
+run without a GPU instead of timing anything on the CPU (the product has no CPU fallback), and --dump-outputs writes
+what the timed steps computed (on the GPU: the oracle's state)."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -108,3 +111,65 @@ def test_gpus_flag_spawns_one_rank_per_gpu_without_touching_the_gpu_in_the_paren
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], env=dict(os.environ, WORLD_SIZE="2", RANK="0"),
                        capture_output=True, text=True, timeout=120, cwd=ROOT)
     assert r.returncode != 0 and "disagrees" in r.stderr
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_above_the_budget(tmp_path):
+    import numpy as np
+    bench = _load_bench()
+    small = {"positions": np.arange(10, dtype=np.float64), "spins": -np.ones(10)}
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    assert sorted(os.listdir(tmp_path / "small")) == ["positions.npy", "spins.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "positions.npy"), small["positions"])
+    n = bench.DUMP_BYTES_MAX // 8                       # two such arrays exceed the budget
+    big = {"positions": np.arange(n, dtype=np.float64), "spins": np.arange(n, dtype=np.float64) * 2}
+    for d in ("a", "b"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    got = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == ["positions.npy", "sample_index.npy", "spins.npy"]
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_BYTES_MAX
+    assert all(a.dtype == np.float64 for a in got.values())
+    idx = got["sample_index.npy"]
+    assert np.array_equal(got["positions.npy"], idx) and np.array_equal(got["spins.npy"], 2 * idx)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "sample_index.npy"))   # the same sample every run
+
+
+def test_dump_outputs_is_refused_where_it_does_not_apply():
+    for extra in (["--workload", "pde"], ["--gpus", "2"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", "unused"] + extra,
+                           capture_output=True, text=True, timeout=120, cwd=ROOT)
+        assert r.returncode != 0 and "--dump-outputs" in r.stderr and r.stdout.strip() == ""
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_the_given_steps_and_dumps_the_oracle_s_state(tmp_path):
+    """A plain run times exactly --steps steps once, carries no --full fields, and its dump is the state the oracle reaches
+    from bench.py's seeded inputs after warm-up + timed steps."""
+    import numpy as np
+    from oracle.gillespie_numpy import LatticeGasParams
+    from oracle import sync_oracle as so
+    bench = _load_bench()
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr
+    line = json.loads(r.stdout)
+    assert line["steps"] == 3 and line["repeats"] == 1 and len(line["repeats_ms_per_step"]) == 1
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 100000 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert "roofline" not in line and "cpu_baseline" not in line
+    w = bench.WORK
+    par = LatticeGasParams.from_kwargs(L=w["L"], xlim=w["xlim"], rate_diffusion=w["rate_diffusion"], rate_active=w["rate_active"],
+                                       beta=w["beta"], scale_rates=False, local_kernel_sigma=w["sigma"], site_capacity=w["K"])
+    orc = so.SyncOracle(par, dt=w["dt"], seed=w["seed"])
+    orc.set_state(*bench.initial_state(w))
+    orc.run(5)                                          # ~2 s per step at this size
+    for name, ref in (("positions", orc.pos), ("spins", orc.spin), ("bound", orc.bound), ("alive", orc.alive)):
+        got = np.load(out / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, ref.astype(np.float64)), name

@@ -4,5 +4,6 @@ out=$1; shift
 ctrs=()
 while [ "$1" != "--" ]; do ctrs+=("$1"); shift; done
 shift
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc "${ctrs[@]}" --kernel-trace -d "$GRAFT_REPO_ROOT/$out" -o pmc -- python3 "$GRAFT_REPO_ROOT/bench.py" "$@" > "$GRAFT_REPO_ROOT/$out.log" 2>&1
+rocprofv3 --pmc "${ctrs[@]}" --kernel-trace -d "$root/$out" -o pmc -- python3 "$root/bench.py" --full "$@" > "$root/$out.log" 2>&1
