@@ -1199,17 +1199,25 @@ __global__ __launch_bounds__(256) void ws_to_double(const int2 *__restrict__ in,
 
 // halo of a site-sharded tiles handle: its segments (ranges of the cell / ws / dcnt / dep arrays) <-> ONE packed message per
 // neighbour.  Every transport (ncclSend / ncclRecv, device copy between two handles, host bytes) moves packed messages
-// that this one kernel packs and unpacks.  All segment sizes are multiples of 4 bytes.
+// that this one kernel packs and unpacks.  All segment sizes are multiples of 4 bytes.  Segments of array HALO_ADD (the
+// coefficients of the convolution) are ADDED to what the receiver holds (int32 words); all others are copied.
 struct HaloSegD { unsigned long long arr_off, msg_off; unsigned bytes; int array; };
 constexpr int HALO_BPS = 32;                 // workgroups per segment
-__global__ __launch_bounds__(256) void halo_move(const HaloSegD *__restrict__ segs, char *a0, char *a1, char *a2, char *a3, char *msg, int unpack) {
+constexpr int HALO_ADD = 4;
+__device__ __forceinline__ char *halo_arr(const HaloSegD &g, char *a0, char *a1, char *a2, char *a3, char *a4) {
+    return (g.array == 0 ? a0 : g.array == 1 ? a1 : g.array == 2 ? a2 : g.array == 3 ? a3 : a4) + g.arr_off;
+}
+__global__ __launch_bounds__(256) void halo_move(const HaloSegD *__restrict__ segs, char *a0, char *a1, char *a2, char *a3, char *a4, char *msg, int unpack) {
     const HaloSegD g = segs[blockIdx.x / HALO_BPS];
-    char *arr = (g.array == 0 ? a0 : g.array == 1 ? a1 : g.array == 2 ? a2 : a3) + g.arr_off;
+    char *arr = halo_arr(g, a0, a1, a2, a3, a4);
     char *m = msg + g.msg_off;
     const unsigned words = g.bytes >> 2;
+    const bool add = g.array == HALO_ADD;
     for (unsigned i = (blockIdx.x % HALO_BPS) * 256 + threadIdx.x; i < words; i += HALO_BPS * 256) {
-        if (unpack) reinterpret_cast<uint32_t *>(arr)[i] = reinterpret_cast<const uint32_t *>(m)[i];
-        else reinterpret_cast<uint32_t *>(m)[i] = reinterpret_cast<const uint32_t *>(arr)[i];
+        if (unpack) {
+            const uint32_t v = reinterpret_cast<const uint32_t *>(m)[i];
+            if (add) reinterpret_cast<uint32_t *>(arr)[i] += v; else reinterpret_cast<uint32_t *>(arr)[i] = v;
+        } else reinterpret_cast<uint32_t *>(m)[i] = reinterpret_cast<const uint32_t *>(arr)[i];
     }
 }
 
@@ -1227,12 +1235,12 @@ struct HaloPushArgs {
     unsigned *done;                       // [2] local completion counters (zero between launches)
     unsigned tag;
 };
-__global__ __launch_bounds__(256) void halo_push(const HaloPushArgs a, char *a0, char *a1, char *a2, char *a3) {
+__global__ __launch_bounds__(256) void halo_push(const HaloPushArgs a, char *a0, char *a1, char *a2, char *a3, char *a4) {
     const int nb0 = a.nseg[0] * HALO_BPS;
     const int side = (int)blockIdx.x < nb0 ? 0 : 1;
     const int bl = (int)blockIdx.x - (side ? nb0 : 0);
     const HaloSegD g = a.segs[side][bl / HALO_BPS];
-    const char *arr = (g.array == 0 ? a0 : g.array == 1 ? a1 : g.array == 2 ? a2 : a3) + g.arr_off;
+    const char *arr = halo_arr(g, a0, a1, a2, a3, a4);
     char *m = a.dst[side] + g.msg_off;
     const unsigned words = g.bytes >> 2;
     for (unsigned i = (unsigned)(bl % HALO_BPS) * 256 + threadIdx.x; i < words; i += HALO_BPS * 256)
@@ -1258,7 +1266,7 @@ struct HaloPullArgs {
     unsigned long long timeout_ticks;     // of the 100 MHz clock
     unsigned *err_host;                   // host-mapped: a wait ran out
 };
-__global__ __launch_bounds__(256) void halo_pull(const HaloPullArgs a, char *a0, char *a1, char *a2, char *a3) {
+__global__ __launch_bounds__(256) void halo_pull(const HaloPullArgs a, char *a0, char *a1, char *a2, char *a3, char *a4) {
     __shared__ int ok_s;
     const int nb0 = a.nseg[0] * HALO_BPS;
     const int side = (int)blockIdx.x < nb0 ? 0 : 1;
@@ -1279,12 +1287,15 @@ __global__ __launch_bounds__(256) void halo_pull(const HaloPullArgs a, char *a0,
     if (!ok_s) return;
     __threadfence_system();
     const HaloSegD g = a.segs[side][bl / HALO_BPS];
-    char *arr = (g.array == 0 ? a0 : g.array == 1 ? a1 : g.array == 2 ? a2 : a3) + g.arr_off;
+    char *arr = halo_arr(g, a0, a1, a2, a3, a4);
     const char *m = a.src[side] + g.msg_off;
     const unsigned words = g.bytes >> 2;
+    const bool add = g.array == HALO_ADD;
     // (system-scope loads: written by another device / process, never served from this device's caches)
-    for (unsigned i = (unsigned)(bl % HALO_BPS) * 256 + threadIdx.x; i < words; i += HALO_BPS * 256)
-        reinterpret_cast<uint32_t *>(arr)[i] = __hip_atomic_load(reinterpret_cast<const uint32_t *>(m) + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (unsigned i = (unsigned)(bl % HALO_BPS) * 256 + threadIdx.x; i < words; i += HALO_BPS * 256) {
+        const uint32_t v = __hip_atomic_load(reinterpret_cast<const uint32_t *>(m) + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (add) reinterpret_cast<uint32_t *>(arr)[i] += v; else reinterpret_cast<uint32_t *>(arr)[i] = v;
+    }
 }
 
 // streaming copy, 16 bytes per lane: the HBM ceiling this box reaches in practice (bench.py quotes it beside the 8 TB/s spec)
@@ -1986,6 +1997,8 @@ TileArgs tile_args(aps_handle *h, bool field_only) {
     const int par = (int)(h->step & 1), out = field_only ? par : par ^ 1;
     a.L = h->p.L; a.K = h->p.K; a.tlen = h->tlen; a.own = h->ts_own; a.ntile = h->ts_ntile; a.dcap = h->ts_dcap; a.par = par;
     a.dense = h->ntt_on ? h->d_ntt_csig : nullptr; a.dense_rt = h->ntt.Rt; a.dense_m = h->ntt.m; a.periodic = h->p.periodic;
+    a.dense_org = h->ntt.org; a.dense_shard = h->world > 1 ? 1 : 0;
+    a.dense_lo = h->world > 1 ? h->own_lo : 0; a.dense_hi = h->world > 1 ? h->own_hi : h->p.L;
     a.tile_lo = h->ts_lo; a.field_only = field_only ? 1 : 0; a.field_mode = h->model.field_mode; a.ens_base = h->model.ens_base; a.E = h->E;
     a.seed_lo = h->model.seed_lo; a.seed_hi = h->model.seed_hi;
     a.model = h->d_model; a.rare = h->d_rare;
@@ -2005,7 +2018,7 @@ int launch_tile_step(aps_handle *h, bool field_only = false) {
     if (h->ntt_on) {                                            // the convolution keeps {W, S} complete: the step without any sweep (tile_dense.hpp)
         if (field_only) return fail(h, APS_ERR_STATE, "tiles, convolution: no deposits are ever pending");
         a.tile_lo = 0;
-        const dim3 grid((unsigned)td_tiles(h->p.L), (unsigned)h->E), block(FU_THREADS);
+        const dim3 grid((unsigned)td_tiles(a.dense_hi - a.dense_lo), (unsigned)h->E), block(FU_THREADS);
         const void *fn = h->f32 ? (h->p.K == 1 ? reinterpret_cast<const void *>(&tile_dense<true, true>) : reinterpret_cast<const void *>(&tile_dense<false, true>))
                                 : (h->p.K == 1 ? reinterpret_cast<const void *>(&tile_dense<true, false>) : reinterpret_cast<const void *>(&tile_dense<false, false>));
         void *args[] = {(void *)&a};
@@ -2086,21 +2099,59 @@ int launch_ntt_conv(aps_handle *h) {
     return APS_OK;
 }
 
+// the convolution of the step's coefficients; a launch that fails leaves coefficients of unknown state behind: they are cleared
+// and {W, S} are rebuilt from scratch before the next step (ensure_tiles: from the cells of the step that failed).  A site range
+// cannot rebuild its window from its own particles: it refuses to step until the state is uploaded again.
+int run_ntt_conv(aps_handle *h) {
+    const int rc = launch_ntt_conv(h);
+    if (rc) {
+        h->field_dirty = true;
+        h->field_pending = false;
+        (void)hipGetLastError();
+        (void)hipMemsetAsync(h->d_ntt_csig, 0, (size_t)h->E * 2 * ((size_t)1 << h->ntt.m) * 4, h->stream);
+        if (h->world > 1) for (int64_t &n : h->n_set) n = -1;
+    }
+    return rc;
+}
+
+void rank_tiles(const aps_handle *h, int r, int &lo, int &hi);
+
 // eligibility and tables of the convolution; called from aps_create once the geometry and the (integer) table exist
 int ntt_setup(aps_handle *h) {
     h->ntt_on = false;
     const char *env = std::getenv("APS_NTT");
     if (env && env[0] == '0') return APS_OK;
     const bool forced = env && env[0] == '1';
-    if (!is_tiles(h) || !h->model.field_mode || h->world != 1) return APS_OK;
+    if (!is_tiles(h) || !h->model.field_mode) return APS_OK;
     if (h->ts_table_in_lds && !forced) return APS_OK;           // the in-LDS sweep (and the resident loop) is faster for short tables
     const int Rt = h->tlen - 1, L = h->p.L;
-    // one image per deposit at most: between walls the table must be short of half the box; on a torus (ring-wide table, Rt <= L / 2: a
-    // deposit within Rt of either end of [0, L) is entered a second time one period on) the box must be far longer than a frame of tile_dense
-    if (h->p.periodic ? !(2 * Rt <= L && L >= 4 * TD_SITES) : !(2 * Rt + 64 * h->ts_RS + h->ts_own + 4 < L)) return APS_OK;
-    int m = 14;
-    while (((int64_t)1 << m) < (int64_t)L + 2 * Rt) ++m;
+    const bool shard = h->world > 1;
+    int64_t span = (int64_t)L + 2 * Rt;                         // signal words the transform must hold
+    if (!shard) {
+        // one image per deposit at most: between walls the table must be short of half the box; on a torus (ring-wide table, Rt <= L / 2: a
+        // deposit within Rt of either end of [0, L) is entered a second time one period on) the box must be far longer than a frame of tile_dense
+        if (h->p.periodic ? !(2 * Rt <= L && L >= 4 * TD_SITES) : !(2 * Rt + 64 * h->ts_RS + h->ts_own + 4 < L)) return APS_OK;
+    } else {
+        // site ranges (overlap-save): a rank transforms the window [own_lo - Rt - g, own_hi + Rt + g) -- its own deposits and the slices of
+        // the neighbours' within reach (the halo) -- and keeps {W, S} on [own_lo - g, own_hi + g), g = 2 the halo sites its frames read.
+        // Eligible with one exchange per step (an explicit interval k > 1 keeps the sweep and its ghost zone), every range at least
+        // Rt + g + 1 sites (only the neighbours' deposits reach a window; only the end ranks hold wall images), and on a torus no
+        // window longer than the ring (no site twice in a window)
+        const char *kenv = std::getenv("APS_HALO_INTERVAL");
+        if (h->p.halo_interval > 1 || (h->p.halo_interval == 0 && kenv && std::atoi(kenv) > 1)) return APS_OK;
+        int own_min = L, own_max = 0;
+        for (int r = 0; r < h->world; ++r) {
+            int lo, hi;
+            rank_tiles(h, r, lo, hi);
+            const int n = std::min(L, hi * h->ts_own) - lo * h->ts_own;
+            own_min = std::min(own_min, n); own_max = std::max(own_max, n);
+        }
+        span = (int64_t)own_max + 2 * (Rt + TD_HALO);
+        if (own_min < Rt + TD_HALO + 1 || (h->p.periodic && span > L)) return APS_OK;
+    }
     const int np = h->f32 ? 1 : 2;                              // the binary64 field: two primes, put together by the last sweep
+    int m = shard && np == 2 ? 15 : 14;                         // (a site range of the binary64 field takes a longer window than it needs)
+    while (((int64_t)1 << m) < span) ++m;
     if (m > 21 || (np == 2 && m < 15) || td_lds_bytes(h->p.K) > 160 * 1024) return APS_OK;
     if (td_lds_bytes(h->p.K) > 48 * 1024) {                     // frames of tile_dense with many cells per site
         const void *fn = h->f32 ? reinterpret_cast<const void *>(&tile_dense<false, true>) : reinterpret_cast<const void *>(&tile_dense<false, false>);
@@ -2112,6 +2163,10 @@ int ntt_setup(aps_handle *h) {
     if (2.0 * h->p.K * wsum >= 0.5 * (np == 1 ? (double)NTT_PRIMES[0] : (double)NTT_PRIMES[0] * (double)NTT_PRIMES[1])) return APS_OK;
     NttPlan &pl = h->ntt;
     pl.m = m; ntt_split(m, pl.a0, pl.a1, pl.a2); pl.L = L; pl.Rt = Rt; pl.E = h->E; pl.np = np;
+    pl.org = shard ? h->own_lo - Rt - TD_HALO : -Rt;
+    pl.out_lo = shard ? h->own_lo - TD_HALO : 0;
+    pl.out_hi = shard ? h->own_hi + TD_HALO : L;
+    if (shard && !h->p.periodic) { pl.out_lo = std::max(pl.out_lo, 0); pl.out_hi = std::min(pl.out_hi, L); }
     pl.crt_inv = ntt_powmod(NTT_PRIMES[0] % NTT_PRIMES[1], NTT_PRIMES[1] - 2ull, NTT_PRIMES[1]);
     pl.unit = std::ldexp(1.0, -h->q);
     const size_t M = (size_t)1 << m;
@@ -2181,6 +2236,7 @@ int ntt_setup(aps_handle *h) {
     // {W, S} need no second buffer: the tile kernel only reads them and the last sweep of the convolution updates them in place
     if (h->d_wsi[1] && h->d_wsi[1] != h->d_wsi[0]) { (void)hipFree(h->d_wsi[1]); h->d_wsi[1] = h->d_wsi[0]; }
     if (!h->f32 && h->d_wsb[1] && h->d_wsb[1] != h->d_wsb[0]) { (void)hipFree(h->d_wsb[1]); h->d_wsb[1] = h->d_wsb[0]; }
+    if (shard) h->ts_kx = 1;                                    // one exchange per step: cells and coefficients (halo_segments)
     h->ntt_on = true;
     return APS_OK;
 }
@@ -2317,11 +2373,30 @@ int launch_tile_loop(aps_handle *h, int64_t n) {
 // ---- halo of a site-sharded tiles handle: what the two neighbour ranks need of this rank's freshly written buffers.
 // Everything is addressed by GLOBAL index (every rank allocates the whole lattice), so a segment is received at the very
 // offsets it was sent from.  side 0: this rank's FIRST sites / tiles (for the left neighbour), side 1: its LAST ones.
-struct HaloSeg { size_t off, bytes; int array; };   // array: 0 cells, 1 ws, 2 dcnt, 3 dep (byte offsets into the [buf] arrays)
+// The convolution (ntt_setup): 3 sites of cells and the coefficient slice the neighbour's window covers -- its own deposits
+// there and the hops across the boundary, Rt + g + 1 sites of c_W and c_S per ensemble; no {W, S}, no deposit lists.  The
+// coefficients sit at window positions (site - org), which differ between sender and receiver, and are ADDED on arrival (both
+// ranks may hold a coefficient of the same site).
+struct HaloSeg { size_t off, bytes; int array; };   // array: 0 cells, 1 ws, 2 dcnt, 3 dep, 4 coefficients (byte offsets into the [buf] arrays)
 
-void halo_segments(const aps_handle *h, int owner_lo_tile, int owner_hi_tile, int side, std::vector<HaloSeg> &out) {
+// recv: the block of the neighbour rank owning [owner_lo_tile, owner_hi_tile) as THIS rank unpacks it
+void halo_segments(const aps_handle *h, int owner_lo_tile, int owner_hi_tile, int side, bool recv, std::vector<HaloSeg> &out) {
     const int L = h->p.L, K = h->p.K, own = h->ts_own;
     const int s_lo = owner_lo_tile * own, s_hi = std::min(L, owner_hi_tile * own);
+    if (h->ntt_on) {
+        const int reach = h->ntt.Rt + TD_HALO;
+        const size_t M = (size_t)1 << h->ntt.m;
+        // the slice's first window position: the sender's own coordinates, or (receiver) the neighbour's boundary is this rank's
+        // other boundary -- own_hi for the right neighbour's first block, own_lo for the left one's last (unwrapped, on a torus too)
+        const int p0 = !recv ? (side == 0 ? s_lo - 1 : s_hi - reach) - h->ntt.org
+                             : (side == 0 ? h->own_hi - 1 : h->own_lo - reach) - h->ntt.org;
+        for (int e = 0; e < h->E; ++e) {
+            const int c0 = side == 0 ? s_lo : s_hi - 3, c1 = side == 0 ? s_lo + 3 : s_hi;
+            out.push_back({((size_t)e * L + c0) * K * 4, (size_t)(c1 - c0) * K * 4, 0});
+            for (int sg = 0; sg < 2; ++sg) out.push_back({(((size_t)e * 2 + sg) * M + (size_t)p0) * 4, (size_t)(reach + 1) * 4, 4});
+        }
+        return;
+    }
     const int nt = std::min(h->ts_kx * h->ts_reach, owner_hi_tile - owner_lo_tile);
     // whole tiles of cells and {W, S}: the ghost zone the receiver steps itself between two exchanges
     const int64_t gs = (int64_t)(h->ts_kx - 1) * h->ts_reach * own;
@@ -2346,7 +2421,8 @@ char *halo_array(aps_handle *h, int array, int buf) {
         case 0: return reinterpret_cast<char *>(h->d_cell[buf]);
         case 1: return h->f32 ? reinterpret_cast<char *>(h->d_wsi[buf]) : reinterpret_cast<char *>(h->d_wsb[buf]);
         case 2: return reinterpret_cast<char *>(h->d_tdcnt[buf]);
-        default: return reinterpret_cast<char *>(h->d_tdep[buf]);
+        case 3: return reinterpret_cast<char *>(h->d_tdep[buf]);
+        default: return reinterpret_cast<char *>(h->d_ntt_csig);
     }
 }
 
@@ -2369,12 +2445,12 @@ int halo_setup(aps_handle *h) {
     for (int side = 0; side < 2; ++side) {
         for (int recv = 0; recv < 2; ++recv) {
             std::vector<HaloSeg> segs;
-            if (!recv) halo_segments(h, h->ts_lo, h->ts_hi, side, segs);
+            if (!recv) halo_segments(h, h->ts_lo, h->ts_hi, side, false, segs);
             else {
                 const int peer = side == 0 ? right : left;       // recv[0]: the right neighbour's first block, recv[1]: the left one's last
                 if (peer < 0) continue;
                 rank_tiles(h, peer, lo, hi);
-                halo_segments(h, lo, hi, side, segs);
+                halo_segments(h, lo, hi, side, true, segs);
             }
             std::vector<HaloSegD> tab;
             size_t off = 0;
@@ -2403,7 +2479,7 @@ int halo_launch(aps_handle *h, int side, bool unpack) {
     if (!nseg) return APS_OK;
     hipLaunchKernelGGL(halo_move, dim3((unsigned)(nseg * HALO_BPS)), dim3(256), 0, h->stream,
                        unpack ? h->d_halo_seg_recv[side] : h->d_halo_seg_send[side], halo_array(h, 0, buf), halo_array(h, 1, buf),
-                       halo_array(h, 2, buf), halo_array(h, 3, buf), unpack ? h->d_halo_recv[side] : h->d_halo_send[side], unpack ? 1 : 0);
+                       halo_array(h, 2, buf), halo_array(h, 3, buf), halo_array(h, HALO_ADD, buf), unpack ? h->d_halo_recv[side] : h->d_halo_send[side], unpack ? 1 : 0);
     HIP_TRY(h, hipGetLastError());
     return APS_OK;
 }
@@ -2417,6 +2493,11 @@ unsigned halo_expected(const aps_handle *h) {
 }
 
 bool halo_due(const aps_handle *h) { return h->world > 1 && h->halo_age + 1 == h->ts_kx; }
+
+// a convolution rank whose caller moves the halo (aps_halo_copy / pack): its blocks are packed by aps_propose, before a neighbour's
+// coefficients can be added to its own -- the boundary sites lie in both slices, and a block packed after an arrival would send
+// the neighbour its own coefficients back
+bool halo_prepacked(const aps_handle *h) { return h->ntt_on && h->world > 1 && !h->ipc_on && !h->comm; }
 
 int halo_exchange_rccl(aps_handle *h) {
     int left, right, rc;
@@ -2465,10 +2546,10 @@ int halo_exchange_ipc(aps_handle *h) {
     pl.tag = tag; pl.err_host = h->h_ipc_err_dev;
     pl.timeout_ticks = 20ull * 100000000ull;                     // 20 s: the neighbour may be far behind (another process)
     if (const char *env = std::getenv("APS_HALO_TIMEOUT_MS")) pl.timeout_ticks = (unsigned long long)std::max(1, std::atoi(env)) * 100000ull;
-    char *a0 = halo_array(h, 0, buf), *a1 = halo_array(h, 1, buf), *a2 = halo_array(h, 2, buf), *a3 = halo_array(h, 3, buf);
+    char *a0 = halo_array(h, 0, buf), *a1 = halo_array(h, 1, buf), *a2 = halo_array(h, 2, buf), *a3 = halo_array(h, 3, buf), *a4 = halo_array(h, HALO_ADD, buf);
     const unsigned nbu = (unsigned)(pu.nseg[0] + pu.nseg[1]) * HALO_BPS, nbl = (unsigned)(pl.nseg[0] + pl.nseg[1]) * HALO_BPS;
-    if (nbu) hipLaunchKernelGGL(halo_push, dim3(nbu), dim3(256), 0, h->stream, pu, a0, a1, a2, a3);
-    if (nbl) hipLaunchKernelGGL(halo_pull, dim3(nbl), dim3(256), 0, h->stream, pl, a0, a1, a2, a3);
+    if (nbu) hipLaunchKernelGGL(halo_push, dim3(nbu), dim3(256), 0, h->stream, pu, a0, a1, a2, a3, a4);
+    if (nbl) hipLaunchKernelGGL(halo_pull, dim3(nbl), dim3(256), 0, h->stream, pl, a0, a1, a2, a3, a4);
     HIP_TRY(h, hipGetLastError());
     h->ipc_seq += 1u;
     h->halo_got = halo_expected(h);
@@ -2479,6 +2560,7 @@ int halo_exchange_ipc(aps_handle *h) {
 // of the current cells.  Exact arithmetic: when the deposits are added changes no bit of any later result.
 int flush_field(aps_handle *h) {
     if (!is_tiles(h) || !h->field_pending) return APS_OK;
+    if (h->ntt_on) return fail(h, APS_ERR_STATE, "tiles, convolution on a site range: the step's convolution runs in aps_commit, after the halo exchange");
     const int cur = (int)(h->step & 1);
     if (h->model.field_mode) {
         int rc = launch_tile_step(h, true);
@@ -2528,6 +2610,10 @@ int sync_slots(aps_handle *h) {
 // the per-tile parts of the global sums, the step words
 int ensure_tiles(aps_handle *h) {
     if (!h->field_dirty) return APS_OK;
+    if (h->slots_dirty) {                                    // (after a failed convolution) the particle arrays first follow the cells
+        int rc = sync_slots(h);
+        if (rc) return rc;
+    }
     const int cur = (int)(h->step & 1), L = h->p.L;
     if (h->model.field_mode)
         for (int e = 0; e < h->E; ++e) {
@@ -2580,7 +2666,13 @@ int upload_cells(aps_handle *h, int e, const int32_t *pos, const int8_t *sigma, 
 int do_propose(aps_handle *h) {
     if (is_tiles(h)) {
         int rc = launch_tile_step(h);
-        if (!rc && h->ntt_on) rc = launch_ntt_conv(h);
+        if (!rc && h->ntt_on && h->world == 1) rc = run_ntt_conv(h);   // a site range: after the halo has arrived (do_commit)
+        if (!rc && halo_prepacked(h)) {
+            int left, right;
+            halo_peers(h, left, right);
+            if (left >= 0) rc = halo_launch(h, 0, false);
+            if (!rc && right >= 0) rc = halo_launch(h, 1, false);
+        }
         return rc;
     }
     if (h->method == APS_METHOD_LATTICE) {
@@ -2596,6 +2688,10 @@ int do_commit(aps_handle *h) {
         if (h->world > 1) {
             if (halo_due(h)) {
                 if (h->halo_got != halo_expected(h)) return fail(h, APS_ERR_STATE, "aps_commit: the halo exchange is due before this commit (aps_halo_info)");
+                if (h->ntt_on) {                             // the neighbours' coefficients are in: this step's convolution
+                    int rc = run_ntt_conv(h);
+                    if (rc) return rc;
+                }
                 h->halo_age = 0;
             } else h->halo_age += 1;
             h->halo_got = 0;
@@ -3664,11 +3760,15 @@ int aps_halo_copy(aps_handle *dst, aps_handle *src) {
     if (dst->step != src->step) return fail(h, APS_ERR_STATE, "aps_halo_copy: the two handles are at different steps");
     if (dst->ts_kx != src->ts_kx || dst->halo_age != src->halo_age) return fail(h, APS_ERR_STATE, "aps_halo_copy: the two handles differ in halo interval or age");
     if (!halo_due(dst)) return fail(h, APS_ERR_STATE, "aps_halo_copy: no halo exchange is due at this step (aps_halo_info)");
+    // a convolution rank ADDS the coefficients of a block: a block delivered twice in one step would count them twice
+    for (int side = 0; side < 2; ++side)
+        if (dst->ntt_on && src->rank == (side == 0 ? right : left) && (dst->halo_got >> side & 1u))
+            return fail(h, APS_ERR_STATE, "aps_halo_copy: this neighbour's block has already arrived at this step");
     int rc;
     for (int side = 0; side < 2; ++side) {                       // side 0: src's first block (src is dst's right neighbour), 1: its last
         if (src->rank != (side == 0 ? right : left)) continue;
         if (src->halo_bytes_send[side] != dst->halo_bytes_recv[side]) return fail(h, APS_ERR_STATE, "aps_halo_copy: block sizes differ");
-        if ((rc = halo_launch(src, side, false))) { h->err = src->err; return rc; }
+        if (!halo_prepacked(src) && (rc = halo_launch(src, side, false))) { h->err = src->err; return rc; }
         HIP_TRY(h, hipStreamSynchronize(src->stream));
         HIP_TRY(h, hipMemcpyAsync(dst->d_halo_recv[side], src->d_halo_send[side], src->halo_bytes_send[side], hipMemcpyDeviceToDevice, dst->stream));
         if ((rc = halo_launch(dst, side, true))) return rc;
@@ -3687,7 +3787,7 @@ int aps_halo_pack(aps_handle *h, int32_t side, uint8_t *host, int64_t cap, int64
     if (!host) return APS_OK;
     if (!halo_due(h)) return fail(h, APS_ERR_STATE, "aps_halo_pack: no halo exchange is due at this step (aps_halo_info)");
     if (cap < *nbytes) return fail(h, APS_ERR_ARG, "aps_halo_pack: buffer too small");
-    int rc = halo_launch(h, side, false);
+    int rc = halo_prepacked(h) ? APS_OK : halo_launch(h, side, false);
     if (rc) return rc;
     if (*nbytes) HIP_TRY(h, hipMemcpyAsync(host, h->d_halo_send[side], (size_t)*nbytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -3700,6 +3800,8 @@ int aps_halo_unpack(aps_handle *h, int32_t from_side, const uint8_t *host, int64
     if (!h->halo_nseg_recv[from_side]) return fail(h, APS_ERR_ARG, "aps_halo_unpack: no neighbour on that side (reflecting wall)");
     if ((int64_t)h->halo_bytes_recv[from_side] != nbytes) return fail(h, APS_ERR_ARG, "aps_halo_unpack: byte count does not match the neighbour's block");
     if (!halo_due(h)) return fail(h, APS_ERR_STATE, "aps_halo_unpack: no halo exchange is due at this step (aps_halo_info)");
+    if (h->ntt_on && (h->halo_got >> from_side & 1u))          // coefficients are ADDED: a second delivery would count them twice
+        return fail(h, APS_ERR_STATE, "aps_halo_unpack: this block has already arrived at this step");
     HIP_TRY(h, hipMemcpyAsync(h->d_halo_recv[from_side], host, (size_t)nbytes, hipMemcpyHostToDevice, h->stream));
     int rc = halo_launch(h, from_side, true);
     if (rc) return rc;

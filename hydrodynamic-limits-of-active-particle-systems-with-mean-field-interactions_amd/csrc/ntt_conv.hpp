@@ -17,6 +17,8 @@
 // (-1 - p, 2L - 1 - p), i.e. the signals live on [-Rt, L + Rt) and a plain linear convolution gives the reference's
 // mode='reflect' sums on [0, L); M >= L + 2 Rt makes the circular convolution equal to the linear one there.
 // Torus: the second entry is the same site one period on (p + L, p - L); the tap at distance L / 2 of an even ring counts once.
+// Site ranges (sharded handles): the signals live on the rank's window [lo - Rt - 2, hi + Rt + 2) (plan field `org`: its first
+// site), the rank's own deposits plus the neighbours' within reach (the halo); the last sweep writes [lo - 2, hi + 2) only.
 //
 // Transform: M = R2 R1 R0 (R0 = 128 along memory, R1, R2 <= 128), index i = i0 + R0 i1 + R0 R1 i2, frequency
 // k = k2 + R2 k1 + R2 R1 k0:  w^(ik) = w_R2^(i2 k2) . w^(R0 i1 k2) . w_R1^(i1 k1) . w^(i0 (k2 + R2 k1)) . w_R0^(i0 k0)
@@ -73,7 +75,9 @@ struct NttPrime {                          // the tables of one prime (device po
 };
 struct NttPlan {
     int m, a0, a1, a2;                     // M = 2^m = R2 R1 R0, R_x = 2^a_x (a0 = 7; a2 = 0: two sweeps only)
-    int L, Rt;                             // lattice sites, table reach; signal index = site + Rt
+    int L, Rt;                             // lattice sites, table reach
+    int org, out_lo, out_hi;               // signal index = site - org (one handle: org = -Rt); the last sweep writes {W, S} of the sites
+                                           // [out_lo, out_hi) (one handle: [0, L); a site range: its own sites +- 2, taken mod L on a torus)
     int E, np;                             // ensembles; primes: 1 (32-bit field: int32 {W, S}) or 2 (binary64 field: double {W, S} = integers * unit)
     uint32_t crt_inv;                      // P0^-1 mod P1
     double unit;                           // 2^-q of the binary64 field
@@ -134,6 +138,12 @@ __device__ __forceinline__ void ntt_lds_transform(double *buf, const int lg_nc, 
     }
 }
 __device__ __forceinline__ int ntt_bitrev(int v, int bits) { return (int)(__brev((unsigned)v) >> (32 - bits)); }
+// the site whose {W, S} signal word g changes, or -1: not one the plan writes
+__device__ __forceinline__ long long ntt_out_site(const NttPlan &pl, const size_t g) {
+    const long long s = (long long)g + pl.org;
+    if (s < pl.out_lo || s >= pl.out_hi) return -1;
+    return s < 0 ? s + pl.L : (s >= pl.L ? s - pl.L : s);
+}
 
 // ---- sweep along a strided axis (i2: stride R0 R1, or i1: stride R0): a workgroup takes NC consecutive words (same other digits)
 // for all R = 2^A values of the axis digit, of one signal (blockIdx.y).
@@ -223,8 +233,8 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_strided(const NttPlan pl, uin
             if constexpr (NP == 1) {
                 old_w[u] = 0;
                 if (combine) {
-                    const long long site = (long long)(base + (size_t)r * stride + c) - pl.Rt;
-                    if (site >= 0 && site < pl.L) old_w[u] = reinterpret_cast<const int *>(reinterpret_cast<const int2 *>(ws) + (size_t)ens * pl.L + site)[sgl];
+                    const long long site = ntt_out_site(pl, base + (size_t)r * stride + c);
+                    if (site >= 0) old_w[u] = reinterpret_cast<const int *>(reinterpret_cast<const int2 *>(ws) + (size_t)ens * pl.L + site)[sgl];
                 }
             }
         }
@@ -236,11 +246,11 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_strided(const NttPlan pl, uin
             if (AXIS == 1 && INV) d0 = ntt_mul(d0, (double)twv[u], md);
             const uint32_t v0 = (uint32_t)d0;
             if (!last) { sig0[g] = v0; continue; }
-            // natural order again: word g is the change of W (or S) at site g - Rt
-            const long long site = (long long)g - pl.Rt;
+            // natural order again: word g is the change of W (or S) at site g + org
+            const long long site = ntt_out_site(pl, g);
             const uint32_t vc = ntt_canon(v0, pp.P);
             if (!combine) { if constexpr (NP > 1) res0[u] = vc; continue; }
-            if (site < 0 || site >= pl.L) continue;
+            if (site < 0) continue;
             if constexpr (NP == 1) {
                 if (vc) reinterpret_cast<int *>(reinterpret_cast<int2 *>(ws) + (size_t)ens * pl.L + site)[sgl] = old_w[u] + (vc > pp.P / 2 ? (int)(vc - pp.P) : (int)vc);
             } else {

@@ -11,12 +11,16 @@
 //   2  a lane per owned site: exclusion (tile_step's rules, same code), new cell(s), the event's deposits as atomic adds into
 //      c_W, c_S at site + Rt and -- within the table's reach of a wall -- at the mirror site (ntt_conv.hpp)
 // The frames are this kernel's own (the cells are indexed by site, not by tile): TD_OWN owned sites, two halo sites either side.
+// A site range of a sharded handle (dense_shard): the frames start at its first own site and cover its own sites only; a
+// deposit goes in at its unwrapped site (own_lo - 1 .. own_hi) of the rank's window, never a second time one period on (the
+// neighbour's halo slice brings the deposits beyond the range, ntt_setup); wall images occur on the end ranks only.
 #pragma once
 
 #ifndef APS_TD_SITES
 #define APS_TD_SITES 1024                  /* tuning builds: sites per frame */
 #endif
 constexpr int TD_SITES = APS_TD_SITES, TD_OWN = TD_SITES - 4;
+constexpr int TD_HALO = 2;                 // sites either side of the owned ones whose {W, S} a frame reads
 __host__ __device__ inline size_t td_lds_cells(int K) { return ((size_t)(TD_SITES + 2) * K * 4 + 7) / 8 * 8; }
 __host__ __device__ inline size_t td_lds_bytes(int K) { return td_lds_cells(K) + (size_t)TD_SITES * K * 8 + ((size_t)TD_SITES * K + 15) / 16 * 16 + 16; }
 inline int td_tiles(int L) { return (L + TD_OWN - 1) / TD_OWN; }
@@ -38,7 +42,7 @@ __global__ TD_WAVES_ATTR __launch_bounds__(FU_THREADS) void tile_dense(const Til
     uint8_t *propL = reinterpret_cast<uint8_t *>(plist + (size_t)TD_SITES * K);              // [TD_SITES K]
     int *misc = reinterpret_cast<int *>(propL + ((size_t)TD_SITES * K + 15) / 16 * 16);      // 0: particles on the frame
     const int t = threadIdx.x, lane = t & 63, e = blockIdx.y, tile = (int)blockIdx.x;
-    const int own0 = tile * TD_OWN, own_n = min(TD_OWN, L - own0), nfr = own_n + 4;          // owned sites, valid frame positions
+    const int own0 = a.dense_lo + tile * TD_OWN, own_n = min(TD_OWN, a.dense_hi - own0), nfr = own_n + 4;   // owned sites, valid frame positions
     const int x0 = own0 - 2;                                                                 // site of frame position 0
     const uint32_t *__restrict__ cell_e = a.cell_in + (size_t)e * L * K;
     const WS *__restrict__ ws_e = reinterpret_cast<const WS *>(a.ws_in) + (size_t)e * L;
@@ -129,22 +133,25 @@ __global__ TD_WAVES_ATTR __launch_bounds__(FU_THREADS) void tile_dense(const Til
     auto cap_at = [&](int j) -> int { const int c = K - occ_at(j); return c < 1 ? 1 : (c > 32 ? 32 : c); };
     uint32_t *cell_o = a.cell_out + (size_t)e * L * K;
     int *const cw_sig = a.dense + ((size_t)e << (a.dense_m + 1)), *const cs_sig = cw_sig + ((size_t)1 << a.dense_m);
-    const int Rt = a.dense_rt;
-    // a field change at site s, with its image: the mirror site beyond a wall (-1 - s, 2 L - 1 - s), or the same site one period on (s + L, s - L)
+    const int Rt = a.dense_rt, org = a.dense_org;
+    const bool shard = a.dense_shard != 0;
+    // a field change at site s, with its image: the mirror site beyond a wall (-1 - s, 2 L - 1 - s), or the same site one period on
+    // (s + L, s - L; not on a site range)
     auto emit = [&](const int s, const int cw, const int cs) {
-        const int at = s + Rt;
+        const int at = s - org;
         if (cw) atomicAdd(cw_sig + at, cw);
         atomicAdd(cs_sig + at, cs);
-        const int img = s < Rt ? (torus ? at + L : Rt - 1 - s) : (s >= L - Rt ? (torus ? at - L : 2 * L - 1 - s + Rt) : -1);
+        const int img = (shard && torus) ? -1 : s < Rt ? (torus ? at + L : -1 - s - org) : (s >= L - Rt ? (torus ? at - L : 2 * L - 1 - s - org) : -1);
         if (img >= 0) { if (cw) atomicAdd(cw_sig + img, cw); atomicAdd(cs_sig + img, cs); }
     };
+    auto dep_site = [&](const int j) -> int { return shard ? x0 + j : frame_site(j); };   // where a hop to frame position j lands
     // the event of the particle `c` on site s: returns whether it is still on the site afterwards (c updated);
     // hop_granted: the exclusion rule let its hop to frame position j through
     auto own_event = [&](uint32_t &c, const int ev, const int s, const int j, const bool hop_granted) -> bool {
         const int sgn = (c & CELL_PLUS) ? 1 : -1;
         bool stays = true;
         if (ev == EV_LEFT || ev == EV_RIGHT || ev == EV_FWD) {
-            if (hop_granted) { stays = false; emit(s, -1, -sgn); emit(frame_site(j), 1, sgn); }
+            if (hop_granted) { stays = false; emit(s, -1, -sgn); emit(dep_site(j), 1, sgn); }
         } else if (ev == EV_BIND) c |= CELL_BOUND;
         else if (ev == EV_UNBIND) c &= ~CELL_BOUND;
         else if (ev == EV_FLIP) { c ^= CELL_PLUS; emit(s, 0, -2 * sgn); }

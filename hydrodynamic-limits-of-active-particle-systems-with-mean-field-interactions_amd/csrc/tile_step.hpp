@@ -32,7 +32,8 @@ struct TileRare { double *exit_log; unsigned *n_exit; uint32_t *src; const uint3
 struct TileArgs {
     int L, K, tlen, own, ntile, dcap, par, tile_lo, field_only, field_mode, ens_base, E, periodic;
     int dense_rt, dense_m;                             // tile_dense.hpp only: the deposits of the step go into the coefficient signals of the
-    int *dense;                                        // convolution (ntt_conv.hpp) [E][2][2^dense_m], index = site + dense_rt, instead of lists
+    int *dense;                                        // convolution (ntt_conv.hpp) [E][2][2^dense_m], index = site - dense_org, instead of lists
+    int dense_org, dense_lo, dense_hi, dense_shard;    // window origin (one handle: -dense_rt); the sites stepped; a site range of a sharded handle
     uint32_t seed_lo, seed_hi;                         // Philox key
     const Model *model;                                // device copy of the rate parameters (read by the proposal phase)
     const TileRare *rare;

@@ -153,7 +153,11 @@ int aps_halo_unpack(aps_handle *h, int32_t from_side, const uint8_t *host, int64
  * (due = 1 exactly when age + 1 == interval; a handle that is not site-sharded reports interval 0, due 0).  A caller that
  * moves the halo itself transfers only when due; aps_commit refuses a due step whose blocks have not all arrived, and
  * aps_halo_copy / pack / unpack refuse a step that is not due.  With interval k the blocks hold (k - 1) * reach whole
- * tiles of cells and {W, S} (+ three / two sites) and k * reach tiles of deposit lists per side. */
+ * tiles of cells and {W, S} (+ three / two sites) and k * reach tiles of deposit lists per side.  A handle that updates the
+ * field by the convolution (aps_ntt_info) exchanges every step (interval 1) and its blocks hold three sites of cells and, per
+ * ensemble, the slice of its convolution coefficients c_W, c_S the neighbour's window covers (reach + 3 sites each); the
+ * receiver ADDS those coefficients to its own (a block delivered twice in one step is refused) and runs the step's convolution in
+ * aps_commit. */
 int aps_halo_info(aps_handle *h, int32_t *interval, int32_t *age, int32_t *due);
 /* Byte counts of the four blocks: send_bytes[0] / [1] = this rank's first / last block (0: no neighbour on that side),
  * recv_bytes[0] = the RIGHT neighbour's first block, recv_bytes[1] = the LEFT neighbour's last block. */
@@ -251,12 +255,15 @@ int aps_step_info(aps_handle *h, int64_t *graph_steps, int64_t *single_steps);
  * returns to the Curie-Weiss rate.  Rates must be finite and >= 0. */
 int aps_set_flip_table(aps_handle *h, const double *table, int32_t n);
 
-/* The field update as an exact convolution (csrc/ntt_conv.hpp): TILES handles (reflecting walls or torus) with one rank and a weight
- * table beyond LDS (BASELINE config 5) add a step's deposits to W, S by a number-theoretic transform of length
+/* The field update as an exact convolution (csrc/ntt_conv.hpp): TILES handles (reflecting walls or torus) with a weight table
+ * beyond LDS (BASELINE config 5) add a step's deposits to W, S by a number-theoretic transform of length
  * 2^log2_m >= L + 2 reach instead of gathering deposits x taps table entries -- exact integers, same bits as the sweep: mod
  * P0 = 15 * 2^27 + 1 for the 32-bit field (fp32), mod P0 and P1 = 27 * 2^26 + 1 with the Chinese remainder for the binary64 field.
  * on: whether this handle does (APS_NTT=0 keeps the sweep, APS_NTT=1 takes the convolution for tables that fit
- * LDS as well); prof_ms / prof_launches: summed duration and number of the convolution's launches in the last aps_step_profile. */
+ * LDS as well); prof_ms / prof_launches: summed duration and number of the convolution's launches in the last aps_step_profile.
+ * A site-sharded handle (rank r of [lo, hi)) transforms its own window [lo - reach - 2, hi + reach + 2): 2^log2_m >= hi - lo +
+ * 2 (reach + 2), per rank; it takes the convolution when halo_interval is 0 or 1, every rank's range is at least reach + 3
+ * sites and, on a torus, no window is longer than L. */
 int aps_ntt_info(aps_handle *h, int32_t *on, int32_t *log2_m, double *prof_ms, int64_t *prof_launches);
 /* Launches per convolution: 3 when the transform has at least two 128 x 128 slabs (log2_m >= 15: sweep along the slab index, ONE
  * launch for everything inside a slab -- two sweeps, the product with the table's spectrum, two sweeps back -- in LDS, sweep back;
