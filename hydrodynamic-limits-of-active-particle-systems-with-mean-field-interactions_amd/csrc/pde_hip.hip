@@ -28,10 +28,11 @@
 #include <vector>
 
 #include "pde.h"
+#include "pde_common.hpp"                 // factorisation, taps, rate, Philox, workgroup sum and scan: shared with pde_wide_hip.hip
 
 namespace {
 
-constexpr int NT = 256;                 // threads per workgroup = chunks of the recurrences
+using namespace pde_common;
 std::string g_err;
 
 struct PdeArgs {
@@ -51,60 +52,6 @@ struct PdeArgs {
     double *hist;                       // [n_systems][window][n_tracers] ring of unwrapped tracer positions
     double *trx; int8_t *trs;           // [n_systems][n_tracers] working tracer state
 };
-
-__device__ inline double cw_rate(double beta, double sigma, double m) {      // ref :64-66
-    const double r = exp(-beta * sigma * m);
-    return r < 1e-8 ? 1e-8 : (r > 1e8 ? 1e8 : r);
-}
-
-// Philox4x32-10 (Random123), as in the particle stepper
-__device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// sum over the workgroup; every thread gets the result.  `red` = NT doubles of LDS scratch.
-__device__ inline double block_sum(double v, double *red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();                                          // scratch may still be read from the previous call
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) s += red[w];
-    return s;
-}
-
-// Exclusive scan of 2 x NT affine maps x -> A x + B (two fields at once) in LDS, Hillis-Steele.  Logical order:
-// thread t is element t (forward) or NT-1-t (backward).  Returns the composition of all maps BEFORE this thread's
-// element applied to the start value 0, i.e. the value entering this thread's chunk.
-__device__ inline void scan_affine2(double A0, double B0, double A1, double B1, double4 *buf, bool backward, double &in0, double &in1) {
-    const int j = backward ? NT - 1 - (int)threadIdx.x : (int)threadIdx.x;
-    double4 *cur = buf, *nxt = buf + NT;
-    __syncthreads();
-    cur[j] = make_double4(A0, B0, A1, B1);
-    __syncthreads();
-    for (int off = 1; off < NT; off <<= 1) {
-        double4 me = cur[j];
-        if (j >= off) {                                       // me after prev:  x -> me.A (prev.A x + prev.B) + me.B
-            const double4 pv = cur[j - off];
-            me = make_double4(me.x * pv.x, me.x * pv.y + me.y, me.z * pv.z, me.z * pv.w + me.w);
-        }
-        nxt[j] = me;
-        __syncthreads();
-        double4 *sw = cur; cur = nxt; nxt = sw;
-    }
-    if (j == 0) { in0 = 0.0; in1 = 0.0; }
-    else { const double4 pv = cur[j - 1]; in0 = pv.y; in1 = pv.w; }
-}
 
 // x = A^{-1} d for both fields: d in (dp, dm), result overwrites them.
 __device__ inline void diffuse2(const PdeArgs &a, double *dp, double *dm, double4 *scan, double *red) {
@@ -313,22 +260,6 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
     }
 }
 
-struct DevBuf {            // frees everything it allocated when it goes out of scope
-    std::vector<void *> ptrs;
-    ~DevBuf() { for (void *q : ptrs) (void)hipFree(q); }
-    template <typename T> T *alloc(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-        ptrs.push_back(q);
-        return static_cast<T *>(q);
-    }
-    template <typename T> T *upload(const T *src, size_t n) {
-        T *q = alloc<T>(n);
-        if (q && n && hipMemcpy(q, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return q;
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -341,14 +272,7 @@ int pde_solve_batch(const pde_params *p, int32_t n_systems, const double *beta, 
                     double *D_eff_series, double *snapshots, double *m_snapshots, double *fft_re, double *fft_im,
                     double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
     auto bad = [&](const char *m) { g_err = std::string("pde_solve_batch: ") + m; return PDE_ERR_ARG; };
-    if (!p || !beta || !rho_p0 || !rho_m0 || n_systems < 1) return bad("null argument or n_systems < 1");
-    if (p->L < 4 || p->L > PDE_MAX_L) return bad("L must be in [4, PDE_MAX_L]");
-    if (p->nsteps < 0 || !(p->dt > 0.0) || !(p->xlim > 0.0)) return bad("nsteps >= 0, dt > 0, xlim > 0 required");
-    if (p->snapshot_interval < 1) return bad("snapshot_interval must be >= 1");
-    if (p->kernel_mode < 0 || p->kernel_mode > 2) return bad("kernel_mode must be 0, 1 or 2");
-    if (p->n_tracers < 0 || (p->n_tracers > 0 && (!tracer_x0 || !tracer_s0 || p->window < 1))) return bad("tracers need initial positions, states and window >= 1");
-    if ((rand_u == nullptr) != (rand_n == nullptr)) return bad("rand_u and rand_n come together");
-    if (p->n_fft_modes < 0 || p->n_fft_modes > p->L / 2 + 1 || ((fft_re == nullptr) != (fft_im == nullptr))) return bad("bad fft request");
+    if (const char *why = check_args(p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, fft_re, fft_im)) return bad(why);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_err = "pde_solve_batch: no HIP device"; return PDE_ERR_NODEVICE; }
     if (p->device < 0 || p->device >= ndev) return bad("device ordinal out of range");
@@ -356,45 +280,15 @@ int pde_solve_batch(const pde_params *p, int32_t n_systems, const double *beta, 
 
     const int L = p->L, ntr = p->n_tracers, ns = p->nsteps + 1;
     const double dx = p->xlim / L;
-    // ---- constant matrix: Thomas factorisation (and the Sherman-Morrison vector for periodic corners)
-    const double av = p->gamma * p->dt / (dx * dx), bv = 1.0 + 2.0 * av;
-    std::vector<double> lo(L, -av), di(L, bv), up(L, -av), fw(L, 0.0), finv(L), fz(L, 0.0);
-    lo[0] = 0.0; up[L - 1] = 0.0;
-    double sm_coef = 0.0, sm_denom = 1.0;
-    if (!p->periodic) { up[0] = -2.0 * av; lo[L - 1] = -2.0 * av; }
-    else {
-        const double corner = -av, gam = -bv;
-        di[0] = bv - gam; di[L - 1] = bv - corner * corner / gam;
-        sm_coef = corner / gam;
-    }
-    std::vector<double> piv(L);
-    piv[0] = di[0];
-    for (int i = 1; i < L; ++i) { fw[i] = lo[i] / piv[i - 1]; piv[i] = di[i] - fw[i] * up[i - 1]; }
-    for (int i = 0; i < L; ++i) finv[i] = 1.0 / piv[i];
-    if (p->periodic) {                                         // A' z = u,  u = (gam, 0, ..., 0, corner)
-        const double corner = -av, gam = -bv;
-        std::vector<double> y(L, 0.0);
-        y[0] = gam; y[L - 1] = corner;
-        for (int i = 1; i < L; ++i) y[i] -= fw[i] * y[i - 1];
-        fz[L - 1] = y[L - 1] * finv[L - 1];
-        for (int i = L - 2; i >= 0; --i) fz[i] = (y[i] - up[i] * fz[i + 1]) * finv[i];
-        sm_denom = 1.0 + fz[0] + sm_coef * fz[L - 1];
-    }
-    // ---- kernel taps (ref :84-93), normalised over the whole ring, cut where negligible
-    std::vector<double> ktab(1, 1.0);
-    int ktaps = 0;
-    if (p->kernel_mode == 1) {
-        std::vector<double> full(L);
-        double sum = 0.0;
-        for (int i = 0; i < L; ++i) { const double d = std::min(i, L - i) * dx / p->kernel_sigma; full[i] = std::exp(-0.5 * d * d); sum += full[i]; }
-        ktaps = 0;
-        for (int i = 0; i <= L / 2; ++i) if (full[i] >= 1e-17 * full[0]) ktaps = i;
-        ktab.assign(ktaps + 1, 0.0);
-        for (int i = 0; i <= ktaps; ++i) ktab[i] = full[i] / sum;
-        if (L % 2 == 0 && ktaps == L / 2) ktab[ktaps] *= 0.5;  // the antipodal site is met from both sides of the sweep
-    }
-    std::vector<double> twc(L), tws(L);
-    for (int j = 0; j < L; ++j) { const double ang = 6.283185307179586476925 * (double)j / (double)L; twc[j] = std::cos(ang); tws[j] = std::sin(ang); }
+    // ---- constant matrix: Thomas factorisation (and the Sherman-Morrison vector for periodic corners); kernel taps (ref :84-93)
+    Factor fac;
+    factorise(p, dx, fac);
+    const std::vector<double> &up = fac.up, &fw = fac.fw, &finv = fac.finv, &fz = fac.fz;
+    const double sm_coef = fac.sm_coef, sm_denom = fac.sm_denom;
+    std::vector<double> ktab;
+    const int ktaps = kernel_taps(p, dx, ktab);
+    std::vector<double> twc, tws;
+    twiddles(L, twc, tws);
 
     DevBuf d;
     PdeArgs a{};

@@ -6,6 +6,11 @@ Same constructor keywords (ref :13-28), `initialize()` (ref :96-131, host NumPy 
 one persistent HIP kernel per system behind the C ABI of include/pde.h; `solve_batch` runs many beta values at once
 (the reference's sweep drivers loop over them serially, IMEX_PDE_solver_run_sweep.py:17-48).
 
+Two execution shapes, one class.  `workgroups=None` (default): one workgroup per system (`pde_solve_batch`), right for
+sweeps of small grids.  `workgroups=G` or `"auto"`: the wide shape of include/pde_wide.h (`pdew_solve`), one system cut
+into G slabs on G workgroups, a time step a chain of kernel launches; right for one fine grid.  `plan()` tells what
+the wide shape would use.
+
 Differences that are part of the design: tracer noise comes from Philox4x32-10 keyed by `seed` on the device (the
 reference draws from NumPy's global MT19937 inside the loop); the magnetisation kernel is applied by direct circular
 convolution instead of rfft products; no output directory is created; plotting methods are not reproduced.
@@ -29,6 +34,13 @@ class PdeParams(C.Structure):
                 ("kernel_sigma", C.c_double), ("seed", C.c_uint64)]
 
 
+class PdewPlanInfo(C.Structure):
+    """struct pdew_plan_info of include/pde_wide.h, field for field."""
+    _fields_ = [("workgroups", C.c_int32), ("slab_len", C.c_int32), ("slab_len_min", C.c_int32), ("n_long_slabs", C.c_int32),
+                ("ktaps", C.c_int32), ("launches_per_step", C.c_int32), ("lds_bytes", C.c_int32), ("reserved", C.c_int32),
+                ("work_bytes", C.c_int64)]
+
+
 PDE_MAX_L = 1 << 22          # fields in LDS up to L ~ 3000 (PDE_LDS_L of include/pde.h), in global memory beyond
 
 
@@ -39,6 +51,11 @@ def _lib():
         lib.pde_last_error.restype, lib.pde_last_error.argtypes = C.c_char_p, []
         lib.pde_solve_batch.restype = C.c_int
         lib.pde_solve_batch.argtypes = [C.POINTER(PdeParams), C.c_int32] + [vp] * 19 + [C.POINTER(C.c_double)]
+        lib.pdew_last_error.restype, lib.pdew_last_error.argtypes = C.c_char_p, []
+        lib.pdew_solve.restype = C.c_int
+        lib.pdew_solve.argtypes = [C.POINTER(PdeParams), C.c_int32, C.c_int32] + [vp] * 19 + [C.POINTER(C.c_double)]
+        lib.pdew_plan.restype = C.c_int
+        lib.pdew_plan.argtypes = [C.POINTER(PdeParams), C.c_int32, C.c_int32, C.POINTER(PdewPlanInfo)]
         lib._pde_ready = True
     return lib
 
@@ -47,12 +64,78 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _check_workgroups(workgroups):
+    """None: one workgroup per system; "auto" -> 0 (the library chooses); an integer >= 1: that many slabs per system."""
+    if workgroups is None:
+        return None
+    if isinstance(workgroups, str):
+        if workgroups != "auto":
+            raise ValueError("workgroups must be None, 'auto' or an integer >= 1")
+        return 0
+    if isinstance(workgroups, bool) or not isinstance(workgroups, (int, np.integer)) or workgroups < 1:
+        raise ValueError("workgroups must be None, 'auto' or an integer >= 1")
+    return int(workgroups)
+
+
+def _check_fft_modes(fft_modes, L):
+    if fft_modes is None:
+        return None
+    if isinstance(fft_modes, bool) or not isinstance(fft_modes, (int, np.integer)) or not 0 <= fft_modes <= L // 2 + 1:
+        raise ValueError("fft_modes must be None or an integer in [0, L // 2 + 1]")
+    return int(fft_modes)
+
+
+def _params(*, L, xlim, dt, nsteps, gamma, lam, bc, active_model, gaussian_kernel, kernel_sigma, snapshot_interval, n_tracers,
+            n_fft_modes, seed, device):
+    if not gaussian_kernel:
+        mode = 0
+    elif kernel_sigma > 100000:                                    # ref :161
+        mode = 2
+    else:
+        mode = 1
+    window = int(0.05 / dt)                                        # ref :238-239
+    return PdeParams(L=L, nsteps=nsteps, periodic=int(bc == "periodic"), anchored_minus=int(active_model != "bidirectional"),
+                     kernel_mode=mode, snapshot_interval=snapshot_interval, n_tracers=n_tracers, window=max(window, 1),
+                     n_fft_modes=n_fft_modes, device=device, xlim=xlim, dt=dt, gamma=gamma, lam=lam,
+                     kernel_sigma=kernel_sigma, seed=int(seed) & (2 ** 64 - 1))
+
+
+def plan(*, L, workgroups="auto", n_systems=1, xlim=1.0, dt=5e-4, T=None, nsteps=None, gamma=2.33e-4, lam=0.6, bc="periodic",
+         active_model="bidirectional", gaussian_kernel=False, kernel_sigma=0.02, snapshot_interval=50, n_tracers=0,
+         fft_modes=0, device=0):
+    """What the wide shape would use for these parameters (pdew_plan; nothing is launched, no GPU is needed): dict with
+    workgroups, slab_len / slab_len_min / n_long_slabs, slab_lengths (sums to L), ktaps, launches_per_step, lds_bytes,
+    work_bytes."""
+    lib = _lib()
+    wg = _check_workgroups(workgroups)
+    if wg is None:
+        raise ValueError("plan() describes the wide shape: workgroups must be 'auto' or an integer >= 1")
+    if nsteps is None:
+        nsteps = int(T / dt) if T is not None else 0
+    par = _params(L=L, xlim=xlim, dt=dt, nsteps=nsteps, gamma=gamma, lam=lam, bc=bc, active_model=active_model,
+                  gaussian_kernel=gaussian_kernel, kernel_sigma=kernel_sigma, snapshot_interval=snapshot_interval,
+                  n_tracers=n_tracers, n_fft_modes=_check_fft_modes(fft_modes, L) or 0, seed=0, device=device)
+    info = PdewPlanInfo()
+    rc = lib.pdew_plan(C.byref(par), n_systems, wg, C.byref(info))
+    if rc != 0:
+        raise capi.ApsError(rc, lib.pdew_last_error().decode())
+    out = {name: getattr(info, name) for name, _ in PdewPlanInfo._fields_ if name != "reserved"}
+    out["slab_lengths"] = [info.slab_len] * info.n_long_slabs + [info.slab_len_min] * (info.workgroups - info.n_long_slabs)
+    return out
+
+
 def solve_batch_raw(*, L, xlim, dt, nsteps, gamma, lam, betas, bc, active_model, gaussian_kernel, kernel_sigma,
                     snapshot_interval, rho_p0, rho_m0, tracer_x0=None, tracer_s0=None, rand_u=None, rand_n=None,
-                    n_fft_modes=0, seed=0, device=0, want_snapshots=True):
+                    n_fft_modes=0, seed=0, device=0, want_snapshots=True, workgroups=None, fft_modes=None):
     """All systems of `betas` from their initial states to step nsteps on the GPU; dict of arrays with a leading
-    system axis.  rand_u / rand_n [n_systems, nsteps+1, n_tracers] replace the device's Philox draws (tests)."""
+    system axis.  rand_u / rand_n [n_systems, nsteps+1, n_tracers] replace the device's Philox draws (tests).
+    workgroups: None = one workgroup per system (pde_solve_batch); "auto" or an integer >= 1 = the wide shape with that
+    many slabs per system (pdew_solve).  fft_modes: when given, the number of lowest Fourier modes (replaces n_fft_modes)."""
     lib = _lib()
+    wg = _check_workgroups(workgroups)
+    fm = _check_fft_modes(fft_modes, L)
+    if fm is not None:
+        n_fft_modes = fm
     betas = np.ascontiguousarray(np.atleast_1d(betas), dtype=np.float64)
     S = len(betas)
     rho_p0 = np.ascontiguousarray(np.broadcast_to(rho_p0, (S, L)), dtype=np.float64)
@@ -64,17 +147,9 @@ def solve_batch_raw(*, L, xlim, dt, nsteps, gamma, lam, betas, bc, active_model,
     if rand_u is not None:
         rand_u = np.ascontiguousarray(np.broadcast_to(rand_u, (S, nsteps + 1, ntr)), dtype=np.float64)
         rand_n = np.ascontiguousarray(np.broadcast_to(rand_n, (S, nsteps + 1, ntr)), dtype=np.float64)
-    if not gaussian_kernel:
-        mode = 0
-    elif kernel_sigma > 100000:                                    # ref :161
-        mode = 2
-    else:
-        mode = 1
-    window = int(0.05 / dt)                                        # ref :238-239
-    par = PdeParams(L=L, nsteps=nsteps, periodic=int(bc == "periodic"), anchored_minus=int(active_model != "bidirectional"),
-                    kernel_mode=mode, snapshot_interval=snapshot_interval, n_tracers=ntr, window=max(window, 1),
-                    n_fft_modes=n_fft_modes, device=device, xlim=xlim, dt=dt, gamma=gamma, lam=lam,
-                    kernel_sigma=kernel_sigma, seed=int(seed) & (2 ** 64 - 1))
+    par = _params(L=L, xlim=xlim, dt=dt, nsteps=nsteps, gamma=gamma, lam=lam, bc=bc, active_model=active_model,
+                  gaussian_kernel=gaussian_kernel, kernel_sigma=kernel_sigma, snapshot_interval=snapshot_interval,
+                  n_tracers=ntr, n_fft_modes=n_fft_modes, seed=seed, device=device)
     if bc not in ("periodic", "neumann"):
         raise ValueError("bc must be 'periodic' or 'neumann'")
     n_snap = nsteps // snapshot_interval + 1
@@ -88,13 +163,19 @@ def solve_batch_raw(*, L, xlim, dt, nsteps, gamma, lam, betas, bc, active_model,
     tx = np.zeros((S, ntr)) if ntr else None
     ts = np.zeros((S, ntr), np.int8) if ntr else None
     ms = C.c_double()
-    rc = lib.pde_solve_batch(C.byref(par), S, _p(betas), _p(rho_p0), _p(rho_m0), _p(tracer_x0) if ntr else None,
-                             _p(tracer_s0) if ntr else None, _p(rand_u), _p(rand_n), _p(out["rho_p"]), _p(out["rho_m"]),
-                             _p(out["m_series"]), _p(out["var_series"]), _p(out["v_eff_series"]) if ntr else None,
-                             _p(out["D_eff_series"]) if ntr else None, _p(snaps), _p(msnaps), _p(fre), _p(fim), _p(tx), _p(ts),
-                             C.byref(ms))
-    if rc != 0:
-        raise capi.ApsError(rc, lib.pde_last_error().decode())
+    bufs = (_p(betas), _p(rho_p0), _p(rho_m0), _p(tracer_x0) if ntr else None,
+            _p(tracer_s0) if ntr else None, _p(rand_u), _p(rand_n), _p(out["rho_p"]), _p(out["rho_m"]),
+            _p(out["m_series"]), _p(out["var_series"]), _p(out["v_eff_series"]) if ntr else None,
+            _p(out["D_eff_series"]) if ntr else None, _p(snaps), _p(msnaps), _p(fre), _p(fim), _p(tx), _p(ts),
+            C.byref(ms))
+    if wg is None:
+        rc = lib.pde_solve_batch(C.byref(par), S, *bufs)
+        if rc != 0:
+            raise capi.ApsError(rc, lib.pde_last_error().decode())
+    else:
+        rc = lib.pdew_solve(C.byref(par), S, wg, *bufs)
+        if rc != 0:
+            raise capi.ApsError(rc, lib.pdew_last_error().decode())
     out.update(snapshots=snaps, m_snapshots=msnaps, fft_re=fre, fft_im=fim, tracers_unwrapped=tx, tracer_state=ts,
                times=np.arange(n_snap) * snapshot_interval * dt, kernel_ms=ms.value)
     return out
@@ -105,7 +186,7 @@ class IMEXPDE:
                  active_model="bidirectional", gaussian_kernel=False, kernel_sigma=0.02, snapshot_interval=50,
                  outdir="IMEX_output", seed=None,
                  # extensions (optional, after the reference's keywords)
-                 device=0, record_fft=True):
+                 device=0, record_fft=True, workgroups=None, fft_modes=None):
         self.L, self.xlim, self.dx = L, xlim, xlim / L
         self.x = np.linspace(0, xlim, L, endpoint=False)
         self.T, self.dt, self.nsteps = T, dt, int(T / dt)
@@ -117,6 +198,9 @@ class IMEXPDE:
         self.device, self.record_fft = int(device), bool(record_fft)
         if L > PDE_MAX_L:
             raise ValueError(f"L <= {PDE_MAX_L}")
+        _check_workgroups(workgroups)
+        _check_fft_modes(fft_modes, L)
+        self.workgroups, self.fft_modes = workgroups, fft_modes    # None: one workgroup per system; record_fft decides the modes
         if seed is not None:
             np.random.seed(seed)                                   # ref :55-56
         self.rho_mean = 1.0 / self.xlim
@@ -154,7 +238,7 @@ class IMEXPDE:
                                snapshot_interval=self.snapshot_interval, rho_p0=rho_p0, rho_m0=rho_m0, tracer_x0=tx0,
                                tracer_s0=ts0, rand_u=rand_u, rand_n=rand_n,
                                n_fft_modes=self.L // 2 + 1 if self.record_fft else 0, seed=seed, device=self.device,
-                               want_snapshots=want_snapshots)
+                               want_snapshots=want_snapshots, workgroups=self.workgroups, fft_modes=self.fft_modes)
 
     def solve(self, rand_u=None, rand_n=None):                     # ref :236-290, on the GPU
         r = self._run([self.beta], self.rho_p, self.rho_m, self.tracers_unwrapped if self.n_tracers else None,
@@ -180,9 +264,29 @@ class IMEXPDE:
             self.tracer_state = r["tracer_state"][s].astype(int)
         self.kernel_ms = r["kernel_ms"]
 
-    def solve_batch(self, betas, want_snapshots=False):
-        """The same initial condition evolved for every beta of `betas` in ONE launch (one workgroup per beta;
-        independent tracer noise per system).  Returns the raw dict of arrays with a leading system axis."""
+    def plan(self, n_systems=1):
+        """What the wide shape would use for this solver (see `plan`); with workgroups=None, what "auto" would."""
+        return plan(L=self.L, workgroups=self.workgroups if self.workgroups is not None else "auto", n_systems=n_systems,
+                    xlim=self.xlim, dt=self.dt, nsteps=self.nsteps, gamma=self.gamma, lam=self.lam, bc=self.bc,
+                    active_model=self.active_model, gaussian_kernel=self.gaussian_kernel, kernel_sigma=self.kernel_sigma,
+                    snapshot_interval=self.snapshot_interval, n_tracers=getattr(self, "n_tracers", 0),
+                    fft_modes=self.fft_modes if self.fft_modes is not None else (self.L // 2 + 1 if self.record_fft else 0),
+                    device=self.device)
+
+    def solve_batch(self, betas, want_snapshots=False, workgroups=None, fft_modes=None):
+        """The same initial condition evolved for every beta of `betas` in ONE launch (one workgroup per beta, or
+        `workgroups` slabs per beta on the wide shape; independent tracer noise per system).  workgroups / fft_modes
+        given here override the constructor's.  Returns the raw dict of arrays with a leading system axis."""
+        if workgroups is not None or fft_modes is not None:
+            _check_workgroups(workgroups)
+            _check_fft_modes(fft_modes, self.L)
+            keep = self.workgroups, self.fft_modes
+            self.workgroups = workgroups if workgroups is not None else keep[0]
+            self.fft_modes = fft_modes if fft_modes is not None else keep[1]
+            try:
+                return self.solve_batch(betas, want_snapshots=want_snapshots)
+            finally:
+                self.workgroups, self.fft_modes = keep
         return self._run(betas, self.rho_p, self.rho_m, self.tracers_unwrapped if self.n_tracers else None,
                          self.tracer_state if self.n_tracers else None, want_snapshots=want_snapshots)
 
@@ -201,18 +305,20 @@ class IMEXPDE:
                                   "outside the accelerated path")
 
 
-def sweep_over_betas(beta_values, n_runs=3, t_min=20.0, t_max=40.0, seeds=None, init_kwargs=None, **ctor_kwargs):
+def sweep_over_betas(beta_values, n_runs=3, t_min=20.0, t_max=40.0, seeds=None, init_kwargs=None, workgroups=None, fft_modes=None,
+                     **ctor_kwargs):
     """The reference's PDE tracer sweep (IMEX_PDE_solver_run_sweep.py:7-75) as ONE launch: every (beta, run) pair is a
     system with its own seeded initial condition.  Returns (v_mean, v_err, D_mean, D_err) per beta exactly as the
     driver forms them: v = |nanmean(v_eff_series[t_min <= t <= t_max])|, D = nanmean(D_eff_series[...]), mean over runs,
-    err = std(ddof=1) / sqrt(n_runs)."""
+    err = std(ddof=1) / sqrt(n_runs).  workgroups selects the execution shape as in `IMEXPDE`; fft_modes > 0 adds the
+    Fourier modes of every system to the work (the sweep itself does not use them)."""
     init_kwargs = dict(init_kwargs or {})
     betas, rp, rm, tx, ts = [], [], [], [], []
     proto = None
     for bi, beta in enumerate(beta_values):
         for run in range(n_runs):
             seed = run if seeds is None else seeds[bi][run]         # the reference seeds each run with its run index
-            s = IMEXPDE(beta=beta, seed=seed, record_fft=False, **ctor_kwargs)
+            s = IMEXPDE(beta=beta, seed=seed, record_fft=False, workgroups=workgroups, fft_modes=fft_modes, **ctor_kwargs)
             s.initialize(**init_kwargs)
             proto = proto or s
             betas.append(float(beta)); rp.append(s.rho_p); rm.append(s.rho_m); tx.append(s.tracers_unwrapped); ts.append(s.tracer_state)
@@ -220,7 +326,7 @@ def sweep_over_betas(beta_values, n_runs=3, t_min=20.0, t_max=40.0, seeds=None, 
                         bc=proto.bc, active_model=proto.active_model, gaussian_kernel=proto.gaussian_kernel,
                         kernel_sigma=proto.kernel_sigma, snapshot_interval=proto.snapshot_interval, rho_p0=np.array(rp),
                         rho_m0=np.array(rm), tracer_x0=np.array(tx), tracer_s0=np.array(ts), seed=proto.seed or 0,
-                        device=proto.device, want_snapshots=False)
+                        device=proto.device, want_snapshots=False, workgroups=workgroups, fft_modes=fft_modes)
     t = np.linspace(0, proto.T, proto.nsteps + 1)
     mask = (t >= t_min) & (t <= t_max)
     v = np.abs(np.nanmean(r["v_eff_series"][:, mask], axis=1)).reshape(len(beta_values), n_runs)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """BASELINE config 5: the particle system at N ~ 1e6 against the hydrodynamic-limit PDE on the same domain, both on the GPU.
 
-    python tools/compare_hydrodynamic.py [--L 2000000] [--L-pde 1000] [--T 1.0] [--beta 0.7] [--json out.json]
+    python tools/compare_hydrodynamic.py [--L 2000000] [--L-pde 1000] [--pde-workgroups auto|G] [--T 1.0] [--beta 0.7] [--json out.json]
 
 Particles: L sites on [0, 1), K = 1, reflecting walls, sigma = 0.005, rate_active = 5, rate_diffusion = 0.02 (lattice units,
 scale_rates=False as in every BASELINE configuration), fixed dt = 0.0125, tiles formulation.  Initial condition: a site is
@@ -82,8 +82,9 @@ class _Ranks:
 
 
 def compare(L=2_000_000, L_pde=1000, T=1.0, beta=0.7, sigma=0.005, rate_active=5.0, rate_diffusion=0.02, dt=0.0125,
-            dt_pde=5e-4, seed=0, n_obs=4, device=0, fp32=False, world=1):
-    """fp32: the 32-bit field of aps_params.fp32 (BASELINE config 5 says float32); world: site-range shards (it says 8 GPUs)."""
+            dt_pde=5e-4, seed=0, n_obs=4, device=0, fp32=False, world=1, pde_workgroups=None):
+    """pde_workgroups: None = the PDE on one workgroup (right for L_pde ~ 1000); "auto" or G = its wide shape, one grid over many
+    workgroups (for a fine L_pde).  fp32: the 32-bit field of aps_params.fp32 (BASELINE config 5 says float32); world: site-range shards (it says 8 GPUs)."""
     capi = importlib.import_module(PKG + ".capi")
     pde = importlib.import_module(PKG + ".pde")
     assert L % L_pde == 0
@@ -99,7 +100,7 @@ def compare(L=2_000_000, L_pde=1000, T=1.0, beta=0.7, sigma=0.005, rate_active=5
         # ---- PDE from the particles' coarse-grained initial densities
         s = pde.IMEXPDE(L=L_pde, xlim=1.0, T=T + 0.5 * dt_pde, dt=dt_pde, gamma=rate_diffusion * dx * dx, lam=rate_active * dx, beta=beta,
                         bc="neumann", active_model="anchored_minus", gaussian_kernel=True, kernel_sigma=sigma,
-                        snapshot_interval=max(1, int(round(T / dt_pde / n_obs))), seed=1, record_fft=False)
+                        snapshot_interval=max(1, int(round(T / dt_pde / n_obs))), seed=1, record_fft=False, workgroups=pde_workgroups)
         s.initialize(mode="homogeneous", rho0=1.0, noise=0.0, n_tracers=16)
         s.rho_p, s.rho_m = cp0 / float(N), cm0 / float(N)
         t0 = time.perf_counter()
@@ -131,20 +132,22 @@ def compare(L=2_000_000, L_pde=1000, T=1.0, beta=0.7, sigma=0.005, rate_active=5
                 site_range_shards=world, particles_per_cell=per_cell,
                 sampling_noise_m=float(1.0 / np.sqrt(per_cell)), gamma_convention="gamma = rate_diffusion * dx^2 (lattice walk: D = r dx^2)",
                 lam=rate_active * dx, gamma=rate_diffusion * dx * dx, caveat="the PDE has no exclusion term; transport is negligible on the PDE grid at this L",
-                wall_s_particles=t_part, wall_s_pde=t_pde, rows=rows)
+                pde_workgroups=pde_workgroups, wall_s_particles=t_part, wall_s_pde=t_pde, rows=rows)
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--L", type=int, default=2_000_000)
     ap.add_argument("--L-pde", type=int, default=1000)
+    ap.add_argument("--pde-workgroups", default=None, help="the PDE's wide shape: 'auto' or slabs per system (default: one workgroup)")
     ap.add_argument("--T", type=float, default=1.0)
     ap.add_argument("--beta", type=float, default=0.7)
     ap.add_argument("--json", default="")
     ap.add_argument("--fp32", action="store_true", help="the 32-bit field (BASELINE config 5: float32)")
     ap.add_argument("--world", type=int, default=1, help="site-range shards emulated on one device (BASELINE config 5: 8)")
     a = ap.parse_args()
-    res = compare(L=a.L, L_pde=a.L_pde, T=a.T, beta=a.beta, fp32=a.fp32, world=a.world)
+    wg = a.pde_workgroups if a.pde_workgroups in (None, "auto") else int(a.pde_workgroups)
+    res = compare(L=a.L, L_pde=a.L_pde, T=a.T, beta=a.beta, fp32=a.fp32, world=a.world, pde_workgroups=wg)
     print(json.dumps(res, indent=1))
     if a.json:
         with open(a.json, "w") as fh:
