@@ -38,6 +38,7 @@
 
 #include "aps.h"
 #include "aps_common.hpp"
+#include "dev_mem.hpp"
 
 namespace {
 
@@ -1427,7 +1428,10 @@ std::string g_create_error;
 
 }  // namespace
 
+// GPU memory of a handle belongs to `mem`, which frees it in aps_destroy.  The d_* / h_* pointers below are views the
+// kernels' argument structs are filled from: none of them owns anything, and several may name the same buffer.
 struct aps_handle {
+    DevMem mem;
     aps_params p{};
     Model model{};
     std::vector<double> beta;
@@ -1601,7 +1605,7 @@ void build_table(aps_handle *h) { weight_table(h->p.sigma_grid, h->p.L, h->p.K, 
 
 template <typename T>
 int dev_alloc(aps_handle *h, T **ptr, size_t count) {
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(ptr), std::max<size_t>(count, 1) * sizeof(T)));
+    HIP_TRY(h, h->mem.alloc(ptr, count));
     HIP_TRY(h, hipMemsetAsync(*ptr, 0, std::max<size_t>(count, 1) * sizeof(T), h->stream));
     return APS_OK;
 }
@@ -2234,8 +2238,8 @@ int ntt_setup(aps_handle *h) {
     HIP_TRY(h, hipMemsetAsync(h->d_ntt_sig, 0, (size_t)np * h->E * 2 * M * 4, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     // {W, S} need no second buffer: the tile kernel only reads them and the last sweep of the convolution updates them in place
-    if (h->d_wsi[1] && h->d_wsi[1] != h->d_wsi[0]) { (void)hipFree(h->d_wsi[1]); h->d_wsi[1] = h->d_wsi[0]; }
-    if (!h->f32 && h->d_wsb[1] && h->d_wsb[1] != h->d_wsb[0]) { (void)hipFree(h->d_wsb[1]); h->d_wsb[1] = h->d_wsb[0]; }
+    if (h->d_wsi[1] != h->d_wsi[0]) { h->mem.release(h->d_wsi[1]); h->d_wsi[1] = h->d_wsi[0]; }
+    if (!h->f32 && h->d_wsb[1] != h->d_wsb[0]) { h->mem.release(h->d_wsb[1]); h->d_wsb[1] = h->d_wsb[0]; }
     if (shard) h->ts_kx = 1;                                    // one exchange per step: cells and coefficients (halo_segments)
     h->ntt_on = true;
     return APS_OK;
@@ -2310,9 +2314,8 @@ int loop_prepare(aps_handle *h) {
     h->loop_rec = (h->loop_drec + 6 * h->p.K + 15) / 16 * 16;
     int rc;
     if ((rc = dev_alloc(h, &h->d_xrec, (size_t)2 * h->E * h->ts_ntile * h->loop_rec)) || (rc = dev_alloc(h, &h->d_abort, 4))) return rc;
-    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&h->h_abort), 64, hipHostMallocMapped));
+    HIP_TRY(h, h->mem.alloc_host_mapped(&h->h_abort, &h->h_abort_dev, 16));
     h->h_abort[0] = 0u;
-    HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->h_abort_dev), h->h_abort, 0));
     h->loop_tag = 0;
     h->loop_state = 1;
     return APS_OK;
@@ -2336,6 +2339,7 @@ int launch_tile_loop(aps_handle *h, int64_t n) {
     la.timeout_ticks = 5000000ull;                                             // 50 ms of the 100 MHz clock per wait (a hand-off takes microseconds)
     if (const char *env = std::getenv("APS_LOOP_TIMEOUT_MS")) la.timeout_ticks = (unsigned long long)std::max(1, std::atoi(env)) * 100000ull;
 #ifdef APS_LOOP_DEBUG
+    // the one allocation outside DevMem: shared by all handles of the process and never freed, so no handle may own it (debug builds only)
     static uint32_t *dbg = nullptr;
     if (!dbg) (void)hipMalloc(reinterpret_cast<void **>(&dbg), (size_t)64 * 3 * h->p.L * 4);
     (void)hipMemsetAsync(dbg, 0xEE, (size_t)64 * 3 * h->p.L * 4, h->stream);
@@ -2782,7 +2786,6 @@ int aps_create(const aps_params *p, aps_handle **out) {
         h->nb = (p->L + B - 1) / B;
         h->dcap = (int)std::min<int64_t>(2LL * p->K * B, std::max<int64_t>(2 * p->n_particles, 2));
         const double dep_bytes = (double)h->E * h->nb * h->dcap * 4.0;
-        // tiles: site-centric state, one kernel per step (single GPU handles; ids must fit the 30-bit cell field)
         // tiles: site-centric state, one kernel per step; ids must fit the 30-bit cell field.  Sharded (world > 1): by site
         // ranges with a halo exchange -- needs the local field (the global mean would be an all-reduce) and one ensemble
         const bool tiles_ok = p->n_particles < (int64_t)CELL_ID && dep_bytes <= 16e9 && (p->world == 1 || M.field_mode);
@@ -2802,7 +2805,6 @@ int aps_create(const aps_params *p, aps_handle **out) {
         h->f32 = p->fp32 != 0 && h->method == APS_METHOD_TILES;
         if (p->fp32 && M.field_mode && h->q < 4) { delete h; return bad("fp32: the sums of this lattice do not fit a 32-bit field (q < 4)"); }
         ts_choose_geometry(h);
-        // sites per lane of field_update: the largest tile that still gives about two workgroups per CU
         // sites per lane of field_update (tile = 64 * RS sites per workgroup): about 2.4 workgroups per CU was the
         // fastest grid on MI355X (measured, RS = 5 at L = 2e5); large lattices take the largest tile (fewest table copies)
         h->fu_R = 2;
@@ -2915,26 +2917,9 @@ void aps_destroy(aps_handle *h) {
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     drop_graphs(h);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
-    if (h->method == APS_METHOD_TILES) h->d_ws = nullptr;   // an alias of d_wsb[cur] there
-    for (int b = 0; b < 2; ++b)
-        for (void *q : {(void *)(b == 1 && h->d_wsb[1] == h->d_wsb[0] ? nullptr : h->d_wsb[b]), (void *)h->d_cell[b], (void *)h->d_tdcnt[b], (void *)h->d_tdep[b], (void *)h->d_gpart[b]}) if (q) (void)hipFree(q);
-    if (h->h_abort) (void)hipHostFree(h->h_abort);
-    if (h->d_flip_tab) (void)hipFree(h->d_flip_tab);
-    for (void *q : {(void *)h->d_ntt_sig, (void *)h->d_ntt_tab, (void *)h->d_ntt_csig}) if (q) (void)hipFree(q);
-    for (void *q : h->ipc_opened) if (q) (void)hipIpcCloseMemHandle(q);
-    if (h->ipc_land) (void)hipFree(h->ipc_land);
-    if (h->d_ipc_done) (void)hipFree(h->d_ipc_done);
-    if (h->h_ipc_err) (void)hipHostFree(h->h_ipc_err);
+    for (void *q : h->ipc_opened) if (q) (void)hipIpcCloseMemHandle(q);   // a neighbour's memory: closed, not freed, and before this rank's own landing buffer goes
     for (hipEvent_t ev : h->loop_ev) if (ev) (void)hipEventDestroy(ev);
-    for (void *q : {(void *)h->d_xrec, (void *)h->d_abort}) if (q) (void)hipFree(q);
-    for (void *q : {(void *)h->d_slot_of, (void *)h->d_model, (void *)h->d_rare, (void *)h->d_table_i, (void *)h->d_wsi[0], (void *)(h->d_wsi[1] == h->d_wsi[0] ? nullptr : h->d_wsi[1]),
-                    (void *)h->d_halo_send[0], (void *)h->d_halo_send[1], (void *)h->d_halo_recv[0], (void *)h->d_halo_recv[1], (void *)h->d_halo_seg_send[0],
-                    (void *)h->d_halo_seg_send[1], (void *)h->d_halo_seg_recv[0], (void *)h->d_halo_seg_recv[1]}) if (q) (void)hipFree(q);
-    for (void *q : {(void *)h->d_ref, (void *)h->d_cnt_pm, (void *)h->d_block_table, (void *)h->d_scal, (void *)h->d_lo_hi, (void *)h->d_ref_ok, (void *)h->d_ws, (void *)h->d_occ_site, (void *)h->d_dcnt, (void *)h->d_dep, (void *)h->d_stepw}) if (q) (void)hipFree(q);
-    void *ptrs[] = {h->d_src, h->d_orig, h->d_pcnt, h->d_plist, h->d_prop_own, h->d_anchor, h->d_sp8, h->d_tinfo,
-                    h->d_stamps, h->d_plan, h->d_plan_n, h->d_accW, h->d_accS, h->d_occ, h->d_table, h->d_beta, h->d_exit, h->d_S, h->d_W, h->d_mfield, h->d_occ4, h->d_gsum,
-                    h->d_nexit, h->d_tmp_sp8, h->d_tmp_tinfo};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
+    h->mem.free_all();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -3304,21 +3289,20 @@ int aps_step_info(aps_handle *h, int64_t *graph_steps, int64_t *single_steps) {
 int aps_copy_bandwidth(aps_handle *h, int64_t nbytes, int32_t reps, double *gbytes_per_s) {
     if (!h || !gbytes_per_s || nbytes < (1 << 20) || reps < 1) return APS_ERR_ARG;
     const size_t n16 = (size_t)nbytes / 16;
+    DevMem tmp;
+    EventPair ev;
     uint4 *a = nullptr, *b = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&a), n16 * 16));
-    if (hipMalloc(reinterpret_cast<void **>(&b), n16 * 16) != hipSuccess) { (void)hipFree(a); return fail(h, APS_ERR_HIP, "aps_copy_bandwidth: out of device memory"); }
+    HIP_TRY(h, tmp.alloc(&a, n16));
+    if (tmp.alloc(&b, n16) != hipSuccess) return fail(h, APS_ERR_HIP, "aps_copy_bandwidth: out of device memory");
     (void)hipMemsetAsync(a, 1, n16 * 16, h->stream);
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    (void)ev.create();
     const unsigned blocks = (unsigned)((n16 + 1023) / 1024);
     hipLaunchKernelGGL(copy16, dim3(blocks), dim3(256), 0, h->stream, a, b, n16);        // warm-up
-    (void)hipEventRecord(e0, h->stream);
+    ev.start(h->stream);
     for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(copy16, dim3(blocks), dim3(256), 0, h->stream, a, b, n16);
-    (void)hipEventRecord(e1, h->stream);
+    ev.stop(h->stream);
     const hipError_t se = hipStreamSynchronize(h->stream);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(a); (void)hipFree(b);
+    const float ms = ev.ms();
     if (se != hipSuccess || !(ms > 0.f)) return fail(h, APS_ERR_HIP, "aps_copy_bandwidth: copy kernel failed");
     *gbytes_per_s = 2.0 * (double)(n16 * 16) * reps / (ms * 1e-3) / 1e9;                // bytes read + bytes written
     return APS_OK;
@@ -3446,19 +3430,19 @@ int aps_observe_structure(aps_handle *h, int32_t e, int32_t k_max, double *out) 
     const int L = h->p.L;
     const size_t nout = 4 + 2 * (size_t)k_max;
     if (!h->d_cnt_pm && (rc = dev_alloc(h, &h->d_cnt_pm, (size_t)L * h->E))) return rc;
+    DevMem tmp;
     double *d_out = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&d_out), nout * sizeof(double)));
-    auto done = [&](int code) { (void)hipFree(d_out); return code; };
+    HIP_TRY(h, tmp.alloc(&d_out, nout));
     if (hipMemsetAsync(d_out, 0, nout * sizeof(double), h->stream) != hipSuccess ||
-        hipMemsetAsync(h->d_cnt_pm, 0, (size_t)L * 4, h->stream) != hipSuccess) return done(fail(h, APS_ERR_HIP, "aps_observe_structure: memset failed"));
+        hipMemsetAsync(h->d_cnt_pm, 0, (size_t)L * 4, h->stream) != hipSuccess) return fail(h, APS_ERR_HIP, "aps_observe_structure: memset failed");
     const uint32_t *src = h->d_src + (size_t)e * h->Npad;
     hipLaunchKernelGGL(count_sites, dim3((unsigned)(h->Npad / 256), 1u), dim3(256), 0, h->stream, src, h->d_cnt_pm, (int)h->Npad, L);
-    if ((rc = launch_field(h, e, h->d_sp8 + (size_t)e * h->Npad, h->d_tinfo + (size_t)e * h->ntiles, (int)h->ntiles, h->d_mfield))) return done(rc);
+    if ((rc = launch_field(h, e, h->d_sp8 + (size_t)e * h->Npad, h->d_tinfo + (size_t)e * h->ntiles, (int)h->ntiles, h->d_mfield))) return rc;
     hipLaunchKernelGGL(structure_sites, dim3((unsigned)std::min(1024, (L + 255) / 256)), dim3(256), 0, h->stream, h->d_cnt_pm, h->d_mfield, L, d_out);
     hipLaunchKernelGGL(structure_dft, dim3((unsigned)k_max), dim3(256), 0, h->stream, src, (int)h->Npad, L, d_out);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess) return done(fail(h, APS_ERR_HIP, "aps_observe_structure: kernel or copy failed"));
-    return done(APS_OK);
+        hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, APS_ERR_HIP, "aps_observe_structure: kernel or copy failed");
+    return APS_OK;
 }
 
 int aps_observe_bins(aps_handle *h, int32_t e, int32_t nbins, int64_t *plus, int64_t *minus) {
@@ -3468,16 +3452,16 @@ int aps_observe_bins(aps_handle *h, int32_t e, int32_t nbins, int64_t *plus, int
     int rc = sync_slots(h);
     if (rc) return rc;
     const int bin_sites = (h->p.L + nbins - 1) / nbins;
+    DevMem tmp;
     unsigned long long *d = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&d), (size_t)2 * nbins * 8));
-    auto done = [&](int code) { (void)hipFree(d); return code; };
-    if (hipMemsetAsync(d, 0, (size_t)2 * nbins * 8, h->stream) != hipSuccess) return done(fail(h, APS_ERR_HIP, "aps_observe_bins: memset failed"));
+    HIP_TRY(h, tmp.alloc(&d, (size_t)2 * nbins));
+    if (hipMemsetAsync(d, 0, (size_t)2 * nbins * 8, h->stream) != hipSuccess) return fail(h, APS_ERR_HIP, "aps_observe_bins: memset failed");
     hipLaunchKernelGGL(bin_counts, dim3((unsigned)(h->Npad / 256)), dim3(256), 0, h->stream, h->d_src + (size_t)e * h->Npad, (int)h->Npad, bin_sites, d, d + nbins,
                        is_tiles(h) && h->world > 1 ? h->own_lo : 0, is_tiles(h) && h->world > 1 ? h->own_hi : h->p.L);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(plus, d, (size_t)nbins * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
         hipMemcpyAsync(minus, d + nbins, (size_t)nbins * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess) return done(fail(h, APS_ERR_HIP, "aps_observe_bins: kernel or copy failed"));
-    return done(APS_OK);
+        hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, APS_ERR_HIP, "aps_observe_bins: kernel or copy failed");
+    return APS_OK;
 }
 
 int aps_method(aps_handle *h) { return h ? h->method : APS_ERR_ARG; }
@@ -3542,26 +3526,22 @@ int aps_rates_from_field(aps_handle *h, int32_t e, const int32_t *pos, const int
         if (pos[i] < 0 || pos[i] >= L) return fail(h, APS_ERR_ARG, "aps_rates_from_field: position outside [0, L)");
     std::vector<int32_t> occ((size_t)L);
     for (int x = 0; x < L; ++x) occ[(size_t)x] = (int32_t)(counts_p[x] + counts_m[x]);
-    void *d_pos = nullptr, *d_sig = nullptr, *d_bnd = nullptr, *d_m = nullptr, *d_occ = nullptr, *d_out = nullptr;
-    auto cleanup = [&]() { for (void *q : {d_pos, d_sig, d_bnd, d_m, d_occ, d_out}) if (q) (void)hipFree(q); };
-#define TRY_(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); h->err = std::string(#expr) + ": " + hipGetErrorString(e_); return APS_ERR_HIP; } } while (0)
-    TRY_(hipMalloc(&d_pos, (size_t)n * 4)); TRY_(hipMalloc(&d_sig, (size_t)n)); TRY_(hipMalloc(&d_bnd, (size_t)n));
-    TRY_(hipMalloc(&d_m, (size_t)L * 8)); TRY_(hipMalloc(&d_occ, (size_t)L * 4)); TRY_(hipMalloc(&d_out, (size_t)n * 9 * 8));
-    TRY_(hipMemcpyAsync(d_pos, pos, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    TRY_(hipMemcpyAsync(d_sig, sigma, (size_t)n, hipMemcpyHostToDevice, h->stream));
-    TRY_(hipMemcpyAsync(d_bnd, bound, (size_t)n, hipMemcpyHostToDevice, h->stream));
-    TRY_(hipMemcpyAsync(d_m, m_field, (size_t)L * 8, hipMemcpyHostToDevice, h->stream));
-    TRY_(hipMemcpyAsync(d_occ, occ.data(), (size_t)L * 4, hipMemcpyHostToDevice, h->stream));
+    DevMem tmp;
+    int32_t *d_pos = nullptr, *d_occ = nullptr; int8_t *d_sig = nullptr; uint8_t *d_bnd = nullptr; double *d_m = nullptr, *d_out = nullptr;
+    HIP_TRY(h, tmp.alloc(&d_pos, (size_t)n)); HIP_TRY(h, tmp.alloc(&d_sig, (size_t)n)); HIP_TRY(h, tmp.alloc(&d_bnd, (size_t)n));
+    HIP_TRY(h, tmp.alloc(&d_m, (size_t)L)); HIP_TRY(h, tmp.alloc(&d_occ, (size_t)L)); HIP_TRY(h, tmp.alloc(&d_out, (size_t)n * 9));
+    HIP_TRY(h, hipMemcpyAsync(d_pos, pos, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_sig, sigma, (size_t)n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_bnd, bound, (size_t)n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_m, m_field, (size_t)L * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_occ, occ.data(), (size_t)L * 4, hipMemcpyHostToDevice, h->stream));
     RatesArgs a{};
-    a.m = h->model; a.beta = h->beta[(size_t)e]; a.pos = (const int32_t *)d_pos; a.sigma = (const int8_t *)d_sig;
-    a.bound = (const uint8_t *)d_bnd; a.m_field = (const double *)d_m; a.occ = (const int32_t *)d_occ; a.anchor = h->d_anchor;
-    a.out = (double *)d_out; a.n = n;
+    a.m = h->model; a.beta = h->beta[(size_t)e]; a.pos = d_pos; a.sigma = d_sig; a.bound = d_bnd; a.m_field = d_m; a.occ = d_occ;
+    a.anchor = h->d_anchor; a.out = d_out; a.n = n;
     hipLaunchKernelGGL(rates_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, a);
-    TRY_(hipGetLastError());
-    TRY_(hipMemcpyAsync(out9n, d_out, (size_t)n * 9 * 8, hipMemcpyDeviceToHost, h->stream));
-    TRY_(hipStreamSynchronize(h->stream));
-#undef TRY_
-    cleanup();
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out9n, d_out, (size_t)n * 9 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return APS_OK;
 }
 
@@ -3602,9 +3582,10 @@ int aps_comm_selftest(aps_handle *h, int64_t nbytes) {
     if (!h || nbytes < 1 || nbytes > (1 << 26)) return APS_ERR_ARG;
     if (!h->comm) return fail(h, APS_ERR_STATE, "aps_comm_selftest: no communicator (aps_comm_init first)");
     // the halo's transport calls (ncclGroupStart, ncclSend, ncclRecv, ncclGroupEnd on the handle's stream), rank -> itself
+    DevMem tmp;
     uint8_t *snd = nullptr, *rcv = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&snd), (size_t)nbytes));
-    if (hipMalloc(reinterpret_cast<void **>(&rcv), (size_t)nbytes) != hipSuccess) { (void)hipFree(snd); return fail(h, APS_ERR_HIP, "aps_comm_selftest: out of device memory"); }
+    HIP_TRY(h, tmp.alloc(&snd, (size_t)nbytes));
+    if (tmp.alloc(&rcv, (size_t)nbytes) != hipSuccess) return fail(h, APS_ERR_HIP, "aps_comm_selftest: out of device memory");
     std::vector<uint8_t> pat((size_t)nbytes), got((size_t)nbytes, 0);
     for (size_t i = 0; i < pat.size(); ++i) pat[i] = (uint8_t)(i * 131u + 7u + (unsigned)h->rank);
     hipError_t he = hipMemcpyAsync(snd, pat.data(), pat.size(), hipMemcpyHostToDevice, h->stream);
@@ -3616,7 +3597,6 @@ int aps_comm_selftest(aps_handle *h, int64_t nbytes) {
     if (nr == ncclSuccess) nr = ge;
     if (he == hipSuccess) he = hipMemcpyAsync(got.data(), rcv, got.size(), hipMemcpyDeviceToHost, h->stream);
     const hipError_t se = hipStreamSynchronize(h->stream);
-    (void)hipFree(snd); (void)hipFree(rcv);
     if (nr != ncclSuccess) return fail(h, APS_ERR_HIP, std::string("aps_comm_selftest (ncclSend/ncclRecv): ") + g_rccl.GetErrorString(nr));
     if (he != hipSuccess || se != hipSuccess) return fail(h, APS_ERR_HIP, "aps_comm_selftest: HIP error");
     if (got != pat) return fail(h, APS_ERR_HIP, "aps_comm_selftest: received bytes differ from the bytes sent");
@@ -3644,17 +3624,13 @@ int aps_ipc_export(aps_handle *h, uint8_t *blob256) {
             for (int side = 0; side < 2; ++side) { h->ipc_land_off[par][side] = off; off += (h->halo_bytes_recv[side] + 255) / 256 * 256; }
         h->ipc_land_bytes = off;
         // fine-grained device memory: written by another device while this one polls it, never cached on the way
-        void *ptr = nullptr;
-        hipError_t e = hipExtMallocWithFlags(&ptr, off, hipDeviceMallocFinegrained);
-        if (e != hipSuccess) { (void)hipGetLastError(); e = hipMalloc(&ptr, off); }
+        const hipError_t e = h->mem.alloc_finegrained(&h->ipc_land, off);
         if (e != hipSuccess) return fail(h, APS_ERR_HIP, std::string("aps_ipc_export: landing buffer: ") + hipGetErrorString(e));
-        h->ipc_land = static_cast<char *>(ptr);
         HIP_TRY(h, hipMemset(h->ipc_land, 0, off));
         int rc;
         if ((rc = dev_alloc(h, &h->d_ipc_done, 2))) return rc;
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&h->h_ipc_err), 64, hipHostMallocMapped));
+        HIP_TRY(h, h->mem.alloc_host_mapped(&h->h_ipc_err, &h->h_ipc_err_dev, 16));
         h->h_ipc_err[0] = 0u;
-        HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void **>(&h->h_ipc_err_dev), h->h_ipc_err, 0));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     IpcBlob b{};
@@ -3713,13 +3689,14 @@ int aps_set_flip_table(aps_handle *h, const double *table, int32_t n) {
     if (!h) return APS_ERR_ARG;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (h->graphs_built_f[0] || h->graphs_built_f[1]) drop_graphs(h);      // captured kernels hold the rate parameters by value
-    if (h->d_flip_tab) { (void)hipFree(h->d_flip_tab); h->d_flip_tab = nullptr; }
+    h->mem.release(h->d_flip_tab);
+    h->d_flip_tab = nullptr;
     h->model.flip_tab = nullptr; h->model.flip_n = 0;
     if (table) {
         if (n < 1 || n > (1 << 24)) return fail(h, APS_ERR_ARG, "aps_set_flip_table: n must be in [1, 2^24]");
         for (int64_t i = 0; i < 2 * ((int64_t)n + 1); ++i)
             if (!(table[i] >= 0.0) || !std::isfinite(table[i])) return fail(h, APS_ERR_ARG, "aps_set_flip_table: rates must be finite and >= 0");
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(&h->d_flip_tab), (size_t)2 * ((size_t)n + 1) * sizeof(double)));
+        HIP_TRY(h, h->mem.alloc(&h->d_flip_tab, (size_t)2 * ((size_t)n + 1)));
         HIP_TRY(h, hipMemcpy(h->d_flip_tab, table, (size_t)2 * ((size_t)n + 1) * sizeof(double), hipMemcpyHostToDevice));
         h->model.flip_tab = h->d_flip_tab; h->model.flip_n = n;
     }
@@ -3979,10 +3956,8 @@ int aps_field_from_counts(aps_handle *h, int32_t e, const int64_t *counts_p, con
     std::vector<uint32_t> sp8; std::vector<int4> tinfo;
     derive_sources(src, sp8, tinfo);
     if (nt > h->tmp_cap) {
-        if (h->d_tmp_sp8) {
-            (void)hipFree(h->d_tmp_sp8); (void)hipFree(h->d_tmp_tinfo);
-            h->d_tmp_sp8 = nullptr; h->d_tmp_tinfo = nullptr;
-        }
+        h->mem.release(h->d_tmp_sp8); h->mem.release(h->d_tmp_tinfo);
+        h->d_tmp_sp8 = nullptr; h->d_tmp_tinfo = nullptr;
         int rc;
         if ((rc = dev_alloc(h, &h->d_tmp_sp8, nt * TILE)) || (rc = dev_alloc(h, &h->d_tmp_tinfo, nt))) return rc;
         h->tmp_cap = nt;

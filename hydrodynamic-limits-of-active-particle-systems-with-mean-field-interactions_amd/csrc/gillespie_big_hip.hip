@@ -24,6 +24,7 @@
 
 #include "gillespie.h"
 #include "aps_common.hpp"
+#include "gillespie_common.hpp"
 
 namespace {
 
@@ -440,23 +441,6 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const BigArgs a) {
     }
 }
 
-struct DevB {
-    std::vector<void *> ptrs;
-    ~DevB() { for (void *q : ptrs) (void)hipFree(q); }
-    template <typename T> T *alloc(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-        (void)hipMemset(q, 0, std::max<size_t>(n, 1) * sizeof(T));
-        ptrs.push_back(q);
-        return static_cast<T *>(q);
-    }
-    template <typename T> T *upload(const T *src, size_t n) {
-        T *q = alloc<T>(n);
-        if (q && n && hipMemcpy(q, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return q;
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -472,79 +456,37 @@ int gil_run_large(const gil_params *p, int32_t n0, const int32_t *pos0, const in
     if ((int64_t)p->L * p->K > (1ll << 27)) return bad("L * K must not exceed 2^27 (site map)");
     if (p->n_cap < 1 || p->n_cap > MAX_NB * PB || n0 < 0 || n0 > p->n_cap || p->n_obs < 1 || p->max_events < 0) return bad("bad n_cap / n0 / n_obs / max_events");
     const int L = p->L, N = p->n_cap;
-    {
-        std::vector<int> occ((size_t)L, 0);
-        for (int i = 0; i < n0; ++i) {
-            if (pos0[i] < 0 || pos0[i] >= L) return bad("position outside [0, L)");
-            if (++occ[(size_t)pos0[i]] > p->K) return bad("site capacity exceeded");
-            if (sigma0[i] != 1 && sigma0[i] != -1) return bad("sigma must be +1 or -1");
-        }
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_big_err = "gil_run_large: no HIP device"; return GIL_ERR_NODEVICE; }
-    if (p->device < 0 || p->device >= ndev) return bad("device ordinal out of range");
-    if (hipSetDevice(p->device) != hipSuccess) { g_big_err = "hipSetDevice failed"; return GIL_ERR_HIP; }
+    if (const char *why = gil_check_state(p, n0, pos0, sigma0)) return bad(why);
+    OneShot job{"gil_run_large", g_big_err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: the scratch arrays start from zero
+    if (int rc = job.select_device(p->device)) return rc;
     std::vector<double> table; int tlen = 0, q = 0;
     weight_table(p->sigma_grid, L, p->K, p->periodic != 0, table, tlen, q);
     BigArgs a{};
     a.p = *p; a.tlen = tlen; a.n_init = n0; a.nblk = (N + PB - 1) / PB; a.cb = (a.nblk + BT - 1) / BT;
     a.tab_in_lds = tlen + 1 <= TAB_LDS_MAX ? 1 : 0; a.beta = p->beta[0];
-    Model &M = a.m;
-    M.L = L; M.K = p->K; M.periodic = p->periodic ? 1 : 0; M.field_mode = p->sigma_grid > 0.0 ? 1 : 0;
-    M.minus_anchor = p->minus_anchor ? 1 : 0; M.immobilize = p->immobilize ? 1 : 0; M.suppress_flip = p->suppress_flip ? 1 : 0;
-    M.crowding = p->crowding ? 1 : 0; M.rate_diffusion = p->rate_diffusion; M.rate_active = p->rate_active;
-    M.k_on = p->k_on; M.k_off = p->k_off; M.k_exit = p->k_exit; M.dt = 0.0;
-    M.seed_lo = (uint32_t)p->seed; M.seed_hi = (uint32_t)(p->seed >> 32); M.ens_base = 0;
-    DevB d;
+    a.m = gil_model(p);
     const size_t SO = (size_t)p->n_obs * N;
-#define UPB(dst, src, n) do { a.dst = d.upload(src, n); if (!a.dst) { g_big_err = "gil_run_large: device upload failed (" #dst ")"; return GIL_ERR_HIP; } } while (0)
-#define ALB(dst, T, n) do { a.dst = d.alloc<T>(n); if (!a.dst) { g_big_err = "gil_run_large: device allocation failed (" #dst ")"; return GIL_ERR_HIP; } } while (0)
-    UPB(table, table.data(), table.size()); UPB(times, p->times_obs, (size_t)p->n_obs);
-    UPB(pos0, pos0, (size_t)std::max(n0, 1)); UPB(sigma0, sigma0, (size_t)std::max(n0, 1));
-    if (bound0) UPB(bound0, bound0, (size_t)std::max(n0, 1));
-    if (p->anchor_mask) UPB(anchor, p->anchor_mask, (size_t)L);
-    if (uniforms) UPB(uniforms, uniforms, (size_t)p->max_events * 4);
-    M.flip_n = 0; M.flip_tab = nullptr;
-    if (p->flip_table) {                                       // a caller's flip_rate_fn, tabulated (aps_set_flip_table's layout)
-        if (p->flip_n < 1 || p->flip_n > (1 << 24)) return bad("flip_n must be in [1, 2^24]");
-        M.flip_tab = d.upload(p->flip_table, (size_t)2 * ((size_t)p->flip_n + 1));
-        if (!M.flip_tab) { g_big_err = "gil_run_large: device upload failed (flip_table)"; return GIL_ERR_HIP; }
-        M.flip_n = p->flip_n;
-    }
-    ALB(pos, int, (size_t)N); ALB(occ, int, (size_t)L); ALB(occp, int, (size_t)L); ALB(slot, int, (size_t)L * p->K); ALB(work, int, (size_t)N);
-    ALB(flg, uint8_t, (size_t)N); ALB(rate, double, (size_t)N); ALB(bsum, double, (size_t)a.nblk); ALB(W, double, (size_t)L); ALB(S, double, (size_t)L);
-    if (pos_obs) ALB(pos_obs, int32_t, SO);
-    if (sigma_obs) ALB(sigma_obs, int8_t, SO);
-    if (flags_obs) ALB(flags_obs, uint8_t, SO);
-    if (n_recorded) ALB(n_recorded, int32_t, 1);
-    if (n_events) ALB(n_events, long long, 1);
-    if (t_final) ALB(t_final, double, 1);
-    if (exits) ALB(exits, double, (size_t)N * 3);
-    if (n_exits) ALB(n_exits, int32_t, 1);
-#undef UPB
-#undef ALB
+    UP(table, table.data(), table.size()); UP(times, p->times_obs, (size_t)p->n_obs);
+    UP(pos0, pos0, (size_t)std::max(n0, 1)); UP(sigma0, sigma0, (size_t)std::max(n0, 1));
+    if (bound0) UP(bound0, bound0, (size_t)std::max(n0, 1));
+    if (p->anchor_mask) UP(anchor, p->anchor_mask, (size_t)L);
+    if (uniforms) UP(uniforms, uniforms, (size_t)p->max_events * 4);
+    if (int rc = gil_upload_flip_table(job, p, a.m)) return rc;
+    WORK(pos, (size_t)N); WORK(occ, (size_t)L); WORK(occp, (size_t)L); WORK(slot, (size_t)L * p->K); WORK(work, (size_t)N);
+    WORK(flg, (size_t)N); WORK(rate, (size_t)N); WORK(bsum, (size_t)a.nblk); WORK(W, (size_t)L); WORK(S, (size_t)L);
+    OUT(pos_obs, pos_obs, SO); OUT(sigma_obs, sigma_obs, SO); OUT(flags_obs, flags_obs, SO);
+    OUT(n_recorded, n_recorded, 1); OUT(n_events, n_events, 1); OUT(t_final, t_final, 1); OUT(exits, exits, (size_t)N * 3); OUT(n_exits, n_exits, 1);
     const size_t lds = ((size_t)(a.tab_in_lds ? ((tlen + 2) & ~1) : 0) + 32 + 4 * BT + 4) * sizeof(double) + ((size_t)2 * MAX_NB + 32) * sizeof(int);
     if (lds > 160 * 1024) return bad("LDS budget exceeded");
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&gil_big_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        g_big_err = "gil_run_large: cannot raise the dynamic LDS limit"; return GIL_ERR_HIP;
-    }
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { g_big_err = "hipEventCreate failed"; return GIL_ERR_HIP; }
+    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel), lds)) return rc;
+    if (int rc = job.create_events()) return rc;
     hipLaunchKernelGGL(big_field_init, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, nullptr, a);
-    (void)hipEventRecord(e0, nullptr);
+    job.ev.start();
     hipLaunchKernelGGL(gil_big_kernel, dim3(1), dim3(BT), lds, nullptr, a);
-    (void)hipEventRecord(e1, nullptr);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipDeviceSynchronize();
-    float ms = 0.f;
-    if (err == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (err != hipSuccess) { g_big_err = std::string("gil_big_kernel: ") + hipGetErrorString(err); return GIL_ERR_HIP; }
-    if (kernel_ms) *kernel_ms = ms;
-#define DNB(host, dev, bytes) do { if (host && hipMemcpy(host, a.dev, (bytes), hipMemcpyDeviceToHost) != hipSuccess) { g_big_err = "gil_run_large: download failed (" #dev ")"; return GIL_ERR_HIP; } } while (0)
-    DNB(pos_obs, pos_obs, SO * 4); DNB(sigma_obs, sigma_obs, SO); DNB(flags_obs, flags_obs, SO);
-    DNB(n_recorded, n_recorded, 4); DNB(n_events, n_events, 8); DNB(t_final, t_final, 8); DNB(exits, exits, (size_t)N * 3 * 8); DNB(n_exits, n_exits, 4);
-#undef DNB
+    job.ev.stop();
+    if (int rc = job.finish(hipGetLastError(), "gil_big_kernel", kernel_ms)) return rc;
+    DOWN(pos_obs, pos_obs, SO * 4); DOWN(sigma_obs, sigma_obs, SO); DOWN(flags_obs, flags_obs, SO);
+    DOWN(n_recorded, n_recorded, 4); DOWN(n_events, n_events, 8); DOWN(t_final, t_final, 8); DOWN(exits, exits, (size_t)N * 3 * 8); DOWN(n_exits, n_exits, 4);
     return GIL_OK;
 }
 

@@ -24,6 +24,7 @@
 
 #include "gillespie.h"
 #include "aps_common.hpp"
+#include "gillespie_common.hpp"           // model, initial-state check, the driver of the one-shot entry points
 
 namespace {
 
@@ -388,23 +389,6 @@ __global__ __launch_bounds__(NT) void gil_kernel(const GilArgs a) {
     }
 }
 
-struct Dev {
-    std::vector<void *> ptrs;
-    ~Dev() { for (void *q : ptrs) (void)hipFree(q); }
-    template <typename T> T *alloc(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-        (void)hipMemset(q, 0, std::max<size_t>(n, 1) * sizeof(T));
-        ptrs.push_back(q);
-        return static_cast<T *>(q);
-    }
-    template <typename T> T *upload(const T *src, size_t n) {
-        T *q = alloc<T>(n);
-        if (q && n && hipMemcpy(q, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return q;
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -422,80 +406,43 @@ int gil_run_batch(const gil_params *p, const int32_t *n0, const int32_t *pos0, c
     const int S = p->n_systems, L = p->L, ncap = p->n_cap;
     for (int s = 0; s < S; ++s) {
         if (n0[s] < 0 || n0[s] > ncap) return bad("n0 outside [0, n_cap]");
-        std::vector<int> occ((size_t)L, 0);
-        for (int i = 0; i < n0[s]; ++i) {
-            const int x = pos0[(size_t)s * ncap + i];
-            if (x < 0 || x >= L) return bad("position outside [0, L)");
-            if (++occ[(size_t)x] > p->K) return bad("site capacity exceeded");
-            const int sg = sigma0[(size_t)s * ncap + i];
-            if (sg != 1 && sg != -1) return bad("sigma must be +1 or -1");
-        }
+        if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * ncap, sigma0 + (size_t)s * ncap)) return bad(why);
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_gil_err = "gil_run_batch: no HIP device"; return GIL_ERR_NODEVICE; }
-    if (p->device < 0 || p->device >= ndev) return bad("device ordinal out of range");
-    if (hipSetDevice(p->device) != hipSuccess) { g_gil_err = "hipSetDevice failed"; return GIL_ERR_HIP; }
+    OneShot job{"gil_run_batch", g_gil_err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: a run may record fewer observations than it has room for
+    if (int rc = job.select_device(p->device)) return rc;
 
     std::vector<double> table; int tlen = 0, q = 0;
     weight_table(p->sigma_grid, L, p->K, p->periodic != 0, table, tlen, q);
     GilArgs a{};
     const int NT = ncap <= 1024 ? 64 : 256;                   // one wavefront per system while a lane owns at most 16 particles
     a.p = *p; a.tlen = tlen; a.chunk = (ncap + NT - 1) / NT;
-    Model &M = a.m;
-    M.L = L; M.K = p->K; M.periodic = p->periodic ? 1 : 0; M.field_mode = p->sigma_grid > 0.0 ? 1 : 0;
-    M.minus_anchor = p->minus_anchor ? 1 : 0; M.immobilize = p->immobilize ? 1 : 0; M.suppress_flip = p->suppress_flip ? 1 : 0;
-    M.crowding = p->crowding ? 1 : 0; M.rate_diffusion = p->rate_diffusion; M.rate_active = p->rate_active;
-    M.k_on = p->k_on; M.k_off = p->k_off; M.k_exit = p->k_exit; M.dt = 0.0;
-    M.seed_lo = (uint32_t)p->seed; M.seed_hi = (uint32_t)(p->seed >> 32); M.ens_base = 0;
-    Dev d;
+    a.m = gil_model(p);
     const size_t SN = (size_t)S * ncap, SO = (size_t)S * p->n_obs;
-#define UPL(dst, src, n) do { a.dst = d.upload(src, n); if (!a.dst) { g_gil_err = "gil_run_batch: device upload failed (" #dst ")"; return GIL_ERR_HIP; } } while (0)
-#define OUTB(dst, host, n) do { if (host) { a.dst = d.alloc<std::remove_pointer<decltype(a.dst)>::type>(n); if (!a.dst) { g_gil_err = "gil_run_batch: device allocation failed (" #dst ")"; return GIL_ERR_HIP; } } } while (0)
-    UPL(beta, p->beta, (size_t)S); UPL(table, table.data(), table.size()); UPL(times, p->times_obs, (size_t)p->n_obs);
-    UPL(n0, n0, (size_t)S); UPL(pos0, pos0, SN); UPL(sigma0, sigma0, SN);
-    if (bound0) UPL(bound0, bound0, SN);
-    if (p->anchor_mask) UPL(anchor, p->anchor_mask, (size_t)L);
-    if (p->front_lo) UPL(front_lo, p->front_lo, (size_t)L);
-    if (p->block_table) UPL(block_table, p->block_table, (size_t)(p->K + 1) * (p->K + 1));
-    M.flip_n = 0; M.flip_tab = nullptr;
-    if (p->flip_table) {                                       // a caller's flip_rate_fn, tabulated (aps_set_flip_table's layout)
-        if (p->flip_n < 1 || p->flip_n > (1 << 24)) return bad("flip_n must be in [1, 2^24]");
-        M.flip_tab = d.upload(p->flip_table, (size_t)2 * ((size_t)p->flip_n + 1));
-        if (!M.flip_tab) { g_gil_err = "gil_run_batch: device upload failed (flip_table)"; return GIL_ERR_HIP; }
-        M.flip_n = p->flip_n;
-    }
-    if (uniforms) UPL(uniforms, uniforms, (size_t)S * p->max_events * 4);
-    OUTB(pos_obs, pos_obs, SO * ncap); OUTB(sigma_obs, sigma_obs, SO * ncap); OUTB(flags_obs, flags_obs, SO * ncap);
-    if (scalars_obs) { a.scalars = d.alloc<long long>(SO * GIL_NSCALARS); if (!a.scalars) { g_gil_err = "gil_run_batch: device allocation failed (scalars)"; return GIL_ERR_HIP; } }
-    OUTB(n_recorded, n_recorded, (size_t)S); OUTB(t_final, t_final, (size_t)S); OUTB(exits, exits, SN * 3); OUTB(n_exits, n_exits, (size_t)S);
-    if (n_events) { a.n_events = d.alloc<long long>((size_t)S); if (!a.n_events) { g_gil_err = "gil_run_batch: device allocation failed (n_events)"; return GIL_ERR_HIP; } }
-#undef UPL
-#undef OUTB
+    UP(beta, p->beta, (size_t)S); UP(table, table.data(), table.size()); UP(times, p->times_obs, (size_t)p->n_obs);
+    UP(n0, n0, (size_t)S); UP(pos0, pos0, SN); UP(sigma0, sigma0, SN);
+    if (bound0) UP(bound0, bound0, SN);
+    if (p->anchor_mask) UP(anchor, p->anchor_mask, (size_t)L);
+    if (p->front_lo) UP(front_lo, p->front_lo, (size_t)L);
+    if (p->block_table) UP(block_table, p->block_table, (size_t)(p->K + 1) * (p->K + 1));
+    if (int rc = gil_upload_flip_table(job, p, a.m)) return rc;
+    if (uniforms) UP(uniforms, uniforms, (size_t)S * p->max_events * 4);
+    OUT(pos_obs, pos_obs, SO * ncap); OUT(sigma_obs, sigma_obs, SO * ncap); OUT(flags_obs, flags_obs, SO * ncap);
+    OUT(scalars, scalars_obs, SO * GIL_NSCALARS);
+    OUT(n_recorded, n_recorded, (size_t)S); OUT(t_final, t_final, (size_t)S); OUT(exits, exits, SN * 3); OUT(n_exits, n_exits, (size_t)S);
+    OUT(n_events, n_events, (size_t)S);
     const size_t lds = ((size_t)2 * L + ((tlen + 2) & ~1) + ncap + (ncap & 1) + 8 + 5 * NT + 8) * sizeof(double) +
                        ((size_t)3 * ncap + 16) * sizeof(int) + (size_t)((ncap + 15) & ~15) + (size_t)2 * ((L + 15) & ~15);
     if (lds > 160 * 1024) return bad("system does not fit the 160 KB of LDS");
-    if (lds > 48 * 1024 && hipFuncSetAttribute(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64>) : reinterpret_cast<const void *>(&gil_kernel<256>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        g_gil_err = "gil_run_batch: cannot raise the dynamic LDS limit"; return GIL_ERR_HIP;
-    }
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { g_gil_err = "hipEventCreate failed"; return GIL_ERR_HIP; }
-    (void)hipEventRecord(e0, nullptr);
+    if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64>) : reinterpret_cast<const void *>(&gil_kernel<256>), lds)) return rc;
+    if (int rc = job.create_events()) return rc;
+    job.ev.start();
     if (NT == 64) hipLaunchKernelGGL(gil_kernel<64>, dim3((unsigned)S), dim3(64), lds, nullptr, a);
     else hipLaunchKernelGGL(gil_kernel<256>, dim3((unsigned)S), dim3(256), lds, nullptr, a);
-    (void)hipEventRecord(e1, nullptr);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipDeviceSynchronize();
-    float ms = 0.f;
-    if (err == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (err != hipSuccess) { g_gil_err = std::string("gil_kernel: ") + hipGetErrorString(err); return GIL_ERR_HIP; }
-    if (kernel_ms) *kernel_ms = ms;
-#define DOWNL(host, dev, bytes) do { if (host && hipMemcpy(host, a.dev, (bytes), hipMemcpyDeviceToHost) != hipSuccess) { g_gil_err = "gil_run_batch: download failed (" #dev ")"; return GIL_ERR_HIP; } } while (0)
-    DOWNL(pos_obs, pos_obs, SO * ncap * 4); DOWNL(sigma_obs, sigma_obs, SO * ncap); DOWNL(flags_obs, flags_obs, SO * ncap);
-    DOWNL(scalars_obs, scalars, SO * GIL_NSCALARS * 8); DOWNL(n_recorded, n_recorded, (size_t)S * 4); DOWNL(n_events, n_events, (size_t)S * 8);
-    DOWNL(t_final, t_final, (size_t)S * 8); DOWNL(exits, exits, SN * 3 * 8); DOWNL(n_exits, n_exits, (size_t)S * 4);
-#undef DOWNL
+    job.ev.stop();
+    if (int rc = job.finish(hipGetLastError(), "gil_kernel", kernel_ms)) return rc;
+    DOWN(pos_obs, pos_obs, SO * ncap * 4); DOWN(sigma_obs, sigma_obs, SO * ncap); DOWN(flags_obs, flags_obs, SO * ncap);
+    DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8); DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8);
+    DOWN(t_final, t_final, (size_t)S * 8); DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
     return GIL_OK;
 }
 

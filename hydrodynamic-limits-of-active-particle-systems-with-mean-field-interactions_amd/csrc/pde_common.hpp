@@ -2,7 +2,7 @@
 // system, include/pde.h) and pde_wide_hip.hip (one system over many workgroups, include/pde_wide.h).
 //
 // Host side: argument checks, the Thomas factorisation of the constant diffusion matrix with its Sherman-Morrison vector,
-// the normalised kernel taps, the Fourier twiddles, a device-buffer owner.  Device side: the Curie-Weiss rate, Philox4x32-10,
+// the normalised kernel taps, the Fourier twiddles.  Device side: the Curie-Weiss rate, Philox4x32-10,
 // the workgroup sum and the workgroup scan of affine maps.  One copy, so both shapes solve with the same numbers.
 #pragma once
 
@@ -92,22 +92,6 @@ inline void twiddles(int L, std::vector<double> &twc, std::vector<double> &tws) 
     twc.resize(L); tws.resize(L);
     for (int j = 0; j < L; ++j) { const double ang = 6.283185307179586476925 * (double)j / (double)L; twc[j] = std::cos(ang); tws[j] = std::sin(ang); }
 }
-
-struct DevBuf {            // frees everything it allocated when it goes out of scope
-    std::vector<void *> ptrs;
-    ~DevBuf() { for (void *q : ptrs) (void)hipFree(q); }
-    template <typename T> T *alloc(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-        ptrs.push_back(q);
-        return static_cast<T *>(q);
-    }
-    template <typename T> T *upload(const T *src, size_t n) {
-        T *q = alloc<T>(n);
-        if (q && n && hipMemcpy(q, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return q;
-    }
-};
 
 // -------------------------------------------------------------------------------------------------------------- device
 

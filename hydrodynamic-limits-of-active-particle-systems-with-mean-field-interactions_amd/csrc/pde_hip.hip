@@ -29,6 +29,7 @@
 
 #include "pde.h"
 #include "pde_common.hpp"                 // factorisation, taps, rate, Philox, workgroup sum and scan: shared with pde_wide_hip.hip
+#include "dev_mem.hpp"                    // buffer owner, event pair, the driver of the one-shot entry points
 
 namespace {
 
@@ -273,10 +274,8 @@ int pde_solve_batch(const pde_params *p, int32_t n_systems, const double *beta, 
                     double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
     auto bad = [&](const char *m) { g_err = std::string("pde_solve_batch: ") + m; return PDE_ERR_ARG; };
     if (const char *why = check_args(p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, fft_re, fft_im)) return bad(why);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_err = "pde_solve_batch: no HIP device"; return PDE_ERR_NODEVICE; }
-    if (p->device < 0 || p->device >= ndev) return bad("device ordinal out of range");
-    if (hipSetDevice(p->device) != hipSuccess) { g_err = "hipSetDevice failed"; return PDE_ERR_HIP; }
+    OneShot job{"pde_solve_batch", g_err, false, PDE_ERR_NODEVICE, PDE_ERR_ARG, PDE_ERR_HIP};   // no zero-fill: the kernel writes every output in full
+    if (int rc = job.select_device(p->device)) return rc;
 
     const int L = p->L, ntr = p->n_tracers, ns = p->nsteps + 1;
     const double dx = p->xlim / L;
@@ -290,59 +289,40 @@ int pde_solve_batch(const pde_params *p, int32_t n_systems, const double *beta, 
     std::vector<double> twc, tws;
     twiddles(L, twc, tws);
 
-    DevBuf d;
     PdeArgs a{};
     a.p = *p; a.dx = dx; a.sm_coef = sm_coef; a.sm_denom = sm_denom; a.ktaps = ktaps;
     a.chunk = (L + NT - 1) / NT; a.n_snap = p->nsteps / p->snapshot_interval + 1;
     const size_t SL = (size_t)n_systems * L, SN = (size_t)n_systems * ns, ST = (size_t)n_systems * ntr;
-#define UP(dst, src, n) do { a.dst = d.upload(src, n); if (!a.dst) { g_err = "pde_solve_batch: device upload failed (" #dst ")"; return PDE_ERR_HIP; } } while (0)
-#define OUT(dst, host, n) do { if (host) { a.dst = d.alloc<std::remove_pointer<decltype(a.dst)>::type>(n); if (!a.dst) { g_err = "pde_solve_batch: device allocation failed (" #dst ")"; return PDE_ERR_HIP; } } } while (0)
     UP(beta, beta, (size_t)n_systems); UP(rho_p0, rho_p0, SL); UP(rho_m0, rho_m0, SL);
     UP(fw, fw.data(), (size_t)L); UP(finv, finv.data(), (size_t)L); UP(fu, up.data(), (size_t)L); UP(fz, fz.data(), (size_t)L);
     UP(ktab, ktab.data(), ktab.size()); UP(twc, twc.data(), (size_t)L); UP(tws, tws.data(), (size_t)L);
     if (ntr) {
         UP(tracer_x0, tracer_x0, ST); UP(tracer_s0, tracer_s0, ST);
         if (rand_u) { UP(rand_u, rand_u, SN * ntr); UP(rand_n, rand_n, SN * ntr); }
-        a.hist = d.alloc<double>((size_t)n_systems * p->window * ntr);
-        a.trx = d.alloc<double>(ST); a.trs = d.alloc<int8_t>(ST);
-        if (!a.hist || !a.trx || !a.trs) { g_err = "pde_solve_batch: device allocation failed (tracers)"; return PDE_ERR_HIP; }
+        WORK(hist, (size_t)n_systems * p->window * ntr); WORK(trx, ST); WORK(trs, ST);
     }
     OUT(rho_p, rho_p, SL); OUT(rho_m, rho_m, SL); OUT(m_series, m_series, SN); OUT(var_series, var_series, SN);
     OUT(v_eff, v_eff_series, SN); OUT(D_eff, D_eff_series, SN);
     OUT(snapshots, snapshots, (size_t)n_systems * a.n_snap * L); OUT(m_snapshots, m_snapshots, (size_t)n_systems * a.n_snap * L);
     OUT(fft_re, fft_re, SN * p->n_fft_modes); OUT(fft_im, fft_im, SN * p->n_fft_modes);
     OUT(tracer_x, tracer_x, ST); OUT(tracer_s, tracer_s, ST);
-#undef UP
-#undef OUT
     size_t lds = (size_t)((5 * L + ((ktaps + 2) & ~1) + NT + 3) & ~3) * sizeof(double) + (size_t)2 * NT * sizeof(double4);
     if (lds > 160 * 1024) {                                    // beyond LDS: the fields live in global memory, the scans' scratch in LDS
         a.work_stride = (long long)((5 * (size_t)L + ((ktaps + 2) & ~1) + 3) & ~(size_t)3);
-        a.work = d.alloc<double>((size_t)n_systems * (size_t)a.work_stride);
-        if (!a.work) { g_err = "pde_solve_batch: device allocation failed (work)"; return PDE_ERR_HIP; }
+        WORK(work, (size_t)n_systems * (size_t)a.work_stride);
         lds = (size_t)((NT + 3) & ~3) * sizeof(double) + (size_t)2 * NT * sizeof(double4);
     }
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&pde_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        g_err = "pde_solve_batch: cannot raise the dynamic LDS limit"; return PDE_ERR_HIP;
-    }
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { g_err = "hipEventCreate failed"; return PDE_ERR_HIP; }
-    (void)hipEventRecord(e0, nullptr);
+    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&pde_kernel), lds)) return rc;
+    if (int rc = job.create_events()) return rc;
+    job.ev.start();
     hipLaunchKernelGGL(pde_kernel, dim3((unsigned)n_systems), dim3(NT), lds, nullptr, a);
-    (void)hipEventRecord(e1, nullptr);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipDeviceSynchronize();
-    float ms = 0.f;
-    if (err == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (err != hipSuccess) { g_err = std::string("pde_kernel: ") + hipGetErrorString(err); return PDE_ERR_HIP; }
-    if (kernel_ms) *kernel_ms = ms;
-#define DOWN(host, dev, n) do { if (host && hipMemcpy(host, a.dev, (n), hipMemcpyDeviceToHost) != hipSuccess) { g_err = "pde_solve_batch: download failed (" #dev ")"; return PDE_ERR_HIP; } } while (0)
+    job.ev.stop();
+    if (int rc = job.finish(hipGetLastError(), "pde_kernel", kernel_ms)) return rc;
     DOWN(rho_p, rho_p, SL * 8); DOWN(rho_m, rho_m, SL * 8); DOWN(m_series, m_series, SN * 8); DOWN(var_series, var_series, SN * 8);
     DOWN(v_eff_series, v_eff, SN * 8); DOWN(D_eff_series, D_eff, SN * 8);
     DOWN(snapshots, snapshots, (size_t)n_systems * a.n_snap * L * 8); DOWN(m_snapshots, m_snapshots, (size_t)n_systems * a.n_snap * L * 8);
     DOWN(fft_re, fft_re, SN * p->n_fft_modes * 8); DOWN(fft_im, fft_im, SN * p->n_fft_modes * 8);
     DOWN(tracer_x, tracer_x, ST * 8); DOWN(tracer_s, tracer_s, ST);
-#undef DOWN
     return PDE_OK;
 }
 

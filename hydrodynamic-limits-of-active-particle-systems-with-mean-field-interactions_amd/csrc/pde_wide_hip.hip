@@ -39,6 +39,7 @@
 
 #include "pde_wide.h"
 #include "pde_common.hpp"
+#include "dev_mem.hpp"
 
 namespace {
 
@@ -516,25 +517,19 @@ int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const
     const int ktaps = kernel_taps(p, dx, ktab);
     Plan pl;
     if (const char *why = make_plan(p, n_systems, workgroups, ktaps, pl)) return bad(why);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_err = "pdew_solve: no HIP device"; return PDE_ERR_NODEVICE; }
-    if (p->device < 0 || p->device >= ndev) return bad("device ordinal out of range");
-    if (hipSetDevice(p->device) != hipSuccess) { g_err = "hipSetDevice failed"; return PDE_ERR_HIP; }
+    OneShot job{"pdew_solve", g_err, false, PDE_ERR_NODEVICE, PDE_ERR_ARG, PDE_ERR_HIP};   // no zero-fill: the kernels write every buffer before it is read
+    if (int rc = job.select_device(p->device)) return rc;
 
     Factor fac;                                                // the factorisation pde_solve_batch uses
     factorise(p, dx, fac);
     std::vector<double> twc, tws;
     twiddles(L, twc, tws);
 
-    DevBuf d;
     WArgs a{};
     a.p = *p; a.dx = dx; a.sm_coef = fac.sm_coef; a.sm_denom = fac.sm_denom; a.ktaps = ktaps;
     a.G = pl.G; a.q = pl.q; a.r = pl.r; a.n_snap = p->nsteps / p->snapshot_interval + 1;
     const int G = pl.G;
     const size_t S = (size_t)n_systems, SL = S * L, SN = S * ns, ST = S * ntr;
-#define UP(dst, src, n) do { a.dst = d.upload(src, n); if (!a.dst) { g_err = "pdew_solve: device upload failed (" #dst ")"; return PDE_ERR_HIP; } } while (0)
-#define OUT(dst, host, n) do { if (host) { a.dst = d.alloc<std::remove_pointer<decltype(a.dst)>::type>(n); if (!a.dst) { g_err = "pdew_solve: device allocation failed (" #dst ")"; return PDE_ERR_HIP; } } } while (0)
-#define WORK(dst, n) do { a.dst = d.alloc<std::remove_pointer<decltype(a.dst)>::type>(n); if (!a.dst) { g_err = "pdew_solve: device allocation failed (" #dst ")"; return PDE_ERR_HIP; } } while (0)
     UP(beta, beta, S); UP(rho_p0, rho_p0, SL); UP(rho_m0, rho_m0, SL);
     UP(fw, fac.fw.data(), (size_t)L); UP(finv, fac.finv.data(), (size_t)L); UP(fu, fac.up.data(), (size_t)L); UP(fz, fac.fz.data(), (size_t)L);
     UP(ktab, ktab.data(), ktab.size()); UP(twc, twc.data(), (size_t)L); UP(tws, tws.data(), (size_t)L);
@@ -550,18 +545,12 @@ int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const
     if (ntr) { OUT(v_eff, v_eff_series, SN); OUT(D_eff, D_eff_series, SN); }
     OUT(snapshots, snapshots, S * a.n_snap * L); OUT(m_snapshots, m_snapshots, S * a.n_snap * L);
     OUT(fft_re, fft_re, SN * p->n_fft_modes); OUT(fft_im, fft_im, SN * p->n_fft_modes);
-#undef UP
-#undef OUT
-#undef WORK
-    if (pl.lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&pdew_mag), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds) != hipSuccess) {
-        g_err = "pdew_solve: cannot raise the dynamic LDS limit"; return PDE_ERR_HIP;
-    }
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { g_err = "hipEventCreate failed"; return PDE_ERR_HIP; }
+    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&pdew_mag), pl.lds)) return rc;
+    if (int rc = job.create_events()) return rc;
     // the whole run is one chain of launches on the null stream: nothing here waits for the device until the end
     const dim3 grid((unsigned)G, (unsigned)n_systems), one(1, (unsigned)n_systems), tgrid((unsigned)((ntr + NT - 1) / NT), (unsigned)n_systems);
     const bool want_obs = a.m_series || a.var_series || a.fft_re || a.v_eff || a.D_eff;
-    (void)hipEventRecord(e0, nullptr);
+    job.ev.start();
     hipLaunchKernelGGL(pdew_renorm_fwd, grid, dim3(NT), 0, nullptr, a, 1);
     hipError_t err = hipGetLastError();
     for (int n = 0; n <= p->nsteps && err == hipSuccess; ++n) {
@@ -576,20 +565,12 @@ int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const
         }
         err = hipGetLastError();
     }
-    (void)hipEventRecord(e1, nullptr);
-    const hipError_t serr = hipDeviceSynchronize();
-    if (err == hipSuccess) err = serr;
-    float ms = 0.f;
-    if (err == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (err != hipSuccess) { g_err = std::string("pdew_solve: ") + hipGetErrorString(err); return PDE_ERR_HIP; }
-    if (kernel_ms) *kernel_ms = ms;
-#define DOWN(host, dev, n) do { if (host && hipMemcpy(host, a.dev, (n), hipMemcpyDeviceToHost) != hipSuccess) { g_err = "pdew_solve: download failed (" #dev ")"; return PDE_ERR_HIP; } } while (0)
+    job.ev.stop();
+    if (int rc = job.finish(err, "pdew_solve", kernel_ms)) return rc;
     DOWN(rho_p, rp, SL * 8); DOWN(rho_m, rm, SL * 8); DOWN(m_series, m_series, SN * 8); DOWN(var_series, var_series, SN * 8);
     if (ntr) { DOWN(v_eff_series, v_eff, SN * 8); DOWN(D_eff_series, D_eff, SN * 8); DOWN(tracer_x, trx, ST * 8); DOWN(tracer_s, trs, ST); }
     DOWN(snapshots, snapshots, S * a.n_snap * L * 8); DOWN(m_snapshots, m_snapshots, S * a.n_snap * L * 8);
     DOWN(fft_re, fft_re, SN * p->n_fft_modes * 8); DOWN(fft_im, fft_im, SN * p->n_fft_modes * 8);
-#undef DOWN
     return PDE_OK;
 }
 

@@ -134,3 +134,82 @@ def test_communicator_argument_and_ordering_errors(capi):
     finally:
         for h in (a, b, c, sharded):
             h.close()
+
+
+def test_device_memory_comes_back(capi):
+    """Ten create / set state / step / destroy cycles of a handle of every formulation, and ten calls of each one-shot entry
+    point, give the device its memory back: free memory afterwards is lower by at most `d_parent + S / 2`.  S = bytes of the
+    per-slot buffers every handle of this size allocates (computed below, 86 MB; a handle's other buffers come on top);
+    d_parent = the drop of this same body measured on the library as it was before a handle's memory had one owner.
+    Measured on an MI355X: d_parent = 0 bytes, and 0 bytes with the one owner (the runtime gives freed memory back at once)."""
+    import os
+    torch = pytest.importorskip("torch")                  # reads the device's free memory through the runtime the library shares
+    pde = importlib.import_module(PKG + ".pde")
+    gil = importlib.import_module(PKG + ".gillespie")
+    L, N, K = 500_000, 250_000, 1
+    d_parent = 0                                          # bytes, measured (see above)
+    npad = max(256, -(-N // 256) * 256)
+    S = npad * (4 + 4 + 1 + 4 + 4 * 192 // 64 + 16 * (8 + 8 + 4))    # src, orig, prop, sp8, plan (192 per 64-slot tile), accW / accS / occ (16 shares)
+    assert S >= 64 << 20
+    par = LatticeGasParams.from_kwargs(L=L, xlim=1.0, rate_diffusion=0.5, rate_active=4.0, beta=1.0, scale_rates=False,
+                                       local_kernel_sigma=0.002, site_capacity=K)
+    rng = np.random.default_rng(11)
+    pos = rng.choice(L, size=N, replace=False).astype(np.int32)
+    spin = rng.choice(np.array([1, -1], np.int8), size=N)
+    kw = dict(L=L, K=K, periodic=False, sigma_grid=par.sigma_grid, rate_diffusion=0.5, rate_active=4.0, beta=[1.0], dt=0.03, seed=2,
+              n_particles=N)
+
+    def cycle(method, fp32=False, ntt=None, world=1):
+        if ntt is not None:
+            os.environ["APS_NTT"] = ntt
+        try:
+            ranks = [capi.Handle(method=method, fp32=fp32, rank=r, world=world, halo_interval=int(world > 1), **kw) for r in range(world)]
+        finally:
+            os.environ.pop("APS_NTT", None)
+        try:
+            for h in ranks:
+                h.set_state(pos, spin)
+            if world == 1:
+                ranks[0].step(3)
+                ranks[0].observe()
+            else:
+                for _ in range(3):                         # two site ranges in one process: the halo goes from handle to handle
+                    for h in ranks:
+                        h.propose()
+                    ranks[0].halo_from(ranks[1])
+                    ranks[1].halo_from(ranks[0])
+                    for h in ranks:
+                        h.commit()
+            if ntt == "1":
+                assert ranks[0].ntt_info()["on"]
+        finally:
+            for h in ranks:
+                h.close()
+
+    def one_shots():
+        rho = np.full(256, 0.5)
+        pkw = dict(L=256, xlim=1.0, dt=5e-4, nsteps=4, gamma=2.33e-4, lam=0.6, betas=[0.5, 1.5], bc="periodic",
+                   active_model="bidirectional", gaussian_kernel=False, kernel_sigma=0.02, snapshot_interval=2, rho_p0=rho, rho_m0=rho)
+        pde.solve_batch_raw(**pkw)
+        pde.solve_batch_raw(workgroups=2, **pkw)
+        st = (np.arange(0, 64, 2, dtype=np.int32), np.ones(32, np.int8))
+        gkw = dict(L=64, K=1, periodic=True, sigma_grid=0.0, rate_diffusion=0.5, rate_active=1.0, times_obs=[0.0, 0.05], T=0.05)
+        gil.run_raw(betas=[0.5], states=[st], **gkw)
+        gil.run_large_raw(beta=0.5, state=st, **gkw)
+
+    variants = [dict(method="pairs"), dict(method="lattice"), dict(method="tiles"), dict(method="tiles", fp32=True, ntt="1"),
+                dict(method="tiles", world=2)]
+    torch.cuda.init()
+    cycle(method="tiles")                                  # warm-up: the runtime's own one-time allocations (code objects, queues)
+    one_shots()
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for v in variants:
+        for _ in range(10):
+            cycle(**v)
+    for _ in range(10):
+        one_shots()
+    torch.cuda.synchronize()
+    drop = free0 - torch.cuda.mem_get_info()[0]
+    print(f"device memory: drop {drop} bytes after the cycles, S = {S} bytes, bar = {d_parent + S // 2} bytes")
+    assert drop <= d_parent + S // 2

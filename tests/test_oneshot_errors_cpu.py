@@ -1,0 +1,75 @@
+"""CPU suite: the texts and codes the four one-shot entry points (pde_solve_batch, pdew_solve, gil_run_batch, gil_run_large)
+report on the paths that need no GPU.  They share one host-side driver (csrc/dev_mem.hpp); each keeps its own name in front
+of the message.  The literals below were recorded from the library as it was before the entry points shared that driver."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+
+PKG = "hydrodynamic-limits-of-active-particle-systems-with-mean-field-interactions_amd"
+ERR_ARG, ERR_NODEVICE = -1, -4
+
+PDE_KW = dict(xlim=1.0, dt=5e-4, nsteps=2, gamma=2.33e-4, lam=0.6, betas=[0.5], bc="periodic", active_model="bidirectional",
+              gaussian_kernel=False, kernel_sigma=0.02, snapshot_interval=1)
+GIL_KW = dict(K=1, periodic=True, sigma_grid=0.0, rate_diffusion=0.1, rate_active=1.0, times_obs=[0.0, 0.01], T=0.01, max_events=16)
+
+
+@pytest.fixture(scope="module")
+def mods():
+    capi = importlib.import_module(PKG + ".capi")
+    pde = importlib.import_module(PKG + ".pde")
+    gil = importlib.import_module(PKG + ".gillespie")
+    return capi, pde, gil, pde._lib(), gil._lib()
+
+
+def _pde(pde, L, workgroups):
+    rho = np.full(L, 0.5)
+    return lambda: pde.solve_batch_raw(L=L, rho_p0=rho, rho_m0=rho, workgroups=workgroups, **PDE_KW)
+
+
+def _gil_batch(gil, L):
+    return lambda: gil.run_raw(L=L, betas=[0.5], states=[(np.array([0]), np.array([1]))], **GIL_KW)
+
+
+def _gil_large(gil, L):
+    return lambda: gil.run_large_raw(L=L, beta=0.5, state=(np.array([0]), np.array([1])), **GIL_KW)
+
+
+def _expect(capi, call, last_error, code, text):
+    with pytest.raises(capi.ApsError) as exc:
+        call()
+    assert exc.value.code == code
+    assert last_error().decode() == text
+    assert str(exc.value) == f"libaps_hip error {code}: {text}"
+
+
+def test_null_required_pointer(mods):
+    capi, pde, gil, plib, glib = mods
+    ms = C.c_double()
+    assert plib.pde_solve_batch(None, 1, *[None] * 19, C.byref(ms)) == ERR_ARG
+    assert plib.pde_last_error() == b"pde_solve_batch: null argument or n_systems < 1"
+    assert plib.pdew_solve(None, 1, 1, *[None] * 19, C.byref(ms)) == ERR_ARG
+    assert plib.pdew_last_error() == b"pdew_solve: null argument or n_systems < 1"
+    assert glib.gil_run_batch(None, *[None] * 14, C.byref(ms)) == ERR_ARG
+    assert glib.gil_last_error() == b"gil_run_batch: null argument"
+    assert glib.gil_run_large(None, 0, *[None] * 12, C.byref(ms)) == ERR_ARG
+    assert glib.gil_large_last_error() == b"gil_run_large: null argument"
+
+
+def test_lattice_size_out_of_range(mods):
+    capi, pde, gil, plib, glib = mods
+    _expect(capi, _pde(pde, 2, None), plib.pde_last_error, ERR_ARG, "pde_solve_batch: L must be in [4, PDE_MAX_L]")
+    _expect(capi, _pde(pde, 2, 1), plib.pdew_last_error, ERR_ARG, "pdew_solve: L must be in [4, PDE_MAX_L]")
+    _expect(capi, _gil_batch(gil, 1), glib.gil_last_error, ERR_ARG, "gil_run_batch: L must be in [2, GIL_MAX_L]")
+    _expect(capi, _gil_large(gil, 1), glib.gil_large_last_error, ERR_ARG, "gil_run_large: L must be in [2, 2^25]")
+
+
+def test_valid_arguments_without_a_gpu(mods):
+    capi, pde, gil, plib, glib = mods
+    if capi.device_count() > 0:
+        pytest.skip("GPU present")
+    _expect(capi, _pde(pde, 256, None), plib.pde_last_error, ERR_NODEVICE, "pde_solve_batch: no HIP device")
+    _expect(capi, _pde(pde, 256, 1), plib.pdew_last_error, ERR_NODEVICE, "pdew_solve: no HIP device")
+    _expect(capi, _gil_batch(gil, 64), glib.gil_last_error, ERR_NODEVICE, "gil_run_batch: no HIP device")
+    _expect(capi, _gil_large(gil, 64), glib.gil_large_last_error, ERR_NODEVICE, "gil_run_large: no HIP device")
