@@ -132,6 +132,8 @@ def load():
         "aps_set_flip_table": (C.c_int, [vp, vp, i32]),
         "aps_ntt_info": (C.c_int, [vp, P(i32), P(i32), P(dbl), P(i64)]),
         "aps_ntt_launches": (C.c_int, [vp]),
+        "aps_ntt_plan": (C.c_int, [i32, i32, i32, i32, P(i32), P(i32), P(i32)]),
+        "aps_ntt_blocks": (C.c_int, [vp, P(i32), P(i32)]),
         "aps_tiles_info": (C.c_int, [vp, P(i32), P(i32), P(i32), P(i32)]),
     }
     lenient = os.environ.get("APS_LIB_LENIENT") == "1"     # tuning tools that load an older build of the library for A/B timing
@@ -320,10 +322,14 @@ class Handle:
         self._ck(self.lib.aps_set_flip_table(self._h, _ptr(tab), tab.shape[1] - 1))
 
     def ntt_info(self):
-        """dict(on, log2_m, prof_ms, prof_launches, launches): does this handle update the field by the exact convolution (aps_ntt_info)"""
+        """dict(on, log2_m, prof_ms, prof_launches, launches, blocks, block_sites): does this handle update the field by the exact
+        convolution (aps_ntt_info), and in how many blocks of how many sites (aps_ntt_blocks; log2_m is the block's transform)"""
         on, m, ms, n = C.c_int32(), C.c_int32(), C.c_double(), C.c_int64()
         self._ck(self.lib.aps_ntt_info(self._h, C.byref(on), C.byref(m), C.byref(ms), C.byref(n)))
-        return dict(on=bool(on.value), log2_m=m.value, prof_ms=ms.value, prof_launches=n.value, launches=int(self.lib.aps_ntt_launches(self._h)))
+        nb, bs = C.c_int32(), C.c_int32()
+        self._ck(self.lib.aps_ntt_blocks(self._h, C.byref(nb), C.byref(bs)))
+        return dict(on=bool(on.value), log2_m=m.value, prof_ms=ms.value, prof_launches=n.value, launches=int(self.lib.aps_ntt_launches(self._h)),
+                    blocks=nb.value, block_sites=bs.value)
 
     def tiles_info(self):
         """dict(frame_sites, owned_sites, n_tiles, table_in_lds) of a tiles handle (aps_tiles_info)."""
@@ -475,6 +481,17 @@ class Handle:
 
 def device_count():
     return load().aps_device_count()
+
+
+def ntt_plan(L, Rt, primes, max_log2=21):
+    """dict(blocks, log2_m, block_sites): how a single handle of L sites whose table reaches Rt sites would run the exact convolution
+    (aps_ntt_plan; no GPU needed) -- primes 1: the 32-bit field, 2: the binary64 field.  blocks = 0: not eligible."""
+    lib = load()
+    nb, m, bs = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = lib.aps_ntt_plan(int(L), int(Rt), int(primes), int(max_log2), C.byref(nb), C.byref(m), C.byref(bs))
+    if rc != APS_OK:
+        raise ApsError(rc, lib.aps_last_error(None).decode())
+    return dict(blocks=nb.value, log2_m=m.value, block_sites=bs.value)
 
 
 def comm_unique_id() -> bytes:

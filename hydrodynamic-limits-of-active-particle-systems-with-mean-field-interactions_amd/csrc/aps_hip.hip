@@ -1507,8 +1507,8 @@ struct aps_handle {
     // the field update as an exact number-theoretic convolution (ntt_conv.hpp): 32-bit field, table beyond LDS, one rank, walls
     bool ntt_on = false, ntt_fused = false;
     NttPlan ntt{};
-    uint32_t *d_ntt_sig = nullptr, *d_ntt_tab = nullptr;       // [E][2][M] residues; all the tables in one allocation
-    int *d_ntt_csig = nullptr;                                 // [E][2][M] deposit coefficients of the step (index = site + Rt), cleared by the transform
+    uint32_t *d_ntt_sig = nullptr, *d_ntt_tab = nullptr;       // [primes][E][blocks][2][M] residues; all the tables in one allocation
+    int *d_ntt_csig = nullptr;                                 // [E][2][2^lc] deposit coefficients of the step (index = site + Rt), cleared by the transform
     double prof_ntt_ms = 0.0; int64_t prof_ntt_n = 0;          // last profiling run: the convolution's launches
     int *d_table_i = nullptr;
     int2 *d_wsi[2] = {nullptr, nullptr};
@@ -2000,7 +2000,7 @@ TileArgs tile_args(aps_handle *h, bool field_only) {
     TileArgs a{};
     const int par = (int)(h->step & 1), out = field_only ? par : par ^ 1;
     a.L = h->p.L; a.K = h->p.K; a.tlen = h->tlen; a.own = h->ts_own; a.ntile = h->ts_ntile; a.dcap = h->ts_dcap; a.par = par;
-    a.dense = h->ntt_on ? h->d_ntt_csig : nullptr; a.dense_rt = h->ntt.Rt; a.dense_m = h->ntt.m; a.periodic = h->p.periodic;
+    a.dense = h->ntt_on ? h->d_ntt_csig : nullptr; a.dense_rt = h->ntt.Rt; a.dense_m = h->ntt.lc; a.periodic = h->p.periodic;
     a.dense_org = h->ntt.org; a.dense_shard = h->world > 1 ? 1 : 0;
     a.dense_lo = h->world > 1 ? h->own_lo : 0; a.dense_hi = h->world > 1 ? h->own_hi : h->p.L;
     a.tile_lo = h->ts_lo; a.field_only = field_only ? 1 : 0; a.field_mode = h->model.field_mode; a.ens_base = h->model.ens_base; a.E = h->E;
@@ -2064,12 +2064,14 @@ int launch_tile_step(aps_handle *h, bool field_only = false) {
     return APS_OK;
 }
 
-// ---- the step's deposits -> W, S of every site by ONE exact convolution (ntt_conv.hpp): five launches behind the tile kernel
+// ---- the step's deposits -> W, S of every site by ONE exact convolution (ntt_conv.hpp): five launches behind the tile kernel;
+// a handle of several blocks (aps_ntt_plan) runs them all inside the same launches (grid z)
 int launch_ntt_conv(aps_handle *h) {
     const int out = (int)((h->step & 1) ^ 1);                   // the buffer the tile kernel of this step wrote
     const NttPlan &pl = h->ntt;
     const unsigned tiles = (unsigned)(((size_t)1 << pl.m) / NTT_TILE);
-    const dim3 grid_e(tiles, 2u, (unsigned)h->E), grid_p(tiles, 2u, (unsigned)(h->E * pl.np)), block(NTT_THREADS);   // y: the two signals; z: ensembles (x primes)
+    const dim3 grid_e(tiles, 2u, (unsigned)(h->E * pl.nb)), grid_p(tiles, 2u, (unsigned)(h->E * pl.np * pl.nb)), block(NTT_THREADS);   // y: the two signals; z: ensembles (x primes) x blocks
+    int *const clr = pl.nb > 1 ? h->d_ntt_csig : nullptr;       // blocks: the last sweep clears the coefficients (one block: the first, behind its read)
     void *ws = h->f32 ? (void *)h->d_wsi[out] : (void *)h->d_wsb[out];
     int rc;
     const bool timed = h->profiling && h->prof_dispatch;
@@ -2080,8 +2082,8 @@ int launch_ntt_conv(aps_handle *h) {
     if (h->ntt_fused) {                                         // i2 sweep, the whole middle in one launch, i2 sweep back
         NTT_ENDS(2, false, pl.a2, h->d_ntt_csig, nullptr);
         if ((rc = prof_mark(h, KIND_NTT))) return rc;
-        APS_K(h, ntt_mid, dim3(1u << pl.a2, 2u, (unsigned)(h->E * pl.np)), dim3(NTT_MID_THREADS), NTT_MID_LDS, pl, h->d_ntt_sig);
-        NTT_ENDS(2, true, pl.a2, (int *)nullptr, ws);
+        APS_K(h, ntt_mid, dim3(1u << pl.a2, 2u, (unsigned)(h->E * pl.np * pl.nb)), dim3(NTT_MID_THREADS), NTT_MID_LDS, pl, h->d_ntt_sig);
+        NTT_ENDS(2, true, pl.a2, clr, ws);
         HIP_TRY(h, hipGetLastError());
         h->field_pending = false;
         return APS_OK;
@@ -2094,8 +2096,8 @@ int launch_ntt_conv(aps_handle *h) {
     APS_K(h, (ntt_contig<false>), grid_p, block, 0, pl, h->d_ntt_sig);
     if (pl.a2 > 0) {
         NTT_STRIDED(1, true, 1, grid_p, pl.a1, (int *)nullptr, nullptr, 0);
-        NTT_ENDS(2, true, pl.a2, (int *)nullptr, ws);
-    } else NTT_ENDS(1, true, pl.a1, (int *)nullptr, ws);
+        NTT_ENDS(2, true, pl.a2, clr, ws);
+    } else NTT_ENDS(1, true, pl.a1, clr, ws);
 #undef NTT_ENDS
 #undef NTT_STRIDED
     HIP_TRY(h, hipGetLastError());
@@ -2112,7 +2114,7 @@ int run_ntt_conv(aps_handle *h) {
         h->field_dirty = true;
         h->field_pending = false;
         (void)hipGetLastError();
-        (void)hipMemsetAsync(h->d_ntt_csig, 0, (size_t)h->E * 2 * ((size_t)1 << h->ntt.m) * 4, h->stream);
+        (void)hipMemsetAsync(h->d_ntt_csig, 0, (size_t)h->E * 2 * ((size_t)1 << h->ntt.lc) * 4, h->stream);
         if (h->world > 1) for (int64_t &n : h->n_set) n = -1;
     }
     return rc;
@@ -2154,9 +2156,23 @@ int ntt_setup(aps_handle *h) {
         if (own_min < Rt + TD_HALO + 1 || (h->p.periodic && span > L)) return APS_OK;
     }
     const int np = h->f32 ? 1 : 2;                              // the binary64 field: two primes, put together by the last sweep
-    int m = shard && np == 2 ? 15 : 14;                         // (a site range of the binary64 field takes a longer window than it needs)
-    while (((int64_t)1 << m) < span) ++m;
-    if (m > 21 || (np == 2 && m < 15) || td_lds_bytes(h->p.K) > 160 * 1024) return APS_OK;
+    int m, nb = 1, bs = 0;
+    if (shard) {                                                // one window per rank (blocks inside a rank are not built)
+        m = ntt_min_log2(np);                                   // (a site range of the binary64 field takes a longer window than it needs)
+        while (((int64_t)1 << m) < span) ++m;
+        if (m > NTT_MAX_LOG2) return APS_OK;
+    } else {
+        // one handle: as many blocks as the lattice needs (ntt_plan_blocks); APS_NTT_MAX_LOG2=<14..21> shortens the block transform so
+        // that small lattices run as several blocks (tests, development)
+        int cap = NTT_MAX_LOG2;
+        if (const char *cenv = std::getenv("APS_NTT_MAX_LOG2")) { const int v = std::atoi(cenv); if (v >= 14 && v <= NTT_MAX_LOG2) cap = v; }
+        if (!ntt_plan_blocks(L, Rt, np, cap, nb, m, bs)) return APS_OK;
+        if ((int64_t)np * h->E * nb > 65535) return APS_OK;     // grid z of the launches
+        // several blocks are taken on request only (APS_NTT=1) until tools/time_blocked_convolution.py has been run on a device: their
+        // time against the windowed sweep is unmeasured, and an unmeasured path is not a default (Blocks)
+        if (nb > 1 && !forced) return APS_OK;
+    }
+    if (td_lds_bytes(h->p.K) > 160 * 1024) return APS_OK;
     if (td_lds_bytes(h->p.K) > 48 * 1024) {                     // frames of tile_dense with many cells per site
         const void *fn = h->f32 ? reinterpret_cast<const void *>(&tile_dense<false, true>) : reinterpret_cast<const void *>(&tile_dense<false, false>);
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)td_lds_bytes(h->p.K)) != hipSuccess) { (void)hipGetLastError(); return APS_OK; }
@@ -2171,6 +2187,9 @@ int ntt_setup(aps_handle *h) {
     pl.out_lo = shard ? h->own_lo - TD_HALO : 0;
     pl.out_hi = shard ? h->own_hi + TD_HALO : L;
     if (shard && !h->p.periodic) { pl.out_lo = std::max(pl.out_lo, 0); pl.out_hi = std::min(pl.out_hi, L); }
+    // blocks: every window [b bs, b bs + M) of the coefficient signals in bounds (the tail stays zero: the kernels need no bounds branch)
+    pl.nb = nb; pl.bs = nb > 1 ? bs : pl.out_hi - pl.out_lo; pl.lc = m;
+    if (nb > 1) while (((int64_t)1 << pl.lc) < (int64_t)(nb - 1) * bs + ((int64_t)1 << m)) ++pl.lc;
     pl.crt_inv = ntt_powmod(NTT_PRIMES[0] % NTT_PRIMES[1], NTT_PRIMES[1] - 2ull, NTT_PRIMES[1]);
     pl.unit = std::ldexp(1.0, -h->q);
     const size_t M = (size_t)1 << m;
@@ -2179,8 +2198,8 @@ int ntt_setup(aps_handle *h) {
     const size_t o_wr = 0, o_t1 = o_wr + T[0].wr.size(), o_hi = o_t1 + T[0].t1.size(), o_lo = o_hi + T[0].t2hi.size(), o_what = o_lo + T[0].t2lo.size(),
                  o_whatp = o_what + M, per_prime = o_whatp + M;
     int rc;
-    if ((rc = dev_alloc(h, &h->d_ntt_tab, per_prime * np)) || (rc = dev_alloc(h, &h->d_ntt_sig, (size_t)np * h->E * 2 * M)) ||
-        (rc = dev_alloc(h, &h->d_ntt_csig, (size_t)h->E * 2 * M))) return rc;
+    if ((rc = dev_alloc(h, &h->d_ntt_tab, per_prime * np)) || (rc = dev_alloc(h, &h->d_ntt_sig, (size_t)np * h->E * nb * 2 * M)) ||
+        (rc = dev_alloc(h, &h->d_ntt_csig, ((size_t)h->E * 2) << pl.lc))) return rc;
     for (int k = 0; k < np; ++k) {
         uint32_t *tb = h->d_ntt_tab + (size_t)k * per_prime;
         HIP_TRY(h, hipMemcpyAsync(tb + o_wr, T[k].wr.data(), T[k].wr.size() * 4, hipMemcpyHostToDevice, h->stream));
@@ -2202,7 +2221,7 @@ int ntt_setup(aps_handle *h) {
     // One signal per prime in the layout of a plan with one ensemble ([prime][1][W | S][M]: the S halves stay unused).
     {
         NttPlan ps = pl;
-        ps.E = 1;
+        ps.E = 1; ps.nb = 1;
         std::vector<uint32_t> wext((size_t)np * 2 * M, 0u);
         for (int k = 0; k < np; ++k)
             for (int t = 0; t < h->tlen; ++t) {
@@ -2235,7 +2254,7 @@ int ntt_setup(aps_handle *h) {
             }
         }
     }
-    HIP_TRY(h, hipMemsetAsync(h->d_ntt_sig, 0, (size_t)np * h->E * 2 * M * 4, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_ntt_sig, 0, (size_t)np * h->E * nb * 2 * M * 4, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     // {W, S} need no second buffer: the tile kernel only reads them and the last sweep of the convolution updates them in place
     if (h->d_wsi[1] != h->d_wsi[0]) { h->mem.release(h->d_wsi[1]); h->d_wsi[1] = h->d_wsi[0]; }
@@ -3341,6 +3360,24 @@ int aps_ntt_info(aps_handle *h, int32_t *on, int32_t *log2_m, double *prof_ms, i
     if (log2_m) *log2_m = h->ntt_on ? h->ntt.m : 0;
     if (prof_ms) *prof_ms = h->prof_ntt_ms;
     if (prof_launches) *prof_launches = h->prof_ntt_n;
+    return APS_OK;
+}
+int aps_ntt_plan(int32_t L, int32_t Rt, int32_t primes, int32_t max_log2, int32_t *blocks, int32_t *log2_m, int32_t *block_sites) {
+    if (L < 2 || L > (1 << 25) || Rt < 0 || (primes != 1 && primes != 2)) {
+        g_create_error = "aps_ntt_plan: 2 <= L <= 2^25, Rt >= 0, primes 1 or 2";
+        return APS_ERR_ARG;
+    }
+    int nb, m, bs;
+    ntt_plan_blocks(L, Rt, primes, max_log2, nb, m, bs);
+    if (blocks) *blocks = nb;
+    if (log2_m) *log2_m = m;
+    if (block_sites) *block_sites = bs;
+    return APS_OK;
+}
+int aps_ntt_blocks(aps_handle *h, int32_t *blocks, int32_t *block_sites) {
+    if (!h) return APS_ERR_ARG;
+    if (blocks) *blocks = h->ntt_on ? h->ntt.nb : 0;
+    if (block_sites) *block_sites = h->ntt_on ? h->ntt.bs : 0;
     return APS_OK;
 }
 int aps_ntt_launches(aps_handle *h) {

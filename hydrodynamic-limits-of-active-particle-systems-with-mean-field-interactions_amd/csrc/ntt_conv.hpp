@@ -19,6 +19,12 @@
 // Torus: the second entry is the same site one period on (p + L, p - L); the tap at distance L / 2 of an even ring counts once.
 // Site ranges (sharded handles): the signals live on the rank's window [lo - Rt - 2, hi + Rt + 2) (plan field `org`: its first
 // site), the rank's own deposits plus the neighbours' within reach (the halo); the last sweep writes [lo - 2, hi + 2) only.
+// Blocks (one handle, L + 2 Rt beyond one transform; aps_ntt_plan): the same overlap-save cut inside the handle.  The coefficients
+// stay ONE array per signal (index = site + Rt, 2^lc words); block b owns the sites [b bs, (b + 1) bs), transforms the window
+// [b bs, b bs + M) of that array (its sites +- Rt) and writes {W, S} of its own sites only.  All blocks share m, the tables and the
+// spectrum; the block index rides in blockIdx.z of every launch.  Neighbouring windows overlap by 2 Rt words, so the first sweep
+// must not clear what it read (another block of the same launch may still read it): with blocks the LAST sweep clears -- every
+// block the words of its own sites, the end blocks the margins as well.  One block: cleared behind the read, as ever.
 //
 // Transform: M = R2 R1 R0 (R0 = 128 along memory, R1, R2 <= 128), index i = i0 + R0 i1 + R0 R1 i2, frequency
 // k = k2 + R2 k1 + R2 R1 k0:  w^(ik) = w_R2^(i2 k2) . w^(R0 i1 k2) . w_R1^(i1 k1) . w^(i0 (k2 + R2 k1)) . w_R0^(i0 k0)
@@ -79,9 +85,11 @@ struct NttPlan {
     int org, out_lo, out_hi;               // signal index = site - org (one handle: org = -Rt); the last sweep writes {W, S} of the sites
                                            // [out_lo, out_hi) (one handle: [0, L); a site range: its own sites +- 2, taken mod L on a torus)
     int E, np;                             // ensembles; primes: 1 (32-bit field: int32 {W, S}) or 2 (binary64 field: double {W, S} = integers * unit)
+    int nb, bs, lc;                        // blocks; sites a block owns (one block: out_hi - out_lo): block b has org + b bs, writes [out_lo + b bs,
+                                           // min(out_hi, out_lo + (b + 1) bs)); coefficient signals of 2^lc words (one block: lc = m)
     uint32_t crt_inv;                      // P0^-1 mod P1
     double unit;                           // 2^-q of the binary64 field
-    NttPrime pr[2];                        // signals: [prime][ensemble][W | S][M] words
+    NttPrime pr[2];                        // signals: [prime][ensemble][block][W | S][M] words
 };
 
 // B butterfly levels on the 2^B values of one thread.  The values are rows  n + (t << lo_shift), t = 0 .. 2^B - 1, of a transform
@@ -138,10 +146,11 @@ __device__ __forceinline__ void ntt_lds_transform(double *buf, const int lg_nc, 
     }
 }
 __device__ __forceinline__ int ntt_bitrev(int v, int bits) { return (int)(__brev((unsigned)v) >> (32 - bits)); }
-// the site whose {W, S} signal word g changes, or -1: not one the plan writes
-__device__ __forceinline__ long long ntt_out_site(const NttPlan &pl, const size_t g) {
-    const long long s = (long long)g + pl.org;
-    if (s < pl.out_lo || s >= pl.out_hi) return -1;
+// the site whose {W, S} word g of block blk's signal changes, or -1: not one the block writes
+__device__ __forceinline__ long long ntt_out_site(const NttPlan &pl, const int blk, const size_t g) {
+    const int off = blk * pl.bs, lo = pl.out_lo + off, hi = min(pl.out_hi, lo + pl.bs);
+    const long long s = (long long)g + pl.org + off;
+    if (s < lo || s >= hi) return -1;
     return s < 0 ? s + pl.L : (s >= pl.L ? s - pl.L : s);
 }
 
@@ -149,8 +158,8 @@ __device__ __forceinline__ long long ntt_out_site(const NttPlan &pl, const size_
 // for all R = 2^A values of the axis digit, of one signal (blockIdx.y).
 // first forward sweep (INIT): the input are the deposit signals -- int32 coefficients, cleared behind the read -- instead of
 // residues; last inverse sweep (FINAL): the result is added to {W, S} of the sites.  Both take every prime of the plan in turn
-// (blockIdx.z = ensemble): the coefficients are read once, and the last sweep needs all residues of a word to put the integer
-// together; in between a launch covers the primes by blockIdx.z = prime * E + ensemble.
+// (blockIdx.z = ensemble * nb + block): the coefficients are read once, and the last sweep needs all residues of a word to put the
+// integer together; in between a launch covers the primes by blockIdx.z = (prime * E + ensemble) * nb + block.
 // AXIS 1: forward: multiply by w^(R0 i1 k2), transform over i1; inverse: transform, multiply by w^(-R0 i1 k2).
 // NP: primes of the plan (2 is only instantiated for the i2 sweeps: the binary64 field wants m >= 15)
 template <int AXIS, bool INV, int A, int NP>
@@ -167,15 +176,22 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_strided(const NttPlan pl, uin
     const size_t outer = blockIdx.x / per_outer, inner0 = (blockIdx.x % per_outer) * NC;
     const size_t base = outer * stride * R + inner0;             // word index of (axis digit 0, first column)
     const bool first = !INV && init_or_final, last = INV && init_or_final;
-    const int ens = (first || last) ? (int)blockIdx.z : (int)blockIdx.z % pl.E;
+    // (readfirstlane: a division by a kernel argument goes through the vector unit; its result is uniform all the same)
+    const int ze = __builtin_amdgcn_readfirstlane((int)blockIdx.z / pl.nb), blk = (int)blockIdx.z - ze * pl.nb;
+    const int zp = (first || last) ? 0 : __builtin_amdgcn_readfirstlane(ze / pl.E);
+    const int ens = ze - zp * pl.E;
     const int npr = (first || last) ? NP : 1;
+    // the block's window of the coefficient signal (first sweep: read; last sweep, nb > 1: the words this block clears)
+    int *const c0 = csig + (((size_t)ens * 2 + sgl) << pl.lc) + (size_t)blk * pl.bs;
+    const bool clear_first = pl.nb == 1;
+    const size_t clr_lo = last && !clear_first && blk > 0 ? (size_t)(pl.out_lo - pl.org) : 0;
+    const size_t clr_hi = !last || clear_first ? 0 : blk < pl.nb - 1 ? (size_t)(pl.out_lo - pl.org + pl.bs) : M;
     constexpr int ld = NC + 1;
     const int k2 = (int)outer;                                   // AXIS 1: the digit above (slot i2 holds k2)
     constexpr int NI = NTT_TILE / NTT_THREADS;                   // words per thread: all their loads are issued before the first is used
     int coef[NP > 1 ? NI : 1];                                   // INIT with two primes: the deposit coefficients, read once for both
     uint32_t res0[NP > 1 ? NI : 1];                              // FINAL with two primes: the residues mod the first one
     if (NP > 1 && first) {
-        int *c0 = csig + ((size_t)ens * 2 + sgl) * M;
 #pragma unroll
         for (int u = 0; u < NI; ++u) {
             const int w = t + u * NTT_THREADS, c = w & (NC - 1), r = w >> lg_nc;
@@ -184,15 +200,15 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_strided(const NttPlan pl, uin
 #pragma unroll
         for (int u = 0; u < NI; ++u) {                           // cleared for the next step
             const int w = t + u * NTT_THREADS, c = w & (NC - 1), r = w >> lg_nc;
-            if (coef[u]) c0[base + (size_t)r * stride + c] = 0;
+            if (clear_first && coef[u]) c0[base + (size_t)r * stride + c] = 0;
         }
     }
 #pragma unroll 1
     for (int q = 0; q < npr; ++q) {
-        const int pi = (first || last) ? q : (int)blockIdx.z / pl.E;
+        const int pi = (first || last) ? q : zp;
         const NttPrime pp = pi ? pl.pr[1] : pl.pr[0];            // (a select of scalars: indexing the argument would put the array into registers)
         const NttMod md = pp.md;
-        uint32_t *sig0 = data + (((size_t)pi * pl.E + ens) * 2 + sgl) * M;
+        uint32_t *sig0 = data + ((((size_t)pi * pl.E + ens) * pl.nb + blk) * 2 + sgl) * M;
         if (q) __syncthreads();                                  // everyone has read the previous prime's result out of LDS
         int tl = t;                                              // opaque per iteration: hoisted out of the loop, the 16 word addresses (and as many
         if (NP > 1) asm volatile("" : "+v"(tl));                 // LDS offsets) of a thread would stay in registers across both transforms
@@ -204,7 +220,7 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_strided(const NttPlan pl, uin
             for (int u = 0; u < NI; ++u) {
                 const int w = tl + u * NTT_THREADS, c = w & (NC - 1), r = w >> lg_nc;
                 const size_t g = base + (size_t)r * stride + c;
-                raw[u] = first ? (NP > 1 ? 0u : (uint32_t)csig[((size_t)ens * 2 + sgl) * M + g]) : sig0[g];
+                raw[u] = first ? (NP > 1 ? 0u : (uint32_t)c0[g]) : sig0[g];
                 twv[u] = (AXIS == 1 && !INV) ? pp.t1[(size_t)r * k2] : 1u;       // w^(R0 i1 k2), i1 = r
             }
 #pragma unroll
@@ -213,7 +229,7 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_strided(const NttPlan pl, uin
                 double v0;
                 if (first) {                                     // deposit coefficients: small signed integers
                     const int x0 = NP > 1 ? coef[u] : (int)raw[u];
-                    if (NP == 1 && x0) csig[((size_t)ens * 2 + sgl) * M + base + (size_t)r * stride + c] = 0;   // cleared for the next step
+                    if (NP == 1 && clear_first && x0) c0[base + (size_t)r * stride + c] = 0;   // cleared for the next step
                     v0 = (double)x0;
                 } else v0 = (double)raw[u];
                 if (AXIS == 1 && !INV) v0 = ntt_mul(v0, (double)twv[u], md);
@@ -233,7 +249,7 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_strided(const NttPlan pl, uin
             if constexpr (NP == 1) {
                 old_w[u] = 0;
                 if (combine) {
-                    const long long site = ntt_out_site(pl, base + (size_t)r * stride + c);
+                    const long long site = ntt_out_site(pl, blk, base + (size_t)r * stride + c);
                     if (site >= 0) old_w[u] = reinterpret_cast<const int *>(reinterpret_cast<const int2 *>(ws) + (size_t)ens * pl.L + site)[sgl];
                 }
             }
@@ -247,7 +263,7 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_strided(const NttPlan pl, uin
             const uint32_t v0 = (uint32_t)d0;
             if (!last) { sig0[g] = v0; continue; }
             // natural order again: word g is the change of W (or S) at site g + org
-            const long long site = ntt_out_site(pl, g);
+            const long long site = ntt_out_site(pl, blk, g);
             const uint32_t vc = ntt_canon(v0, pp.P);
             if (!combine) { if constexpr (NP > 1) res0[u] = vc; continue; }
             if (site < 0) continue;
@@ -264,6 +280,16 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_strided(const NttPlan pl, uin
                 if (xs) reinterpret_cast<double *>(reinterpret_cast<double2 *>(ws) + (size_t)ens * pl.L + site)[sgl] += (double)xs * pl.unit;   // (exact: both on the grid 2^-q)
             }
         }
+        if (combine && clr_hi) {                                 // blocks: the coefficients are cleared here, behind every block's read
+            int tc = t;                                          // (opaque: addresses of its own, nothing of this loop is kept in registers across the stores above)
+            asm volatile("" : "+v"(tc));
+#pragma unroll
+            for (int u = 0; u < NI; ++u) {
+                const int w = tc + u * NTT_THREADS, c = w & (NC - 1), r = w >> lg_nc;
+                const size_t g = base + (size_t)r * stride + c;
+                if (g >= clr_lo && g < clr_hi) c0[g] = 0;
+            }
+        }
     }
 }
 
@@ -278,7 +304,7 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_contig(const NttPlan pl, uint
     constexpr int A0 = 7, R0 = 1 << A0, lg_nr = 12 - A0, NR = 1 << lg_nr;   // rows per tile
     const size_t M = (size_t)1 << pl.m;
     const size_t row0 = (size_t)blockIdx.x * NR;                 // row = (i1-slot, i2-slot) = k1 + R1 k2
-    const NttPrime pp = (int)blockIdx.z >= pl.E ? pl.pr[1] : pl.pr[0];              // blockIdx.z = prime * E + ensemble: the signals are laid out in that order
+    const NttPrime pp = (int)blockIdx.z >= pl.E * pl.nb ? pl.pr[1] : pl.pr[0];      // blockIdx.z = (prime * E + ensemble) * nb + block: the signals are laid out in that order
     const NttMod md = pp.md;
     uint32_t *sig0 = data + ((size_t)blockIdx.z * 2 + sgl) * M;
     constexpr int ld = NR + 1;                                   // element (transform row i0, tile row r) at i0 * ld + r
@@ -396,7 +422,7 @@ __global__ __launch_bounds__(NTT_MID_THREADS) void ntt_mid(const NttPlan pl, uin
     const int n = __builtin_amdgcn_readfirstlane(t >> 7);        // 0 .. 7, the same for the 64 lanes of a wave
     const int sgl = blockIdx.y, k2 = blockIdx.x;
     const size_t M = (size_t)1 << pl.m;
-    const NttPrime pp = (int)blockIdx.z >= pl.E ? pl.pr[1] : pl.pr[0];              // blockIdx.z = prime * E + ensemble
+    const NttPrime pp = (int)blockIdx.z >= pl.E * pl.nb ? pl.pr[1] : pl.pr[0];      // blockIdx.z = (prime * E + ensemble) * nb + block
     const NttMod md = pp.md;
     uint32_t *const slab = data + ((size_t)blockIdx.z * 2 + sgl) * M + (size_t)k2 * NTT_MID_WORDS;
     const uint32_t *const wslab = pp.whatp + (size_t)k2 * NTT_MID_WORDS;
@@ -503,7 +529,26 @@ inline void ntt_launch_strided(int a, dim3 grid, dim3 block, hipStream_t stream,
 #undef NTT_CASE
 }
 
-// ---- host side: tables of a plan for one prime (everything mod P by 64-bit integer arithmetic)
+// ---- host side: the blocks of one handle (aps_ntt_plan; no device).  cap = min(max_log2, 21) bounds the transform; a block's window
+// is its sites +- Rt, and at most half a full-length window may be overlap (beyond that the sweep is kept).  B = ceil(L / (2^cap - 2 Rt))
+// blocks of S = ceil(L / B) sites (the last one shorter), m the smallest admissible with 2^m >= S + 2 Rt.  L + 2 Rt <= 2^cap: one block.
+constexpr int NTT_MAX_LOG2 = 21;
+inline int ntt_min_log2(int primes) { return primes == 2 ? 15 : 14; }      // (ntt_strided with two primes exists for the i2 sweeps only)
+inline bool ntt_plan_blocks(int64_t L, int64_t Rt, int primes, int max_log2, int &blocks, int &m, int &block_sites) {
+    blocks = 0; m = 0; block_sites = 0;
+    const int cap = std::min(max_log2, NTT_MAX_LOG2);
+    if (cap < ntt_min_log2(primes) || 4 * Rt > ((int64_t)1 << cap)) return false;
+    const int64_t usable = ((int64_t)1 << cap) - 2 * Rt;
+    int64_t B = (L + usable - 1) / usable;
+    const int64_t S = (L + B - 1) / B;
+    B = (L + S - 1) / S;                                     // (no empty block at the end)
+    m = ntt_min_log2(primes);
+    while (((int64_t)1 << m) < S + 2 * Rt) ++m;              // <= cap: S <= usable
+    blocks = (int)B; block_sites = (int)S;
+    return true;
+}
+
+// ---- tables of a plan for one prime (everything mod P by 64-bit integer arithmetic)
 struct NttTables { std::vector<uint32_t> wr, t1, t2hi, t2lo; };
 inline void ntt_split(int m, int &a0, int &a1, int &a2) { a0 = 7; a1 = std::min(7, m - 7); a2 = m - 7 - a1; }
 inline void ntt_build_tables(int m, uint32_t P, uint32_t G, NttTables &T) {

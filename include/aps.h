@@ -257,7 +257,7 @@ int aps_set_flip_table(aps_handle *h, const double *table, int32_t n);
 
 /* The field update as an exact convolution (csrc/ntt_conv.hpp): TILES handles (reflecting walls or torus) with a weight table
  * beyond LDS (BASELINE config 5) add a step's deposits to W, S by a number-theoretic transform of length
- * 2^log2_m >= L + 2 reach instead of gathering deposits x taps table entries -- exact integers, same bits as the sweep: mod
+ * 2^log2_m >= L + 2 reach (longer lattices: in blocks, see aps_ntt_plan) instead of gathering deposits x taps table entries -- exact integers, same bits as the sweep: mod
  * P0 = 15 * 2^27 + 1 for the 32-bit field (fp32), mod P0 and P1 = 27 * 2^26 + 1 with the Chinese remainder for the binary64 field.
  * on: whether this handle does (APS_NTT=0 keeps the sweep, APS_NTT=1 takes the convolution for tables that fit
  * LDS as well); prof_ms / prof_launches: summed duration and number of the convolution's launches in the last aps_step_profile.
@@ -265,6 +265,19 @@ int aps_set_flip_table(aps_handle *h, const double *table, int32_t n);
  * 2 (reach + 2), per rank; it takes the convolution when halo_interval is 0 or 1, every rank's range is at least reach + 3
  * sites and, on a torus, no window is longer than L. */
 int aps_ntt_info(aps_handle *h, int32_t *on, int32_t *log2_m, double *prof_ms, int64_t *prof_launches);
+/* Blocks of the convolution (one handle, world = 1).  A lattice whose L + 2 reach exceeds one transform (2^21 words) is cut into
+ * B blocks of consecutive sites; each block transforms its own sites +- reach (overlap-save: a convolution with a table of that
+ * reach is local) and writes {W, S} of its own sites only, all blocks inside the same launches -- same bits, any L the ABI allows.
+ * aps_ntt_plan is the rule, and touches no device: cap = min(max_log2, 21); B = ceil(L / (2^cap - 2 Rt)) blocks of
+ * block_sites = ceil(L / B) sites (the last one shorter, never empty); 2^log2_m >= block_sites + 2 Rt, log2_m >= 14 (one prime:
+ * the 32-bit field) or 15 (two primes: the binary64 field).  blocks = 0: not eligible -- more than half a full block would be
+ * overlap (2 Rt > 2^cap / 2), or cap below the shortest transform.  L + 2 Rt <= 2^cap gives one block.  APS_NTT_MAX_LOG2=<14..21>
+ * (default 21) is the max_log2 a handle plans with (tests and development: small lattices in several blocks).
+ * aps_ntt_blocks: what this handle runs (blocks = 0 when it does not take the convolution; its log2_m is that of aps_ntt_info,
+ * the block's).  Several blocks are taken with APS_NTT=1 only (their time against the sweep is not measured yet); one block is
+ * the default pick as before.  A site-sharded handle stays at one window per rank with log2_m <= 21 per rank. */
+int aps_ntt_plan(int32_t L, int32_t Rt, int32_t primes, int32_t max_log2, int32_t *blocks, int32_t *log2_m, int32_t *block_sites);
+int aps_ntt_blocks(aps_handle *h, int32_t *blocks, int32_t *block_sites);
 /* Launches per convolution: 3 when the transform has at least two 128 x 128 slabs (log2_m >= 15: sweep along the slab index, ONE
  * launch for everything inside a slab -- two sweeps, the product with the table's spectrum, two sweeps back -- in LDS, sweep back;
  * APS_NTT_FUSED=0 keeps them apart), 5 otherwise (3 at log2_m = 14, a single slab); 0 when the handle does not take the convolution. */
