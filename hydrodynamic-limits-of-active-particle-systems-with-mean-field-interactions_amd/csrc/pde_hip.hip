@@ -274,6 +274,7 @@ int pde_solve_batch(const pde_params *p, int32_t n_systems, const double *beta, 
                     double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
     auto bad = [&](const char *m) { g_err = std::string("pde_solve_batch: ") + m; return PDE_ERR_ARG; };
     if (const char *why = check_args(p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, fft_re, fft_im)) return bad(why);
+    if (p->convolution != 0) return bad("convolution must be 0 here: the spectral convolution belongs to the wide shape (pdew_solve, include/pde_wide.h)");
     OneShot job{"pde_solve_batch", g_err, false, PDE_ERR_NODEVICE, PDE_ERR_ARG, PDE_ERR_HIP};   // no zero-fill: the kernel writes every output in full
     if (int rc = job.select_device(p->device)) return rc;
 

@@ -28,23 +28,29 @@
 // the spare threads take a share of the tap range each and the shares are added in a fixed order.  Source window and
 // taps are staged through LDS in chunks of TB taps; window slots are padded by one per 8 so that lanes 8 sites apart hit
 // different banks.  fma() is explicit here (the build has -ffp-contract=off).
+// With pde_params.convolution = 1 the convolution is evaluated by the convolution theorem instead (pde_spectral.hpp): 3 or 5
+// launches in front of pdew_mag write the magnetisation field, and pdew_mag does the rest (sums, snapshots, Fourier partials).
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "pde_wide.h"
+#include "pde_spectral.h"
 #include "pde_common.hpp"
 #include "dev_mem.hpp"
 
 namespace {
 
 using namespace pde_common;
-std::string g_err;
+std::string g_err, g_spec_err;
+
+#include "pde_spectral.hpp"
 
 constexpr int R = 8;                    // consecutive sites per thread in the convolution
 constexpr int TB = 128;                 // taps per staged chunk, a multiple of R
@@ -57,6 +63,8 @@ struct WArgs {
     pde_params p;
     int G, q, r;                        // slab g: q + (g < r) sites from g * q + min(g, r)
     int n_snap, ktaps;
+    int spectral;                       // the kernel_mode 1 convolution comes from the transforms of pde_spectral.hpp (sp)
+    SpecPlan sp;
     double dx, sm_coef, sm_denom;
     const double *beta, *rho_p0, *rho_m0, *tracer_x0;
     const int8_t *tracer_s0;
@@ -271,6 +279,7 @@ __global__ __launch_bounds__(NT) void pdew_mag(const WArgs a, const int nstep) {
         const double s = combine(part + (size_t)P_SS * a.G, a.G, red), w = combine(part + (size_t)P_ST * a.G, a.G, red);
         const double m_global = s / (w + 1e-12);
         for (int i = a0 + t; i < a0 + n; i += NT) mf[i] = m_global;
+    } else if (a.spectral) {                                   // mf of every site was written by the transforms launched before this kernel
     } else {
         for (int sub0 = 0; sub0 < n; sub0 += SUB) {
             const int nsub = min(SUB, n - sub0), s0 = a0 + sub0;
@@ -456,11 +465,18 @@ __global__ __launch_bounds__(NT) void pdew_obs(const WArgs a, const int nstep) {
     }
 }
 
-struct Plan { int G, q, r, ktaps, launches; size_t lds; long long work_bytes; };
+struct Plan { int G, q, r, ktaps, launches; size_t lds; long long work_bytes; int spectral, conv_m, conv_B, conv_S; };
+
+// PDE_SPECTRAL_MAX_LOG2 of the environment bounds the transform of the spectral convolution (default and most: 21)
+int spectral_cap() {
+    const char *e = std::getenv("PDE_SPECTRAL_MAX_LOG2");
+    return e && *e ? std::atoi(e) : PDES_MAX_LOG2;
+}
 
 // the checks and choices shared by pdew_plan and pdew_solve; nullptr or the complaint
 const char *make_plan(const pde_params *p, int32_t n_systems, int32_t workgroups, int ktaps, Plan &pl) {
     if (n_systems > 65535) return "n_systems must be <= 65535";
+    if (p->convolution != 0 && p->convolution != 1) return "convolution must be 0 (direct) or 1 (spectral)";
     if (workgroups < 0) return "workgroups must be >= 1 (or 0: chosen by the library)";
     int G = workgroups;
     if (G == 0) {
@@ -479,6 +495,16 @@ const char *make_plan(const pde_params *p, int32_t n_systems, int32_t workgroups
                 if (nsub > 0) pl.lds = std::max(pl.lds, conv_lds_doubles(conv_shape(nsub, ktaps)) * sizeof(double));
     const long long S = n_systems, L = p->L, ntr = p->n_tracers;
     pl.work_bytes = 8 * (5 * S * L + S * NSLOT * G + S * 2 * p->n_fft_modes * G + 2 * S * G * 3 + 4 * S + S * p->window * ntr + S * ntr) + S * ntr;
+    pl.spectral = p->kernel_mode == 1 && p->convolution == 1;
+    pl.conv_m = pl.conv_B = pl.conv_S = 0;
+    if (pl.spectral) {                                         // no fall-back: a shape the transforms cannot take is refused
+        if (const char *why = pdes_plan_blocks(L, ktaps, spectral_cap(), pl.conv_B, pl.conv_m, pl.conv_S)) return why;
+        if ((long long)pl.conv_B * n_systems > 65535) return "spectral convolution: blocks * n_systems must be <= 65535";
+        const long long M = 1ll << pl.conv_m;
+        pl.launches += pdes_launches(pl.conv_m);
+        pl.lds = PDES_LDS_BYTES;
+        pl.work_bytes += 16 * S * pl.conv_B * M + 8 * M + 16 * (64 + std::max(M >> 10, 1ll) + 1024);   // windows, spectrum, tables
+    }
     return nullptr;
 }
 
@@ -487,6 +513,16 @@ const char *make_plan(const pde_params *p, int32_t n_systems, int32_t workgroups
 extern "C" {
 
 const char *pdew_last_error(void) { return g_err.c_str(); }
+const char *pdes_last_error(void) { return g_spec_err.c_str(); }
+
+int pdes_plan(int32_t L, int32_t ktaps, int32_t max_log2, int32_t *blocks, int32_t *log2_m, int32_t *block_sites) {
+    auto bad = [&](const char *m) { g_spec_err = std::string("pdes_plan: ") + m; return PDE_ERR_ARG; };
+    if (!blocks || !log2_m || !block_sites) return bad("null argument");
+    int B, m, S;
+    if (const char *why = pdes_plan_blocks(L, ktaps, max_log2, B, m, S)) return bad(why);
+    *blocks = B; *log2_m = m; *block_sites = S;
+    return PDE_OK;
+}
 
 int pdew_plan(const pde_params *p, int32_t n_systems, int32_t workgroups, pdew_plan_info *out) {
     auto bad = [&](const char *m) { g_err = std::string("pdew_plan: ") + m; return PDE_ERR_ARG; };
@@ -501,6 +537,7 @@ int pdew_plan(const pde_params *p, int32_t n_systems, int32_t workgroups, pdew_p
     std::memset(out, 0, sizeof *out);
     out->workgroups = pl.G; out->slab_len = pl.q + (pl.r ? 1 : 0); out->slab_len_min = pl.q; out->n_long_slabs = pl.r;
     out->ktaps = pl.ktaps; out->launches_per_step = pl.launches; out->lds_bytes = (int32_t)pl.lds; out->work_bytes = pl.work_bytes;
+    out->conv_log2 = pl.conv_m;
     return PDE_OK;
 }
 
@@ -536,6 +573,21 @@ int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const
     WORK(rp, SL); WORK(rm, SL); WORK(xp, SL); WORK(xm, SL); WORK(mf, SL);
     WORK(part, S * NSLOT * G); WORK(fmap, S * G * 3); WORK(bmap, S * G * 3); WORK(corner, S * 4);
     if (fft_re) WORK(fpart, S * 2 * (size_t)p->n_fft_modes * G);
+    a.spectral = pl.spectral;
+    double2 *taps_dev = nullptr;
+    double *spec_dev = nullptr;
+    if (pl.spectral) {
+        SpecTables tab;
+        pdes_build_tables(pl.conv_m, ktaps, ktab, tab);
+        const size_t M = (size_t)1 << pl.conv_m;
+        a.sp.m = pl.conv_m; pdes_split(pl.conv_m, a.sp.a1, a.sp.a2);
+        a.sp.L = L; a.sp.kt = ktaps; a.sp.S = pl.conv_S; a.sp.B = pl.conv_B;
+        UP(sp.w128, tab.w128.data(), tab.w128.size()); UP(sp.thi, tab.hi.data(), tab.hi.size()); UP(sp.tlo, tab.lo.data(), tab.lo.size());
+        WORK(sp.data, S * pl.conv_B * M);
+        if (int rc = job.upload(&taps_dev, tab.taps.data(), M, "taps")) return rc;
+        if (int rc = job.alloc(&spec_dev, M, "spec")) return rc;
+        a.sp.spec = spec_dev; a.sp.rp = a.rp; a.sp.rm = a.rm; a.sp.mf = a.mf;
+    }
     if (ntr) {
         UP(tracer_x0, tracer_x0, ST); UP(tracer_s0, tracer_s0, ST);
         if (rand_u) { UP(rand_u, rand_u, SN * ntr); UP(rand_n, rand_n, SN * ntr); }
@@ -545,16 +597,24 @@ int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const
     if (ntr) { OUT(v_eff, v_eff_series, SN); OUT(D_eff, D_eff_series, SN); }
     OUT(snapshots, snapshots, S * a.n_snap * L); OUT(m_snapshots, m_snapshots, S * a.n_snap * L);
     OUT(fft_re, fft_re, SN * p->n_fft_modes); OUT(fft_im, fft_im, SN * p->n_fft_modes);
-    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&pdew_mag), pl.lds)) return rc;
+    const size_t mag_lds = pl.spectral ? 0 : pl.lds;            // (spectral: pl.lds is the transforms' static LDS)
+    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&pdew_mag), mag_lds)) return rc;
     if (int rc = job.create_events()) return rc;
     // the whole run is one chain of launches on the null stream: nothing here waits for the device until the end
     const dim3 grid((unsigned)G, (unsigned)n_systems), one(1, (unsigned)n_systems), tgrid((unsigned)((ntr + NT - 1) / NT), (unsigned)n_systems);
     const bool want_obs = a.m_series || a.var_series || a.fft_re || a.v_eff || a.D_eff;
+    const unsigned nz = (unsigned)(n_systems * std::max(pl.conv_B, 1));
+    if (pl.spectral) {                                         // once per solve: the taps' spectrum by the device's own forward sweeps
+        SpecPlan one_block = a.sp;
+        one_block.B = 1; one_block.data = taps_dev;
+        pdes_build_spectrum(one_block, spec_dev);
+    }
     job.ev.start();
     hipLaunchKernelGGL(pdew_renorm_fwd, grid, dim3(NT), 0, nullptr, a, 1);
     hipError_t err = hipGetLastError();
     for (int n = 0; n <= p->nsteps && err == hipSuccess; ++n) {
-        hipLaunchKernelGGL(pdew_mag, grid, dim3(NT), pl.lds, nullptr, a, n);
+        if (pl.spectral) pdes_convolve(a.sp, nz);
+        hipLaunchKernelGGL(pdew_mag, grid, dim3(NT), mag_lds, nullptr, a, n);
         if (ntr) hipLaunchKernelGGL(pdew_tracers, tgrid, dim3(NT), 0, nullptr, a, n);
         if (want_obs) hipLaunchKernelGGL(pdew_obs, one, dim3(NT), 0, nullptr, a, n);
         if (n < p->nsteps) {

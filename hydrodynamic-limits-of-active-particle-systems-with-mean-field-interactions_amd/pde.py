@@ -9,16 +9,18 @@ one persistent HIP kernel per system behind the C ABI of include/pde.h; `solve_b
 Two execution shapes, one class.  `workgroups=None` (default): one workgroup per system (`pde_solve_batch`), right for
 sweeps of small grids.  `workgroups=G` or `"auto"`: the wide shape of include/pde_wide.h (`pdew_solve`), one system cut
 into G slabs on G workgroups, a time step a chain of kernel launches; right for one fine grid.  `plan()` tells what
-the wide shape would use.
+the wide shape would use.  On the wide shape `convolution="spectral"` evaluates the Gaussian-kernel magnetisation by complex
+binary64 transforms over overlap-save blocks (include/pde_spectral.h) instead of the direct sum; the default stays direct.
 
 Differences that are part of the design: tracer noise comes from Philox4x32-10 keyed by `seed` on the device (the
 reference draws from NumPy's global MT19937 inside the loop); the magnetisation kernel is applied by direct circular
-convolution instead of rfft products; no output directory is created; plotting methods are not reproduced.
+convolution instead of rfft products (unless convolution="spectral" is asked for); no output directory is created; plotting methods are not reproduced.
 There is no CPU fallback: without libaps_hip.so or without a GPU `solve()` raises.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -29,7 +31,8 @@ class PdeParams(C.Structure):
     """struct pde_params of include/pde.h, field for field."""
     _fields_ = [("L", C.c_int32), ("nsteps", C.c_int32), ("periodic", C.c_int32), ("anchored_minus", C.c_int32),
                 ("kernel_mode", C.c_int32), ("snapshot_interval", C.c_int32), ("n_tracers", C.c_int32),
-                ("window", C.c_int32), ("n_fft_modes", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("window", C.c_int32), ("n_fft_modes", C.c_int32), ("device", C.c_int32), ("convolution", C.c_int32),
+                ("reserved", C.c_int32),
                 ("xlim", C.c_double), ("dt", C.c_double), ("gamma", C.c_double), ("lam", C.c_double),
                 ("kernel_sigma", C.c_double), ("seed", C.c_uint64)]
 
@@ -37,7 +40,7 @@ class PdeParams(C.Structure):
 class PdewPlanInfo(C.Structure):
     """struct pdew_plan_info of include/pde_wide.h, field for field."""
     _fields_ = [("workgroups", C.c_int32), ("slab_len", C.c_int32), ("slab_len_min", C.c_int32), ("n_long_slabs", C.c_int32),
-                ("ktaps", C.c_int32), ("launches_per_step", C.c_int32), ("lds_bytes", C.c_int32), ("reserved", C.c_int32),
+                ("ktaps", C.c_int32), ("launches_per_step", C.c_int32), ("lds_bytes", C.c_int32), ("conv_log2", C.c_int32),
                 ("work_bytes", C.c_int64)]
 
 
@@ -56,6 +59,9 @@ def _lib():
         lib.pdew_solve.argtypes = [C.POINTER(PdeParams), C.c_int32, C.c_int32] + [vp] * 19 + [C.POINTER(C.c_double)]
         lib.pdew_plan.restype = C.c_int
         lib.pdew_plan.argtypes = [C.POINTER(PdeParams), C.c_int32, C.c_int32, C.POINTER(PdewPlanInfo)]
+        lib.pdes_last_error.restype, lib.pdes_last_error.argtypes = C.c_char_p, []
+        lib.pdes_plan.restype = C.c_int
+        lib.pdes_plan.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 3
         lib._pde_ready = True
     return lib
 
@@ -77,6 +83,28 @@ def _check_workgroups(workgroups):
     return int(workgroups)
 
 
+def _check_convolution(convolution, workgroups=0):
+    """None or "direct" -> 0, "spectral" -> 1 (the wide shape only: workgroups must not be None)."""
+    if convolution is None or (isinstance(convolution, str) and convolution == "direct"):
+        return 0
+    if not isinstance(convolution, str) or convolution != "spectral":
+        raise ValueError("convolution must be None, 'direct' or 'spectral'")
+    if workgroups is None:
+        raise ValueError("convolution='spectral' belongs to the wide shape: give workgroups ('auto' or an integer >= 1)")
+    return 1
+
+
+def spectral_plan(L, ktaps, max_log2=21):
+    """The overlap-save blocks of the spectral convolution (pdes_plan; no GPU is needed): dict with blocks, log2_m,
+    block_sites for a ring of L sites and a kernel reaching ktaps sites either side; ApsError when not eligible."""
+    lib = _lib()
+    b, m, s = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = lib.pdes_plan(int(L), int(ktaps), int(max_log2), C.byref(b), C.byref(m), C.byref(s))
+    if rc != 0:
+        raise capi.ApsError(rc, lib.pdes_last_error().decode())
+    return dict(blocks=b.value, log2_m=m.value, block_sites=s.value)
+
+
 def _check_fft_modes(fft_modes, L):
     if fft_modes is None:
         return None
@@ -86,7 +114,7 @@ def _check_fft_modes(fft_modes, L):
 
 
 def _params(*, L, xlim, dt, nsteps, gamma, lam, bc, active_model, gaussian_kernel, kernel_sigma, snapshot_interval, n_tracers,
-            n_fft_modes, seed, device):
+            n_fft_modes, seed, device, convolution=0):
     if not gaussian_kernel:
         mode = 0
     elif kernel_sigma > 100000:                                    # ref :161
@@ -96,43 +124,54 @@ def _params(*, L, xlim, dt, nsteps, gamma, lam, bc, active_model, gaussian_kerne
     window = int(0.05 / dt)                                        # ref :238-239
     return PdeParams(L=L, nsteps=nsteps, periodic=int(bc == "periodic"), anchored_minus=int(active_model != "bidirectional"),
                      kernel_mode=mode, snapshot_interval=snapshot_interval, n_tracers=n_tracers, window=max(window, 1),
-                     n_fft_modes=n_fft_modes, device=device, xlim=xlim, dt=dt, gamma=gamma, lam=lam,
+                     n_fft_modes=n_fft_modes, device=device, convolution=convolution, xlim=xlim, dt=dt, gamma=gamma, lam=lam,
                      kernel_sigma=kernel_sigma, seed=int(seed) & (2 ** 64 - 1))
 
 
 def plan(*, L, workgroups="auto", n_systems=1, xlim=1.0, dt=5e-4, T=None, nsteps=None, gamma=2.33e-4, lam=0.6, bc="periodic",
          active_model="bidirectional", gaussian_kernel=False, kernel_sigma=0.02, snapshot_interval=50, n_tracers=0,
-         fft_modes=0, device=0):
+         fft_modes=0, device=0, convolution=None):
     """What the wide shape would use for these parameters (pdew_plan; nothing is launched, no GPU is needed): dict with
     workgroups, slab_len / slab_len_min / n_long_slabs, slab_lengths (sums to L), ktaps, launches_per_step, lds_bytes,
-    work_bytes."""
+    work_bytes, and of the convolution: convolution ("direct" | "spectral"), conv_log2 (m; 0 when no transform runs),
+    conv_blocks, conv_block_sites (pdes_plan under PDE_SPECTRAL_MAX_LOG2 of the environment; 0 when no transform runs)."""
     lib = _lib()
     wg = _check_workgroups(workgroups)
+    conv = _check_convolution(convolution, wg)
     if wg is None:
         raise ValueError("plan() describes the wide shape: workgroups must be 'auto' or an integer >= 1")
     if nsteps is None:
         nsteps = int(T / dt) if T is not None else 0
     par = _params(L=L, xlim=xlim, dt=dt, nsteps=nsteps, gamma=gamma, lam=lam, bc=bc, active_model=active_model,
                   gaussian_kernel=gaussian_kernel, kernel_sigma=kernel_sigma, snapshot_interval=snapshot_interval,
-                  n_tracers=n_tracers, n_fft_modes=_check_fft_modes(fft_modes, L) or 0, seed=0, device=device)
+                  n_tracers=n_tracers, n_fft_modes=_check_fft_modes(fft_modes, L) or 0, seed=0, device=device, convolution=conv)
     info = PdewPlanInfo()
     rc = lib.pdew_plan(C.byref(par), n_systems, wg, C.byref(info))
     if rc != 0:
         raise capi.ApsError(rc, lib.pdew_last_error().decode())
-    out = {name: getattr(info, name) for name, _ in PdewPlanInfo._fields_ if name != "reserved"}
+    out = {name: getattr(info, name) for name, _ in PdewPlanInfo._fields_}
+    out["convolution"] = "spectral" if conv else "direct"
+    out["conv_blocks"] = out["conv_block_sites"] = 0
+    if info.conv_log2:
+        sp = spectral_plan(L, info.ktaps, int(os.environ.get("PDE_SPECTRAL_MAX_LOG2") or 21))
+        assert sp["log2_m"] == info.conv_log2
+        out["conv_blocks"], out["conv_block_sites"] = sp["blocks"], sp["block_sites"]
     out["slab_lengths"] = [info.slab_len] * info.n_long_slabs + [info.slab_len_min] * (info.workgroups - info.n_long_slabs)
     return out
 
 
 def solve_batch_raw(*, L, xlim, dt, nsteps, gamma, lam, betas, bc, active_model, gaussian_kernel, kernel_sigma,
                     snapshot_interval, rho_p0, rho_m0, tracer_x0=None, tracer_s0=None, rand_u=None, rand_n=None,
-                    n_fft_modes=0, seed=0, device=0, want_snapshots=True, workgroups=None, fft_modes=None):
+                    n_fft_modes=0, seed=0, device=0, want_snapshots=True, workgroups=None, fft_modes=None,
+                    convolution=None):
     """All systems of `betas` from their initial states to step nsteps on the GPU; dict of arrays with a leading
     system axis.  rand_u / rand_n [n_systems, nsteps+1, n_tracers] replace the device's Philox draws (tests).
     workgroups: None = one workgroup per system (pde_solve_batch); "auto" or an integer >= 1 = the wide shape with that
-    many slabs per system (pdew_solve).  fft_modes: when given, the number of lowest Fourier modes (replaces n_fft_modes)."""
+    many slabs per system (pdew_solve).  fft_modes: when given, the number of lowest Fourier modes (replaces n_fft_modes).
+    convolution: None / "direct" = the direct sum, "spectral" = transforms over overlap-save blocks (wide shape only)."""
     lib = _lib()
     wg = _check_workgroups(workgroups)
+    conv = _check_convolution(convolution, wg)
     fm = _check_fft_modes(fft_modes, L)
     if fm is not None:
         n_fft_modes = fm
@@ -149,7 +188,7 @@ def solve_batch_raw(*, L, xlim, dt, nsteps, gamma, lam, betas, bc, active_model,
         rand_n = np.ascontiguousarray(np.broadcast_to(rand_n, (S, nsteps + 1, ntr)), dtype=np.float64)
     par = _params(L=L, xlim=xlim, dt=dt, nsteps=nsteps, gamma=gamma, lam=lam, bc=bc, active_model=active_model,
                   gaussian_kernel=gaussian_kernel, kernel_sigma=kernel_sigma, snapshot_interval=snapshot_interval,
-                  n_tracers=ntr, n_fft_modes=n_fft_modes, seed=seed, device=device)
+                  n_tracers=ntr, n_fft_modes=n_fft_modes, seed=seed, device=device, convolution=conv)
     if bc not in ("periodic", "neumann"):
         raise ValueError("bc must be 'periodic' or 'neumann'")
     n_snap = nsteps // snapshot_interval + 1
@@ -186,7 +225,7 @@ class IMEXPDE:
                  active_model="bidirectional", gaussian_kernel=False, kernel_sigma=0.02, snapshot_interval=50,
                  outdir="IMEX_output", seed=None,
                  # extensions (optional, after the reference's keywords)
-                 device=0, record_fft=True, workgroups=None, fft_modes=None):
+                 device=0, record_fft=True, workgroups=None, fft_modes=None, convolution=None):
         self.L, self.xlim, self.dx = L, xlim, xlim / L
         self.x = np.linspace(0, xlim, L, endpoint=False)
         self.T, self.dt, self.nsteps = T, dt, int(T / dt)
@@ -200,7 +239,9 @@ class IMEXPDE:
             raise ValueError(f"L <= {PDE_MAX_L}")
         _check_workgroups(workgroups)
         _check_fft_modes(fft_modes, L)
+        _check_convolution(convolution, workgroups)
         self.workgroups, self.fft_modes = workgroups, fft_modes    # None: one workgroup per system; record_fft decides the modes
+        self.convolution = convolution                             # None: the direct sum
         if seed is not None:
             np.random.seed(seed)                                   # ref :55-56
         self.rho_mean = 1.0 / self.xlim
@@ -238,7 +279,8 @@ class IMEXPDE:
                                snapshot_interval=self.snapshot_interval, rho_p0=rho_p0, rho_m0=rho_m0, tracer_x0=tx0,
                                tracer_s0=ts0, rand_u=rand_u, rand_n=rand_n,
                                n_fft_modes=self.L // 2 + 1 if self.record_fft else 0, seed=seed, device=self.device,
-                               want_snapshots=want_snapshots, workgroups=self.workgroups, fft_modes=self.fft_modes)
+                               want_snapshots=want_snapshots, workgroups=self.workgroups, fft_modes=self.fft_modes,
+                               convolution=self.convolution)
 
     def solve(self, rand_u=None, rand_n=None):                     # ref :236-290, on the GPU
         r = self._run([self.beta], self.rho_p, self.rho_m, self.tracers_unwrapped if self.n_tracers else None,
@@ -264,29 +306,32 @@ class IMEXPDE:
             self.tracer_state = r["tracer_state"][s].astype(int)
         self.kernel_ms = r["kernel_ms"]
 
-    def plan(self, n_systems=1):
-        """What the wide shape would use for this solver (see `plan`); with workgroups=None, what "auto" would."""
+    def plan(self, n_systems=1, convolution=None):
+        """What the wide shape would use for this solver (see `plan`); with workgroups=None, what "auto" would.
+        convolution given here overrides the constructor's."""
         return plan(L=self.L, workgroups=self.workgroups if self.workgroups is not None else "auto", n_systems=n_systems,
                     xlim=self.xlim, dt=self.dt, nsteps=self.nsteps, gamma=self.gamma, lam=self.lam, bc=self.bc,
                     active_model=self.active_model, gaussian_kernel=self.gaussian_kernel, kernel_sigma=self.kernel_sigma,
                     snapshot_interval=self.snapshot_interval, n_tracers=getattr(self, "n_tracers", 0),
                     fft_modes=self.fft_modes if self.fft_modes is not None else (self.L // 2 + 1 if self.record_fft else 0),
-                    device=self.device)
+                    device=self.device, convolution=convolution if convolution is not None else self.convolution)
 
-    def solve_batch(self, betas, want_snapshots=False, workgroups=None, fft_modes=None):
+    def solve_batch(self, betas, want_snapshots=False, workgroups=None, fft_modes=None, convolution=None):
         """The same initial condition evolved for every beta of `betas` in ONE launch (one workgroup per beta, or
-        `workgroups` slabs per beta on the wide shape; independent tracer noise per system).  workgroups / fft_modes
-        given here override the constructor's.  Returns the raw dict of arrays with a leading system axis."""
-        if workgroups is not None or fft_modes is not None:
+        `workgroups` slabs per beta on the wide shape; independent tracer noise per system).  workgroups / fft_modes /
+        convolution given here override the constructor's.  Returns the raw dict of arrays with a leading system axis."""
+        if workgroups is not None or fft_modes is not None or convolution is not None:
             _check_workgroups(workgroups)
             _check_fft_modes(fft_modes, self.L)
-            keep = self.workgroups, self.fft_modes
+            keep = self.workgroups, self.fft_modes, self.convolution
+            _check_convolution(convolution, workgroups if workgroups is not None else keep[0])
             self.workgroups = workgroups if workgroups is not None else keep[0]
             self.fft_modes = fft_modes if fft_modes is not None else keep[1]
+            self.convolution = convolution if convolution is not None else keep[2]
             try:
                 return self.solve_batch(betas, want_snapshots=want_snapshots)
             finally:
-                self.workgroups, self.fft_modes = keep
+                self.workgroups, self.fft_modes, self.convolution = keep
         return self._run(betas, self.rho_p, self.rho_m, self.tracers_unwrapped if self.n_tracers else None,
                          self.tracer_state if self.n_tracers else None, want_snapshots=want_snapshots)
 
@@ -306,19 +351,20 @@ class IMEXPDE:
 
 
 def sweep_over_betas(beta_values, n_runs=3, t_min=20.0, t_max=40.0, seeds=None, init_kwargs=None, workgroups=None, fft_modes=None,
-                     **ctor_kwargs):
+                     convolution=None, **ctor_kwargs):
     """The reference's PDE tracer sweep (IMEX_PDE_solver_run_sweep.py:7-75) as ONE launch: every (beta, run) pair is a
     system with its own seeded initial condition.  Returns (v_mean, v_err, D_mean, D_err) per beta exactly as the
     driver forms them: v = |nanmean(v_eff_series[t_min <= t <= t_max])|, D = nanmean(D_eff_series[...]), mean over runs,
     err = std(ddof=1) / sqrt(n_runs).  workgroups selects the execution shape as in `IMEXPDE`; fft_modes > 0 adds the
-    Fourier modes of every system to the work (the sweep itself does not use them)."""
+    Fourier modes of every system to the work (the sweep itself does not use them); convolution as in `IMEXPDE`."""
     init_kwargs = dict(init_kwargs or {})
     betas, rp, rm, tx, ts = [], [], [], [], []
     proto = None
     for bi, beta in enumerate(beta_values):
         for run in range(n_runs):
             seed = run if seeds is None else seeds[bi][run]         # the reference seeds each run with its run index
-            s = IMEXPDE(beta=beta, seed=seed, record_fft=False, workgroups=workgroups, fft_modes=fft_modes, **ctor_kwargs)
+            s = IMEXPDE(beta=beta, seed=seed, record_fft=False, workgroups=workgroups, fft_modes=fft_modes, convolution=convolution,
+                        **ctor_kwargs)
             s.initialize(**init_kwargs)
             proto = proto or s
             betas.append(float(beta)); rp.append(s.rho_p); rm.append(s.rho_m); tx.append(s.tracers_unwrapped); ts.append(s.tracer_state)
@@ -326,7 +372,8 @@ def sweep_over_betas(beta_values, n_runs=3, t_min=20.0, t_max=40.0, seeds=None, 
                         bc=proto.bc, active_model=proto.active_model, gaussian_kernel=proto.gaussian_kernel,
                         kernel_sigma=proto.kernel_sigma, snapshot_interval=proto.snapshot_interval, rho_p0=np.array(rp),
                         rho_m0=np.array(rm), tracer_x0=np.array(tx), tracer_s0=np.array(ts), seed=proto.seed or 0,
-                        device=proto.device, want_snapshots=False, workgroups=workgroups, fft_modes=fft_modes)
+                        device=proto.device, want_snapshots=False, workgroups=workgroups, fft_modes=fft_modes,
+                        convolution=convolution)
     t = np.linspace(0, proto.T, proto.nsteps + 1)
     mask = (t >= t_min) & (t <= t_max)
     v = np.abs(np.nanmean(r["v_eff_series"][:, mask], axis=1)).reshape(len(beta_values), n_runs)

@@ -36,7 +36,8 @@ typedef struct pde_params {
     int32_t window;             /* int(0.05 / dt): steps of the v_eff / D_eff window      ref :238-239 */
     int32_t n_fft_modes;        /* lowest rfft modes of the total density recorded per step (0: none)  ref :249-251 */
     int32_t device;
-    int32_t reserved[2];
+    int32_t convolution;        /* kernel_mode 1 on the wide shape (include/pde_wide.h): 0 direct sum, 1 spectral (include/pde_spectral.h); pde_solve_batch takes 0 only */
+    int32_t reserved;
     double xlim, dt, gamma, lam, kernel_sigma;
     uint64_t seed;              /* Philox key of the tracer noise when no random numbers are supplied */
 } pde_params;

@@ -32,20 +32,23 @@ typedef struct pdew_plan_info {
     int32_t n_long_slabs;       /* L % G: the first so many slabs have slab_len sites, the others slab_len_min (all, when 0) */
     int32_t ktaps;              /* reach of the Gaussian kernel in sites (0 unless kernel_mode == 1) */
     int32_t launches_per_step;  /* kernel launches enqueued per time step */
-    int32_t lds_bytes;          /* dynamic LDS of the magnetisation kernel */
-    int32_t reserved;
+    int32_t lds_bytes;          /* direct: dynamic LDS of the magnetisation kernel; spectral: LDS of a transform kernel */
+    int32_t conv_log2;          /* m: the spectral convolution transforms 2^m words per block (0 when no transform runs) */
     int64_t work_bytes;         /* global working memory: fields, per-slab partials and maps, tracer ring (not inputs / outputs) */
 } pdew_plan_info;
 
 const char *pdew_last_error(void);
 
 /* What pdew_solve would use for these parameters: no device is touched, nothing is launched.
- * workgroups = 0 lets the library choose. */
+ * workgroups = 0 lets the library choose.  p->convolution: 0 or 1; launches_per_step, lds_bytes and work_bytes describe the
+ * chosen path. */
 int pdew_plan(const pde_params *p, int32_t n_systems, int32_t workgroups, pdew_plan_info *out);
 
 /* pde_solve_batch on the wide shape.  The buffer arguments are those of pde_solve_batch, in the same order, with the same
  * meaning.  workgroups = G per system (0: the library chooses); 1 <= G <= PDEW_MAX_WORKGROUPS, floor(L / G) >= PDEW_MIN_SLAB,
- * G * n_systems <= PDEW_MAX_GRID, n_systems <= 65535. */
+ * G * n_systems <= PDEW_MAX_GRID, n_systems <= 65535.
+ * p->convolution (used with kernel_mode 1 only): 0 = direct circular convolution, 1 = spectral (include/pde_spectral.h); a shape
+ * the spectral path cannot take fails with PDE_ERR_ARG and a text that says why -- there is no fall-back to the direct sum. */
 int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const double *beta, const double *rho_p0,
                const double *rho_m0, const double *tracer_x0, const int8_t *tracer_s0, const double *rand_u, const double *rand_n,
                double *rho_p, double *rho_m, double *m_series, double *var_series, double *v_eff_series,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """BASELINE config 5: the particle system at N ~ 1e6 against the hydrodynamic-limit PDE on the same domain, both on the GPU.
 
-    python tools/compare_hydrodynamic.py [--L 2000000] [--L-pde 1000] [--pde-workgroups auto|G] [--T 1.0] [--beta 0.7] [--json out.json]
+    python tools/compare_hydrodynamic.py [--L 2000000] [--L-pde 1000] [--pde-workgroups auto|G] [--pde-convolution direct|spectral] [--T 1.0] [--beta 0.7] [--json out.json]
 
 Particles: L sites on [0, 1), K = 1, reflecting walls, sigma = 0.005, rate_active = 5, rate_diffusion = 0.02 (lattice units,
 scale_rates=False as in every BASELINE configuration), fixed dt = 0.0125, tiles formulation.  Initial condition: a site is
@@ -82,9 +82,9 @@ class _Ranks:
 
 
 def compare(L=2_000_000, L_pde=1000, T=1.0, beta=0.7, sigma=0.005, rate_active=5.0, rate_diffusion=0.02, dt=0.0125,
-            dt_pde=5e-4, seed=0, n_obs=4, device=0, fp32=False, world=1, pde_workgroups=None):
+            dt_pde=5e-4, seed=0, n_obs=4, device=0, fp32=False, world=1, pde_workgroups=None, pde_convolution=None):
     """pde_workgroups: None = the PDE on one workgroup (right for L_pde ~ 1000); "auto" or G = its wide shape, one grid over many
-    workgroups (for a fine L_pde).  fp32: the 32-bit field of aps_params.fp32 (BASELINE config 5 says float32); world: site-range shards (it says 8 GPUs)."""
+    workgroups (for a fine L_pde); pde_convolution: "spectral" = its kernel convolution by transforms (wide shape only).  fp32: the 32-bit field of aps_params.fp32 (BASELINE config 5 says float32); world: site-range shards (it says 8 GPUs)."""
     capi = importlib.import_module(PKG + ".capi")
     pde = importlib.import_module(PKG + ".pde")
     assert L % L_pde == 0
@@ -100,7 +100,8 @@ def compare(L=2_000_000, L_pde=1000, T=1.0, beta=0.7, sigma=0.005, rate_active=5
         # ---- PDE from the particles' coarse-grained initial densities
         s = pde.IMEXPDE(L=L_pde, xlim=1.0, T=T + 0.5 * dt_pde, dt=dt_pde, gamma=rate_diffusion * dx * dx, lam=rate_active * dx, beta=beta,
                         bc="neumann", active_model="anchored_minus", gaussian_kernel=True, kernel_sigma=sigma,
-                        snapshot_interval=max(1, int(round(T / dt_pde / n_obs))), seed=1, record_fft=False, workgroups=pde_workgroups)
+                        snapshot_interval=max(1, int(round(T / dt_pde / n_obs))), seed=1, record_fft=False, workgroups=pde_workgroups,
+                        convolution=pde_convolution)
         s.initialize(mode="homogeneous", rho0=1.0, noise=0.0, n_tracers=16)
         s.rho_p, s.rho_m = cp0 / float(N), cm0 / float(N)
         t0 = time.perf_counter()
@@ -132,7 +133,7 @@ def compare(L=2_000_000, L_pde=1000, T=1.0, beta=0.7, sigma=0.005, rate_active=5
                 site_range_shards=world, particles_per_cell=per_cell,
                 sampling_noise_m=float(1.0 / np.sqrt(per_cell)), gamma_convention="gamma = rate_diffusion * dx^2 (lattice walk: D = r dx^2)",
                 lam=rate_active * dx, gamma=rate_diffusion * dx * dx, caveat="the PDE has no exclusion term; transport is negligible on the PDE grid at this L",
-                pde_workgroups=pde_workgroups, wall_s_particles=t_part, wall_s_pde=t_pde, rows=rows)
+                pde_workgroups=pde_workgroups, pde_convolution=pde_convolution or "direct", wall_s_particles=t_part, wall_s_pde=t_pde, rows=rows)
 
 
 if __name__ == "__main__":
@@ -140,6 +141,8 @@ if __name__ == "__main__":
     ap.add_argument("--L", type=int, default=2_000_000)
     ap.add_argument("--L-pde", type=int, default=1000)
     ap.add_argument("--pde-workgroups", default=None, help="the PDE's wide shape: 'auto' or slabs per system (default: one workgroup)")
+    ap.add_argument("--pde-convolution", default=None, choices=["direct", "spectral"],
+                    help="the PDE's kernel convolution: the direct sum (default) or transforms over overlap-save blocks (needs --pde-workgroups)")
     ap.add_argument("--T", type=float, default=1.0)
     ap.add_argument("--beta", type=float, default=0.7)
     ap.add_argument("--json", default="")
@@ -147,7 +150,7 @@ if __name__ == "__main__":
     ap.add_argument("--world", type=int, default=1, help="site-range shards emulated on one device (BASELINE config 5: 8)")
     a = ap.parse_args()
     wg = a.pde_workgroups if a.pde_workgroups in (None, "auto") else int(a.pde_workgroups)
-    res = compare(L=a.L, L_pde=a.L_pde, T=a.T, beta=a.beta, fp32=a.fp32, world=a.world, pde_workgroups=wg)
+    res = compare(L=a.L, L_pde=a.L_pde, T=a.T, beta=a.beta, fp32=a.fp32, world=a.world, pde_workgroups=wg, pde_convolution=a.pde_convolution)
     print(json.dumps(res, indent=1))
     if a.json:
         with open(a.json, "w") as fh:
