@@ -1,10 +1,12 @@
-// gillespie_big_hip.hip -- gil_run_large of include/gillespie.h: the reference's exact event loop
-// (PARTICLE_solver_CLASS.py:511-538) for ONE system far too large for a workgroup's LDS (the BASELINE size:
+// gillespie_big_hip.hip -- gil_run_large of include/gillespie.h and gilm_run of include/gillespie_many.h: the reference's
+// exact event loop (PARTICLE_solver_CLASS.py:511-538) for systems far too large for a workgroup's LDS (the BASELINE size:
 // N = 1e5 particles on L = 2e5 sites, where the reference manages 0.8 events/s because it recomputes the whole
-// field and all N rates before every event).
+// field and all N rates before every event).  One kernel and one host driver serve both entry points: a batch is a grid
+// of independent workgroups, gil_run_large is the batch of one.
 //
-// One persistent workgroup of 1024 threads; the state lives in global memory (L2-resident), only the weight table
-// and small work areas in LDS.  What makes an event cheap:
+// One persistent workgroup of 1024 threads per system (blockIdx.x; no workgroup waits on another, so a batch larger
+// than the device simply queues); the state lives in global memory (L2-resident), every per-system array in slices of
+// one system's length, only the weight table and small work areas in LDS.  What makes an event cheap:
 //   * the smoothed histograms W, S are kept incrementally (exact weight grid) -- an event changes them on
 //     the sites within the table's reach of one or two sites;
 //   * a site -> particle map (K slots per site) finds the particles whose rates that changes without scanning all N;
@@ -23,6 +25,7 @@
 #include <vector>
 
 #include "gillespie.h"
+#include "gillespie_many.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"
 
@@ -32,30 +35,60 @@ constexpr int BT = 1024, BW = BT / 64;      // threads, waves of the workgroup
 constexpr int PB = 256;                     // particles per rate block
 constexpr int MAX_NB = 4096;                // rate blocks (N <= 2^20)
 constexpr int TAB_LDS_MAX = 10000;          // table entries kept in LDS
-std::string g_big_err;
+constexpr int64_t MAX_BYTES = 1ll << 38;    // work + output bytes a plan accepts without asking a device
+std::string g_big_err, g_many_err;
 enum { F_PLUS = 1, F_BOUND = 2, F_ALIVE = 4 };
+enum { GS_N = 0, GS_SPIN, GS_POS, GS_WALL, GS_MAXPOS, GS_FRONT, GS_ATTEMPT, GS_BLOCKED, GS_DISP, GS_DISP2, GS_NDISP, GS_EVENTS };
 
 struct BigArgs {
     Model m;
     gil_params p;
     int tlen, n_init, nblk, cb, tab_in_lds;
-    double beta;
-    const double *table, *times, *uniforms;
-    const uint8_t *anchor;
+    double beta;                                             // n_init, beta: of the workgroup's system (select_system)
+    const double *table, *times, *uniforms, *betas;          // shared: table, times, anchor, front_lo, block_table
+    const uint8_t *anchor, *block_table;
+    const int32_t *front_lo, *n0;
     const int32_t *pos0; const int8_t *sigma0; const uint8_t *bound0;
-    // global scratch
-    int *pos, *occ, *occp, *slot, *work;
+    // global scratch, [n_systems] slices
+    int *pos, *occ, *occp, *slot, *work, *ref;
     uint8_t *flg;
     double *rate, *bsum, *W, *S;
-    // outputs
-    int32_t *pos_obs; int8_t *sigma_obs; uint8_t *flags_obs;
+    // outputs, [n_systems] slices
+    int32_t *pos_obs; int8_t *sigma_obs; uint8_t *flags_obs; long long *scalars;
     int32_t *n_recorded; long long *n_events; double *t_final, *exits; int32_t *n_exits;
 };
 
-// W, S from scratch on all sites (one-time): a thread per site over all particles
-__global__ __launch_bounds__(256) void big_field_init(const BigArgs a) {
+// Narrows a copy of the arguments to system `sys` (uniform over the workgroup, so the slices' addresses stay in scalar
+// registers): the code below indexes one system.  Philox key = seed + sys, i.e. system s of a batch draws what a
+// single run with seed + s draws.
+__device__ inline void select_system(BigArgs &a, size_t sys) {
+    const size_t N = (size_t)a.p.n_cap, L = (size_t)a.m.L, O = (size_t)a.p.n_obs;
+    a.n_init = a.n0[sys]; a.beta = a.betas[sys];
+    const unsigned long long key = (((unsigned long long)a.m.seed_hi << 32) | a.m.seed_lo) + sys;
+    a.m.seed_lo = (uint32_t)key; a.m.seed_hi = (uint32_t)(key >> 32);
+    a.pos0 += sys * N; a.sigma0 += sys * N;
+    if (a.bound0) a.bound0 += sys * N;
+    if (a.uniforms) a.uniforms += sys * (size_t)a.p.max_events * 4;
+    a.pos += sys * N; a.work += sys * N; a.ref += sys * N; a.flg += sys * N; a.rate += sys * N;
+    a.occ += sys * L; a.occp += sys * L; a.W += sys * L; a.S += sys * L;
+    a.slot += sys * L * (size_t)a.m.K; a.bsum += sys * (size_t)a.nblk;
+    if (a.pos_obs) a.pos_obs += sys * O * N;
+    if (a.sigma_obs) a.sigma_obs += sys * O * N;
+    if (a.flags_obs) a.flags_obs += sys * O * N;
+    if (a.scalars) a.scalars += sys * O * GIL_NSCALARS;
+    if (a.exits) a.exits += sys * N * 3;
+    if (a.n_recorded) a.n_recorded += sys;
+    if (a.n_events) a.n_events += sys;
+    if (a.t_final) a.t_final += sys;
+    if (a.n_exits) a.n_exits += sys;
+}
+
+// W, S from scratch on all sites (one-time): a thread per site over all particles; the system in grid.y
+__global__ __launch_bounds__(256) void big_field_init(const BigArgs a0) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= a.m.L) return;
+    if (x >= a0.m.L) return;
+    BigArgs a = a0;
+    select_system(a, (size_t)blockIdx.y);
     double w = 0.0, s = 0.0;
     if (a.m.field_mode)
         for (int j = 0; j < a.n_init; ++j) {
@@ -103,20 +136,82 @@ __device__ inline double block_scan_inclusive(double v, double *xw) {
     return inc + before;
 }
 
-__global__ __launch_bounds__(BT) void gil_big_kernel(const BigArgs a) {
+// Adds this wavefront's sum of v to *dst (LDS): one atomic per wavefront
+__device__ inline void wave_add_ll(long long v, long long *dst) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0 && v != 0) atomicAdd(reinterpret_cast<unsigned long long *>(dst), (unsigned long long)v);
+}
+
+// The twelve sums of gil_run_batch (gillespie_hip.hip, record) over one system's particles at an observation: integers, so
+// the order of summation is free.  `acc` = GIL_NSCALARS words of LDS.  A particle index belongs to the same thread in
+// both passes, also where `ref` is written: no barrier is needed for `ref`.
+__device__ inline void big_scalar_sums(const int *pos, const uint8_t *flg, int *ref, const int *occ, const int *occp,
+                                       const uint8_t *block_table, const int32_t *front_lo, long long *out, long long *acc,
+                                       int N, int L, int K, bool set_ref, int x_wall, long long n_ev) {
+    const int t = threadIdx.x;
+    if (t < GIL_NSCALARS) acc[t] = t == GS_MAXPOS ? -1 : (t == GS_EVENTS ? n_ev : 0);
+    __syncthreads();
+    {
+        long long v_n = 0, v_spin = 0, v_pos = 0, v_wall = 0;
+        int v_max = -1;
+#pragma unroll 1
+        for (int i = t; i < N; i += BT) {
+            const uint8_t f = flg[i];
+            const int p = pos[i];
+            if (set_ref) ref[i] = (f & F_ALIVE) ? p : -1;
+            if (!(f & F_ALIVE)) continue;
+            v_n += 1; v_spin += (f & F_PLUS) ? 1 : -1; v_pos += p; v_wall += p >= x_wall;
+            v_max = max(v_max, p);
+        }
+        wave_add_ll(v_n, acc + GS_N); wave_add_ll(v_spin, acc + GS_SPIN); wave_add_ll(v_pos, acc + GS_POS); wave_add_ll(v_wall, acc + GS_WALL);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v_max = max(v_max, __shfl_xor(v_max, off));
+        if ((t & 63) == 0) atomicMax(acc + GS_MAXPOS, (long long)v_max);
+    }
+    __syncthreads();
+    {
+        const long long mx = acc[GS_MAXPOS];
+        const int lo = (front_lo && mx >= 0) ? front_lo[mx] : L;   // no window: no site counts
+        long long v_front = 0, v_att = 0, v_blk = 0, v_d = 0, v_d2 = 0, v_nd = 0;
+#pragma unroll 1
+        for (int i = t; i < N; i += BT) {
+            const uint8_t f = flg[i];
+            if (!(f & F_ALIVE)) continue;
+            const int p = pos[i], r0 = ref[i];
+            v_front += p >= lo;
+            if ((f & F_PLUS) && p < L - 1) {                   // plus movers, and whether the right neighbour blocks them
+                v_att += 1;
+                const int cp = occp[p + 1], cm = occ[p + 1] - cp;
+                v_blk += block_table ? block_table[cp * (K + 1) + cm] : (cp + cm >= 1);
+            }
+            if (r0 >= 0) { const long long d = (long long)p - r0; v_d += d; v_d2 += d * d; v_nd += 1; }
+        }
+        wave_add_ll(v_front, acc + GS_FRONT); wave_add_ll(v_att, acc + GS_ATTEMPT); wave_add_ll(v_blk, acc + GS_BLOCKED);
+        wave_add_ll(v_d, acc + GS_DISP); wave_add_ll(v_d2, acc + GS_DISP2); wave_add_ll(v_nd, acc + GS_NDISP);
+    }
+    __syncthreads();
+    if (t < GIL_NSCALARS) out[t] = acc[t];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(BT) void gil_big_kernel(const BigArgs a0) {
     extern __shared__ double lds[];
+    BigArgs a = a0;
+    select_system(a, (size_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x));
     const Model &M = a.m;
     const int L = M.L, K = M.K, t = threadIdx.x, lane = t & 63, wave = t >> 6, nobs = a.p.n_obs, N = a.p.n_cap;
     double *tabl = lds;                                        // [tlen + 1] when it fits
     double *xw = tabl + (a.tab_in_lds ? ((a.tlen + 2) & ~1) : 0);   // [32] cross-wave scratch
     double *draws = xw + 32;                                   // [BT][4]
     double *dsel = draws + 4 * BT;                             // [4] cumulative rate before the chosen block etc.
-    int *bflag = reinterpret_cast<int *>(dsel + 4);            // [MAX_NB] block needs re-summing
-    int *blist = bflag + MAX_NB;                               // [MAX_NB] list of those blocks
-    int *ctl = blist + MAX_NB;                                 // [32]
+    long long *acc = reinterpret_cast<long long *>(dsel + 4);  // [GIL_NSCALARS] the scalar sums of an observation
+    int *bflag = reinterpret_cast<int *>(acc + GIL_NSCALARS);  // [nblk] block needs re-summing
+    int *blist = bflag + a.nblk;                               // [nblk] list of those blocks
+    int *ctl = blist + a.nblk;                                 // [32]
     const double *tab = a.tab_in_lds ? tabl : a.table;
     if (a.tab_in_lds) for (int i = t; i <= a.tlen; i += BT) tabl[i] = a.table[i];
-    for (int j = t; j < MAX_NB; j += BT) bflag[j] = 0;
+    for (int j = t; j < a.nblk; j += BT) bflag[j] = 0;
     // ---- load the system: particles, occupancy, site -> particle map
     for (int x = t; x < L; x += BT) { a.occ[x] = 0; a.occp[x] = 0; }
     for (size_t q = t; q < (size_t)L * K; q += BT) a.slot[q] = -1;
@@ -126,7 +221,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const BigArgs a) {
         const bool live = i < a.n_init;
         const int p = live ? a.pos0[i] : 0;
         const uint8_t f = live ? (uint8_t)(F_ALIVE | (a.sigma0[i] > 0 ? F_PLUS : 0) | ((a.bound0 && a.bound0[i]) ? F_BOUND : 0)) : 0;
-        a.pos[i] = p; a.flg[i] = f; a.rate[i] = 0.0;
+        a.pos[i] = p; a.flg[i] = f; a.rate[i] = 0.0; a.ref[i] = -1;
         if (live) {
             a.slot[(size_t)p * K + atomicAdd(&a.occ[p], 1)] = i;
             if (f & F_PLUS) atomicAdd(&a.occp[p], 1);
@@ -158,14 +253,18 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const BigArgs a) {
     long long n_ev = 0, ev_base = 0;
     int k_obs = 0, n_exit = 0;
 
-    auto record = [&](int k) {                                 // state at observation k (ref :517-524)
+    auto record = [&](int k) {                                 // observation k: state and scalar sums (ref :517-536)
         const size_t o = (size_t)k * N;
-        for (int i = t; i < N; i += BT) {
-            const uint8_t f = a.flg[i];
-            if (a.pos_obs) a.pos_obs[o + i] = a.pos[i];
-            if (a.sigma_obs) a.sigma_obs[o + i] = (f & F_PLUS) ? 1 : -1;
-            if (a.flags_obs) a.flags_obs[o + i] = (uint8_t)(((f & F_BOUND) ? 1 : 0) | ((f & F_ALIVE) ? 2 : 0));
-        }
+        if (a.pos_obs || a.sigma_obs || a.flags_obs)
+            for (int i = t; i < N; i += BT) {
+                const uint8_t f = a.flg[i];
+                if (a.pos_obs) a.pos_obs[o + i] = a.pos[i];
+                if (a.sigma_obs) a.sigma_obs[o + i] = (f & F_PLUS) ? 1 : -1;
+                if (a.flags_obs) a.flags_obs[o + i] = (uint8_t)(((f & F_BOUND) ? 1 : 0) | ((f & F_ALIVE) ? 2 : 0));
+            }
+        if (a.scalars)
+            big_scalar_sums(a.pos, a.flg, a.ref, a.occ, a.occp, a.block_table, a.front_lo, a.scalars + (size_t)k * GIL_NSCALARS,
+                            acc, N, L, K, k == a.p.ref_obs, a.p.x_wall, n_ev);
     };
     record(0);
     k_obs = 1;
@@ -428,7 +527,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const BigArgs a) {
         n_ev += 1;
         tnow += tau;
         if (tnow > a.p.T) break;
-        while (k_obs < nobs && t_next <= tnow) { record(k_obs); ++k_obs; t_next = k_obs < nobs ? a.times[k_obs] : INFINITY; }
+        while (__builtin_expect(k_obs < nobs && t_next <= tnow, 0)) { record(k_obs); ++k_obs; t_next = k_obs < nobs ? a.times[k_obs] : INFINITY; }
     }
 #ifdef APS_STAMPS
     if (t == 0 && a.exits) for (int k = 0; k < 12; ++k) a.exits[k] = (double)st[k];   // diagnostic build only
@@ -441,6 +540,91 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const BigArgs a) {
     }
 }
 
+// What a batch of p->n_systems large systems needs, by host arithmetic alone (gilm_plan); the weight table comes back
+// through `table` where the caller wants it.  0, or e_arg with the text in `err`.
+int big_plan(const char *who, std::string &err, const gil_params *p, bool want_states, bool want_scalars, gilm_plan_info *out,
+             std::vector<double> *table) {
+    auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    if (p->L < 2 || p->L > (1 << 25)) return bad("L must be in [2, 2^25]");
+    if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
+    if ((int64_t)p->L * p->K > (1ll << 27)) return bad("L * K must not exceed 2^27 (site map)");
+    if (p->n_cap < 1 || p->n_cap > MAX_NB * PB || p->n_obs < 1 || p->max_events < 0) return bad("bad n_cap / n0 / n_obs / max_events");
+    std::vector<double> tab; int tlen = 0, q = 0;
+    weight_table(p->sigma_grid, p->L, p->K, p->periodic != 0, tab, tlen, q);
+    const int64_t S = p->n_systems, L = p->L, N = p->n_cap, O = p->n_obs, nblk = (N + PB - 1) / PB;
+    gilm_plan_info info{};
+    info.n_systems = p->n_systems; info.n_blocks = (int32_t)nblk; info.table_len = tlen;
+    info.table_in_lds = tlen + 1 <= TAB_LDS_MAX ? 1 : 0;
+    info.lds_bytes = (int32_t)(((int64_t)(info.table_in_lds ? ((tlen + 2) & ~1) : 0) + 32 + 4 * BT + 4 + GIL_NSCALARS) * 8 + (2 * nblk + 32) * 4);
+    // pos, work, ref (int), flg (byte), rate (double) per slot; occ, occp (int), W, S (double) per site; the site map; the block sums
+    info.work_bytes_per_system = N * (4 + 4 + 4 + 1 + 8) + L * (4 + 4 + 8 + 8) + L * p->K * 4 + nblk * 8;
+    // states: pos (int) + sigma + flags per slot and observation; scalars; exits; n_recorded, n_events, t_final, n_exits
+    info.output_bytes = (want_states ? S * O * N * 6 : 0) + (want_scalars ? S * O * GIL_NSCALARS * 8 : 0) + S * N * 24 + S * 24;
+    if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
+    if (S * info.work_bytes_per_system + info.output_bytes > MAX_BYTES)
+        return bad("the batch needs " + std::to_string(S * info.work_bytes_per_system) + " bytes of work memory and " +
+                   std::to_string(info.output_bytes) + " bytes of outputs, more than the " + std::to_string(MAX_BYTES) + " bytes a plan accepts");
+    if (out) *out = info;
+    if (table) *table = std::move(tab);
+    return GIL_OK;
+}
+
+// The one host driver of the large-system kernel: S = p->n_systems systems, one workgroup each.  The callers have checked
+// their required pointers and S.  pos0 / sigma0 / bound0 hold [S][n_cap] entries (a single system: its n0[0] particles).
+int big_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
+            const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+            int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
+    auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    gilm_plan_info info{};
+    std::vector<double> table;
+    if (int rc = big_plan(who, err, p, pos_obs || sigma_obs || flags_obs, scalars_obs != nullptr, &info, &table)) return rc;
+    const int S = p->n_systems, L = p->L, N = p->n_cap;
+    for (int s = 0; s < S; ++s) {
+        if (n0[s] < 0 || n0[s] > N) return bad("bad n_cap / n0 / n_obs / max_events");
+        if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * N, sigma0 + (size_t)s * N)) return bad(why);
+    }
+    OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: the scratch arrays start from zero
+    if (int rc = job.select_device(p->device)) return rc;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
+    if ((uint64_t)((int64_t)S * info.work_bytes_per_system + info.output_bytes) > (uint64_t)free_b)
+        return bad("the batch needs " + std::to_string((int64_t)S * info.work_bytes_per_system) + " bytes of work memory and " +
+                   std::to_string(info.output_bytes) + " bytes of outputs, the device has " + std::to_string(free_b) + " bytes free");
+    BigArgs a{};
+    a.p = *p; a.tlen = info.table_len; a.nblk = info.n_blocks; a.cb = (a.nblk + BT - 1) / BT;
+    a.tab_in_lds = info.table_in_lds;
+    a.m = gil_model(p);
+    const size_t SN = (size_t)S * N, SL = (size_t)S * L, SO = (size_t)S * p->n_obs, NIN = S == 1 ? (size_t)n0[0] : SN;
+    UP(table, table.data(), table.size()); UP(times, p->times_obs, (size_t)p->n_obs);
+    UP(betas, p->beta, (size_t)S); UP(n0, n0, (size_t)S);
+    UP(pos0, pos0, NIN); UP(sigma0, sigma0, NIN);
+    if (bound0) UP(bound0, bound0, NIN);
+    if (p->anchor_mask) UP(anchor, p->anchor_mask, (size_t)L);
+    if (scalars_obs && p->front_lo) UP(front_lo, p->front_lo, (size_t)L);
+    if (scalars_obs && p->block_table) UP(block_table, p->block_table, (size_t)(p->K + 1) * (p->K + 1));
+    if (uniforms) UP(uniforms, uniforms, (size_t)S * p->max_events * 4);
+    if (int rc = gil_upload_flip_table(job, p, a.m)) return rc;
+    WORK(pos, SN); WORK(occ, SL); WORK(occp, SL); WORK(slot, SL * p->K); WORK(work, SN); WORK(ref, SN);
+    WORK(flg, SN); WORK(rate, SN); WORK(bsum, (size_t)S * a.nblk); WORK(W, SL); WORK(S, SL);
+    OUT(pos_obs, pos_obs, SO * N); OUT(sigma_obs, sigma_obs, SO * N); OUT(flags_obs, flags_obs, SO * N);
+    OUT(scalars, scalars_obs, SO * GIL_NSCALARS);
+    OUT(n_recorded, n_recorded, (size_t)S); OUT(n_events, n_events, (size_t)S); OUT(t_final, t_final, (size_t)S);
+    OUT(exits, exits, SN * 3); OUT(n_exits, n_exits, (size_t)S);
+    const size_t lds = (size_t)info.lds_bytes;
+    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel), lds)) return rc;
+    if (int rc = job.create_events()) return rc;
+    hipLaunchKernelGGL(big_field_init, dim3((unsigned)((L + 255) / 256), (unsigned)S), dim3(256), 0, nullptr, a);
+    job.ev.start();
+    hipLaunchKernelGGL(gil_big_kernel, dim3((unsigned)S), dim3(BT), lds, nullptr, a);
+    job.ev.stop();
+    if (int rc = job.finish(hipGetLastError(), "gil_big_kernel", kernel_ms)) return rc;
+    DOWN(pos_obs, pos_obs, SO * N * 4); DOWN(sigma_obs, sigma_obs, SO * N); DOWN(flags_obs, flags_obs, SO * N);
+    DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8);
+    DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8); DOWN(t_final, t_final, (size_t)S * 8);
+    DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
+    return GIL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -451,45 +635,29 @@ int gil_run_large(const gil_params *p, int32_t n0, const int32_t *pos0, const in
     auto bad = [&](const char *m) { g_big_err = std::string("gil_run_large: ") + m; return GIL_ERR_ARG; };
     if (!p || !pos0 || !sigma0 || !p->beta || !p->times_obs) return bad("null argument");
     if (p->n_systems != 1) return bad("one system per call");
-    if (p->L < 2 || p->L > (1 << 25)) return bad("L must be in [2, 2^25]");
-    if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
-    if ((int64_t)p->L * p->K > (1ll << 27)) return bad("L * K must not exceed 2^27 (site map)");
-    if (p->n_cap < 1 || p->n_cap > MAX_NB * PB || n0 < 0 || n0 > p->n_cap || p->n_obs < 1 || p->max_events < 0) return bad("bad n_cap / n0 / n_obs / max_events");
-    const int L = p->L, N = p->n_cap;
-    if (const char *why = gil_check_state(p, n0, pos0, sigma0)) return bad(why);
-    OneShot job{"gil_run_large", g_big_err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: the scratch arrays start from zero
-    if (int rc = job.select_device(p->device)) return rc;
-    std::vector<double> table; int tlen = 0, q = 0;
-    weight_table(p->sigma_grid, L, p->K, p->periodic != 0, table, tlen, q);
-    BigArgs a{};
-    a.p = *p; a.tlen = tlen; a.n_init = n0; a.nblk = (N + PB - 1) / PB; a.cb = (a.nblk + BT - 1) / BT;
-    a.tab_in_lds = tlen + 1 <= TAB_LDS_MAX ? 1 : 0; a.beta = p->beta[0];
-    a.m = gil_model(p);
-    const size_t SO = (size_t)p->n_obs * N;
-    UP(table, table.data(), table.size()); UP(times, p->times_obs, (size_t)p->n_obs);
-    UP(pos0, pos0, (size_t)std::max(n0, 1)); UP(sigma0, sigma0, (size_t)std::max(n0, 1));
-    if (bound0) UP(bound0, bound0, (size_t)std::max(n0, 1));
-    if (p->anchor_mask) UP(anchor, p->anchor_mask, (size_t)L);
-    if (uniforms) UP(uniforms, uniforms, (size_t)p->max_events * 4);
-    if (int rc = gil_upload_flip_table(job, p, a.m)) return rc;
-    WORK(pos, (size_t)N); WORK(occ, (size_t)L); WORK(occp, (size_t)L); WORK(slot, (size_t)L * p->K); WORK(work, (size_t)N);
-    WORK(flg, (size_t)N); WORK(rate, (size_t)N); WORK(bsum, (size_t)a.nblk); WORK(W, (size_t)L); WORK(S, (size_t)L);
-    OUT(pos_obs, pos_obs, SO); OUT(sigma_obs, sigma_obs, SO); OUT(flags_obs, flags_obs, SO);
-    OUT(n_recorded, n_recorded, 1); OUT(n_events, n_events, 1); OUT(t_final, t_final, 1); OUT(exits, exits, (size_t)N * 3); OUT(n_exits, n_exits, 1);
-    const size_t lds = ((size_t)(a.tab_in_lds ? ((tlen + 2) & ~1) : 0) + 32 + 4 * BT + 4) * sizeof(double) + ((size_t)2 * MAX_NB + 32) * sizeof(int);
-    if (lds > 160 * 1024) return bad("LDS budget exceeded");
-    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel), lds)) return rc;
-    if (int rc = job.create_events()) return rc;
-    hipLaunchKernelGGL(big_field_init, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, nullptr, a);
-    job.ev.start();
-    hipLaunchKernelGGL(gil_big_kernel, dim3(1), dim3(BT), lds, nullptr, a);
-    job.ev.stop();
-    if (int rc = job.finish(hipGetLastError(), "gil_big_kernel", kernel_ms)) return rc;
-    DOWN(pos_obs, pos_obs, SO * 4); DOWN(sigma_obs, sigma_obs, SO); DOWN(flags_obs, flags_obs, SO);
-    DOWN(n_recorded, n_recorded, 4); DOWN(n_events, n_events, 8); DOWN(t_final, t_final, 8); DOWN(exits, exits, (size_t)N * 3 * 8); DOWN(n_exits, n_exits, 4);
-    return GIL_OK;
+    return big_run("gil_run_large", g_big_err, p, &n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, nullptr,
+                   n_recorded, n_events, t_final, exits, n_exits, kernel_ms);
 }
 
 const char *gil_large_last_error(void) { return g_big_err.c_str(); }
+
+const char *gilm_last_error(void) { return g_many_err.c_str(); }
+
+int gilm_plan(const gil_params *p, int32_t want_states, int32_t want_scalars, gilm_plan_info *out) {
+    auto bad = [&](const char *m) { g_many_err = std::string("gilm_plan: ") + m; return GIL_ERR_ARG; };
+    if (!p || !out) return bad("null argument");
+    if (p->n_systems < 1 || p->n_systems > GILM_MAX_SYSTEMS) return bad("n_systems must be in [1, GILM_MAX_SYSTEMS]");
+    return big_plan("gilm_plan", g_many_err, p, want_states != 0, want_scalars != 0, out, nullptr);
+}
+
+int gilm_run(const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
+             const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+             int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
+    auto bad = [&](const char *m) { g_many_err = std::string("gilm_run: ") + m; return GIL_ERR_ARG; };
+    if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs) return bad("null argument");
+    if (p->n_systems < 1 || p->n_systems > GILM_MAX_SYSTEMS) return bad("n_systems must be in [1, GILM_MAX_SYSTEMS]");
+    return big_run("gilm_run", g_many_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
+                   n_recorded, n_events, t_final, exits, n_exits, kernel_ms);
+}
 
 }  // extern "C"

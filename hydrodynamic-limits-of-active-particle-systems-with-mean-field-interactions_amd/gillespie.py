@@ -1,7 +1,7 @@
-"""Device-resident exact Gillespie loop for batches of systems (include/gillespie.h): the reference's
-`ParticleSystem.run` as written (one event per iteration, PARTICLE_solver_CLASS.py:450-558), one persistent workgroup
-per system.  `run_batched_exact` returns the reference's result dictionaries; `sweep` statistics can be taken from the
-scalar sums without the M x L arrays (`scalars_only=True`).
+"""Device-resident exact Gillespie loop for batches of systems (include/gillespie.h; systems beyond one workgroup's LDS:
+include/gillespie_many.h): the reference's `ParticleSystem.run` as written (one event per iteration,
+PARTICLE_solver_CLASS.py:450-558), one persistent workgroup per system.  `run_batched_exact` returns the reference's
+result dictionaries; `sweep` statistics can be taken from the scalar sums without the M x L arrays (`scalars_only=True`).
 
 Differences to the reference: randomness is Philox4x32-10 keyed by `seed` (the reference consumes a NumPy Generator), so
 trajectories agree in distribution, not draw for draw; `m_local_list[k]` is the field of the observed state (the
@@ -30,6 +30,12 @@ class GilParams(C.Structure):
                 ("flip_table", C.c_void_p)]
 
 
+class GilmPlanInfo(C.Structure):
+    """struct gilm_plan_info of include/gillespie_many.h, field for field."""
+    _fields_ = [("n_systems", C.c_int32), ("n_blocks", C.c_int32), ("table_len", C.c_int32), ("table_in_lds", C.c_int32),
+                ("lds_bytes", C.c_int32), ("reserved", C.c_int32), ("work_bytes_per_system", C.c_int64), ("output_bytes", C.c_int64)]
+
+
 def _lib():
     lib = capi.load()
     if not getattr(lib, "_gil_ready", False):
@@ -39,6 +45,11 @@ def _lib():
         lib.gil_large_last_error.restype, lib.gil_large_last_error.argtypes = C.c_char_p, []
         lib.gil_run_large.restype = C.c_int
         lib.gil_run_large.argtypes = [C.POINTER(GilParams), C.c_int32] + [C.c_void_p] * 12 + [C.POINTER(C.c_double)]
+        lib.gilm_last_error.restype, lib.gilm_last_error.argtypes = C.c_char_p, []
+        lib.gilm_plan.restype = C.c_int
+        lib.gilm_plan.argtypes = [C.POINTER(GilParams), C.c_int32, C.c_int32, C.POINTER(GilmPlanInfo)]
+        lib.gilm_run.restype = C.c_int
+        lib.gilm_run.argtypes = [C.POINTER(GilParams)] + [C.c_void_p] * 14 + [C.POINTER(C.c_double)]
         lib._gil_ready = True
     return lib
 
@@ -52,7 +63,36 @@ def run_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, s
             anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
             block_table=None, device=0, flip_table=None):
     """`states` = list of (pos, sigma[, bound]) per system.  Returns a dict of arrays with a leading system axis."""
+    return _run_batch_entry("gil_run_batch", **locals())       # first statement: locals() are the keywords
+
+
+def run_many_large_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
+                       minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
+                       anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
+                       block_table=None, device=0, flip_table=None):
+    """`run_raw` for systems beyond one workgroup's LDS (gilm_run of include/gillespie_many.h): the large-system kernel, one
+    workgroup per system, all systems in one launch.  Same keywords, same dictionary, scalars included.  System s draws
+    with Philox key seed + s: it is the `run_large_raw` run with that seed."""
+    return _run_batch_entry("gilm_run", **locals())
+
+
+def plan_many_large(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, want_states=True, want_scalars=True):
+    """gilm_plan: what a batch of large systems would use (blocks, table, LDS, bytes), by host arithmetic; no device needed."""
     lib = _lib()
+    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), sigma_grid=float(sigma_grid), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
+    info = GilmPlanInfo()
+    rc = lib.gilm_plan(C.byref(par), int(bool(want_states)), int(bool(want_scalars)), C.byref(info))
+    if rc != 0:
+        raise capi.ApsError(rc, lib.gilm_last_error().decode())
+    return {k: int(getattr(info, k)) for k, _ in GilmPlanInfo._fields_ if k != "reserved"}
+
+
+def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed,
+                     minus_anchor, immobilize, suppress_flip, crowding, k_on, k_off, k_exit, anchor_mask, uniforms, max_events,
+                     want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table):
+    """The two batch entry points take the same arguments: gil_run_batch (systems in LDS) and gilm_run (large systems)."""
+    lib = _lib()
+    call, last_error = getattr(lib, entry), (lib.gil_last_error if entry == "gil_run_batch" else lib.gilm_last_error)
     S = len(states)
     betas = np.ascontiguousarray(np.broadcast_to(np.asarray(betas, dtype=np.float64), (S,)))
     ncap = max(1, max(len(st[0]) for st in states))
@@ -88,10 +128,10 @@ def run_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, s
     n_rec, n_ev, t_fin = np.zeros(S, np.int32), np.zeros(S, np.int64), np.zeros(S)
     exits, n_exit = np.zeros((S, ncap, 3)), np.zeros(S, np.int32)
     ms = C.c_double()
-    rc = lib.gil_run_batch(C.byref(par), _p(n0), _p(pos0), _p(sg0), _p(bd0), _p(uniforms), _p(pos_obs), _p(sg_obs), _p(fl_obs),
-                           _p(scal), _p(n_rec), _p(n_ev), _p(t_fin), _p(exits), _p(n_exit), C.byref(ms))
+    rc = call(C.byref(par), _p(n0), _p(pos0), _p(sg0), _p(bd0), _p(uniforms), _p(pos_obs), _p(sg_obs), _p(fl_obs),
+              _p(scal), _p(n_rec), _p(n_ev), _p(t_fin), _p(exits), _p(n_exit), C.byref(ms))
     if rc != 0:
-        raise capi.ApsError(rc, lib.gil_last_error().decode())
+        raise capi.ApsError(rc, last_error().decode())
     return dict(pos=pos_obs, sigma=sg_obs, flags=fl_obs, scalars=scal, n_recorded=n_rec, n_events=n_ev, t_final=t_fin,
                 exits=exits, n_exits=n_exit, n0=n0, kernel_ms=ms.value)
 
@@ -113,40 +153,14 @@ def run_batched_exact(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var
     seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
     times_obs = np.arange(0.0, T, obs_dt)
     M = len(times_obs)
-    if L > GIL_MAX_L or max(len(p) for p, _ in inits) > GIL_MAX_N:
-        # beyond one workgroup's LDS: the large-system kernel (one system per launch, state in global memory)
-        if uniforms is not None:
-            raise ValueError("run_batched_exact: caller-supplied uniforms with large systems go through run_large_raw")
-        parts = []
-        for s, (ps, st) in enumerate(zip(systems, inits)):
-            one = run_large_raw(L=L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
-                                rate_active=first.rate_active, beta=float(ps.beta), state=st, times_obs=times_obs, T=T, seed=seed + s,
-                                minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
-                                suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
-                                k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, device=first.device,
-                                flip_table=first.flip_table())
-            parts.append(one)
-        ncap = max(p["pos"].shape[1] for p in parts)
-
-        def stack(key, dtype):
-            out = np.zeros((len(parts), M, ncap), dtype)
-            for s, p in enumerate(parts):
-                out[s, :, :p[key].shape[1]] = p[key]
-            return out
-        exits = np.zeros((len(parts), ncap, 3))
-        for s, p in enumerate(parts):
-            exits[s, :p["exits"].shape[0]] = p["exits"]
-        r = dict(pos=stack("pos", np.int32), sigma=stack("sigma", np.int8), flags=stack("flags", np.uint8),
-                 n_recorded=np.array([p["n_recorded"] for p in parts]), n_events=np.array([p["n_events"] for p in parts]),
-                 t_final=np.array([p["t_final"] for p in parts]), exits=exits, n_exits=np.array([p["n_exits"] for p in parts]),
-                 n0=np.array([p["n0"] for p in parts]), kernel_ms=sum(p["kernel_ms"] for p in parts))
-    else:
-        r = run_raw(L=L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
-                rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs, T=T,
-                seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
-                suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
-                k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms, device=first.device,
-                flip_table=first.flip_table())
+    # beyond one workgroup's LDS: the large-system kernel, one workgroup per system in one launch (system s: key seed + s)
+    run = run_many_large_raw if (L > GIL_MAX_L or max(len(p) for p, _ in inits) > GIL_MAX_N) else run_raw
+    r = run(L=L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
+            rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs, T=T,
+            seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
+            suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
+            k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms, device=first.device,
+            flip_table=first.flip_table())
     outs = []
     for s, ps in enumerate(systems):
         n0 = int(r["n0"][s])
@@ -202,12 +216,14 @@ def run_batched_exact_statistics(systems, T=10.0, obs_dt=0.01):
         raise ValueError("run_batched_exact_statistics: the systems' particle numbers give different blocking thresholds; "
                          "run them in separate batches")
     front_lo = np.array([acc0.front_range(s)[0] for s in range(first.L)], np.int32)
-    r = run_raw(L=first.L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
-                rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs, T=T,
-                seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
-                suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
-                k_off=first.k_off, k_exit=0.0, anchor_mask=first.is_anchor_site, want_states=False, x_wall=acc0.x_wall,
-                ref_obs=acc0.start, front_lo=front_lo, block_table=tables[0], device=first.device, flip_table=first.flip_table())
+    # beyond one workgroup's LDS: the large-system kernel takes the same sums (gilm_run); no state array leaves the device either way
+    run = run_many_large_raw if (first.L > GIL_MAX_L or max(len(p) for p, _ in inits) > GIL_MAX_N) else run_raw
+    r = run(L=first.L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
+            rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs, T=T,
+            seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
+            suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
+            k_off=first.k_off, k_exit=0.0, anchor_mask=first.is_anchor_site, want_states=False, x_wall=acc0.x_wall,
+            ref_obs=acc0.start, front_lo=front_lo, block_table=tables[0], device=first.device, flip_table=first.flip_table())
     rows = []
     for s, ps in enumerate(systems):
         if int(r["n_recorded"][s]) < len(times_obs):
