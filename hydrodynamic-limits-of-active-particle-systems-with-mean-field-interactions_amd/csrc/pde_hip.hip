@@ -1,9 +1,10 @@
-// pde_hip.hip -- MI355X (gfx950) implementation of the C ABI in include/pde.h.
+// pde_hip.hip -- MI355X (gfx950) implementation of the C ABIs in include/pde.h and include/pde_sweep.h.
 //
 // Replaces the time loop of the reference's IMEXPDE (IMEX_PDE_solver_class.py:236-290): one PERSISTENT workgroup
 // per system keeps rho_plus, rho_minus, the diffused fields and the magnetisation in LDS and runs all nsteps
 // without leaving the kernel (a step is ~10 phases separated by workgroup barriers; nothing but the requested
-// series is written to HBM).  Systems of a batch differ only in beta (the reference's sweep parameter).
+// series is written to HBM).  Systems of a batch differ only in beta (pde_solve_batch; the reference's sweep parameter), or in
+// beta and in the width of the Gaussian kernel (pdek_solve: the same kernel and host driver, mode, reach and taps per system).
 //
 //   implicit diffusion  (I - gamma dt Lap / dx^2) x = rho          ref :68-82, :192-193
 //       constant matrix -> Thomas factorisation once on the host; the two triangular sweeps are first-order linear
@@ -11,7 +12,8 @@
 //       Hillis-Steele over the 256 chunk maps in LDS); periodic corners by Sherman-Morrison
 //   magnetisation       local ratio | circular Gaussian convolution | global mean      ref :156-168
 //       the reference multiplies rfft's; here the periodic kernel (same normalised taps, cut where they fall below
-//       1e-17 of the centre tap) is applied directly with a sliding 4-site register window
+//       1e-17 of the centre tap) is applied directly with a sliding 4-site register window; pdek_solve with convolution = 1
+//       multiplies complex transforms held in LDS instead (pde_sweep_fft.hpp)
 //   reaction/advection/clip/renormalise                                                   ref :195-233
 //   observables per step: mean m, var(total), lowest rfft modes (direct DFT), snapshots   ref :243-255
 //   tracers: Euler-Maruyama flip + drift + noise, windowed v_eff / D_eff                  ref :257-287
@@ -28,17 +30,24 @@
 #include <vector>
 
 #include "pde.h"
+#include "pde_sweep.h"
 #include "pde_common.hpp"                 // factorisation, taps, rate, Philox, workgroup sum and scan: shared with pde_wide_hip.hip
 #include "dev_mem.hpp"                    // buffer owner, event pair, the driver of the one-shot entry points
+#include "pde_sweep_fft.hpp"              // the transform in LDS of the kernel-width sweep (include/pde_sweep.h)
 
 namespace {
 
 using namespace pde_common;
-std::string g_err;
+std::string g_err, g_err_k;
+
+// The three forms of the kernel.  BATCH is pde_solve_batch: one kernel mode and one table of taps for the launch.  The two sweep
+// forms (pdek_solve) read mode, reach and taps per system; SWEEP_SPECTRAL evaluates mode 1 by the transform of pde_sweep_fft.hpp.
+enum Form { BATCH, SWEEP_DIRECT, SWEEP_SPECTRAL };
+static_assert(pdek::THREADS == NT, "pde_sweep_fft.hpp strides its passes by the workgroup of pde_kernel");
 
 struct PdeArgs {
     pde_params p;
-    int n_snap, ktaps, chunk;           // chunk = sites per thread in the scans
+    int n_snap, ktaps, chunk;           // chunk = sites per thread in the scans; ktaps: of the launch (sweep: the largest), sizes the LDS layout
     double dx, sm_coef, sm_denom;       // Sherman-Morrison: x = y - z * (y_0 + sm_coef y_{L-1}) / sm_denom
     const double *beta, *rho_p0, *rho_m0, *tracer_x0;
     const int8_t *tracer_s0;
@@ -52,6 +61,10 @@ struct PdeArgs {
     long long work_stride;
     double *hist;                       // [n_systems][window][n_tracers] ring of unwrapped tracer positions
     double *trx; int8_t *trs;           // [n_systems][n_tracers] working tracer state
+    // the sweep forms only (null for BATCH): per system [n_systems]
+    const int *sys_mode, *sys_ktaps, *sys_log2;   // kernel mode, reach, log2 of the transform (0: none)
+    const long long *sys_ktab;                    // where the system's taps begin in ktab
+    const double2 *ctw;                           // twiddles of m = PDEK_MIN_LOG2 .., one table after another
 };
 
 // x = A^{-1} d for both fields: d in (dp, dm), result overwrites them.
@@ -80,6 +93,7 @@ __device__ inline void diffuse2(const PdeArgs &a, double *dp, double *dm, double
     (void)red;
 }
 
+template <Form FORM>
 __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
     extern __shared__ double lds[];
     const int L = a.p.L, t = threadIdx.x, sys = blockIdx.x, ntr = a.p.n_tracers, nsteps = a.p.nsteps;
@@ -92,33 +106,50 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
                            : reinterpret_cast<double4 *>(lds + ((5 * L + ((a.ktaps + 2) & ~1) + NT + 3) & ~3));   // 32-byte aligned
     const double beta = a.beta[sys], dx = a.dx, dt = a.p.dt, lam = a.p.lam;
     for (int i = t; i < L; i += NT) { rp[i] = a.rho_p0[(size_t)sys * L + i]; rm[i] = a.rho_m0[(size_t)sys * L + i]; }
-    for (int i = t; i <= a.ktaps; i += NT) ktab[i] = a.ktab[i];
+    const int mode = FORM == BATCH ? a.p.kernel_mode : a.sys_mode[sys], ktaps = FORM == BATCH ? a.ktaps : a.sys_ktaps[sys];
+    const double *ktab_g = FORM == BATCH ? a.ktab : a.ktab + a.sys_ktab[sys];
+    for (int i = t; i <= ktaps; i += NT) ktab[i] = ktab_g[i];
     double *trx = a.trx + (size_t)sys * ntr;
     int8_t *trs = a.trs + (size_t)sys * ntr;
     for (int i = t; i < ntr; i += NT) { trx[i] = a.tracer_x0[(size_t)sys * ntr + i]; trs[i] = a.tracer_s0[(size_t)sys * ntr + i]; }
     __syncthreads();
+    pdek::Ctx fc{};
+    if constexpr (FORM == SWEEP_SPECTRAL) {                     // behind the scans' scratch: buffer, twiddles, spectrum, sized by the launch's largest m
+        fc.m = mode == 1 ? a.sys_log2[sys] : 0;
+        fc.L = L; fc.kt = ktaps; fc.t = t; fc.rp = rp; fc.rm = rm; fc.mf = mf;
+        fc.buf = reinterpret_cast<double2 *>(scan + 2 * NT);
+        if (fc.m) {
+            const int M = 1 << fc.m;
+            fc.tw = fc.buf + M + (M >> 4); fc.spec = reinterpret_cast<double *>(fc.tw + (M >> 1));
+            const double2 *tw_g = a.ctw + pdek::twiddle_offset(fc.m);
+            for (int i = t; i < (M >> 1); i += NT) fc.tw[i] = tw_g[i];
+            pdek::build_spectrum(fc, ktab);
+        }
+    }
     const double noise_amp = sqrt(2.0 * a.p.gamma * dt);
     for (int n = 0; n <= nsteps; ++n) {
         // ---- magnetisation of the current state (ref :156-168): used by the observables, the tracers and step()
         double m_global = 0.0;
-        if (a.p.kernel_mode == 0) {
+        if (mode == 0) {
             for (int i = t; i < L; i += NT) mf[i] = (rp[i] - rm[i]) / (rp[i] + rm[i] + 1e-12);
-        } else if (a.p.kernel_mode == 2) {
+        } else if (mode == 2) {
             double s = 0.0, w = 0.0;
             for (int i = t; i < L; i += NT) { s += rp[i] - rm[i]; w += rp[i] + rm[i]; }
             s = block_sum(s, red); w = block_sum(w, red);
             m_global = s / (w + 1e-12);
             for (int i = t; i < L; i += NT) mf[i] = m_global;
+        } else if (FORM == SWEEP_SPECTRAL) {                   // circular convolution by the transform in LDS
+            pdek::convolve(fc);
         } else {                                               // circular convolution, 4 consecutive sites per thread
             for (int base = 4 * t; base < L; base += 4 * NT) {
                 double num[4] = {0, 0, 0, 0}, den[4] = {0, 0, 0, 0};
                 // window holds s, tot at sites base + j + (0..3); slide j from -ktaps to +ktaps
-                int idx = base - a.ktaps;
+                int idx = base - ktaps;
                 idx %= L; if (idx < 0) idx += L;
                 double sp[4], sm[4];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) { sp[k + 1] = rp[idx]; sm[k + 1] = rm[idx]; idx = idx + 1 == L ? 0 : idx + 1; }
-                for (int j = -a.ktaps; j <= a.ktaps; ++j) {
+                for (int j = -ktaps; j <= ktaps; ++j) {
                     sp[0] = sp[1]; sp[1] = sp[2]; sp[2] = sp[3]; sm[0] = sm[1]; sm[1] = sm[2]; sm[2] = sm[3];
                     sp[3] = rp[idx]; sm[3] = rm[idx]; idx = idx + 1 == L ? 0 : idx + 1;
                     // site base + k sees source base + k + j  <=>  window slot k holds it when the window starts at base + j
@@ -141,7 +172,7 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
             for (int i = t; i < L; i += NT) { const double d = rp[i] + rm[i] - mean_t; sv += d * d; }
             sv = block_sum(sv, red);
             if (t == 0) {
-                if (a.m_series) a.m_series[(size_t)sys * (nsteps + 1) + n] = a.p.kernel_mode == 2 ? m_global : sm_ / L;
+                if (a.m_series) a.m_series[(size_t)sys * (nsteps + 1) + n] = mode == 2 ? m_global : sm_ / L;
                 if (a.var_series) a.var_series[(size_t)sys * (nsteps + 1) + n] = sv / L;
             }
             if (a.fft_re)
@@ -261,6 +292,129 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
     }
 }
 
+
+// ---- host: the plan of a sweep launch (pdek_plan; no device)
+struct SweepPlan {
+    std::vector<int> mode, ktaps, log2;
+    std::vector<long long> ktab_off;
+    std::vector<double> ktab;           // the systems' tables one after another (systems of one width share theirs)
+    pdek_plan_info info{};
+};
+
+size_t base_lds_bytes(int L, int ktaps) {
+    return (size_t)((5 * L + ((ktaps + 2) & ~1) + NT + 3) & ~3) * sizeof(double) + (size_t)2 * NT * sizeof(double4);
+}
+
+// 0, or PDE_ERR_ARG with the complaint in `why`
+int make_sweep_plan(const pde_params *p, int32_t n_systems, const double *kernel_sigma, SweepPlan &pl, std::string &why) {
+    if (!p || n_systems < 1) { why = "null argument or n_systems < 1"; return PDE_ERR_ARG; }
+    if (p->L < 4 || p->L > PDE_MAX_L || !(p->xlim > 0.0)) { why = "L must be in [4, PDE_MAX_L], xlim > 0"; return PDE_ERR_ARG; }
+    if (p->kernel_mode < 0 || p->kernel_mode > 2) { why = "kernel_mode must be 0, 1 or 2"; return PDE_ERR_ARG; }
+    if (p->convolution != 0 && p->convolution != 1) { why = "convolution must be 0 (direct) or 1 (spectral)"; return PDE_ERR_ARG; }
+    if (p->kernel_mode != 0 && !kernel_sigma) { why = "a Gaussian kernel needs kernel_sigma[n_systems]"; return PDE_ERR_ARG; }
+    const int L = p->L;
+    const double dx = p->xlim / L;
+    pl.mode.assign(n_systems, 0); pl.ktaps.assign(n_systems, 0); pl.log2.assign(n_systems, 0); pl.ktab_off.assign(n_systems, 0);
+    pl.ktab.assign(1, 1.0);                                    // modes 0 and 2 read nothing of it: one tap at offset 0
+    int kmax = 0, mmax = 0;
+    for (int s = 0; s < n_systems; ++s) {
+        if (p->kernel_mode == 0) continue;
+        const double sg = kernel_sigma[s];
+        if (!std::isfinite(sg) || !(sg > 0.0)) { why = "kernel_sigma[" + std::to_string(s) + "] must be finite and > 0 for a Gaussian kernel"; return PDE_ERR_ARG; }
+        if (sg > 100000) { pl.mode[s] = 2; continue; }          // ref :161
+        pl.mode[s] = 1;
+        int twin = -1;
+        for (int r = 0; r < s && twin < 0; ++r) if (pl.mode[r] == 1 && kernel_sigma[r] == sg) twin = r;
+        if (twin >= 0) { pl.ktaps[s] = pl.ktaps[twin]; pl.ktab_off[s] = pl.ktab_off[twin]; pl.log2[s] = pl.log2[twin]; continue; }
+        pde_params q = *p;
+        q.kernel_mode = 1; q.kernel_sigma = sg;
+        std::vector<double> tab;
+        pl.ktaps[s] = kernel_taps(&q, dx, tab);
+        pl.ktab_off[s] = (long long)pl.ktab.size();
+        pl.ktab.insert(pl.ktab.end(), tab.begin(), tab.end());
+        if (p->convolution == 1) pl.log2[s] = pdek::log2_for((long long)L + 2ll * pl.ktaps[s]);
+        kmax = std::max(kmax, pl.ktaps[s]); mmax = std::max(mmax, pl.log2[s]);
+    }
+    const size_t base = base_lds_bytes(L, kmax);
+    if (base > PDEK_LDS_LIMIT) { why = "not eligible: the five fields of L = " + std::to_string(L) + " sites do not fit LDS and would live in global memory; that is the wide shape's ground (pdew_solve, include/pde_wide.h)"; return PDE_ERR_ARG; }
+    if (mmax > PDEK_MAX_LOG2) { why = "not eligible for the transform in LDS: L + 2 ktaps = " + std::to_string(L + 2 * kmax) + " needs 2^" + std::to_string(mmax) + " words, the largest is 2^" + std::to_string(PDEK_MAX_LOG2); return PDE_ERR_ARG; }
+    const size_t lds = base + pdek::lds_bytes(mmax);
+    if (lds > PDEK_LDS_LIMIT) { why = "not eligible for the transform in LDS: fields, taps and a transform of 2^" + std::to_string(mmax) + " words need " + std::to_string(lds) + " bytes of " + std::to_string(PDEK_LDS_LIMIT); return PDE_ERR_ARG; }
+    pl.info.ktaps_max = kmax; pl.info.conv_log2_max = mmax; pl.info.lds_bytes = (int32_t)lds; pl.info.fields_in_lds = 1;
+    return PDE_OK;
+}
+
+// ---- host: the driver of both entry points.  sweep == nullptr: pde_solve_batch, one table of taps from p->kernel_sigma.
+int solve_impl(const char *who, std::string &err, const SweepPlan *sweep, const pde_params *p, int32_t n_systems, const double *beta,
+               const double *rho_p0, const double *rho_m0,
+               const double *tracer_x0, const int8_t *tracer_s0, const double *rand_u, const double *rand_n,
+               double *rho_p, double *rho_m, double *m_series, double *var_series, double *v_eff_series,
+               double *D_eff_series, double *snapshots, double *m_snapshots, double *fft_re, double *fft_im,
+               double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
+    OneShot job{who, err, false, PDE_ERR_NODEVICE, PDE_ERR_ARG, PDE_ERR_HIP};   // no zero-fill: the kernel writes every output in full
+    if (int rc = job.select_device(p->device)) return rc;
+
+    const int L = p->L, ntr = p->n_tracers, ns = p->nsteps + 1;
+    const double dx = p->xlim / L;
+    // ---- constant matrix: Thomas factorisation (and the Sherman-Morrison vector for periodic corners); kernel taps (ref :84-93)
+    Factor fac;
+    factorise(p, dx, fac);
+    const std::vector<double> &up = fac.up, &fw = fac.fw, &finv = fac.finv, &fz = fac.fz;
+    const double sm_coef = fac.sm_coef, sm_denom = fac.sm_denom;
+    std::vector<double> ktab;
+    const int ktaps = sweep ? sweep->info.ktaps_max : kernel_taps(p, dx, ktab);
+    if (sweep) ktab = sweep->ktab;
+    std::vector<double> twc, tws;
+    twiddles(L, twc, tws);
+
+    PdeArgs a{};
+    a.p = *p; a.dx = dx; a.sm_coef = sm_coef; a.sm_denom = sm_denom; a.ktaps = ktaps;
+    a.chunk = (L + NT - 1) / NT; a.n_snap = p->nsteps / p->snapshot_interval + 1;
+    const size_t SL = (size_t)n_systems * L, SN = (size_t)n_systems * ns, ST = (size_t)n_systems * ntr;
+    UP(beta, beta, (size_t)n_systems); UP(rho_p0, rho_p0, SL); UP(rho_m0, rho_m0, SL);
+    UP(fw, fw.data(), (size_t)L); UP(finv, finv.data(), (size_t)L); UP(fu, up.data(), (size_t)L); UP(fz, fz.data(), (size_t)L);
+    UP(ktab, ktab.data(), ktab.size()); UP(twc, twc.data(), (size_t)L); UP(tws, tws.data(), (size_t)L);
+    if (sweep) {
+        UP(sys_mode, sweep->mode.data(), (size_t)n_systems); UP(sys_ktaps, sweep->ktaps.data(), (size_t)n_systems);
+        UP(sys_log2, sweep->log2.data(), (size_t)n_systems); UP(sys_ktab, sweep->ktab_off.data(), (size_t)n_systems);
+        if (sweep->info.conv_log2_max) {
+            std::vector<double2> ctw;
+            pdek::build_twiddles(sweep->info.conv_log2_max, ctw);
+            UP(ctw, ctw.data(), ctw.size());
+        }
+    }
+    if (ntr) {
+        UP(tracer_x0, tracer_x0, ST); UP(tracer_s0, tracer_s0, ST);
+        if (rand_u) { UP(rand_u, rand_u, SN * ntr); UP(rand_n, rand_n, SN * ntr); }
+        WORK(hist, (size_t)n_systems * p->window * ntr); WORK(trx, ST); WORK(trs, ST);
+    }
+    OUT(rho_p, rho_p, SL); OUT(rho_m, rho_m, SL); OUT(m_series, m_series, SN); OUT(var_series, var_series, SN);
+    OUT(v_eff, v_eff_series, SN); OUT(D_eff, D_eff_series, SN);
+    OUT(snapshots, snapshots, (size_t)n_systems * a.n_snap * L); OUT(m_snapshots, m_snapshots, (size_t)n_systems * a.n_snap * L);
+    OUT(fft_re, fft_re, SN * p->n_fft_modes); OUT(fft_im, fft_im, SN * p->n_fft_modes);
+    OUT(tracer_x, tracer_x, ST); OUT(tracer_s, tracer_s, ST);
+    size_t lds = base_lds_bytes(L, ktaps);
+    if (sweep) lds = (size_t)sweep->info.lds_bytes;             // the plan has refused what does not fit
+    else if (lds > 160 * 1024) {                               // beyond LDS: the fields live in global memory, the scans' scratch in LDS
+        a.work_stride = (long long)((5 * (size_t)L + ((ktaps + 2) & ~1) + 3) & ~(size_t)3);
+        WORK(work, (size_t)n_systems * (size_t)a.work_stride);
+        lds = (size_t)((NT + 3) & ~3) * sizeof(double) + (size_t)2 * NT * sizeof(double4);
+    }
+    void (*kernel)(const PdeArgs) = !sweep ? pde_kernel<BATCH> : sweep->info.conv_log2_max ? pde_kernel<SWEEP_SPECTRAL> : pde_kernel<SWEEP_DIRECT>;
+    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(kernel), lds)) return rc;
+    if (int rc = job.create_events()) return rc;
+    job.ev.start();
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_systems), dim3(NT), lds, nullptr, a);
+    job.ev.stop();
+    if (int rc = job.finish(hipGetLastError(), "pde_kernel", kernel_ms)) return rc;
+    DOWN(rho_p, rho_p, SL * 8); DOWN(rho_m, rho_m, SL * 8); DOWN(m_series, m_series, SN * 8); DOWN(var_series, var_series, SN * 8);
+    DOWN(v_eff_series, v_eff, SN * 8); DOWN(D_eff_series, D_eff, SN * 8);
+    DOWN(snapshots, snapshots, (size_t)n_systems * a.n_snap * L * 8); DOWN(m_snapshots, m_snapshots, (size_t)n_systems * a.n_snap * L * 8);
+    DOWN(fft_re, fft_re, SN * p->n_fft_modes * 8); DOWN(fft_im, fft_im, SN * p->n_fft_modes * 8);
+    DOWN(tracer_x, tracer_x, ST * 8); DOWN(tracer_s, tracer_s, ST);
+    return PDE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -275,56 +429,39 @@ int pde_solve_batch(const pde_params *p, int32_t n_systems, const double *beta, 
     auto bad = [&](const char *m) { g_err = std::string("pde_solve_batch: ") + m; return PDE_ERR_ARG; };
     if (const char *why = check_args(p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, fft_re, fft_im)) return bad(why);
     if (p->convolution != 0) return bad("convolution must be 0 here: the spectral convolution belongs to the wide shape (pdew_solve, include/pde_wide.h)");
-    OneShot job{"pde_solve_batch", g_err, false, PDE_ERR_NODEVICE, PDE_ERR_ARG, PDE_ERR_HIP};   // no zero-fill: the kernel writes every output in full
-    if (int rc = job.select_device(p->device)) return rc;
+    return solve_impl("pde_solve_batch", g_err, nullptr, p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m,
+                      m_series, var_series, v_eff_series, D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms);
+}
 
-    const int L = p->L, ntr = p->n_tracers, ns = p->nsteps + 1;
-    const double dx = p->xlim / L;
-    // ---- constant matrix: Thomas factorisation (and the Sherman-Morrison vector for periodic corners); kernel taps (ref :84-93)
-    Factor fac;
-    factorise(p, dx, fac);
-    const std::vector<double> &up = fac.up, &fw = fac.fw, &finv = fac.finv, &fz = fac.fz;
-    const double sm_coef = fac.sm_coef, sm_denom = fac.sm_denom;
-    std::vector<double> ktab;
-    const int ktaps = kernel_taps(p, dx, ktab);
-    std::vector<double> twc, tws;
-    twiddles(L, twc, tws);
+const char *pdek_last_error(void) { return g_err_k.c_str(); }
 
-    PdeArgs a{};
-    a.p = *p; a.dx = dx; a.sm_coef = sm_coef; a.sm_denom = sm_denom; a.ktaps = ktaps;
-    a.chunk = (L + NT - 1) / NT; a.n_snap = p->nsteps / p->snapshot_interval + 1;
-    const size_t SL = (size_t)n_systems * L, SN = (size_t)n_systems * ns, ST = (size_t)n_systems * ntr;
-    UP(beta, beta, (size_t)n_systems); UP(rho_p0, rho_p0, SL); UP(rho_m0, rho_m0, SL);
-    UP(fw, fw.data(), (size_t)L); UP(finv, finv.data(), (size_t)L); UP(fu, up.data(), (size_t)L); UP(fz, fz.data(), (size_t)L);
-    UP(ktab, ktab.data(), ktab.size()); UP(twc, twc.data(), (size_t)L); UP(tws, tws.data(), (size_t)L);
-    if (ntr) {
-        UP(tracer_x0, tracer_x0, ST); UP(tracer_s0, tracer_s0, ST);
-        if (rand_u) { UP(rand_u, rand_u, SN * ntr); UP(rand_n, rand_n, SN * ntr); }
-        WORK(hist, (size_t)n_systems * p->window * ntr); WORK(trx, ST); WORK(trs, ST);
+int pdek_plan(const pde_params *p, int32_t n_systems, const double *kernel_sigma,
+              pdek_plan_info *info, int32_t *kernel_mode, int32_t *ktaps, int32_t *conv_log2) {
+    SweepPlan pl;
+    std::string why;
+    if (int rc = make_sweep_plan(p, n_systems, kernel_sigma, pl, why)) { g_err_k = "pdek_plan: " + why; return rc; }
+    if (info) *info = pl.info;
+    for (int s = 0; s < n_systems; ++s) {
+        if (kernel_mode) kernel_mode[s] = pl.mode[s];
+        if (ktaps) ktaps[s] = pl.ktaps[s];
+        if (conv_log2) conv_log2[s] = pl.log2[s];
     }
-    OUT(rho_p, rho_p, SL); OUT(rho_m, rho_m, SL); OUT(m_series, m_series, SN); OUT(var_series, var_series, SN);
-    OUT(v_eff, v_eff_series, SN); OUT(D_eff, D_eff_series, SN);
-    OUT(snapshots, snapshots, (size_t)n_systems * a.n_snap * L); OUT(m_snapshots, m_snapshots, (size_t)n_systems * a.n_snap * L);
-    OUT(fft_re, fft_re, SN * p->n_fft_modes); OUT(fft_im, fft_im, SN * p->n_fft_modes);
-    OUT(tracer_x, tracer_x, ST); OUT(tracer_s, tracer_s, ST);
-    size_t lds = (size_t)((5 * L + ((ktaps + 2) & ~1) + NT + 3) & ~3) * sizeof(double) + (size_t)2 * NT * sizeof(double4);
-    if (lds > 160 * 1024) {                                    // beyond LDS: the fields live in global memory, the scans' scratch in LDS
-        a.work_stride = (long long)((5 * (size_t)L + ((ktaps + 2) & ~1) + 3) & ~(size_t)3);
-        WORK(work, (size_t)n_systems * (size_t)a.work_stride);
-        lds = (size_t)((NT + 3) & ~3) * sizeof(double) + (size_t)2 * NT * sizeof(double4);
-    }
-    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&pde_kernel), lds)) return rc;
-    if (int rc = job.create_events()) return rc;
-    job.ev.start();
-    hipLaunchKernelGGL(pde_kernel, dim3((unsigned)n_systems), dim3(NT), lds, nullptr, a);
-    job.ev.stop();
-    if (int rc = job.finish(hipGetLastError(), "pde_kernel", kernel_ms)) return rc;
-    DOWN(rho_p, rho_p, SL * 8); DOWN(rho_m, rho_m, SL * 8); DOWN(m_series, m_series, SN * 8); DOWN(var_series, var_series, SN * 8);
-    DOWN(v_eff_series, v_eff, SN * 8); DOWN(D_eff_series, D_eff, SN * 8);
-    DOWN(snapshots, snapshots, (size_t)n_systems * a.n_snap * L * 8); DOWN(m_snapshots, m_snapshots, (size_t)n_systems * a.n_snap * L * 8);
-    DOWN(fft_re, fft_re, SN * p->n_fft_modes * 8); DOWN(fft_im, fft_im, SN * p->n_fft_modes * 8);
-    DOWN(tracer_x, tracer_x, ST * 8); DOWN(tracer_s, tracer_s, ST);
     return PDE_OK;
+}
+
+int pdek_solve(const pde_params *p, int32_t n_systems, const double *beta, const double *kernel_sigma,
+               const double *rho_p0, const double *rho_m0, const double *tracer_x0, const int8_t *tracer_s0,
+               const double *rand_u, const double *rand_n,
+               double *rho_p, double *rho_m, double *m_series, double *var_series, double *v_eff_series,
+               double *D_eff_series, double *snapshots, double *m_snapshots, double *fft_re, double *fft_im,
+               double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
+    auto bad = [&](const std::string &m) { g_err_k = "pdek_solve: " + m; return PDE_ERR_ARG; };
+    if (const char *why = check_args(p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, fft_re, fft_im)) return bad(why);
+    SweepPlan pl;
+    std::string why;
+    if (make_sweep_plan(p, n_systems, kernel_sigma, pl, why)) return bad(why);
+    return solve_impl("pdek_solve", g_err_k, &pl, p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m,
+                      m_series, var_series, v_eff_series, D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms);
 }
 
 }  // extern "C"

@@ -12,6 +12,12 @@ into G slabs on G workgroups, a time step a chain of kernel launches; right for 
 the wide shape would use.  On the wide shape `convolution="spectral"` evaluates the Gaussian-kernel magnetisation by complex
 binary64 transforms over overlap-save blocks (include/pde_spectral.h) instead of the direct sum; the default stays direct.
 
+A sweep over the kernel width (the reference's IMEX_PDE_solver_run_sweep_magn*.py) is one launch on the one-workgroup shape:
+`sweep_over_kernel_sigmas`, `solve_sweep_raw`, `IMEXPDE.solve_sweep` give every system its own kernel_sigma next to its own beta
+(include/pde_sweep.h, `pdek_solve`); there `convolution="spectral"` evaluates the Gaussian-kernel magnetisation by a complex
+binary64 transform held in the workgroup's LDS, which is what a kernel that spans the ring wants (eligible while
+L + 2 * reach <= 2048; `sweep_plan` tells).
+
 Differences that are part of the design: tracer noise comes from Philox4x32-10 keyed by `seed` on the device (the
 reference draws from NumPy's global MT19937 inside the loop); the magnetisation kernel is applied by direct circular
 convolution instead of rfft products (unless convolution="spectral" is asked for); no output directory is created; plotting methods are not reproduced.
@@ -44,6 +50,12 @@ class PdewPlanInfo(C.Structure):
                 ("work_bytes", C.c_int64)]
 
 
+class PdekPlanInfo(C.Structure):
+    """struct pdek_plan_info of include/pde_sweep.h, field for field."""
+    _fields_ = [("ktaps_max", C.c_int32), ("conv_log2_max", C.c_int32), ("lds_bytes", C.c_int32), ("fields_in_lds", C.c_int32)]
+
+
+PDEK_MIN_LOG2, PDEK_MAX_LOG2 = 8, 11     # include/pde_sweep.h
 PDE_MAX_L = 1 << 22          # fields in LDS up to L ~ 3000 (PDE_LDS_L of include/pde.h), in global memory beyond
 
 
@@ -62,6 +74,11 @@ def _lib():
         lib.pdes_last_error.restype, lib.pdes_last_error.argtypes = C.c_char_p, []
         lib.pdes_plan.restype = C.c_int
         lib.pdes_plan.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 3
+        lib.pdek_last_error.restype, lib.pdek_last_error.argtypes = C.c_char_p, []
+        lib.pdek_plan.restype = C.c_int
+        lib.pdek_plan.argtypes = [C.POINTER(PdeParams), C.c_int32, vp, C.POINTER(PdekPlanInfo)] + [vp] * 3
+        lib.pdek_solve.restype = C.c_int
+        lib.pdek_solve.argtypes = [C.POINTER(PdeParams), C.c_int32] + [vp] * 20 + [C.POINTER(C.c_double)]
         lib._pde_ready = True
     return lib
 
@@ -220,6 +237,99 @@ def solve_batch_raw(*, L, xlim, dt, nsteps, gamma, lam, betas, bc, active_model,
     return out
 
 
+def _sweep_axes(betas, kernel_sigmas):
+    """betas and kernel_sigmas broadcast against each other -> two contiguous float64 vectors of one length."""
+    b = np.atleast_1d(np.asarray(betas, dtype=np.float64))
+    k = np.atleast_1d(np.asarray(kernel_sigmas, dtype=np.float64))
+    if b.ndim != 1 or k.ndim != 1:
+        raise ValueError("betas and kernel_sigmas must be scalars or one-dimensional")
+    try:
+        b, k = np.broadcast_arrays(b, k)
+    except ValueError:
+        raise ValueError(f"betas ({len(b)}) and kernel_sigmas ({len(k)}) do not broadcast against each other") from None
+    return np.ascontiguousarray(b), np.ascontiguousarray(k)
+
+
+def sweep_plan(*, L, kernel_sigmas, convolution=None, xlim=1.0, dt=5e-4, T=None, nsteps=None, gamma=2.33e-4, lam=0.6, bc="periodic",
+               active_model="bidirectional", gaussian_kernel=False, snapshot_interval=50, n_tracers=0, fft_modes=0, device=0):
+    """What `solve_sweep_raw` would use for these kernel widths (pdek_plan of include/pde_sweep.h; nothing is launched, no GPU
+    is needed): dict with the lists kernel_mode, ktaps, conv_log2 (one entry per width; conv_log2 0 where no transform runs),
+    ktaps_max, conv_log2_max, lds_bytes, fields_in_lds and convolution ("direct" | "spectral").  ApsError when a width is not
+    finite and > 0 under a Gaussian kernel, or the shape is not eligible."""
+    lib = _lib()
+    conv = _check_convolution(convolution)
+    if nsteps is None:
+        nsteps = int(T / dt) if T is not None else 0
+    ks = np.ascontiguousarray(np.atleast_1d(np.asarray(kernel_sigmas, dtype=np.float64)))
+    if ks.ndim != 1:
+        raise ValueError("kernel_sigmas must be a scalar or one-dimensional")
+    S = len(ks)
+    par = _params(L=L, xlim=xlim, dt=dt, nsteps=nsteps, gamma=gamma, lam=lam, bc=bc, active_model=active_model,
+                  gaussian_kernel=gaussian_kernel, kernel_sigma=0.0, snapshot_interval=snapshot_interval, n_tracers=n_tracers,
+                  n_fft_modes=_check_fft_modes(fft_modes, L) or 0, seed=0, device=device, convolution=conv)
+    info = PdekPlanInfo()
+    mode, kt, lg = (np.zeros(S, np.int32) for _ in range(3))
+    rc = lib.pdek_plan(C.byref(par), S, _p(ks), C.byref(info), _p(mode), _p(kt), _p(lg))
+    if rc != 0:
+        raise capi.ApsError(rc, lib.pdek_last_error().decode())
+    out = dict(kernel_mode=mode.tolist(), ktaps=kt.tolist(), conv_log2=lg.tolist())
+    out.update({name: getattr(info, name) for name, _ in PdekPlanInfo._fields_})
+    out["fields_in_lds"] = bool(info.fields_in_lds)
+    out["convolution"] = "spectral" if conv else "direct"
+    return out
+
+
+def solve_sweep_raw(*, L, xlim, dt, nsteps, gamma, lam, betas, kernel_sigmas, bc, active_model, gaussian_kernel,
+                    snapshot_interval, rho_p0, rho_m0, tracer_x0=None, tracer_s0=None, rand_u=None, rand_n=None,
+                    n_fft_modes=0, seed=0, device=0, want_snapshots=True, fft_modes=None, convolution=None):
+    """`solve_batch_raw` with a kernel width per system (pdek_solve of include/pde_sweep.h): `betas` and `kernel_sigmas` are
+    broadcast against each other, system s runs (betas[s], kernel_sigmas[s]) on its own workgroup, all in ONE launch; the same
+    dict of arrays with a leading system axis.  convolution: None / "direct" = the direct sum of `solve_batch_raw`,
+    "spectral" = the Gaussian-kernel magnetisation by a transform in the workgroup's LDS (see `sweep_plan` for what is eligible)."""
+    lib = _lib()
+    conv = _check_convolution(convolution)
+    fm = _check_fft_modes(fft_modes, L)
+    if fm is not None:
+        n_fft_modes = fm
+    betas, ks = _sweep_axes(betas, kernel_sigmas)
+    S = len(betas)
+    if bc not in ("periodic", "neumann"):
+        raise ValueError("bc must be 'periodic' or 'neumann'")
+    rho_p0 = np.ascontiguousarray(np.broadcast_to(rho_p0, (S, L)), dtype=np.float64)
+    rho_m0 = np.ascontiguousarray(np.broadcast_to(rho_m0, (S, L)), dtype=np.float64)
+    ntr = 0 if tracer_x0 is None else np.shape(tracer_x0)[-1]
+    if ntr:
+        tracer_x0 = np.ascontiguousarray(np.broadcast_to(tracer_x0, (S, ntr)), dtype=np.float64)
+        tracer_s0 = np.ascontiguousarray(np.broadcast_to(tracer_s0, (S, ntr)), dtype=np.int8)
+    if rand_u is not None:
+        rand_u = np.ascontiguousarray(np.broadcast_to(rand_u, (S, nsteps + 1, ntr)), dtype=np.float64)
+        rand_n = np.ascontiguousarray(np.broadcast_to(rand_n, (S, nsteps + 1, ntr)), dtype=np.float64)
+    par = _params(L=L, xlim=xlim, dt=dt, nsteps=nsteps, gamma=gamma, lam=lam, bc=bc, active_model=active_model,
+                  gaussian_kernel=gaussian_kernel, kernel_sigma=0.0, snapshot_interval=snapshot_interval,
+                  n_tracers=ntr, n_fft_modes=n_fft_modes, seed=seed, device=device, convolution=conv)
+    n_snap = nsteps // snapshot_interval + 1
+    out = dict(rho_p=np.zeros((S, L)), rho_m=np.zeros((S, L)), m_series=np.zeros((S, nsteps + 1)),
+               var_series=np.zeros((S, nsteps + 1)), v_eff_series=np.full((S, nsteps + 1), np.nan),
+               D_eff_series=np.full((S, nsteps + 1), np.nan))
+    snaps = np.zeros((S, n_snap, L)) if want_snapshots else None
+    msnaps = np.zeros((S, n_snap, L)) if want_snapshots else None
+    fre = np.zeros((S, nsteps + 1, n_fft_modes)) if n_fft_modes else None
+    fim = np.zeros((S, nsteps + 1, n_fft_modes)) if n_fft_modes else None
+    tx = np.zeros((S, ntr)) if ntr else None
+    ts = np.zeros((S, ntr), np.int8) if ntr else None
+    ms = C.c_double()
+    rc = lib.pdek_solve(C.byref(par), S, _p(betas), _p(ks), _p(rho_p0), _p(rho_m0), _p(tracer_x0) if ntr else None,
+                        _p(tracer_s0) if ntr else None, _p(rand_u), _p(rand_n), _p(out["rho_p"]), _p(out["rho_m"]),
+                        _p(out["m_series"]), _p(out["var_series"]), _p(out["v_eff_series"]) if ntr else None,
+                        _p(out["D_eff_series"]) if ntr else None, _p(snaps), _p(msnaps), _p(fre), _p(fim), _p(tx), _p(ts),
+                        C.byref(ms))
+    if rc != 0:
+        raise capi.ApsError(rc, lib.pdek_last_error().decode())
+    out.update(snapshots=snaps, m_snapshots=msnaps, fft_re=fre, fft_im=fim, tracers_unwrapped=tx, tracer_state=ts,
+               times=np.arange(n_snap) * snapshot_interval * dt, kernel_ms=ms.value)
+    return out
+
+
 class IMEXPDE:
     def __init__(self, L=1000, xlim=1.0, T=10.0, dt=5e-4, gamma=2.33e-4, lam=0.6, beta=2.0, bc="periodic",
                  active_model="bidirectional", gaussian_kernel=False, kernel_sigma=0.02, snapshot_interval=50,
@@ -335,6 +445,21 @@ class IMEXPDE:
         return self._run(betas, self.rho_p, self.rho_m, self.tracers_unwrapped if self.n_tracers else None,
                          self.tracer_state if self.n_tracers else None, want_snapshots=want_snapshots)
 
+    def solve_sweep(self, betas=None, kernel_sigmas=None, convolution=None, want_snapshots=False):
+        """This instance's initial condition evolved for every (beta, kernel_sigma) pair in ONE launch on the one-workgroup
+        shape (`solve_sweep_raw`): betas and kernel_sigmas are broadcast against each other, each defaults to the instance's
+        own value.  convolution: None / "direct" or "spectral" (the transform in LDS).  Returns the raw dict of arrays."""
+        seed = self.seed if self.seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
+        fm = self.fft_modes if self.fft_modes is not None else (self.L // 2 + 1 if self.record_fft else 0)
+        return solve_sweep_raw(L=self.L, xlim=self.xlim, dt=self.dt, nsteps=self.nsteps, gamma=self.gamma, lam=self.lam,
+                               betas=self.beta if betas is None else betas,
+                               kernel_sigmas=self.kernel_sigma if kernel_sigmas is None else kernel_sigmas,
+                               bc=self.bc, active_model=self.active_model, gaussian_kernel=self.gaussian_kernel,
+                               snapshot_interval=self.snapshot_interval, rho_p0=self.rho_p, rho_m0=self.rho_m,
+                               tracer_x0=self.tracers_unwrapped if self.n_tracers else None,
+                               tracer_s0=self.tracer_state if self.n_tracers else None, n_fft_modes=fm, seed=seed,
+                               device=self.device, want_snapshots=want_snapshots, convolution=convolution)
+
     def get_output(self):                                          # ref :293-306
         return dict(rho_p=self.rho_p, rho_m=self.rho_m, m_series=self.m_series, var_series=self.var_series,
                     fft_amp=self.fft_amp, fft_phase=self.fft_phase, snapshots=np.array(self.snapshots),
@@ -380,3 +505,42 @@ def sweep_over_betas(beta_values, n_runs=3, t_min=20.0, t_max=40.0, seeds=None, 
     D = np.nanmean(r["D_eff_series"][:, mask], axis=1).reshape(len(beta_values), n_runs)
     root = np.sqrt(n_runs)
     return (v.mean(axis=1), v.std(axis=1, ddof=1) / root, D.mean(axis=1), D.std(axis=1, ddof=1) / root, r["kernel_ms"])
+
+
+def sweep_over_kernel_sigmas(kernel_sigma_values, n_runs=5, base_seed=100, init_kwargs=None, convolution=None, **ctor_kwargs):
+    """The reference's kernel-width sweep (IMEX_PDE_solver_run_sweep_magn.py:55-85) as ONE launch: system (k, r) is the solver
+    of kernel_sigma_values[k] constructed with seed = base_seed + 1000 k + r and initialised on the host like the driver does.
+    Returns a dict: each sigma -> dict of arrays [n_runs, nsteps + 1] with the four quantities the driver collects,
+    m_series = |m_series|, v_eff_series = |v_eff_series|, D_eff_series, var_series; and "kernel_ms".
+    The result is keyed by the sigma values themselves (the driver's `results[kernel_sigma]`) next to the one string key
+    "kernel_ms", so a width given twice is refused (ValueError): its second block of runs would replace the first.
+    convolution: None / "direct" or "spectral" as in `solve_sweep_raw`."""
+    init_kwargs = dict(init_kwargs or {})
+    kernel_sigma_values = list(kernel_sigma_values)
+    if len(set(float(v) for v in kernel_sigma_values)) != len(kernel_sigma_values):
+        raise ValueError(f"kernel_sigma_values holds a width twice ({kernel_sigma_values}): the result is keyed by the width")
+    if not kernel_sigma_values or n_runs < 1:
+        raise ValueError("sweep_over_kernel_sigmas needs at least one width and n_runs >= 1")
+    ctor_kwargs.setdefault("gaussian_kernel", True)                # ref :68
+    sig, rp, rm, tx, ts = [], [], [], [], []
+    proto = None
+    for k, sigma in enumerate(kernel_sigma_values):
+        for run in range(n_runs):
+            s = IMEXPDE(kernel_sigma=sigma, seed=base_seed + 1000 * k + run, record_fft=False, **ctor_kwargs)
+            s.initialize(**init_kwargs)
+            if proto is None:
+                proto = s
+            sig.append(float(sigma)); rp.append(s.rho_p); rm.append(s.rho_m); tx.append(s.tracers_unwrapped); ts.append(s.tracer_state)
+    ntr = proto.n_tracers
+    r = solve_sweep_raw(L=proto.L, xlim=proto.xlim, dt=proto.dt, nsteps=proto.nsteps, gamma=proto.gamma, lam=proto.lam,
+                        betas=proto.beta, kernel_sigmas=sig, bc=proto.bc, active_model=proto.active_model,
+                        gaussian_kernel=proto.gaussian_kernel, snapshot_interval=proto.snapshot_interval, rho_p0=np.array(rp),
+                        rho_m0=np.array(rm), tracer_x0=np.array(tx) if ntr else None, tracer_s0=np.array(ts) if ntr else None,
+                        seed=proto.seed or 0, device=proto.device, want_snapshots=False, convolution=convolution)
+    out = {}
+    for k, sigma in enumerate(kernel_sigma_values):
+        rows = slice(k * n_runs, (k + 1) * n_runs)
+        out[sigma] = dict(m_series=np.abs(r["m_series"][rows]), v_eff_series=np.abs(r["v_eff_series"][rows]),
+                          D_eff_series=r["D_eff_series"][rows], var_series=r["var_series"][rows])
+    out["kernel_ms"] = r["kernel_ms"]
+    return out

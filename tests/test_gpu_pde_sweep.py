@@ -1,0 +1,235 @@
+"""GPU suite (-m gpu): the kernel-width sweep of the hydrodynamic-limit solver (include/pde_sweep.h) -- a kernel width per
+system in one launch, and the Gaussian-kernel magnetisation by a transform in the workgroup's LDS -- against
+oracle/pde_numpy.py, against the one-width path (pde_solve_batch) and against itself.
+
+The bars are those of tests/test_gpu_pde.py, taken over as they are (binary64; the oracle multiplies rffts, the device sums
+the taps directly or multiplies its own complex transforms):
+    densities, m_series, var_series, snapshots ........ 1e-11 relative to the field's scale
+    fft modes ......................................... 1e-12 absolute
+    tracer spin states ................................ equal
+    tracer positions, v_eff / D_eff series ............ 1e-9 when fed the oracle's recorded random numbers
+Where two device runs must agree they must agree in every bit (np.array_equal)."""
+import importlib
+
+import numpy as np
+import pytest
+
+from oracle.pde_numpy import PdeOracle
+
+pytestmark = pytest.mark.gpu
+PKG = "hydrodynamic-limits-of-active-particle-systems-with-mean-field-interactions_amd"
+
+
+@pytest.fixture(scope="module")
+def pde():
+    mod = importlib.import_module(PKG + ".pde")
+    assert importlib.import_module(PKG + ".capi").device_count() >= 1
+    return mod
+
+
+def close(a, b, tol, what):
+    scale = max(np.nanmax(np.abs(b)), 1e-300)
+    err = np.nanmax(np.abs(np.asarray(a) - np.asarray(b))) / scale
+    print(what, f"{err:.3e}")
+    assert err <= tol, (what, err)
+    assert np.array_equal(np.isnan(a), np.isnan(b)), what
+
+
+# The four bc x active-model combinations of CASES in tests/test_gpu_pde.py, each as one launch of all five widths from the
+# "homogeneous" initial condition (densities 1 +- 0.2 before normalisation, nowhere near zero); and the two of them that start
+# from "poisson" there once more from that state, which has sites clipped to exactly zero, without the narrowest width.  The
+# oracle itself cannot hold the bar from "poisson" at sigma = 0.0005: with one tap of 1.5e-8 either side, den + 1e-12 is ~1e-12
+# on an empty site, and the round-off of the oracle's rfft products (~1e-17) is divided by it.  Measured on the host, no device
+# involved, L = 333, 60 steps, the oracle's magnetization() against the same sum accumulated directly in extended precision:
+#     poisson,     sigma 0.0005:  max pointwise 8.3e-07, mean over sites 2.6e-10   (bar on m_series: 1e-11 of ~0.035 = 3.5e-13)
+#     poisson,     sigma 0.02:    7.2e-16, 4.9e-17
+#     homogeneous, sigma 0.0005:  3.3e-16, 3.0e-18
+#     homogeneous, sigma 0.02:    5.6e-17, 3.5e-18
+# From 0.02 on the oracle holds the bar on exact zeros, so both forms of the convolution are compared with it there.
+CASES = [
+    dict(tag="periodic_bidirectional", bc="periodic", active_model="bidirectional", init="homogeneous", first=0),
+    dict(tag="neumann_anchored", bc="neumann", active_model="anchored_minus", init="homogeneous", first=0),
+    dict(tag="periodic_anchored", bc="periodic", active_model="anchored_minus", init="homogeneous", first=0),
+    dict(tag="neumann_bidirectional", bc="neumann", active_model="bidirectional", init="homogeneous", first=0),
+    dict(tag="periodic_bidirectional_poisson", bc="periodic", active_model="bidirectional", init="poisson", first=1),
+    dict(tag="neumann_anchored_poisson", bc="neumann", active_model="anchored_minus", init="poisson", first=1),
+]
+SIGMAS = [0.0005, 0.02, 0.3, 1e5 - 10, 2e5]
+BETAS = [0.5, 1.0, 1.5, 2.0, 2.5]
+BASE = dict(xlim=1.0, dt=5e-4, gamma=2.33e-4, lam=0.6)
+_oracles = {}
+
+
+def oracles(L, case):
+    """The oracle runs of (L, case), one per width from SIGMAS[case["first"]] on, computed once and shared by both forms of the
+    convolution; never modified."""
+    key = (L, case["tag"])
+    if key not in _oracles:
+        runs = []
+        for sigma, beta in zip(SIGMAS[case["first"]:], BETAS[case["first"]:]):
+            o = PdeOracle(L=L, T=0.1, beta=beta, kernel_sigma=sigma, bc=case["bc"], active_model=case["active_model"],
+                          gaussian_kernel=True, snapshot_interval=100, seed=321, **BASE)
+            o.initialize(mode=case["init"], rho0=1.0, noise=0.2, n_tracers=257)
+            start = dict(rho_p=o.rho_p.copy(), rho_m=o.rho_m.copy(), tx=o.tracers_unwrapped.copy(), ts=o.tracer_state.copy())
+            o.solve(record_randoms=True)
+            runs.append((start, o, np.array(o.rand_u), np.array(o.rand_n)))
+        _oracles[key] = runs
+    return _oracles[key]
+
+
+def raw_kw(L, nsteps, bc="periodic", active_model="bidirectional", gaussian_kernel=True, snapshot_interval=100, **over):
+    kw = dict(L=L, nsteps=nsteps, bc=bc, active_model=active_model, gaussian_kernel=gaussian_kernel,
+              snapshot_interval=snapshot_interval, **BASE)
+    kw.update(over)
+    return kw
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c["tag"])
+@pytest.mark.parametrize("L", [333, 334])
+@pytest.mark.parametrize("convolution", ["direct", "spectral"])
+def test_mixed_widths_in_one_launch_match_their_oracles(pde, convolution, L, case):
+    runs = oracles(L, case)
+    sigmas, betas = SIGMAS[case["first"]:], BETAS[case["first"]:]
+    r = pde.solve_sweep_raw(betas=betas, kernel_sigmas=sigmas, convolution=convolution,
+                            rho_p0=np.array([s["rho_p"] for s, *_ in runs]), rho_m0=np.array([s["rho_m"] for s, *_ in runs]),
+                            tracer_x0=np.array([s["tx"] for s, *_ in runs]), tracer_s0=np.array([s["ts"] for s, *_ in runs]),
+                            rand_u=np.array([u for *_, u, _ in runs]), rand_n=np.array([g for *_, g in runs]),
+                            fft_modes=L // 2 + 1, **raw_kw(L, 200, bc=case["bc"], active_model=case["active_model"]))
+    for s, (_, orc, _, _) in enumerate(runs):
+        want = orc.get_output()
+        tag = (convolution, L, case["tag"], sigmas[s])
+        for k in ("rho_p", "rho_m", "m_series", "var_series", "snapshots", "m_snapshots"):
+            close(r[k][s], want[k], 1e-11, tag + (k,))
+        assert np.array_equal(r["times"], want["times"])
+        assert np.max(np.abs(r["fft_re"][s] + 1j * r["fft_im"][s] - want["fft_phase"])) <= 1e-12
+        assert np.max(np.abs(np.abs(r["fft_re"][s] + 1j * r["fft_im"][s]) - want["fft_amp"])) <= 1e-12
+        assert np.array_equal(r["tracer_state"][s], orc.tracer_state), tag
+        close(r["tracers_unwrapped"][s], orc.tracers_unwrapped, 1e-9, tag + ("tracers",))
+        close(r["v_eff_series"][s], want["v_eff_series"], 1e-9, tag + ("v_eff",))
+        close(r["D_eff_series"][s], want["D_eff_series"], 1e-9, tag + ("D_eff",))
+
+
+def largest_ring_wide_L(pde):
+    capi = importlib.import_module(PKG + ".capi")
+    for L in range(3072, 3, -1):
+        try:
+            p = pde.sweep_plan(L=L, gaussian_kernel=True, kernel_sigmas=[1.0], convolution="spectral")
+        except capi.ApsError as e:
+            assert "eligible" in str(e)
+            continue
+        assert p["ktaps"] == [L // 2] and p["fields_in_lds"] and p["lds_bytes"] <= 160 * 1024
+        return L
+    raise AssertionError("no ring-wide L is eligible")
+
+
+EDGES = [dict(tag="window_fills_M", L=256, sigma=0.3, m=9),
+         dict(tag="one_word_over", L=257, sigma=0.3, m=10),
+         dict(tag="M_below_one_pass", L=12, sigma=0.3, m=8),
+         dict(tag="driver_setting_gamma_0", L=1000, sigma=0.1, m=11, gamma=0.0),
+         dict(tag="largest_ring_wide", L=None, sigma=1.0, m=11)]
+
+
+@pytest.mark.parametrize("edge", EDGES, ids=lambda e: e["tag"])
+def test_transform_edges_match_the_oracle(pde, edge):
+    L = edge["L"] if edge["L"] is not None else largest_ring_wide_L(pde)
+    if edge["L"] is None:
+        print("largest ring-wide L", L)
+        assert L >= 1000                                             # the reference drivers' shape must be eligible
+    plan = pde.sweep_plan(L=L, gaussian_kernel=True, kernel_sigmas=[edge["sigma"]], convolution="spectral")
+    assert plan["conv_log2"] == [edge["m"]] and plan["ktaps"] == [L // 2]
+    kw = dict(L=L, xlim=1.0, T=0.05, dt=5e-4, gamma=edge.get("gamma", 2.33e-4), lam=0.6, beta=0.75, bc="periodic",
+              active_model="bidirectional", gaussian_kernel=True, kernel_sigma=edge["sigma"], snapshot_interval=50, seed=77)
+    orc = PdeOracle(**kw)
+    orc.initialize(mode="homogeneous", rho0=1.0, noise=0.3, n_tracers=0)
+    gpu = pde.IMEXPDE(record_fft=False, **kw)
+    gpu.initialize(mode="homogeneous", rho0=1.0, noise=0.3, n_tracers=0)
+    assert np.array_equal(gpu.rho_p, orc.rho_p) and gpu.nsteps == 100
+    orc.solve()
+    r = gpu.solve_sweep(convolution="spectral", want_snapshots=True)
+    want = orc.get_output()
+    for k in ("rho_p", "rho_m", "m_series", "var_series", "snapshots", "m_snapshots"):
+        close(r[k][0], want[k], 1e-11, (edge["tag"], L, k))
+
+
+def test_companions_do_not_matter(pde):
+    L, nsteps = 333, 60
+    rng = np.random.default_rng(5)
+    rho_p0, rho_m0 = rng.random(L) / L, rng.random(L) / L
+    tx0, ts0 = rng.random(64), rng.choice([-1, 1], 64)
+    kw = dict(rho_p0=rho_p0, rho_m0=rho_m0, tracer_x0=tx0, tracer_s0=ts0, fft_modes=5, seed=9, convolution="spectral",
+              **raw_kw(L, nsteps, snapshot_interval=20))
+    a, b, c = (0.02, 1.0), (0.3, 2.0), (0.0005, 1.5)               # (sigma, beta): m = 9, 10, 9
+    first = pde.solve_sweep_raw(kernel_sigmas=[a[0], b[0], c[0]], betas=[a[1], b[1], c[1]], **kw)
+    again = pde.solve_sweep_raw(kernel_sigmas=[a[0], b[0], c[0]], betas=[a[1], b[1], c[1]], **kw)
+    other = pde.solve_sweep_raw(kernel_sigmas=[0.004, b[0], 2e5], betas=[0.3, b[1], 2.2], **kw)       # b with other companions, largest m still 10
+    small = pde.solve_sweep_raw(kernel_sigmas=[a[0], 0.01, c[0]], betas=[a[1], 0.7, c[1]], **kw)      # a and c under a largest m of 9
+    keys = [k for k, v in first.items() if isinstance(v, np.ndarray) and k != "times"]
+    assert {"rho_p", "rho_m", "m_series", "var_series", "snapshots", "fft_re", "tracers_unwrapped", "tracer_state", "v_eff_series"} <= set(keys)
+    for k in keys:
+        assert np.array_equal(first[k], again[k], equal_nan=True), k                                  # a repeated call: equal bits
+        assert np.array_equal(first[k][1], other[k][1], equal_nan=True), k                            # same index, other companions
+        assert np.array_equal(first[k][0], small[k][0], equal_nan=True), k
+        assert np.array_equal(first[k][2], small[k][2], equal_nan=True), k
+    # a launch of its own (index 0: the device's tracer noise differs with the index, fields and their series do not)
+    for s, (sigma, beta) in enumerate((a, b, c)):
+        one = pde.solve_sweep_raw(kernel_sigmas=[sigma], betas=[beta], **kw)
+        for k in ("rho_p", "rho_m", "m_series", "var_series", "snapshots", "m_snapshots", "fft_re", "fft_im"):
+            assert np.array_equal(first[k][s], one[k][0]), (s, k)
+    assert not np.array_equal(first["rho_p"][0], first["rho_p"][1])
+
+
+@pytest.mark.parametrize("gaussian_kernel,sigma", [(True, 0.02), (True, 1e5 - 10), (False, 0.02)], ids=["sigma_0.02", "ring_wide", "local"])
+def test_direct_form_is_the_one_width_path_bit_for_bit(pde, gaussian_kernel, sigma):
+    L, nsteps = 334, 120
+    rng = np.random.default_rng(11)
+    B = [0.5, 1.7, 2.6]
+    kw = dict(rho_p0=rng.random((3, L)) / L, rho_m0=rng.random((3, L)) / L, tracer_x0=rng.random((3, 100)),
+              tracer_s0=rng.choice([-1, 1], (3, 100)), fft_modes=7, seed=1234,           # device-side tracer noise: same index, same seed
+              **raw_kw(L, nsteps, gaussian_kernel=gaussian_kernel, snapshot_interval=40))
+    old = pde.solve_batch_raw(kernel_sigma=sigma, betas=B, **kw)
+    new = pde.solve_sweep_raw(kernel_sigmas=[sigma] * 3, betas=B, convolution=None, **kw)
+    assert set(old) == set(new)
+    for k, v in old.items():
+        if isinstance(v, np.ndarray):
+            assert np.array_equal(v, new[k], equal_nan=True), k
+    assert np.isfinite(new["v_eff_series"][:, -1]).all() and np.ptp(new["tracers_unwrapped"]) > 0
+
+
+def test_driver_call_returns_what_the_reference_driver_collects(pde):
+    sig = [0.0005, 0.05, 1.0]
+    ctor = dict(L=200, T=0.05, dt=5e-4, gamma=0.2, lam=0.6, beta=0.75, bc="periodic", active_model="bidirectional",
+                gaussian_kernel=True, snapshot_interval=50)
+    init = dict(mode="homogeneous", rho0=1.0, noise=0.3, n_tracers=50)
+    for conv in (None, "spectral"):
+        out = pde.sweep_over_kernel_sigmas(sig, n_runs=2, init_kwargs=init, convolution=conv, **ctor)
+        assert set(out) == set(sig) | {"kernel_ms"} and out["kernel_ms"] > 0
+        for k, sigma in enumerate(sig):
+            assert set(out[sigma]) == {"m_series", "v_eff_series", "D_eff_series", "var_series"}
+            for name, arr in out[sigma].items():
+                assert arr.shape == (2, 101), (sigma, name)
+            assert (out[sigma]["m_series"] >= 0).all() and np.isnan(out[sigma]["v_eff_series"][:, 0]).all()
+            assert np.isfinite(out[sigma]["v_eff_series"][:, -1]).all() and (out[sigma]["v_eff_series"][:, -1] >= 0).all()
+            for r in range(2):
+                one = pde.IMEXPDE(seed=100 + 1000 * k + r, kernel_sigma=sigma, record_fft=False, **ctor)
+                one.initialize(**init)
+                one.solve()
+                close(out[sigma]["m_series"][r], np.abs(one.m_series), 1e-11, (conv, sigma, r, "m_series"))
+                close(out[sigma]["var_series"][r], one.var_series, 1e-11, (conv, sigma, r, "var_series"))
+
+
+def test_spectral_is_faster_where_the_kernel_spans_the_ring(pde):
+    """L = 1000, sigma = 0.1 (500 taps either side), four beta, 400 steps: the transform's only purpose is speed, so it has to
+    win against the direct sum (the arithmetic of pde_solve_batch), both measured here after a warm-up call.
+    tools/time_pde_sweep.py times the same shape as its last row."""
+    L = 1000
+    rng = np.random.default_rng(3)
+    kw = dict(rho_p0=(1.0 + 0.3 * rng.random(L)) / (2 * L), rho_m0=(1.0 + 0.3 * rng.random(L)) / (2 * L), betas=[0.5, 0.75, 1.5, 2.5],
+              kernel_sigmas=0.1, want_snapshots=False, **raw_kw(L, 400, snapshot_interval=400, gamma=0.2))
+    ms = {}
+    for conv in ("direct", "spectral"):
+        pde.solve_sweep_raw(convolution=conv, **dict(kw, nsteps=4, snapshot_interval=4))
+        ms[conv] = pde.solve_sweep_raw(convolution=conv, **kw)
+    print(f"direct {ms['direct']['kernel_ms']:.3f} ms, spectral {ms['spectral']['kernel_ms']:.3f} ms, "
+          f"ratio {ms['direct']['kernel_ms'] / ms['spectral']['kernel_ms']:.2f}")
+    close(ms["spectral"]["m_series"], ms["direct"]["m_series"], 1e-11, "m_series, spectral against direct")
+    assert ms["spectral"]["kernel_ms"] < ms["direct"]["kernel_ms"]
