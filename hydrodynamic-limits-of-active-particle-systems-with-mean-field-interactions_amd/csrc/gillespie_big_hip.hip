@@ -22,12 +22,14 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gillespie.h"
 #include "gillespie_many.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"
+#include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiation only)
 
 namespace {
 
@@ -195,7 +197,12 @@ __device__ inline void big_scalar_sums(const int *pos, const uint8_t *flg, int *
     __syncthreads();
 }
 
-__global__ __launch_bounds__(BT) void gil_big_kernel(const BigArgs a0) {
+struct GilsBigArgs : BigArgs { GilsArgs st; };              // arguments of the structure instantiation
+
+// ST = also reduce the structure sums at an observation (gillespie_structure.hpp): a compile-time property, so that the
+// kernel without it is the code it was before they existed.
+template <bool ST>
+__global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<ST, GilsBigArgs, BigArgs> a0) {
     extern __shared__ double lds[];
     BigArgs a = a0;
     select_system(a, (size_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x));
@@ -265,6 +272,15 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const BigArgs a0) {
         if (a.scalars)
             big_scalar_sums(a.pos, a.flg, a.ref, a.occ, a.occp, a.block_table, a.front_lo, a.scalars + (size_t)k * GIL_NSCALARS,
                             acc, N, L, K, k == a.p.ref_obs, a.p.x_wall, n_ev);
+        if constexpr (ST) {
+            const GilsArgs &sa = a0.st;
+            if (k >= sa.first_obs) {
+                double mg = 0.0;                               // global-mean mode: the one value of every site (ref :219-221)
+                if (!M.field_mode && gsum_n > 0) { mg = (double)gsum_s / (double)gsum_n; mg = mg > 1.0 ? 1.0 : (mg < -1.0 ? -1.0 : mg); }
+                gils_record_row<BT>(sa.rows + ((size_t)blockIdx.x * nobs + k) * (size_t)(4 + 2 * sa.k_max), sa.k_max, L, N, a.pos, a.flg,
+                                    a.occ, a.W, a.S, M.field_mode != 0, mg, sa.phase, reinterpret_cast<double *>(ctl + 32), a.work);
+            }
+        }
     };
     record(0);
     k_obs = 1;
@@ -540,6 +556,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const BigArgs a0) {
     }
 }
 
+
 // What a batch of p->n_systems large systems needs, by host arithmetic alone (gilm_plan); the weight table comes back
 // through `table` where the caller wants it.  0, or e_arg with the text in `err`.
 int big_plan(const char *who, std::string &err, const gil_params *p, bool want_states, bool want_scalars, gilm_plan_info *out,
@@ -573,12 +590,19 @@ int big_plan(const char *who, std::string &err, const gil_params *p, bool want_s
 // their required pointers and S.  pos0 / sigma0 / bound0 hold [S][n_cap] entries (a single system: its n0[0] particles).
 int big_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
             const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
-            int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
+            int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
+            int k_max = 0, int first_obs = 0, double *structure_obs = nullptr) {
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilm_plan_info info{};
     std::vector<double> table;
     if (int rc = big_plan(who, err, p, pos_obs || sigma_obs || flags_obs, scalars_obs != nullptr, &info, &table)) return rc;
     const int S = p->n_systems, L = p->L, N = p->n_cap;
+    const size_t row = 4 + 2 * (size_t)k_max;                 // of structure sums (gils_run)
+    if (structure_obs) {
+        info.lds_bytes += (int32_t)(gils_lds_doubles(BT) * sizeof(double));
+        info.output_bytes += (int64_t)S * p->n_obs * (int64_t)row * 8;
+        if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
+    }
     for (int s = 0; s < S; ++s) {
         if (n0[s] < 0 || n0[s] > N) return bad("bad n_cap / n0 / n_obs / max_events");
         if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * N, sigma0 + (size_t)s * N)) return bad(why);
@@ -587,10 +611,11 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
     if (int rc = job.select_device(p->device)) return rc;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
-    if ((uint64_t)((int64_t)S * info.work_bytes_per_system + info.output_bytes) > (uint64_t)free_b)
-        return bad("the batch needs " + std::to_string((int64_t)S * info.work_bytes_per_system) + " bytes of work memory and " +
+    const int64_t work_bytes = (int64_t)S * info.work_bytes_per_system + (structure_obs ? (int64_t)L * 16 : 0);
+    if ((uint64_t)(work_bytes + info.output_bytes) > (uint64_t)free_b)
+        return bad("the batch needs " + std::to_string(work_bytes) + " bytes of work memory and " +
                    std::to_string(info.output_bytes) + " bytes of outputs, the device has " + std::to_string(free_b) + " bytes free");
-    BigArgs a{};
+    GilsBigArgs a{};
     a.p = *p; a.tlen = info.table_len; a.nblk = info.n_blocks; a.cb = (a.nblk + BT - 1) / BT;
     a.tab_in_lds = info.table_in_lds;
     a.m = gil_model(p);
@@ -611,21 +636,49 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
     OUT(n_recorded, n_recorded, (size_t)S); OUT(n_events, n_events, (size_t)S); OUT(t_final, t_final, (size_t)S);
     OUT(exits, exits, SN * 3); OUT(n_exits, n_exits, (size_t)S);
     const size_t lds = (size_t)info.lds_bytes;
-    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel), lds)) return rc;
+    GilsArgs &sa = a.st;
+    if (structure_obs) {
+        double *phase = nullptr;
+        if (int rc = job.alloc(&sa.rows, SO * row, "structure_obs")) return rc;
+        if (int rc = job.alloc(&phase, (size_t)2 * L, "phase")) return rc;
+        sa.phase = phase; sa.k_max = k_max; sa.first_obs = first_obs;
+        if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<true>), lds)) return rc;
+        hipLaunchKernelGGL(gils_phase_table, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, nullptr, phase, L);
+    } else if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false>), lds)) return rc;
     if (int rc = job.create_events()) return rc;
-    hipLaunchKernelGGL(big_field_init, dim3((unsigned)((L + 255) / 256), (unsigned)S), dim3(256), 0, nullptr, a);
+    hipLaunchKernelGGL(big_field_init, dim3((unsigned)((L + 255) / 256), (unsigned)S), dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
     job.ev.start();
-    hipLaunchKernelGGL(gil_big_kernel, dim3((unsigned)S), dim3(BT), lds, nullptr, a);
+    if (structure_obs) hipLaunchKernelGGL(gil_big_kernel<true>, dim3((unsigned)S), dim3(BT), lds, nullptr, a);
+    else hipLaunchKernelGGL(gil_big_kernel<false>, dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const BigArgs &>(a));
     job.ev.stop();
     if (int rc = job.finish(hipGetLastError(), "gil_big_kernel", kernel_ms)) return rc;
     DOWN(pos_obs, pos_obs, SO * N * 4); DOWN(sigma_obs, sigma_obs, SO * N); DOWN(flags_obs, flags_obs, SO * N);
     DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8);
     DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8); DOWN(t_final, t_final, (size_t)S * 8);
     DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
+    if (structure_obs) if (int rc = job.download(structure_obs, sa.rows, SO * row * 8, "structure_obs")) return rc;
     return GIL_OK;
 }
 
 }  // namespace
+
+int gils_large_plan(const char *who, std::string &err, const gil_params *p, int32_t *lds_bytes, int64_t *work_bytes) {
+    if (p->n_systems > GILM_MAX_SYSTEMS) { err = std::string(who) + ": n_systems must be in [1, GILM_MAX_SYSTEMS]"; return GIL_ERR_ARG; }
+    gilm_plan_info info{};
+    if (int rc = big_plan(who, err, p, false, false, &info, nullptr)) return rc;
+    *lds_bytes = info.lds_bytes + (int32_t)(gils_lds_doubles(BT) * sizeof(double));
+    *work_bytes = (int64_t)p->n_systems * info.work_bytes_per_system;
+    if (*lds_bytes > 160 * 1024) { err = std::string(who) + ": LDS budget exceeded"; return GIL_ERR_ARG; }
+    return GIL_OK;
+}
+
+int gils_large_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
+                   const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs,
+                   int64_t *scalars_obs, int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits,
+                   double *kernel_ms, int k_max, int first_obs, double *structure_obs) {
+    return big_run(who, err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
+                   t_final, exits, n_exits, kernel_ms, k_max, first_obs, structure_obs);
+}
 
 extern "C" {
 

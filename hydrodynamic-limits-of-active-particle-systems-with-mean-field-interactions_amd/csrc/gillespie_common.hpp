@@ -45,3 +45,14 @@ inline int gil_upload_flip_table(OneShot &job, const gil_params *p, Model &M) {
 }
 
 }  // namespace
+
+// gils_run (gillespie_hip.hip, include/gillespie_structure.h) reaches the large-system kernel of gillespie_big_hip.hip
+// through these two: inside the library only.  The plan gives the LDS bytes of a workgroup with the structure sums'
+// slots and the work bytes of the whole batch; the run is gilm_run's driver with the rows of structure sums.
+__attribute__((visibility("hidden"))) int gils_large_plan(const char *who, std::string &err, const gil_params *p, int32_t *lds_bytes,
+                                                          int64_t *work_bytes);
+__attribute__((visibility("hidden"))) int gils_large_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0,
+                                                         const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0, const double *uniforms,
+                                                         int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+                                                         int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits,
+                                                         int32_t *n_exits, double *kernel_ms, int k_max, int first_obs, double *structure_obs);

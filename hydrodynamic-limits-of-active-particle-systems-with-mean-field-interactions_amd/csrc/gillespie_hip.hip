@@ -20,11 +20,14 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gillespie.h"
+#include "gillespie_structure.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"           // model, initial-state check, the driver of the one-shot entry points
+#include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiations only)
 
 namespace {
 
@@ -58,9 +61,19 @@ __device__ inline long long wg_sum_ll(long long v, long long *red) {
     return s;
 }
 
-// NT = threads per system: one wavefront (no real barriers, six systems per CU by LDS) for small systems, four for large ones
-template <int NT>
-__global__ __launch_bounds__(NT) void gil_kernel(const GilArgs a) {
+struct GilsBatchArgs : GilArgs { GilsArgs st; };            // arguments of the structure instantiations
+
+// the structure sums' slots: behind the loop's own LDS (which ends with the plus-occupancy bytes), at the next multiple of 8
+__device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L) {
+    const size_t end = (size_t)(reinterpret_cast<char *>(occp + ((L + 15) & ~15)) - reinterpret_cast<char *>(lds));
+    return lds + ((end + 7) >> 3);
+}
+
+// NT = threads per system: one wavefront (no real barriers, six systems per CU by LDS) for small systems, four for large ones.
+// ST = also reduce the structure sums at an observation (gillespie_structure.hpp): a compile-time property, so that the
+// kernels without it are the code they were before it existed.
+template <int NT, bool ST>
+__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<ST, GilsBatchArgs, GilArgs> a) {
     extern __shared__ double lds[];
     const Model &M = a.m;
     const int L = M.L, K = M.K, t = threadIdx.x, sys = blockIdx.x, ncap = a.p.n_cap, nobs = a.p.n_obs;
@@ -87,6 +100,12 @@ __global__ __launch_bounds__(NT) void gil_kernel(const GilArgs a) {
                                   ((a.bound0 && a.bound0[(size_t)sys * ncap + i]) ? F_BOUND : 0)) : 0;
         ref[i] = -1;
         rate[i] = 0.0;                                         // empty and departed slots keep rate zero
+    }
+    if constexpr (ST) {
+        if (a.st.phase_in_lds) {
+            double *ptab = gils_slots(lds, occp, L) + gils_lds_doubles(NT);
+            for (int i = t; i < 2 * L; i += NT) ptab[i] = a.st.phase[i];
+        }
     }
     __syncthreads();
     if (t == 0) for (int i = 0; i < n_init; ++i) { occ[pos[i]]++; if (flg[i] & F_PLUS) occp[pos[i]]++; }
@@ -156,6 +175,17 @@ __global__ __launch_bounds__(NT) void gil_kernel(const GilArgs a) {
             a.scalars[((size_t)sys * nobs + k) * GIL_NSCALARS + GS_EVENTS] = n_ev;
         }
         __syncthreads();
+        if constexpr (ST) {
+            const GilsArgs &sa = a.st;
+            if (k >= sa.first_obs) {
+                double mg = 0.0;                               // global-mean mode: the one value of every site (ref :219-221)
+                if (!M.field_mode && gsum_n > 0) { mg = (double)gsum_s / (double)gsum_n; mg = mg > 1.0 ? 1.0 : (mg < -1.0 ? -1.0 : mg); }
+                double *row = sa.rows + ((size_t)sys * nobs + k) * (size_t)(4 + 2 * sa.k_max), *red = gils_slots(lds, occp, L);
+                // two calls: the gathers of the first are LDS reads, of the second global loads
+                if (sa.phase_in_lds) gils_record_row<NT>(row, sa.k_max, L, ncap, pos, flg, occ, W, S, M.field_mode != 0, mg, red + gils_lds_doubles(NT), red, work);
+                else gils_record_row<NT>(row, sa.k_max, L, ncap, pos, flg, occ, W, S, M.field_mode != 0, mg, sa.phase, red, work);
+            }
+        }
     };
 
     record(0);                                                 // ref :489-508
@@ -389,17 +419,32 @@ __global__ __launch_bounds__(NT) void gil_kernel(const GilArgs a) {
     }
 }
 
-}  // namespace
+// threads and dynamic LDS bytes of one system in the batch kernel; st: with the structure sums' slots, and with a copy of the
+// phase table behind them where the 160 KB leave room for it (phase_in_lds)
+void batch_shape(int L, int ncap, int tlen, bool st, int &NT, size_t &lds, bool *phase_in_lds = nullptr) {
+    NT = ncap <= 1024 ? 64 : 256;                             // one wavefront per system while a lane owns at most 16 particles
+    lds = ((size_t)2 * L + ((tlen + 2) & ~1) + ncap + (ncap & 1) + 8 + 5 * NT + 8) * sizeof(double) +
+          ((size_t)3 * ncap + 16) * sizeof(int) + (size_t)((ncap + 15) & ~15) + (size_t)2 * ((L + 15) & ~15);
+    if (st) lds = ((lds + 7) & ~(size_t)7) + gils_lds_doubles(NT) * sizeof(double);
+    if (st && phase_in_lds) {
+        *phase_in_lds = lds + (size_t)16 * L <= 160 * 1024;
+        if (*phase_in_lds) lds += (size_t)16 * L;
+    }
+}
 
-extern "C" {
+// device copies of the outputs of one call (gils_plan_info.output_bytes)
+int64_t gils_output_bytes(const gil_params *p, int k_max, bool states, bool scalars) {
+    const int64_t S = p->n_systems, O = p->n_obs, N = p->n_cap;
+    return S * ((states ? O * N * 6 : 0) + (scalars ? O * GIL_NSCALARS * 8 : 0) + N * 24 + 24 + O * (4 + 2 * (int64_t)k_max) * 8);
+}
 
-const char *gil_last_error(void) { return g_gil_err.c_str(); }
-
-int gil_run_batch(const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
-                  const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
-                  int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
-    auto bad = [&](const char *m) { g_gil_err = std::string("gil_run_batch: ") + m; return GIL_ERR_ARG; };
-    if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs) return bad("null argument");
+// The one host driver of the batch kernel.  structure_obs: gils_run's rows (k_max modes, from observation first_obs on),
+// nullptr for gil_run_batch.  The callers have checked their required pointers.
+int batch_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
+              const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+              int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
+              int k_max, int first_obs, double *structure_obs) {
+    auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     if (p->L < 2 || p->L > GIL_MAX_L) return bad("L must be in [2, GIL_MAX_L]");
     if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
     if (p->n_systems < 1 || p->n_cap < 1 || p->n_cap > GIL_MAX_N || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
@@ -408,13 +453,22 @@ int gil_run_batch(const gil_params *p, const int32_t *n0, const int32_t *pos0, c
         if (n0[s] < 0 || n0[s] > ncap) return bad("n0 outside [0, n_cap]");
         if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * ncap, sigma0 + (size_t)s * ncap)) return bad(why);
     }
-    OneShot job{"gil_run_batch", g_gil_err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: a run may record fewer observations than it has room for
+    OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: a run may record fewer observations than it has room for
     if (int rc = job.select_device(p->device)) return rc;
+    if (structure_obs) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
+        const int64_t work = (int64_t)L * 16, outb = gils_output_bytes(p, k_max, pos_obs || sigma_obs || flags_obs, scalars_obs != nullptr);
+        if ((uint64_t)(work + outb) > (uint64_t)free_b)
+            return bad("the batch needs " + std::to_string(work) + " bytes of work memory and " + std::to_string(outb) +
+                       " bytes of outputs, the device has " + std::to_string(free_b) + " bytes free");
+    }
 
     std::vector<double> table; int tlen = 0, q = 0;
     weight_table(p->sigma_grid, L, p->K, p->periodic != 0, table, tlen, q);
-    GilArgs a{};
-    const int NT = ncap <= 1024 ? 64 : 256;                   // one wavefront per system while a lane owns at most 16 particles
+    GilsBatchArgs a{};
+    int NT; size_t lds; bool phase_in_lds = false;
+    batch_shape(L, ncap, tlen, structure_obs != nullptr, NT, lds, &phase_in_lds);
     a.p = *p; a.tlen = tlen; a.chunk = (ncap + NT - 1) / NT;
     a.m = gil_model(p);
     const size_t SN = (size_t)S * ncap, SO = (size_t)S * p->n_obs;
@@ -430,20 +484,104 @@ int gil_run_batch(const gil_params *p, const int32_t *n0, const int32_t *pos0, c
     OUT(scalars, scalars_obs, SO * GIL_NSCALARS);
     OUT(n_recorded, n_recorded, (size_t)S); OUT(t_final, t_final, (size_t)S); OUT(exits, exits, SN * 3); OUT(n_exits, n_exits, (size_t)S);
     OUT(n_events, n_events, (size_t)S);
-    const size_t lds = ((size_t)2 * L + ((tlen + 2) & ~1) + ncap + (ncap & 1) + 8 + 5 * NT + 8) * sizeof(double) +
-                       ((size_t)3 * ncap + 16) * sizeof(int) + (size_t)((ncap + 15) & ~15) + (size_t)2 * ((L + 15) & ~15);
     if (lds > 160 * 1024) return bad("system does not fit the 160 KB of LDS");
-    if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64>) : reinterpret_cast<const void *>(&gil_kernel<256>), lds)) return rc;
+    const size_t row = 4 + 2 * (size_t)k_max;
+    GilsArgs &sa = a.st;
+    if (structure_obs) {
+        double *phase = nullptr;
+        if (int rc = job.alloc(&sa.rows, SO * row, "structure_obs")) return rc;
+        if (int rc = job.alloc(&phase, (size_t)2 * L, "phase")) return rc;
+        sa.phase = phase; sa.k_max = k_max; sa.first_obs = first_obs; sa.phase_in_lds = phase_in_lds ? 1 : 0;
+        if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, true>) : reinterpret_cast<const void *>(&gil_kernel<256, true>), lds)) return rc;
+        hipLaunchKernelGGL(gils_phase_table, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, nullptr, phase, L);
+    } else if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false>) : reinterpret_cast<const void *>(&gil_kernel<256, false>), lds)) return rc;
     if (int rc = job.create_events()) return rc;
     job.ev.start();
-    if (NT == 64) hipLaunchKernelGGL(gil_kernel<64>, dim3((unsigned)S), dim3(64), lds, nullptr, a);
-    else hipLaunchKernelGGL(gil_kernel<256>, dim3((unsigned)S), dim3(256), lds, nullptr, a);
+    if (structure_obs) {
+        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
+        else hipLaunchKernelGGL((gil_kernel<256, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
+    } else if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilArgs &>(a));
+    else hipLaunchKernelGGL((gil_kernel<256, false>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilArgs &>(a));
     job.ev.stop();
     if (int rc = job.finish(hipGetLastError(), "gil_kernel", kernel_ms)) return rc;
     DOWN(pos_obs, pos_obs, SO * ncap * 4); DOWN(sigma_obs, sigma_obs, SO * ncap); DOWN(flags_obs, flags_obs, SO * ncap);
     DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8); DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8);
     DOWN(t_final, t_final, (size_t)S * 8); DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
+    if (structure_obs) if (int rc = job.download(structure_obs, sa.rows, SO * row * 8, "structure_obs")) return rc;
     return GIL_OK;
+}
+
+std::string g_gils_err;
+
+// the checks gils_plan and gils_run share, and the shape: 0 with `info` filled, or GIL_ERR_ARG with the text in g_gils_err
+int gils_decide(const char *who, const gil_params *p, int k_max, int first_obs, bool states, bool scalars, gils_plan_info &info) {
+    auto bad = [&](const std::string &m) { g_gils_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    if (p->L < 2) return bad("L must be at least 2");
+    if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
+    if (k_max < 1 || k_max > std::min(p->L, GILS_MAX_K)) return bad("k_max must be in [1, min(L, GILS_MAX_K)]");
+    if (first_obs < 0 || first_obs > p->n_obs) return bad("first_obs must be in [0, n_obs]");
+    info = gils_plan_info{};
+    info.row_len = 4 + 2 * k_max;
+    info.output_bytes = gils_output_bytes(p, k_max, states, scalars);
+    info.shape = GILS_SHAPE_LARGE;
+    if (p->L <= GIL_MAX_L && p->n_cap <= GIL_MAX_N) {
+        if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
+        std::vector<double> table; int tlen = 0, q = 0, NT = 0; size_t lds = 0;
+        weight_table(p->sigma_grid, p->L, p->K, p->periodic != 0, table, tlen, q);
+        bool phase_in_lds = false;
+        batch_shape(p->L, p->n_cap, tlen, true, NT, lds, &phase_in_lds);
+        if (lds <= 160 * 1024) {
+            info.shape = GILS_SHAPE_BATCH; info.threads = NT; info.lds_bytes = (int32_t)lds; info.phase_in_lds = phase_in_lds ? 1 : 0;
+            info.work_bytes = (int64_t)p->L * 16;
+        }
+    }
+    if (info.shape == GILS_SHAPE_LARGE) {
+        int32_t lds = 0; int64_t work = 0;
+        if (int rc = gils_large_plan(who, g_gils_err, p, &lds, &work)) return rc;
+        info.threads = 1024; info.lds_bytes = lds; info.work_bytes = work + (int64_t)p->L * 16;
+    }
+    if (info.work_bytes + info.output_bytes > (1ll << 38))
+        return bad("the batch needs " + std::to_string(info.work_bytes) + " bytes of work memory and " + std::to_string(info.output_bytes) +
+                   " bytes of outputs, more than the " + std::to_string(1ll << 38) + " bytes a plan accepts");
+    return GIL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *gil_last_error(void) { return g_gil_err.c_str(); }
+
+int gil_run_batch(const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
+                  const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+                  int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
+    if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs) { g_gil_err = "gil_run_batch: null argument"; return GIL_ERR_ARG; }
+    return batch_run("gil_run_batch", g_gil_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
+                     n_recorded, n_events, t_final, exits, n_exits, kernel_ms, 0, 0, nullptr);
+}
+
+const char *gils_last_error(void) { return g_gils_err.c_str(); }
+
+int gils_plan(const gil_params *p, int32_t k_max, int32_t first_obs, int32_t want_states, gils_plan_info *out) {
+    if (!p || !out) { g_gils_err = "gils_plan: null argument"; return GIL_ERR_ARG; }
+    gils_plan_info info;
+    if (int rc = gils_decide("gils_plan", p, k_max, first_obs, want_states != 0, true, info)) return rc;
+    *out = info;
+    return GIL_OK;
+}
+
+int gils_run(const gil_params *p, int32_t k_max, int32_t first_obs,
+             const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0, const double *uniforms,
+             int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
+             int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *structure_obs, double *kernel_ms) {
+    if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !structure_obs) { g_gils_err = "gils_run: null argument"; return GIL_ERR_ARG; }
+    gils_plan_info info;
+    if (int rc = gils_decide("gils_run", p, k_max, first_obs, pos_obs || sigma_obs || flags_obs, scalars_obs != nullptr, info)) return rc;
+    if (info.shape == GILS_SHAPE_BATCH)
+        return batch_run("gils_run", g_gils_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
+                         n_recorded, n_events, t_final, exits, n_exits, kernel_ms, k_max, first_obs, structure_obs);
+    return gils_large_run("gils_run", g_gils_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
+                          n_recorded, n_events, t_final, exits, n_exits, kernel_ms, k_max, first_obs, structure_obs);
 }
 
 }  // extern "C"

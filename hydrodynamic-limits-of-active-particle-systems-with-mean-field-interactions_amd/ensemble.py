@@ -4,7 +4,9 @@ together as independent ensembles of one GPU handle, and the per-run observables
 The two outer sweeps of the other drivers are here too: `sweep_over_sigmas` (interaction range,
 ..._sweep_beta_2.py:1030-1075) and `sweep_over_densities` (particle number x beta, ..._double_sweep.py:851-861) --
 one batched handle per sigma / per particle number (the weight table and the state capacity differ), all (beta, run)
-pairs inside it."""
+pairs inside it.  `sweep_betas_for_structures` / `sweep_beta_structure_ensemble` are the pattern study's drivers
+(PARTICLE_solver_BIOLOGY_local_structure.py:105-193), all (beta, run) pairs in one launch, the per-run observables from sums
+taken on the GPU."""
 from __future__ import annotations
 
 import numpy as np
@@ -107,3 +109,59 @@ def sweep_over_densities(n_part_values, beta_values, n_runs_per_beta=4, ps_kwarg
         r["N_part"] = int(n_part)
         out.append(r)
     return out
+
+
+def structure_ensemble_statistics(rows):
+    """The reduction at the end of the reference's sweep_beta_structure_ensemble (PARTICLE_solver_BIOLOGY_local_structure.py
+    :137-165) over the per-run dicts of structure observables; `raw` is the list itself."""
+    n = len(rows)
+    col = {k: np.array([r[k] for r in rows]) for k in ("var_mean", "low_k_power", "dominant_k", "m_local_var", "lowk_variance")}
+    stack = np.stack([r["fft_mean"] for r in rows], axis=0)
+    root = np.sqrt(n)
+    return {"var_mean": col["var_mean"].mean(), "var_se": col["var_mean"].std(ddof=1) / root,
+            "low_k_power_mean": col["low_k_power"].mean(), "low_k_power_se": col["low_k_power"].std(ddof=1) / root,
+            "dominant_k_mode": int(np.round(col["dominant_k"].mean())),
+            "m_local_var_mean": col["m_local_var"].mean(), "m_local_var_se": col["m_local_var"].std(ddof=1) / root,
+            "fft_mean_mean": stack.mean(axis=0), "fft_mean_se": stack.std(axis=0, ddof=1) / root,
+            "lowk_var_mean": col["lowk_variance"].mean(), "lowk_var_se": col["lowk_variance"].std(ddof=1) / root,
+            "raw": rows}
+
+
+def sweep_betas_for_structures(beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwargs, start_fraction=0.5, k_max=None,
+                               rng_seeds=None, dynamics=None):
+    """The reference's structure sweep (PARTICLE_solver_BIOLOGY_local_structure.py:167-193, driver :671-753): {beta: result of
+    sweep_beta_structure_ensemble}.  All (beta, run) pairs run in ONE launch; the per-run structure observables come from sums
+    taken on the GPU at the observations of the window, so nothing of size M x L or M x n_cap exists and `raw` holds the per-run
+    dicts without the reference's 'out'.  `rng_seeds[b][r]` seeds the initial condition of run r at beta b.  `run_kwargs` may
+    hold T, obs_dt and the reference's record_fft / record_var (accepted and ignored: the sums are always taken).
+    `dynamics` as in sweep_over_betas: "exact" (gillespie.run_batched_exact_structure) unless `ps_kwargs` asks for the stepper
+    (`dt` or `mode="sync"`), then "sync" (particle_system.run_batched_structure)."""
+    ps_kwargs, init_kwargs, run_kwargs = dict(ps_kwargs or {}), dict(init_kwargs or {}), dict(run_kwargs or {})
+    if dynamics is None:
+        dynamics = "sync" if (ps_kwargs.get("dt") is not None or ps_kwargs.get("mode") == "sync") else "exact"
+    if dynamics not in ("sync", "exact"):
+        raise ValueError("dynamics must be 'sync' or 'exact'")
+    unknown = set(run_kwargs) - {"T", "obs_dt", "record_fft", "record_var"}
+    if unknown:
+        raise ValueError(f"run_kwargs may hold T, obs_dt, record_fft, record_var; got {sorted(unknown)}")
+    slim = {k: v for k, v in run_kwargs.items() if k in ("T", "obs_dt")}
+    systems, owner = [], []
+    for bi, beta in enumerate(beta_values):
+        for r in range(n_runs_per_beta):
+            rng = None if rng_seeds is None else np.random.default_rng(int(rng_seeds[bi][r]))
+            systems.append(ParticleSystem(beta=beta, rng=rng, **ps_kwargs, **init_kwargs))
+            owner.append(bi)
+    if dynamics == "exact":
+        from .gillespie import run_batched_exact_structure
+        rows = run_batched_exact_structure(systems, start_fraction=start_fraction, k_max=k_max, **slim)
+    else:
+        from .particle_system import run_batched_structure
+        rows = run_batched_structure(systems, start_fraction=start_fraction, k_max=k_max, **slim)
+    return {beta: structure_ensemble_statistics([row for row, o in zip(rows, owner) if o == bi]) for bi, beta in enumerate(beta_values)}
+
+
+def sweep_beta_structure_ensemble(beta, n_runs, ps_kwargs, init_kwargs, run_kwargs, start_fraction=0.5, k_max=None, rng_seeds=None,
+                                  dynamics=None):
+    """One beta, n_runs runs in one launch; the reference's result keys (:146-165).  `rng_seeds[r]` seeds run r."""
+    return sweep_betas_for_structures([beta], n_runs, ps_kwargs, init_kwargs, run_kwargs, start_fraction, k_max,
+                                      None if rng_seeds is None else [rng_seeds], dynamics)[beta]

@@ -1,7 +1,9 @@
 """Device-resident exact Gillespie loop for batches of systems (include/gillespie.h; systems beyond one workgroup's LDS:
 include/gillespie_many.h): the reference's `ParticleSystem.run` as written (one event per iteration,
 PARTICLE_solver_CLASS.py:450-558), one persistent workgroup per system.  `run_batched_exact` returns the reference's
-result dictionaries; `sweep` statistics can be taken from the scalar sums without the M x L arrays (`scalars_only=True`).
+result dictionaries; `sweep` statistics can be taken from the scalar sums without the M x L arrays (`scalars_only=True`),
+and the structure observables from sums the loop takes at every observation (`run_batched_exact_structure`,
+include/gillespie_structure.h).
 
 Differences to the reference: randomness is Philox4x32-10 keyed by `seed` (the reference consumes a NumPy Generator), so
 trajectories agree in distribution, not draw for draw; `m_local_list[k]` is the field of the observed state (the
@@ -36,6 +38,12 @@ class GilmPlanInfo(C.Structure):
                 ("lds_bytes", C.c_int32), ("reserved", C.c_int32), ("work_bytes_per_system", C.c_int64), ("output_bytes", C.c_int64)]
 
 
+class GilsPlanInfo(C.Structure):
+    """struct gils_plan_info of include/gillespie_structure.h, field for field."""
+    _fields_ = [("shape", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32), ("row_len", C.c_int32),
+                ("phase_in_lds", C.c_int32), ("reserved", C.c_int32), ("work_bytes", C.c_int64), ("output_bytes", C.c_int64)]
+
+
 def _lib():
     lib = capi.load()
     if not getattr(lib, "_gil_ready", False):
@@ -50,6 +58,11 @@ def _lib():
         lib.gilm_plan.argtypes = [C.POINTER(GilParams), C.c_int32, C.c_int32, C.POINTER(GilmPlanInfo)]
         lib.gilm_run.restype = C.c_int
         lib.gilm_run.argtypes = [C.POINTER(GilParams)] + [C.c_void_p] * 14 + [C.POINTER(C.c_double)]
+        lib.gils_last_error.restype, lib.gils_last_error.argtypes = C.c_char_p, []
+        lib.gils_plan.restype = C.c_int
+        lib.gils_plan.argtypes = [C.POINTER(GilParams), C.c_int32, C.c_int32, C.c_int32, C.POINTER(GilsPlanInfo)]
+        lib.gils_run.restype = C.c_int
+        lib.gils_run.argtypes = [C.POINTER(GilParams), C.c_int32, C.c_int32] + [C.c_void_p] * 15 + [C.POINTER(C.c_double)]
         lib._gil_ready = True
     return lib
 
@@ -87,12 +100,39 @@ def plan_many_large(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, want
     return {k: int(getattr(info, k)) for k, _ in GilmPlanInfo._fields_ if k != "reserved"}
 
 
+def run_structure_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
+                      minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
+                      anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
+                      block_table=None, device=0, flip_table=None, k_max=None, first_obs=0):
+    """`run_raw` with the structure sums of every observation from `first_obs` on taken inside the event loop (gils_run of
+    include/gillespie_structure.h).  The library picks the kernel: systems that fit a workgroup's LDS run as in `run_raw`,
+    larger ones as in `run_many_large_raw` (system s: Philox key seed + s).  The dictionary of `run_raw` plus
+    `structure` [systems][observations][4 + 2 k_max]: n, sum occ^2, sum m, sum m^2, then Re, Im of the first k_max Fourier sums
+    of the site histogram -- the arguments of observables.DeviceStructure.add.  `k_max=None`: all L modes (at most 4096)."""
+    k_max = min(int(L), 4096) if k_max is None else int(k_max)
+    return _run_batch_entry("gils_run", **locals())
+
+
+def plan_structure(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, k_max, first_obs=0, want_states=True):
+    """gils_plan: which kernel `run_structure_raw` would use (shape 0: systems in LDS, 1: large systems), its threads per system,
+    LDS, work and output bytes, by host arithmetic; no device needed.  Refuses what the run would refuse on these numbers."""
+    lib = _lib()
+    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), sigma_grid=float(sigma_grid), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
+    info = GilsPlanInfo()
+    rc = lib.gils_plan(C.byref(par), int(k_max), int(first_obs), int(bool(want_states)), C.byref(info))
+    if rc != 0:
+        raise capi.ApsError(rc, lib.gils_last_error().decode())
+    return {k: int(getattr(info, k)) for k, _ in GilsPlanInfo._fields_ if k != "reserved"}
+
+
 def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed,
                      minus_anchor, immobilize, suppress_flip, crowding, k_on, k_off, k_exit, anchor_mask, uniforms, max_events,
-                     want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table):
-    """The two batch entry points take the same arguments: gil_run_batch (systems in LDS) and gilm_run (large systems)."""
+                     want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table, k_max=None, first_obs=0):
+    """The batch entry points take the same arguments: gil_run_batch (systems in LDS), gilm_run (large systems) and gils_run
+    (either, with the structure sums: k_max, first_obs)."""
     lib = _lib()
-    call, last_error = getattr(lib, entry), (lib.gil_last_error if entry == "gil_run_batch" else lib.gilm_last_error)
+    call = getattr(lib, entry)
+    last_error = {"gil_run_batch": lib.gil_last_error, "gilm_run": lib.gilm_last_error, "gils_run": lib.gils_last_error}[entry]
     S = len(states)
     betas = np.ascontiguousarray(np.broadcast_to(np.asarray(betas, dtype=np.float64), (S,)))
     ncap = max(1, max(len(st[0]) for st in states))
@@ -128,12 +168,21 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     n_rec, n_ev, t_fin = np.zeros(S, np.int32), np.zeros(S, np.int64), np.zeros(S)
     exits, n_exit = np.zeros((S, ncap, 3)), np.zeros(S, np.int32)
     ms = C.c_double()
-    rc = call(C.byref(par), _p(n0), _p(pos0), _p(sg0), _p(bd0), _p(uniforms), _p(pos_obs), _p(sg_obs), _p(fl_obs),
-              _p(scal), _p(n_rec), _p(n_ev), _p(t_fin), _p(exits), _p(n_exit), C.byref(ms))
+    args = [_p(n0), _p(pos0), _p(sg0), _p(bd0), _p(uniforms), _p(pos_obs), _p(sg_obs), _p(fl_obs), _p(scal), _p(n_rec), _p(n_ev),
+            _p(t_fin), _p(exits), _p(n_exit)]
+    rows = None
+    if entry == "gils_run":
+        rows = np.zeros((S, M, 4 + 2 * max(int(k_max), 0)))
+        rc = call(C.byref(par), int(k_max), int(first_obs), *args, _p(rows), C.byref(ms))
+    else:
+        rc = call(C.byref(par), *args, C.byref(ms))
     if rc != 0:
         raise capi.ApsError(rc, last_error().decode())
-    return dict(pos=pos_obs, sigma=sg_obs, flags=fl_obs, scalars=scal, n_recorded=n_rec, n_events=n_ev, t_final=t_fin,
-                exits=exits, n_exits=n_exit, n0=n0, kernel_ms=ms.value)
+    out = dict(pos=pos_obs, sigma=sg_obs, flags=fl_obs, scalars=scal, n_recorded=n_rec, n_events=n_ev, t_final=t_fin,
+               exits=exits, n_exits=n_exit, n0=n0, kernel_ms=ms.value)
+    if rows is not None:
+        out["structure"] = rows
+    return out
 
 
 def run_batched_exact(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False, uniforms=None, want_m_local=True):
@@ -233,6 +282,52 @@ def run_batched_exact_statistics(systems, T=10.0, obs_dt=0.01):
             sums = dict(zip(SCALARS, (int(v) for v in r["scalars"][s, k])))
             acc.add(k, sums, sums["n_front"] if k >= acc.start and sums["max_pos"] >= 0 else None)
         rows.append(acc.result())
+        ps.n_events = int(r["n_events"][s])
+    first.kernel_ms = r["kernel_ms"]
+    return rows
+
+
+def run_batched_exact_structure(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_max=None, return_series=False):
+    """The structure observables of PARTICLE_solver_BIOLOGY_local_structure.py:55-103 for many systems under the exact dynamics,
+    from sums the event-loop kernel takes at every observation of the window [int(start_fraction * M), M): no state array and
+    nothing of size M x L leaves the GPU.  Returns one dict per system with the reference's eight keys
+    (observables.DeviceStructure.result); `k_max=None` means all L modes, as in the reference.  `return_series=True` takes the
+    sums at every observation and adds `times_obs`, `fft_amp_series` [M][k_max] and `var_series` [M] (what the reference's
+    time_to_pattern, :195-202, reads).  Particles may leave (k_exit > 0): n is the live count of the observation."""
+    from . import observables
+    from .particle_system import _SHAPE_ATTRS
+    first = systems[0]
+    for ps in systems[1:]:
+        for k in _SHAPE_ATTRS:
+            if getattr(ps, k) != getattr(first, k):
+                raise ValueError(f"run_batched_exact_structure: systems differ in {k}")
+    inits = [ps.init_particles() for ps in systems]
+    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+    times_obs = np.arange(0.0, T, obs_dt)
+    M, L = len(times_obs), first.L
+    kk = L if k_max is None else min(int(k_max), L)
+    first_obs = 0 if return_series else int(start_fraction * M)
+    r = run_structure_raw(L=L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
+                          rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs,
+                          T=T, seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
+                          suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
+                          k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, want_states=False,
+                          device=first.device, flip_table=first.flip_table(), k_max=kk, first_obs=first_obs)
+    rows = []
+    for s, ps in enumerate(systems):
+        if int(r["n_recorded"][s]) < M:
+            raise RuntimeError("a system passed T before its last observation time (choose T beyond the last observation)")
+        acc = observables.DeviceStructure(M, L, first.dx, start_fraction, kk)
+        series = observables.DeviceStructure(M, L, first.dx, 0.0, kk) if return_series else None
+        for k in range(first_obs, M):
+            row = r["structure"][s, k]
+            acc.add(k, row[0], row[1], row[2], row[3], row[4:])
+            if series is not None:
+                series.add(k, row[0], row[1], row[2], row[3], row[4:])
+        res = acc.result()
+        if series is not None:
+            res.update(times_obs=times_obs.copy(), fft_amp_series=np.array(series.amp), var_series=np.array(series.var))
+        rows.append(res)
         ps.n_events = int(r["n_events"][s])
     first.kernel_ms = r["kernel_ms"]
     return rows
