@@ -18,7 +18,8 @@ HDR = os.path.join(ROOT, "include", "aps.h")
 HDRS = [HDR, os.path.join(ROOT, "include", "pde.h"), os.path.join(ROOT, "include", "pde_wide.h"), os.path.join(ROOT, "include", "pde_spectral.h"), os.path.join(ROOT, "include", "pde_sweep.h"), os.path.join(HERE, "csrc", "pde_sweep_fft.hpp"), os.path.join(HERE, "csrc", "pde_common.hpp"), os.path.join(HERE, "csrc", "pde_spectral.hpp"), os.path.join(HERE, "csrc", "aps_common.hpp"), os.path.join(HERE, "csrc", "tile_step.hpp"), os.path.join(HERE, "csrc", "tile_dense.hpp"), os.path.join(HERE, "csrc", "tile_loop.hpp"), os.path.join(HERE, "csrc", "ntt_conv.hpp"),
         os.path.join(HERE, "csrc", "dev_mem.hpp"), os.path.join(HERE, "csrc", "gillespie_common.hpp"),
         os.path.join(ROOT, "include", "gillespie.h"), os.path.join(ROOT, "include", "gillespie_many.h"),
-        os.path.join(ROOT, "include", "gillespie_structure.h"), os.path.join(HERE, "csrc", "gillespie_structure.hpp")]
+        os.path.join(ROOT, "include", "gillespie_structure.h"), os.path.join(HERE, "csrc", "gillespie_structure.hpp"),
+        os.path.join(ROOT, "include", "gillespie_capture.h"), os.path.join(HERE, "csrc", "gillespie_capture.hpp")]
 LIB = os.path.join(HERE, "libaps_hip.so")
 ARCH = "gfx950"
 

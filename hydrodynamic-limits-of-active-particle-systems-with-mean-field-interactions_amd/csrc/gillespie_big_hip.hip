@@ -30,6 +30,7 @@
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiation only)
+#include "gillespie_capture.hpp"          // anchor capture and cluster statistics (capture instantiation only)
 
 namespace {
 
@@ -198,11 +199,15 @@ __device__ inline void big_scalar_sums(const int *pos, const uint8_t *flg, int *
 }
 
 struct GilsBigArgs : BigArgs { GilsArgs st; };              // arguments of the structure instantiation
+struct GilcBigArgs : GilsBigArgs { GilcArgs cp; };          // arguments of the capture instantiation (the driver's one struct)
 
 // ST = also reduce the structure sums at an observation (gillespie_structure.hpp): a compile-time property, so that the
 // kernel without it is the code it was before they existed.
-template <bool ST>
-__global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<ST, GilsBigArgs, BigArgs> a0) {
+// CP = anchor capture and cluster statistics (gillespie_capture.hpp), likewise; not combined with ST.  Its slots lie behind
+// ctl[] in LDS, its bind times in global memory; the event loop holds no register for either.
+template <bool ST, bool CP = false>
+__global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<CP, GilcBigArgs, std::conditional_t<ST, GilsBigArgs, BigArgs>> a0) {
+    static_assert(!(ST && CP), "the capture launch takes no structure sums");
     extern __shared__ double lds[];
     BigArgs a = a0;
     select_system(a, (size_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x));
@@ -219,6 +224,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<ST
     const double *tab = a.tab_in_lds ? tabl : a.table;
     if (a.tab_in_lds) for (int i = t; i <= a.tlen; i += BT) tabl[i] = a.table[i];
     for (int j = t; j < a.nblk; j += BT) bflag[j] = 0;
+    if constexpr (CP) gilc_init<BT>(gilc_lds(ctl + 32, a0.cp, BW), a0.cp, a0.cp.tbind + (size_t)blockIdx.x * N, N);
     // ---- load the system: particles, occupancy, site -> particle map
     for (int x = t; x < L; x += BT) { a.occ[x] = 0; a.occp[x] = 0; }
     for (size_t q = t; q < (size_t)L * K; q += BT) a.slot[q] = -1;
@@ -280,6 +286,12 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<ST
                 gils_record_row<BT>(sa.rows + ((size_t)blockIdx.x * nobs + k) * (size_t)(4 + 2 * sa.k_max), sa.k_max, L, N, a.pos, a.flg,
                                     a.occ, a.W, a.S, M.field_mode != 0, mg, sa.phase, reinterpret_cast<double *>(ctl + 32), a.work);
             }
+        }
+        if constexpr (CP) {
+            const GilcArgs &ca = a0.cp;
+            if (k >= ca.first_obs)
+                gilc_record_row<BT>(ca.rows + ((size_t)blockIdx.x * nobs + k) * (size_t)(GILC_FIXED + ca.n_groups + ca.c_bins),
+                                    gilc_lds(ctl + 32, ca, BW), ca, L, N, a.flg, a.occ, n_exit);
         }
     };
     record(0);
@@ -445,8 +457,13 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<ST
             if (v < e_diff) {
                 if (c.left + c.right > 0.0) { kind = 1; to = (u3 < c.left / (c.left + c.right)) ? p - 1 : p + 1; }
             } else if (v < e_act) { kind = 1; to = p + 1; }
-            else if (v < e_bind) f |= F_BOUND;
-            else if (v < e_unbind) f &= (uint8_t)~F_BOUND;
+            else if (v < e_bind) {
+                f |= F_BOUND;
+                if constexpr (CP) gilc_on_bind(gilc_lds(ctl + 32, a0.cp, BW), a0.cp.tbind + (size_t)blockIdx.x * N, i, tnow);
+            } else if (v < e_unbind) {
+                f &= (uint8_t)~F_BOUND;
+                if constexpr (CP) gilc_on_unbind(gilc_lds(ctl + 32, a0.cp, BW), a0.cp, a0.cp.tbind + (size_t)blockIdx.x * N, i, tnow);
+            }
             else if (v < e_exit) kind = 3;
             else kind = 2;
             auto unmap = [&](int site) {                       // take particle i out of the site's slots
@@ -478,6 +495,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<ST
                     double *row = a.exits + (size_t)n_exit * 3;
                     row[0] = tnow; row[1] = (double)p; row[2] = (double)i;
                 }
+                if constexpr (CP) gilc_on_exit(gilc_lds(ctl + 32, a0.cp, BW), a0.cp, a0.cp.tbind + (size_t)blockIdx.x * N, i, p, (f & F_BOUND) != 0, tnow);
             }
             a.flg[i] = f;
             ctl[8] = kind; ctl[9] = p; ctl[10] = to; ctl[11] = plus ? 1 : -1; ctl[12] = i;
@@ -548,6 +566,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<ST
 #ifdef APS_STAMPS
     if (t == 0 && a.exits) for (int k = 0; k < 12; ++k) a.exits[k] = (double)st[k];   // diagnostic build only
 #endif
+    if constexpr (CP) gilc_flush<BT>(gilc_lds(ctl + 32, a0.cp, BW), a0.cp, (size_t)blockIdx.x);
     if (t == 0) {
         if (a.n_recorded) a.n_recorded[0] = k_obs;
         if (a.n_events) a.n_events[0] = n_ev;
@@ -591,7 +610,7 @@ int big_plan(const char *who, std::string &err, const gil_params *p, bool want_s
 int big_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
             const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
             int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
-            int k_max = 0, int first_obs = 0, double *structure_obs = nullptr) {
+            int k_max = 0, int first_obs = 0, double *structure_obs = nullptr, const GilcCall *cap = nullptr) {
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilm_plan_info info{};
     std::vector<double> table;
@@ -603,6 +622,12 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
         info.output_bytes += (int64_t)S * p->n_obs * (int64_t)row * 8;
         if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
     }
+    const size_t crow = cap ? (size_t)(GILC_FIXED + cap->n_groups + cap->c_bins) : 0;   // of capture counts (gilc_run)
+    if (cap) {
+        info.lds_bytes += (int32_t)(gilc_lds_slots(BT, cap->n_groups, cap->c_bins, cap->h_bins) * 8);
+        info.output_bytes += (int64_t)S * (p->n_obs * (int64_t)crow * 8 + 2 * (int64_t)cap->h_bins * 8 + 32);
+        if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
+    }
     for (int s = 0; s < S; ++s) {
         if (n0[s] < 0 || n0[s] > N) return bad("bad n_cap / n0 / n_obs / max_events");
         if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * N, sigma0 + (size_t)s * N)) return bad(why);
@@ -611,11 +636,12 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
     if (int rc = job.select_device(p->device)) return rc;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
-    const int64_t work_bytes = (int64_t)S * info.work_bytes_per_system + (structure_obs ? (int64_t)L * 16 : 0);
+    const int64_t work_bytes = (int64_t)S * info.work_bytes_per_system + (structure_obs ? (int64_t)L * 16 : 0) +
+                               (cap ? (int64_t)S * N * 8 + (cap->n_groups > 0 ? (int64_t)L * 4 : 0) : 0);
     if ((uint64_t)(work_bytes + info.output_bytes) > (uint64_t)free_b)
         return bad("the batch needs " + std::to_string(work_bytes) + " bytes of work memory and " +
                    std::to_string(info.output_bytes) + " bytes of outputs, the device has " + std::to_string(free_b) + " bytes free");
-    GilsBigArgs a{};
+    GilcBigArgs a{};
     a.p = *p; a.tlen = info.table_len; a.nblk = info.n_blocks; a.cb = (a.nblk + BT - 1) / BT;
     a.tab_in_lds = info.table_in_lds;
     a.m = gil_model(p);
@@ -644,11 +670,18 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
         sa.phase = phase; sa.k_max = k_max; sa.first_obs = first_obs;
         if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<true>), lds)) return rc;
         hipLaunchKernelGGL(gils_phase_table, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, nullptr, phase, L);
+    } else if (cap) {
+        GilcArgs &ca = a.cp;
+        ca.n_groups = cap->n_groups; ca.c_bins = cap->c_bins; ca.h_bins = cap->h_bins; ca.first_obs = cap->first_obs; ca.h_dt = cap->h_dt;
+        if (cap->group_of_site) UP(cp.group, cap->group_of_site, (size_t)L);
+        WORK(cp.rows, SO * crow); WORK(cp.life_hist, (size_t)S * 2 * cap->h_bins); WORK(cp.life_sums, (size_t)S * 4); WORK(cp.tbind, SN);
+        if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false, true>), lds)) return rc;
     } else if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false>), lds)) return rc;
     if (int rc = job.create_events()) return rc;
     hipLaunchKernelGGL(big_field_init, dim3((unsigned)((L + 255) / 256), (unsigned)S), dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
     job.ev.start();
-    if (structure_obs) hipLaunchKernelGGL(gil_big_kernel<true>, dim3((unsigned)S), dim3(BT), lds, nullptr, a);
+    if (structure_obs) hipLaunchKernelGGL(gil_big_kernel<true>, dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const GilsBigArgs &>(a));
+    else if (cap) hipLaunchKernelGGL((gil_big_kernel<false, true>), dim3((unsigned)S), dim3(BT), lds, nullptr, a);
     else hipLaunchKernelGGL(gil_big_kernel<false>, dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const BigArgs &>(a));
     job.ev.stop();
     if (int rc = job.finish(hipGetLastError(), "gil_big_kernel", kernel_ms)) return rc;
@@ -657,6 +690,11 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
     DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8); DOWN(t_final, t_final, (size_t)S * 8);
     DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
     if (structure_obs) if (int rc = job.download(structure_obs, sa.rows, SO * row * 8, "structure_obs")) return rc;
+    if (cap) {
+        if (int rc = job.download(cap->capture_obs, a.cp.rows, SO * crow * 8, "capture_obs")) return rc;
+        if (int rc = job.download(cap->life_hist, a.cp.life_hist, (size_t)S * 2 * cap->h_bins * 8, "life_hist")) return rc;
+        if (int rc = job.download(cap->life_sums, a.cp.life_sums, (size_t)S * 4 * 8, "life_sums")) return rc;
+    }
     return GIL_OK;
 }
 
@@ -678,6 +716,24 @@ int gils_large_run(const char *who, std::string &err, const gil_params *p, const
                    double *kernel_ms, int k_max, int first_obs, double *structure_obs) {
     return big_run(who, err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
                    t_final, exits, n_exits, kernel_ms, k_max, first_obs, structure_obs);
+}
+
+int gilc_large_plan(const char *who, std::string &err, const gil_params *p, int32_t cap_lds, int32_t *lds_bytes, int64_t *work_bytes) {
+    if (p->n_systems > GILM_MAX_SYSTEMS) { err = std::string(who) + ": n_systems must be in [1, GILM_MAX_SYSTEMS]"; return GIL_ERR_ARG; }
+    gilm_plan_info info{};
+    if (int rc = big_plan(who, err, p, false, false, &info, nullptr)) return rc;
+    *lds_bytes = info.lds_bytes + cap_lds;
+    *work_bytes = (int64_t)p->n_systems * info.work_bytes_per_system;
+    if (*lds_bytes > 160 * 1024) { err = std::string(who) + ": LDS budget exceeded"; return GIL_ERR_ARG; }
+    return GIL_OK;
+}
+
+int gilc_large_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
+                   const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs,
+                   int64_t *scalars_obs, int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits,
+                   double *kernel_ms, const GilcCall *cap) {
+    return big_run(who, err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
+                   t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, cap);
 }
 
 extern "C" {

@@ -25,9 +25,11 @@
 
 #include "gillespie.h"
 #include "gillespie_structure.h"
+#include "gillespie_capture.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"           // model, initial-state check, the driver of the one-shot entry points
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiations only)
+#include "gillespie_capture.hpp"          // anchor capture and cluster statistics (capture instantiations only)
 
 namespace {
 
@@ -62,6 +64,7 @@ __device__ inline long long wg_sum_ll(long long v, long long *red) {
 }
 
 struct GilsBatchArgs : GilArgs { GilsArgs st; };            // arguments of the structure instantiations
+struct GilcBatchArgs : GilsBatchArgs { GilcArgs cp; };      // arguments of the capture instantiations (the driver's one struct)
 
 // the structure sums' slots: behind the loop's own LDS (which ends with the plus-occupancy bytes), at the next multiple of 8
 __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L) {
@@ -72,8 +75,10 @@ __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L)
 // NT = threads per system: one wavefront (no real barriers, six systems per CU by LDS) for small systems, four for large ones.
 // ST = also reduce the structure sums at an observation (gillespie_structure.hpp): a compile-time property, so that the
 // kernels without it are the code they were before it existed.
-template <int NT, bool ST>
-__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<ST, GilsBatchArgs, GilArgs> a) {
+// CP = anchor capture and cluster statistics (gillespie_capture.hpp), likewise; not combined with ST.
+template <int NT, bool ST, bool CP = false>
+__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<CP, GilcBatchArgs, std::conditional_t<ST, GilsBatchArgs, GilArgs>> a) {
+    static_assert(!(ST && CP), "the capture launches take no structure sums");
     extern __shared__ double lds[];
     const Model &M = a.m;
     const int L = M.L, K = M.K, t = threadIdx.x, sys = blockIdx.x, ncap = a.p.n_cap, nobs = a.p.n_obs;
@@ -106,6 +111,10 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<ST, Gi
             double *ptab = gils_slots(lds, occp, L) + gils_lds_doubles(NT);
             for (int i = t; i < 2 * L; i += NT) ptab[i] = a.st.phase[i];
         }
+    }
+    if constexpr (CP) {                                        // the capture slots, and the bind times behind them
+        const GilcLds cs = gilc_lds(gils_slots(lds, occp, L), a.cp, NT / 64);
+        gilc_init<NT>(cs, a.cp, cs.tbind, ncap);
     }
     __syncthreads();
     if (t == 0) for (int i = 0; i < n_init; ++i) { occ[pos[i]]++; if (flg[i] & F_PLUS) occp[pos[i]]++; }
@@ -185,6 +194,11 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<ST, Gi
                 if (sa.phase_in_lds) gils_record_row<NT>(row, sa.k_max, L, ncap, pos, flg, occ, W, S, M.field_mode != 0, mg, red + gils_lds_doubles(NT), red, work);
                 else gils_record_row<NT>(row, sa.k_max, L, ncap, pos, flg, occ, W, S, M.field_mode != 0, mg, sa.phase, red, work);
             }
+        }
+        if constexpr (CP) {
+            if (k >= a.cp.first_obs)
+                gilc_record_row<NT>(a.cp.rows + ((size_t)sys * nobs + k) * (size_t)(GILC_FIXED + a.cp.n_groups + a.cp.c_bins),
+                                    gilc_lds(gils_slots(lds, occp, L), a.cp, NT / 64), a.cp, L, ncap, flg, occ, n_exit);
         }
     };
 
@@ -340,8 +354,13 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<ST, Gi
             if (v < e_diff) {
                 if (c.left + c.right > 0.0) { kind = 1; to = (u[3] < c.left / (c.left + c.right)) ? p - 1 : p + 1; }
             } else if (v < e_act) { kind = 1; to = p + 1; }
-            else if (v < e_bind) f |= F_BOUND;
-            else if (v < e_unbind) f &= (uint8_t)~F_BOUND;
+            else if (v < e_bind) {
+                f |= F_BOUND;
+                if constexpr (CP) { const GilcLds cs = gilc_lds(gils_slots(lds, occp, L), a.cp, NT / 64); gilc_on_bind(cs, cs.tbind, i, tnow); }
+            } else if (v < e_unbind) {
+                f &= (uint8_t)~F_BOUND;
+                if constexpr (CP) { const GilcLds cs = gilc_lds(gils_slots(lds, occp, L), a.cp, NT / 64); gilc_on_unbind(cs, a.cp, cs.tbind, i, tnow); }
+            }
             else if (v < e_exit) kind = 3;
             else kind = 2;
             if (kind == 1) {
@@ -362,6 +381,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<ST, Gi
                     double *row = a.exits + ((size_t)sys * ncap + n_exit) * 3;
                     row[0] = tnow; row[1] = (double)p; row[2] = (double)i;
                 }
+                if constexpr (CP) { const GilcLds cs = gilc_lds(gils_slots(lds, occp, L), a.cp, NT / 64); gilc_on_exit(cs, a.cp, cs.tbind, i, p, (f & F_BOUND) != 0, tnow); }
             }
             flg[i] = f;
             ctl[2] = kind; ctl[3] = p; ctl[4] = to; ctl[5] = plus ? 1 : -1;
@@ -411,6 +431,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<ST, Gi
 #ifdef APS_STAMPS
     if (t == 0 && sys == 0 && a.exits) for (int k = 0; k < 5; ++k) a.exits[k] = (double)st[k];   // diagnostic build only
 #endif
+    if constexpr (CP) gilc_flush<NT>(gilc_lds(gils_slots(lds, occp, L), a.cp, NT / 64), a.cp, (size_t)sys);
     if (t == 0) {
         if (a.n_recorded) a.n_recorded[sys] = k_obs;
         if (a.n_events) a.n_events[sys] = n_ev;
@@ -420,8 +441,8 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<ST, Gi
 }
 
 // threads and dynamic LDS bytes of one system in the batch kernel; st: with the structure sums' slots, and with a copy of the
-// phase table behind them where the 160 KB leave room for it (phase_in_lds)
-void batch_shape(int L, int ncap, int tlen, bool st, int &NT, size_t &lds, bool *phase_in_lds = nullptr) {
+// phase table behind them where the 160 KB leave room for it (phase_in_lds); cap: with the capture slots and the bind times
+void batch_shape(int L, int ncap, int tlen, bool st, int &NT, size_t &lds, bool *phase_in_lds = nullptr, const GilcCall *cap = nullptr) {
     NT = ncap <= 1024 ? 64 : 256;                             // one wavefront per system while a lane owns at most 16 particles
     lds = ((size_t)2 * L + ((tlen + 2) & ~1) + ncap + (ncap & 1) + 8 + 5 * NT + 8) * sizeof(double) +
           ((size_t)3 * ncap + 16) * sizeof(int) + (size_t)((ncap + 15) & ~15) + (size_t)2 * ((L + 15) & ~15);
@@ -430,6 +451,14 @@ void batch_shape(int L, int ncap, int tlen, bool st, int &NT, size_t &lds, bool 
         *phase_in_lds = lds + (size_t)16 * L <= 160 * 1024;
         if (*phase_in_lds) lds += (size_t)16 * L;
     }
+    if (cap) lds = ((lds + 7) & ~(size_t)7) + (gilc_lds_slots(NT, cap->n_groups, cap->c_bins, cap->h_bins) + (size_t)ncap) * 8;
+}
+
+// device copies of the outputs of one capture call (gilc_plan_info.output_bytes)
+int64_t gilc_output_bytes(const gil_params *p, const GilcCall &c, bool states) {
+    const int64_t S = p->n_systems, O = p->n_obs, N = p->n_cap;
+    return S * ((states ? O * N * 6 : 0) + O * GIL_NSCALARS * 8 + N * 24 + 24 + O * (GILC_NFIXED + c.n_groups + c.c_bins) * 8 +
+                2 * (int64_t)c.h_bins * 8 + 32);
 }
 
 // device copies of the outputs of one call (gils_plan_info.output_bytes)
@@ -443,7 +472,7 @@ int64_t gils_output_bytes(const gil_params *p, int k_max, bool states, bool scal
 int batch_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
               const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
               int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
-              int k_max, int first_obs, double *structure_obs) {
+              int k_max, int first_obs, double *structure_obs, const GilcCall *cap = nullptr) {
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     if (p->L < 2 || p->L > GIL_MAX_L) return bad("L must be in [2, GIL_MAX_L]");
     if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
@@ -455,10 +484,12 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
     }
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: a run may record fewer observations than it has room for
     if (int rc = job.select_device(p->device)) return rc;
-    if (structure_obs) {
+    if (structure_obs || cap) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
-        const int64_t work = (int64_t)L * 16, outb = gils_output_bytes(p, k_max, pos_obs || sigma_obs || flags_obs, scalars_obs != nullptr);
+        const int64_t work = cap ? (cap->n_groups > 0 ? (int64_t)L * 4 : 0) : (int64_t)L * 16,
+                      outb = cap ? gilc_output_bytes(p, *cap, pos_obs || sigma_obs || flags_obs)
+                                 : gils_output_bytes(p, k_max, pos_obs || sigma_obs || flags_obs, scalars_obs != nullptr);
         if ((uint64_t)(work + outb) > (uint64_t)free_b)
             return bad("the batch needs " + std::to_string(work) + " bytes of work memory and " + std::to_string(outb) +
                        " bytes of outputs, the device has " + std::to_string(free_b) + " bytes free");
@@ -466,9 +497,9 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
 
     std::vector<double> table; int tlen = 0, q = 0;
     weight_table(p->sigma_grid, L, p->K, p->periodic != 0, table, tlen, q);
-    GilsBatchArgs a{};
+    GilcBatchArgs a{};
     int NT; size_t lds; bool phase_in_lds = false;
-    batch_shape(L, ncap, tlen, structure_obs != nullptr, NT, lds, &phase_in_lds);
+    batch_shape(L, ncap, tlen, structure_obs != nullptr, NT, lds, &phase_in_lds, cap);
     a.p = *p; a.tlen = tlen; a.chunk = (ncap + NT - 1) / NT;
     a.m = gil_model(p);
     const size_t SN = (size_t)S * ncap, SO = (size_t)S * p->n_obs;
@@ -494,12 +525,22 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
         sa.phase = phase; sa.k_max = k_max; sa.first_obs = first_obs; sa.phase_in_lds = phase_in_lds ? 1 : 0;
         if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, true>) : reinterpret_cast<const void *>(&gil_kernel<256, true>), lds)) return rc;
         hipLaunchKernelGGL(gils_phase_table, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, nullptr, phase, L);
+    } else if (cap) {
+        GilcArgs &ca = a.cp;
+        ca.n_groups = cap->n_groups; ca.c_bins = cap->c_bins; ca.h_bins = cap->h_bins; ca.first_obs = cap->first_obs; ca.h_dt = cap->h_dt;
+        if (cap->group_of_site) UP(cp.group, cap->group_of_site, (size_t)L);
+        WORK(cp.rows, SO * (size_t)(GILC_NFIXED + cap->n_groups + cap->c_bins));
+        WORK(cp.life_hist, (size_t)S * 2 * cap->h_bins); WORK(cp.life_sums, (size_t)S * 4);
+        if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, true>) : reinterpret_cast<const void *>(&gil_kernel<256, false, true>), lds)) return rc;
     } else if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false>) : reinterpret_cast<const void *>(&gil_kernel<256, false>), lds)) return rc;
     if (int rc = job.create_events()) return rc;
     job.ev.start();
     if (structure_obs) {
-        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
-        else hipLaunchKernelGGL((gil_kernel<256, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
+        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, true>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilsBatchArgs &>(a));
+        else hipLaunchKernelGGL((gil_kernel<256, true>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilsBatchArgs &>(a));
+    } else if (cap) {
+        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
+        else hipLaunchKernelGGL((gil_kernel<256, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
     } else if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilArgs &>(a));
     else hipLaunchKernelGGL((gil_kernel<256, false>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilArgs &>(a));
     job.ev.stop();
@@ -508,6 +549,11 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
     DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8); DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8);
     DOWN(t_final, t_final, (size_t)S * 8); DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
     if (structure_obs) if (int rc = job.download(structure_obs, sa.rows, SO * row * 8, "structure_obs")) return rc;
+    if (cap) {
+        if (int rc = job.download(cap->capture_obs, a.cp.rows, SO * (size_t)(GILC_NFIXED + cap->n_groups + cap->c_bins) * 8, "capture_obs")) return rc;
+        if (int rc = job.download(cap->life_hist, a.cp.life_hist, (size_t)S * 2 * cap->h_bins * 8, "life_hist")) return rc;
+        if (int rc = job.download(cap->life_sums, a.cp.life_sums, (size_t)S * 4 * 8, "life_sums")) return rc;
+    }
     return GIL_OK;
 }
 
@@ -546,9 +592,77 @@ int gils_decide(const char *who, const gil_params *p, int k_max, int first_obs, 
     return GIL_OK;
 }
 
+std::string g_gilc_err;
+
+// the checks gilc_plan and gilc_run share, and the shape: 0 with `info` filled, or GIL_ERR_ARG with the text in g_gilc_err
+int gilc_decide(const char *who, const gil_params *p, const GilcCall &c, bool states, gilc_plan_info &info) {
+    auto bad = [&](const std::string &m) { g_gilc_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    if (p->L < 2) return bad("L must be at least 2");
+    if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
+    if (c.n_groups < 0 || c.n_groups > GILC_MAX_GROUPS) return bad("n_groups = " + std::to_string(c.n_groups) + " is outside [0, " + std::to_string(GILC_MAX_GROUPS) + "]");
+    if (c.c_bins < 2 || c.c_bins > GILC_MAX_CBINS) return bad("c_bins = " + std::to_string(c.c_bins) + " is outside [2, " + std::to_string(GILC_MAX_CBINS) + "]");
+    if (c.h_bins < 1 || c.h_bins > GILC_MAX_HBINS) return bad("h_bins = " + std::to_string(c.h_bins) + " is outside [1, " + std::to_string(GILC_MAX_HBINS) + "]");
+    if (!(c.h_dt > 0.0) || !std::isfinite(c.h_dt)) return bad("h_dt = " + std::to_string(c.h_dt) + " must be positive and finite");
+    if (c.first_obs < 0 || c.first_obs > p->n_obs) return bad("first_obs = " + std::to_string(c.first_obs) + " is outside [0, n_obs = " + std::to_string(p->n_obs) + "]");
+    if (c.group_of_site)
+        for (int x = 0; x < p->L; ++x) {
+            const int g = c.group_of_site[x];
+            if (g < -1 || g >= c.n_groups) return bad("group id " + std::to_string(g) + " at site " + std::to_string(x) + " is outside [-1, n_groups = " + std::to_string(c.n_groups) + ")");
+            if (g >= 0 && !(p->anchor_mask && p->anchor_mask[x])) return bad("site " + std::to_string(x) + " carries group " + std::to_string(g) + " but anchor_mask does not mark it");
+        }
+    info = gilc_plan_info{};
+    info.row_len = GILC_NFIXED + c.n_groups + c.c_bins;
+    info.output_bytes = gilc_output_bytes(p, c, states);
+    info.shape = GILS_SHAPE_LARGE;
+    const int64_t group_bytes = c.n_groups > 0 ? (int64_t)p->L * 4 : 0;
+    if (p->L <= GIL_MAX_L && p->n_cap <= GIL_MAX_N) {
+        if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
+        std::vector<double> table; int tlen = 0, q = 0, NT = 0; size_t lds = 0;
+        weight_table(p->sigma_grid, p->L, p->K, p->periodic != 0, table, tlen, q);
+        batch_shape(p->L, p->n_cap, tlen, false, NT, lds, nullptr, &c);
+        if (lds <= 160 * 1024) { info.shape = GILS_SHAPE_BATCH; info.threads = NT; info.lds_bytes = (int32_t)lds; info.work_bytes = group_bytes; }
+    }
+    if (info.shape == GILS_SHAPE_LARGE) {
+        int32_t lds = 0; int64_t work = 0;
+        if (int rc = gilc_large_plan(who, g_gilc_err, p, (int32_t)(gilc_lds_slots(1024, c.n_groups, c.c_bins, c.h_bins) * 8), &lds, &work)) return rc;
+        info.threads = 1024; info.lds_bytes = lds; info.work_bytes = work + (int64_t)p->n_systems * p->n_cap * 8 + group_bytes;
+    }
+    if (info.work_bytes + info.output_bytes > (1ll << 38))
+        return bad("the batch needs " + std::to_string(info.work_bytes) + " bytes of work memory and " + std::to_string(info.output_bytes) +
+                   " bytes of outputs, more than the " + std::to_string(1ll << 38) + " bytes a plan accepts");
+    return GIL_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+const char *gilc_last_error(void) { return g_gilc_err.c_str(); }
+
+int gilc_plan(const gil_params *p, int32_t n_groups, int32_t c_bins, int32_t h_bins, int32_t first_obs, int32_t want_states, gilc_plan_info *out) {
+    if (!p || !out) { g_gilc_err = "gilc_plan: null argument"; return GIL_ERR_ARG; }
+    const GilcCall c{nullptr, n_groups, c_bins, h_bins, first_obs, 1.0, nullptr, nullptr, nullptr};
+    gilc_plan_info info;
+    if (int rc = gilc_decide("gilc_plan", p, c, want_states != 0, info)) return rc;
+    *out = info;
+    return GIL_OK;
+}
+
+int gilc_run(const gil_params *p, const int32_t *group_of_site, int32_t n_groups, int32_t c_bins, int32_t h_bins, double h_dt, int32_t first_obs,
+             const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0, const double *uniforms,
+             int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
+             int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, int64_t *capture_obs, int64_t *life_hist,
+             double *life_sums, double *kernel_ms) {
+    if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !capture_obs || !life_hist || !life_sums) { g_gilc_err = "gilc_run: null argument"; return GIL_ERR_ARG; }
+    const GilcCall c{group_of_site, n_groups, c_bins, h_bins, first_obs, h_dt, capture_obs, life_hist, life_sums};
+    gilc_plan_info info;
+    if (int rc = gilc_decide("gilc_run", p, c, pos_obs || sigma_obs || flags_obs, info)) return rc;
+    if (info.shape == GILS_SHAPE_BATCH)
+        return batch_run("gilc_run", g_gilc_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
+                         n_recorded, n_events, t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, &c);
+    return gilc_large_run("gilc_run", g_gilc_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
+                          n_recorded, n_events, t_final, exits, n_exits, kernel_ms, &c);
+}
 
 const char *gil_last_error(void) { return g_gil_err.c_str(); }
 

@@ -6,8 +6,10 @@ The two outer sweeps of the other drivers are here too: `sweep_over_sigmas` (int
 one batched handle per sigma / per particle number (the weight table and the state capacity differ), all (beta, run)
 pairs inside it.  `sweep_betas_for_structures` / `sweep_beta_structure_ensemble` are the pattern study's drivers
 (PARTICLE_solver_BIOLOGY_local_structure.py:105-193), all (beta, run) pairs in one launch, the per-run observables from sums
-taken on the GPU."""
+taken on the GPU.  `capture_study` is the anchor-capture study (PARTICLE_solver_CLASS.py:766-976) as an ensemble in one launch."""
 from __future__ import annotations
+
+import warnings
 
 import numpy as np
 
@@ -165,3 +167,53 @@ def sweep_beta_structure_ensemble(beta, n_runs, ps_kwargs, init_kwargs, run_kwar
     """One beta, n_runs runs in one launch; the reference's result keys (:146-165).  `rng_seeds[r]` seeds run r."""
     return sweep_betas_for_structures([beta], n_runs, ps_kwargs, init_kwargs, run_kwargs, start_fraction, k_max,
                                       None if rng_seeds is None else [rng_seeds], dynamics)[beta]
+
+
+def capture_study(ps_kwargs, init_kwargs, n_runs, run_kwargs, rng_seeds=None, on_device=True, c_bins=16, h_bins=40, h_dt=None,
+                  start_fraction=0.0):
+    """The anchor-capture study (PARTICLE_solver_BIOLOGY_EXCLUSION.py with its anchors switched on, analysed by
+    PARTICLE_solver_CLASS.py:766-976) as an ensemble: `n_runs` runs of one parameter set in ONE launch of the exact event loop.
+    Returns `<key>_mean`, `<key>_std` (ddof=1) and `<key>_se` across runs for `survival` [M], `cumulative_exits` [M][G],
+    `cumulative_exits_total` [M], `exit_position_hist` [50] and `cluster_hist` [c_bins] (each run's cluster-size counts
+    averaged over its observations from int(start_fraction * M) on), plus `times_obs`, `n_runs` and `raw` (the per-run dicts).
+    `run_kwargs` holds T and obs_dt; `rng_seeds[r]` seeds the initial condition of run r.
+
+    on_device=True (gillespie.run_batched_exact_capture): the counts come from the event loop itself, and the result also has
+    `life_mean_*` [2] (mean bound lifetime per way of ending: unbinding, exit; runs where nothing ended that way are left out
+    of the statistics), `life_hist_sum` [2][h_bins] (the runs' lifetime histograms added) and `life_edges`.
+    on_device=False (gillespie.run_batched_exact + observables.capture_observables): the same keys from full outputs, WITHOUT
+    the lifetime keys -- snapshots show only whether a particle slot is bound at the observation times, so a lifetime could be
+    had to obs_dt at best and binds and unbinds between two observations would be missed; the event times exist on the
+    device only."""
+    from . import gillespie
+    ps_kwargs, init_kwargs, run_kwargs = dict(ps_kwargs or {}), dict(init_kwargs or {}), dict(run_kwargs or {})
+    unknown = set(run_kwargs) - {"T", "obs_dt"}
+    if unknown:
+        raise ValueError(f"run_kwargs may hold T and obs_dt; got {sorted(unknown)}")
+    systems = [ParticleSystem(rng=None if rng_seeds is None else np.random.default_rng(int(rng_seeds[r])), **ps_kwargs, **init_kwargs)
+               for r in range(n_runs)]
+    if on_device:
+        rows = gillespie.run_batched_exact_capture(systems, c_bins=c_bins, h_bins=h_bins, h_dt=h_dt, start_fraction=0.0, **run_kwargs)
+    else:
+        groups = observables.anchor_groups(systems[0]) if len(systems[0].anchor_idxs) else None
+        outs = gillespie.run_batched_exact(systems, want_m_local=False, **run_kwargs)
+        rows = [observables.capture_observables(out, groups, c_bins) for out in outs]
+    M = len(rows[0]["survival"])
+    start = int(start_fraction * M)
+    per_run = {key: np.stack([np.asarray(r[key], dtype=float) for r in rows])
+               for key in ("survival", "cumulative_exits", "cumulative_exits_total", "exit_position_hist")}
+    per_run["cluster_hist"] = np.stack([np.asarray(r["cluster_hist"][start:], dtype=float).mean(axis=0) for r in rows])
+    if on_device:
+        per_run["life_mean"] = np.stack([r["life_mean"] for r in rows])
+    res = {"times_obs": np.arange(0.0, run_kwargs.get("T", 10.0), run_kwargs.get("obs_dt", 0.01)), "n_runs": n_runs, "raw": rows}
+    with np.errstate(invalid="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)            # a way of ending that no run saw: nan, quietly
+        for key, v in per_run.items():
+            n = np.sum(~np.isnan(v), axis=0)
+            res[key + "_mean"] = np.nanmean(v, axis=0)
+            res[key + "_std"] = np.nanstd(v, axis=0, ddof=1)
+            res[key + "_se"] = res[key + "_std"] / np.sqrt(np.maximum(n, 1))
+    if on_device:
+        res["life_hist_sum"] = np.sum([r["life_hist"] for r in rows], axis=0)
+        res["life_edges"] = rows[0]["life_edges"]
+    return res

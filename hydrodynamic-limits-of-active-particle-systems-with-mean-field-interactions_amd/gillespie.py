@@ -3,7 +3,8 @@ include/gillespie_many.h): the reference's `ParticleSystem.run` as written (one 
 PARTICLE_solver_CLASS.py:450-558), one persistent workgroup per system.  `run_batched_exact` returns the reference's
 result dictionaries; `sweep` statistics can be taken from the scalar sums without the M x L arrays (`scalars_only=True`),
 and the structure observables from sums the loop takes at every observation (`run_batched_exact_structure`,
-include/gillespie_structure.h).
+include/gillespie_structure.h); the anchor-capture study's cluster, lifetime and exit statistics likewise
+(`run_batched_exact_capture`, include/gillespie_capture.h).
 
 Differences to the reference: randomness is Philox4x32-10 keyed by `seed` (the reference consumes a NumPy Generator), so
 trajectories agree in distribution, not draw for draw; `m_local_list[k]` is the field of the observed state (the
@@ -44,6 +45,16 @@ class GilsPlanInfo(C.Structure):
                 ("phase_in_lds", C.c_int32), ("reserved", C.c_int32), ("work_bytes", C.c_int64), ("output_bytes", C.c_int64)]
 
 
+class GilcPlanInfo(C.Structure):
+    """struct gilc_plan_info of include/gillespie_capture.h, field for field."""
+    _fields_ = [("shape", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32), ("row_len", C.c_int32),
+                ("work_bytes", C.c_int64), ("output_bytes", C.c_int64)]
+
+
+GILC_NFIXED = 9
+CAPTURE_COLUMNS = ("n", "n_bound", "binds", "unbinds", "exits", "occupied_sites", "n_clusters", "largest_cluster", "sum_size2")
+
+
 def _lib():
     lib = capi.load()
     if not getattr(lib, "_gil_ready", False):
@@ -63,6 +74,13 @@ def _lib():
         lib.gils_plan.argtypes = [C.POINTER(GilParams), C.c_int32, C.c_int32, C.c_int32, C.POINTER(GilsPlanInfo)]
         lib.gils_run.restype = C.c_int
         lib.gils_run.argtypes = [C.POINTER(GilParams), C.c_int32, C.c_int32] + [C.c_void_p] * 15 + [C.POINTER(C.c_double)]
+        if hasattr(lib, "gilc_run"):           # an older build named by APS_LIB (a timing yardstick) has no capture entry points
+            lib.gilc_last_error.restype, lib.gilc_last_error.argtypes = C.c_char_p, []
+            lib.gilc_plan.restype = C.c_int
+            lib.gilc_plan.argtypes = [C.POINTER(GilParams)] + [C.c_int32] * 5 + [C.POINTER(GilcPlanInfo)]
+            lib.gilc_run.restype = C.c_int
+            lib.gilc_run.argtypes = ([C.POINTER(GilParams), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32] +
+                                     [C.c_void_p] * 17 + [C.POINTER(C.c_double)])
         lib._gil_ready = True
     return lib
 
@@ -82,10 +100,11 @@ def run_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, s
 def run_many_large_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
                        minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
                        anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
-                       block_table=None, device=0, flip_table=None):
+                       block_table=None, device=0, flip_table=None, n_cap=None):
     """`run_raw` for systems beyond one workgroup's LDS (gilm_run of include/gillespie_many.h): the large-system kernel, one
     workgroup per system, all systems in one launch.  Same keywords, same dictionary, scalars included.  System s draws
-    with Philox key seed + s: it is the `run_large_raw` run with that seed."""
+    with Philox key seed + s: it is the `run_large_raw` run with that seed.  `n_cap`: particle slots per system, where more
+    than the largest initial state are wanted (the spare ones stay empty)."""
     return _run_batch_entry("gilm_run", **locals())
 
 
@@ -125,17 +144,58 @@ def plan_structure(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, k_max
     return {k: int(getattr(info, k)) for k, _ in GilsPlanInfo._fields_ if k != "reserved"}
 
 
+def run_capture_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
+                    minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
+                    anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
+                    block_table=None, device=0, flip_table=None, group_of_site=None, c_bins=16, h_bins=40, h_dt=None, first_obs=0,
+                    n_groups=None, n_cap=None):
+    """`run_raw` with the anchor-capture and cluster statistics taken inside the event loop (gilc_run of
+    include/gillespie_capture.h); the library picks the kernel as for `run_structure_raw`.  `group_of_site` [L]: the anchor group
+    of a site or -1 (observables.anchor_groups), None: no groups; `n_groups=None`: the largest id + 1.  `h_dt=None`: T / h_bins.
+    `n_cap`: particle slots per system, where more than the largest initial state are wanted (more than 2048 select the
+    large-system kernel).
+    The dictionary of `run_raw` plus
+      `capture`   [systems][observations][9 + n_groups + c_bins] int64: CAPTURE_COLUMNS, exits per group, clusters per size;
+      `life_hist` [systems][2][h_bins] int64 and `life_sums` [systems][2][2] (sum, sum of squares): lifetimes of bound states
+                  ended by unbinding (0) and by exit (1), resolved to the event."""
+    if n_groups is None:
+        n_groups = 0 if group_of_site is None else int(max(-1, np.max(group_of_site))) + 1
+    h_dt = float(T) / int(h_bins) if h_dt is None else float(h_dt)
+    return _run_batch_entry("gilc_run", **locals())
+
+
+def plan_capture(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, n_groups=0, c_bins=16, h_bins=40, first_obs=0,
+                 want_states=True):
+    """gilc_plan: which kernel `run_capture_raw` would use (shape 0: systems in LDS, 1: large systems), its threads per system,
+    LDS, row length, work and output bytes, by host arithmetic; no device needed.  Refuses what the run would refuse on these
+    numbers."""
+    lib = _lib()
+    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), sigma_grid=float(sigma_grid), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
+    info = GilcPlanInfo()
+    rc = lib.gilc_plan(C.byref(par), int(n_groups), int(c_bins), int(h_bins), int(first_obs), int(bool(want_states)), C.byref(info))
+    if rc != 0:
+        raise capi.ApsError(rc, lib.gilc_last_error().decode())
+    return {k: int(getattr(info, k)) for k, _ in GilcPlanInfo._fields_}
+
+
 def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed,
                      minus_anchor, immobilize, suppress_flip, crowding, k_on, k_off, k_exit, anchor_mask, uniforms, max_events,
-                     want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table, k_max=None, first_obs=0):
-    """The batch entry points take the same arguments: gil_run_batch (systems in LDS), gilm_run (large systems) and gils_run
-    (either, with the structure sums: k_max, first_obs)."""
+                     want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table, k_max=None, first_obs=0,
+                     group_of_site=None, n_groups=0, c_bins=0, h_bins=0, h_dt=0.0, n_cap=None):
+    """The batch entry points take the same arguments: gil_run_batch (systems in LDS), gilm_run (large systems), gils_run
+    (either, with the structure sums: k_max, first_obs) and gilc_run (either, with the capture statistics: group_of_site,
+    n_groups, c_bins, h_bins, h_dt, first_obs)."""
     lib = _lib()
     call = getattr(lib, entry)
-    last_error = {"gil_run_batch": lib.gil_last_error, "gilm_run": lib.gilm_last_error, "gils_run": lib.gils_last_error}[entry]
+    last_error = getattr(lib, {"gil_run_batch": "gil_last_error", "gilm_run": "gilm_last_error", "gils_run": "gils_last_error",
+                               "gilc_run": "gilc_last_error"}[entry])
     S = len(states)
     betas = np.ascontiguousarray(np.broadcast_to(np.asarray(betas, dtype=np.float64), (S,)))
     ncap = max(1, max(len(st[0]) for st in states))
+    if n_cap is not None:
+        if int(n_cap) < ncap:
+            raise ValueError("n_cap is smaller than an initial state")
+        ncap = int(n_cap)
     n0 = np.array([len(st[0]) for st in states], np.int32)
     pos0, sg0, bd0 = np.zeros((S, ncap), np.int32), np.ones((S, ncap), np.int8), np.zeros((S, ncap), np.uint8)
     for s, st in enumerate(states):
@@ -170,10 +230,18 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     ms = C.c_double()
     args = [_p(n0), _p(pos0), _p(sg0), _p(bd0), _p(uniforms), _p(pos_obs), _p(sg_obs), _p(fl_obs), _p(scal), _p(n_rec), _p(n_ev),
             _p(t_fin), _p(exits), _p(n_exit)]
-    rows = None
+    rows = capture = None
     if entry == "gils_run":
         rows = np.zeros((S, M, 4 + 2 * max(int(k_max), 0)))
         rc = call(C.byref(par), int(k_max), int(first_obs), *args, _p(rows), C.byref(ms))
+    elif entry == "gilc_run":
+        groups = None if group_of_site is None else np.ascontiguousarray(group_of_site, dtype=np.int32)
+        if groups is not None and groups.shape != (L,):
+            raise ValueError("group_of_site must have one entry per site")
+        capture = np.zeros((S, M, GILC_NFIXED + max(int(n_groups), 0) + max(int(c_bins), 0)), np.int64)
+        life_hist, life_sums = np.zeros((S, 2, max(int(h_bins), 1)), np.int64), np.zeros((S, 2, 2))
+        rc = call(C.byref(par), _p(groups), int(n_groups), int(c_bins), int(h_bins), float(h_dt), int(first_obs), *args,
+                  _p(capture), _p(life_hist), _p(life_sums), C.byref(ms))
     else:
         rc = call(C.byref(par), *args, C.byref(ms))
     if rc != 0:
@@ -182,6 +250,8 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
                exits=exits, n_exits=n_exit, n0=n0, kernel_ms=ms.value)
     if rows is not None:
         out["structure"] = rows
+    if capture is not None:
+        out.update(capture=capture, life_hist=life_hist, life_sums=life_sums)
     return out
 
 
@@ -328,6 +398,50 @@ def run_batched_exact_structure(systems, T=10.0, obs_dt=0.01, start_fraction=0.5
         if series is not None:
             res.update(times_obs=times_obs.copy(), fft_amp_series=np.array(series.amp), var_series=np.array(series.var))
         rows.append(res)
+        ps.n_events = int(r["n_events"][s])
+    first.kernel_ms = r["kernel_ms"]
+    return rows
+
+
+def run_batched_exact_capture(systems, T=10.0, obs_dt=0.01, c_bins=16, h_bins=40, h_dt=None, start_fraction=0.0, uniforms=None):
+    """The anchor-capture study of PARTICLE_solver_CLASS.py:766-976 (cluster sizes, bound-state lifetimes, survival curve and
+    first-passage density, exit positions, cumulative exits per anchor) for many systems under the exact dynamics, from counts
+    the event-loop kernel takes at every event and observation: no state array leaves the GPU.  Returns one dict per system
+    (observables.DeviceCapture.result: the keys of observables.capture_observables plus the lifetime histograms, their means and
+    variances).  The per-observation rows are taken from observation int(start_fraction * M) on; the series are zero before it.
+    `h_dt=None`: T / h_bins.  Lifetimes are resolved to the event and follow the particle, where the reference's are quantised
+    to obs_dt and, after the first exit, attributed to shifted particle ids."""
+    from . import observables
+    from .particle_system import _SHAPE_ATTRS
+    first = systems[0]
+    for ps in systems[1:]:
+        for k in _SHAPE_ATTRS:
+            if getattr(ps, k) != getattr(first, k):
+                raise ValueError(f"run_batched_exact_capture: systems differ in {k}")
+        if not np.array_equal(ps.is_anchor_site, first.is_anchor_site):
+            raise ValueError("run_batched_exact_capture: systems differ in their anchor sites")
+    inits = [ps.init_particles() for ps in systems]
+    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+    times_obs = np.arange(0.0, T, obs_dt)
+    M, L = len(times_obs), first.L
+    groups = observables.anchor_groups(first)
+    n_groups = len(first.anchor_idxs)
+    h_dt = float(T) / int(h_bins) if h_dt is None else float(h_dt)
+    r = run_capture_raw(L=L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
+                        rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs,
+                        T=T, seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
+                        suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
+                        k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms,
+                        want_states=False, device=first.device, flip_table=first.flip_table(),
+                        group_of_site=groups if n_groups else None, n_groups=n_groups, c_bins=c_bins, h_bins=h_bins, h_dt=h_dt,
+                        first_obs=int(start_fraction * M))
+    rows = []
+    for s, ps in enumerate(systems):
+        if int(r["n_recorded"][s]) < M:
+            raise RuntimeError("a system passed T before its last observation time (choose T beyond the last observation)")
+        acc = observables.DeviceCapture(times_obs, L, n_groups, c_bins, h_dt)
+        rows.append(acc.result(r["scalars"][s, :, 0], r["capture"][s], r["exits"][s, :int(r["n_exits"][s])], r["life_hist"][s],
+                               r["life_sums"][s]))
         ps.n_events = int(r["n_events"][s])
     first.kernel_ms = r["kernel_ms"]
     return rows

@@ -246,3 +246,107 @@ class DeviceStructure:
                 "dominant_k": int(np.argmax(fft_mean[1:]) + 1), "low_k_power": float(np.sum(fft_mean[1:cut])),
                 "m_local_var": float(self.m2 / self.nm - mean_m * mean_m),
                 "lowk_variance": float(np.mean(np.sum(amp[:, 1:cut] ** 2, axis=1)))}
+
+
+# ------------------------------------------------------------------------------------------------ anchor-capture study
+EXIT_POSITION_BINS = 50
+
+
+def anchor_groups(ps):
+    """Site -> anchor id (PARTICLE_solver_CLASS.py:923-928): for every site of `ps.anchor_idx_array` the nearest centre of
+    `ps.anchor_idxs` (argmin: the first centre on ties), -1 elsewhere.  int32 [L], the `group_of_site` of gilc_run."""
+    groups = np.full(int(ps.L), -1, np.int32)
+    centres = np.asarray(ps.anchor_idxs, dtype=int)
+    sites = np.asarray(ps.anchor_idx_array, dtype=int)
+    if centres.size and sites.size:
+        groups[sites] = np.argmin(np.abs(centres[None, :] - sites[:, None]), axis=1)
+    return groups
+
+
+def cluster_counts(occupied, c_bins):
+    """Maximal runs of True in `occupied`, scanned from site 0 to L - 1 without joining across the seam
+    (get_cluster_sizes, ref :769-781): (occupied sites, clusters, largest, sum of size^2, histogram over sizes
+    1 .. c_bins - 1 and >= c_bins)."""
+    o = np.concatenate([[0], np.asarray(occupied, dtype=np.int8), [0]])
+    d = np.diff(o)
+    sizes = np.flatnonzero(d == -1) - np.flatnonzero(d == 1)
+    hist = np.bincount(np.minimum(sizes, c_bins) - 1, minlength=c_bins).astype(np.int64)
+    return int(sizes.sum()), int(sizes.size), int(sizes.max()) if sizes.size else 0, int((sizes.astype(np.int64) ** 2).sum()), hist
+
+
+def _survival_keys(times_obs, n_t):
+    """ref :848-855"""
+    n_t = np.asarray(n_t, dtype=float)
+    n0 = n_t[0]
+    flux = np.clip(-np.gradient(n_t, times_obs), 0, None) if len(n_t) > 1 else np.zeros_like(n_t)
+    fpt_pdf = flux / n0
+    total_exited = n0 - n_t[-1]
+    return {"survival": n_t / n0, "fpt_pdf": fpt_pdf, "fpt_pdf_cond": flux / total_exited if total_exited > 0 else fpt_pdf * 0.0}
+
+
+def capture_observables(out, group_of_site, c_bins=16):
+    """The capture study's curves (PARTICLE_solver_CLASS.py:766-976) from the full outputs of one run (`ParticleSystem.run`,
+    gillespie.run_batched_exact): `survival`, `fpt_pdf`, `fpt_pdf_cond` (ref :848-855); `cumulative_exits` [M][G] and
+    `cumulative_exits_total` [M] (ref :934-954: exit times binned by the observation times, searchsorted side="right", then
+    cumulated; G = largest group id + 1); `exit_position_hist`, 50 bins of exit position / L (ref :893; over [0, 1] here,
+    so that runs can be added, where the reference lets the bins follow the data); and per observation the cluster
+    quantities `occupied_sites`, `n_clusters`, `largest_cluster`, `sum_size2` [M] and `cluster_hist` [M][c_bins] (ref :769-783,
+    which looks at the last observation only).  Clusters do not join across the seam of a ring, as in the reference."""
+    times = np.asarray(out["times_obs"], dtype=float)
+    M = len(times)
+    total = np.asarray(out["total_list"])
+    L = total.shape[1]
+    groups = np.full(L, -1, int) if group_of_site is None else np.asarray(group_of_site, dtype=int)
+    G = int(groups.max()) + 1 if groups.size else 0
+    res = _survival_keys(times, out["particle_count_list"])
+    exit_t, exit_x = np.asarray(out["exit_times"], dtype=float), np.asarray(out["exit_positions"], dtype=int)
+    dt = times[1] - times[0] if M > 1 else 1.0
+    edges = np.concatenate([times, [times[-1] + dt]])
+    counts = np.zeros((M, max(G, 0)), np.int64)
+    for t, x in zip(exit_t, exit_x):
+        g = groups[x] if 0 <= x < L else -1
+        b = int(np.searchsorted(edges, t, side="right")) - 1
+        if g >= 0 and 0 <= b < M:
+            counts[b, g] += 1
+    res["cumulative_exits"] = np.cumsum(counts, axis=0)
+    res["cumulative_exits_total"] = res["cumulative_exits"].sum(axis=1)
+    res["exit_position_hist"] = np.histogram(exit_x / L, bins=EXIT_POSITION_BINS, range=(0.0, 1.0))[0].astype(np.int64)
+    rows = [cluster_counts(total[k] > 1e-12, c_bins) for k in range(M)]
+    for j, key in enumerate(("occupied_sites", "n_clusters", "largest_cluster", "sum_size2")):
+        res[key] = np.array([r[j] for r in rows], np.int64)
+    res["cluster_hist"] = np.stack([r[4] for r in rows])
+    return res
+
+
+class DeviceCapture:
+    """The keys of `capture_observables` from what gilc_run returns for one system (include/gillespie_capture.h) -- the live
+    counts of the scalar sums, the rows of capture counts, the exit log -- plus the lifetimes of bound states, which only the
+    event loop resolves: `life_hist` [2][h_bins] (ended by unbinding, by exit), `life_edges`, `life_count`, `life_mean`,
+    `life_var` [2] (nan where nothing ended that way) and `binds`, `unbinds`, `n_bound` [M].
+
+    Row k counts the exits logged with a time < times_obs[k] (the event that crossed an observation was drawn before it), so
+    the reference's bin b of the cumulative exits is row b + 1 and its last bin the last row, the run's total."""
+
+    def __init__(self, times_obs, L, n_groups, c_bins, h_dt):
+        self.times, self.L, self.G, self.c_bins, self.h_dt = np.asarray(times_obs, dtype=float), int(L), int(n_groups), int(c_bins), float(h_dt)
+
+    def result(self, n_live, rows, exits, life_hist, life_sums):
+        rows = np.asarray(rows, dtype=np.int64)
+        G = self.G
+        res = _survival_keys(self.times, n_live)
+        shifted = np.concatenate([rows[1:], rows[-1:]], axis=0)
+        res["cumulative_exits"] = shifted[:, 9:9 + G].copy()
+        res["cumulative_exits_total"] = res["cumulative_exits"].sum(axis=1)
+        exit_x = np.asarray(exits, dtype=float).reshape(-1, 3)[:, 1]
+        res["exit_position_hist"] = np.histogram(exit_x / self.L, bins=EXIT_POSITION_BINS, range=(0.0, 1.0))[0].astype(np.int64)
+        for j, key in enumerate(("occupied_sites", "n_clusters", "largest_cluster", "sum_size2")):
+            res[key] = rows[:, 5 + j].copy()
+        res["cluster_hist"] = rows[:, 9 + G:9 + G + self.c_bins].copy()
+        res.update(n_bound=rows[:, 1].copy(), binds=rows[:, 2].copy(), unbinds=rows[:, 3].copy())
+        hist, sums = np.asarray(life_hist, dtype=np.int64), np.asarray(life_sums, dtype=float)
+        count = hist.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = np.where(count > 0, sums[:, 0] / count, np.nan)
+            var = np.where(count > 0, sums[:, 1] / count - mean * mean, np.nan)
+        res.update(life_hist=hist.copy(), life_edges=self.h_dt * np.arange(hist.shape[1] + 1), life_count=count, life_mean=mean, life_var=var)
+        return res
