@@ -31,6 +31,7 @@
 #include "gillespie_common.hpp"
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiation only)
 #include "gillespie_capture.hpp"          // anchor capture and cluster statistics (capture instantiation only)
+#include "gillespie_profile.hpp"          // ensemble density and field profiles (profile instantiation only)
 
 namespace {
 
@@ -199,15 +200,19 @@ __device__ inline void big_scalar_sums(const int *pos, const uint8_t *flg, int *
 }
 
 struct GilsBigArgs : BigArgs { GilsArgs st; };              // arguments of the structure instantiation
-struct GilcBigArgs : GilsBigArgs { GilcArgs cp; };          // arguments of the capture instantiation (the driver's one struct)
+struct GilcBigArgs : GilsBigArgs { GilcArgs cp; };          // arguments of the capture instantiation
+struct GilpBigArgs : GilcBigArgs { GilpArgs pf; };          // arguments of the profile instantiation (the driver's one struct)
 
 // ST = also reduce the structure sums at an observation (gillespie_structure.hpp): a compile-time property, so that the
 // kernel without it is the code it was before they existed.
 // CP = anchor capture and cluster statistics (gillespie_capture.hpp), likewise; not combined with ST.  Its slots lie behind
 // ctl[] in LDS, its bind times in global memory; the event loop holds no register for either.
-template <bool ST, bool CP = false>
-__global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<CP, GilcBigArgs, std::conditional_t<ST, GilsBigArgs, BigArgs>> a0) {
+// PF = ensemble density and field profiles (gillespie_profile.hpp), likewise; not combined with ST or CP.  Its slots lie
+// behind ctl[] in LDS and are used at an observation only.
+template <bool ST, bool CP = false, bool PF = false>
+__global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<PF, GilpBigArgs, std::conditional_t<CP, GilcBigArgs, std::conditional_t<ST, GilsBigArgs, BigArgs>>> a0) {
     static_assert(!(ST && CP), "the capture launch takes no structure sums");
+    static_assert(!(PF && (ST || CP)), "the profile launch takes no structure sums and no capture statistics");
     extern __shared__ double lds[];
     BigArgs a = a0;
     select_system(a, (size_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x));
@@ -292,6 +297,13 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<CP
             if (k >= ca.first_obs)
                 gilc_record_row<BT>(ca.rows + ((size_t)blockIdx.x * nobs + k) * (size_t)(GILC_FIXED + ca.n_groups + ca.c_bins),
                                     gilc_lds(ctl + 32, ca, BW), ca, L, N, a.flg, a.occ, n_exit);
+        }
+        if constexpr (PF) {
+            if (k >= a0.pf.first_obs) {
+                double mg = 0.0;                               // global-mean mode: the one value of every site (ref :219-221)
+                if (!M.field_mode && gsum_n > 0) { mg = (double)gsum_s / (double)gsum_n; mg = mg > 1.0 ? 1.0 : (mg < -1.0 ? -1.0 : mg); }
+                gilp_record<BT>(a0.pf, ctl + 32, (size_t)blockIdx.x, k, nobs, L, N, a.pos, a.flg, a.W, a.S, M.field_mode != 0, mg);
+            }
         }
     };
     record(0);
@@ -610,7 +622,7 @@ int big_plan(const char *who, std::string &err, const gil_params *p, bool want_s
 int big_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
             const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
             int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
-            int k_max = 0, int first_obs = 0, double *structure_obs = nullptr, const GilcCall *cap = nullptr) {
+            int k_max = 0, int first_obs = 0, double *structure_obs = nullptr, const GilcCall *cap = nullptr, const GilpCall *prof = nullptr) {
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilm_plan_info info{};
     std::vector<double> table;
@@ -628,6 +640,11 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
         info.output_bytes += (int64_t)S * (p->n_obs * (int64_t)crow * 8 + 2 * (int64_t)cap->h_bins * 8 + 32);
         if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
     }
+    if (prof) {                                               // of ensemble profiles (gilp_run)
+        info.lds_bytes += (int32_t)gilp_lds_bytes(prof->n_bins, prof->want_field != 0);
+        info.output_bytes = gilp_output_bytes(p, prof->n_groups, prof->n_bins, pos_obs || sigma_obs || flags_obs, prof->profile_obs != nullptr);
+        if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
+    }
     for (int s = 0; s < S; ++s) {
         if (n0[s] < 0 || n0[s] > N) return bad("bad n_cap / n0 / n_obs / max_events");
         if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * N, sigma0 + (size_t)s * N)) return bad(why);
@@ -637,11 +654,11 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
     const int64_t work_bytes = (int64_t)S * info.work_bytes_per_system + (structure_obs ? (int64_t)L * 16 : 0) +
-                               (cap ? (int64_t)S * N * 8 + (cap->n_groups > 0 ? (int64_t)L * 4 : 0) : 0);
+                               (cap ? (int64_t)S * N * 8 + (cap->n_groups > 0 ? (int64_t)L * 4 : 0) : 0) + (prof ? (int64_t)S * 4 : 0);
     if ((uint64_t)(work_bytes + info.output_bytes) > (uint64_t)free_b)
         return bad("the batch needs " + std::to_string(work_bytes) + " bytes of work memory and " +
                    std::to_string(info.output_bytes) + " bytes of outputs, the device has " + std::to_string(free_b) + " bytes free");
-    GilcBigArgs a{};
+    GilpBigArgs a{};
     a.p = *p; a.tlen = info.table_len; a.nblk = info.n_blocks; a.cb = (a.nblk + BT - 1) / BT;
     a.tab_in_lds = info.table_in_lds;
     a.m = gil_model(p);
@@ -676,12 +693,22 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
         if (cap->group_of_site) UP(cp.group, cap->group_of_site, (size_t)L);
         WORK(cp.rows, SO * crow); WORK(cp.life_hist, (size_t)S * 2 * cap->h_bins); WORK(cp.life_sums, (size_t)S * 4); WORK(cp.tbind, SN);
         if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false, true>), lds)) return rc;
+    } else if (prof) {
+        GilpArgs &pa = a.pf;
+        const size_t GO = (size_t)prof->n_groups * p->n_obs;
+        pa.n_bins = prof->n_bins; pa.width = (L + prof->n_bins - 1) / prof->n_bins; pa.n_used = (L + pa.width - 1) / pa.width;
+        pa.first_obs = prof->first_obs; pa.want_field = prof->want_field;
+        if (prof->group_of_system) UP(pf.group, prof->group_of_system, (size_t)S); else WORK(pf.group, (size_t)S);   // zero-filled: group 0
+        WORK(pf.sums, GO * GILP_COLS * prof->n_bins); WORK(pf.members, GO);
+        if (prof->profile_obs) WORK(pf.rows, SO * 3 * prof->n_bins);
+        if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false, false, true>), lds)) return rc;
     } else if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false>), lds)) return rc;
     if (int rc = job.create_events()) return rc;
     hipLaunchKernelGGL(big_field_init, dim3((unsigned)((L + 255) / 256), (unsigned)S), dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
     job.ev.start();
     if (structure_obs) hipLaunchKernelGGL(gil_big_kernel<true>, dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const GilsBigArgs &>(a));
-    else if (cap) hipLaunchKernelGGL((gil_big_kernel<false, true>), dim3((unsigned)S), dim3(BT), lds, nullptr, a);
+    else if (cap) hipLaunchKernelGGL((gil_big_kernel<false, true>), dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const GilcBigArgs &>(a));
+    else if (prof) hipLaunchKernelGGL((gil_big_kernel<false, false, true>), dim3((unsigned)S), dim3(BT), lds, nullptr, a);
     else hipLaunchKernelGGL(gil_big_kernel<false>, dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const BigArgs &>(a));
     job.ev.stop();
     if (int rc = job.finish(hipGetLastError(), "gil_big_kernel", kernel_ms)) return rc;
@@ -694,6 +721,12 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
         if (int rc = job.download(cap->capture_obs, a.cp.rows, SO * crow * 8, "capture_obs")) return rc;
         if (int rc = job.download(cap->life_hist, a.cp.life_hist, (size_t)S * 2 * cap->h_bins * 8, "life_hist")) return rc;
         if (int rc = job.download(cap->life_sums, a.cp.life_sums, (size_t)S * 4 * 8, "life_sums")) return rc;
+    }
+    if (prof) {
+        const size_t GO = (size_t)prof->n_groups * p->n_obs;
+        if (int rc = job.download(prof->ensemble_sums, a.pf.sums, GO * GILP_COLS * prof->n_bins * 8, "ensemble_sums")) return rc;
+        if (int rc = job.download(prof->members, a.pf.members, GO * 4, "members")) return rc;
+        if (int rc = job.download(prof->profile_obs, a.pf.rows, SO * 3 * prof->n_bins * 4, "profile_obs")) return rc;
     }
     return GIL_OK;
 }
@@ -734,6 +767,18 @@ int gilc_large_run(const char *who, std::string &err, const gil_params *p, const
                    double *kernel_ms, const GilcCall *cap) {
     return big_run(who, err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
                    t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, cap);
+}
+
+int gilp_large_plan(const char *who, std::string &err, const gil_params *p, int32_t prof_lds, int32_t *lds_bytes, int64_t *work_bytes) {
+    return gilc_large_plan(who, err, p, prof_lds, lds_bytes, work_bytes);   // the same arithmetic: the kernel's own LDS plus the slots
+}
+
+int gilp_large_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
+                   const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs,
+                   int64_t *scalars_obs, int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits,
+                   double *kernel_ms, const GilpCall *prof) {
+    return big_run(who, err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
+                   t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, nullptr, prof);
 }
 
 extern "C" {

@@ -26,10 +26,12 @@
 #include "gillespie.h"
 #include "gillespie_structure.h"
 #include "gillespie_capture.h"
+#include "gillespie_profile.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"           // model, initial-state check, the driver of the one-shot entry points
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiations only)
 #include "gillespie_capture.hpp"          // anchor capture and cluster statistics (capture instantiations only)
+#include "gillespie_profile.hpp"          // ensemble density and field profiles (profile instantiations only)
 
 namespace {
 
@@ -64,7 +66,8 @@ __device__ inline long long wg_sum_ll(long long v, long long *red) {
 }
 
 struct GilsBatchArgs : GilArgs { GilsArgs st; };            // arguments of the structure instantiations
-struct GilcBatchArgs : GilsBatchArgs { GilcArgs cp; };      // arguments of the capture instantiations (the driver's one struct)
+struct GilcBatchArgs : GilsBatchArgs { GilcArgs cp; };      // arguments of the capture instantiations
+struct GilpBatchArgs : GilcBatchArgs { GilpArgs pf; };      // arguments of the profile instantiations (the driver's one struct)
 
 // the structure sums' slots: behind the loop's own LDS (which ends with the plus-occupancy bytes), at the next multiple of 8
 __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L) {
@@ -76,9 +79,11 @@ __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L)
 // ST = also reduce the structure sums at an observation (gillespie_structure.hpp): a compile-time property, so that the
 // kernels without it are the code they were before it existed.
 // CP = anchor capture and cluster statistics (gillespie_capture.hpp), likewise; not combined with ST.
-template <int NT, bool ST, bool CP = false>
-__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<CP, GilcBatchArgs, std::conditional_t<ST, GilsBatchArgs, GilArgs>> a) {
+// PF = ensemble density and field profiles (gillespie_profile.hpp), likewise; not combined with ST or CP.
+template <int NT, bool ST, bool CP = false, bool PF = false>
+__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, GilpBatchArgs, std::conditional_t<CP, GilcBatchArgs, std::conditional_t<ST, GilsBatchArgs, GilArgs>>> a) {
     static_assert(!(ST && CP), "the capture launches take no structure sums");
+    static_assert(!(PF && (ST || CP)), "the profile launches take no structure sums and no capture statistics");
     extern __shared__ double lds[];
     const Model &M = a.m;
     const int L = M.L, K = M.K, t = threadIdx.x, sys = blockIdx.x, ncap = a.p.n_cap, nobs = a.p.n_obs;
@@ -199,6 +204,13 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<CP, Gi
             if (k >= a.cp.first_obs)
                 gilc_record_row<NT>(a.cp.rows + ((size_t)sys * nobs + k) * (size_t)(GILC_FIXED + a.cp.n_groups + a.cp.c_bins),
                                     gilc_lds(gils_slots(lds, occp, L), a.cp, NT / 64), a.cp, L, ncap, flg, occ, n_exit);
+        }
+        if constexpr (PF) {
+            if (k >= a.pf.first_obs) {
+                double mg = 0.0;                               // global-mean mode: the one value of every site (ref :219-221)
+                if (!M.field_mode && gsum_n > 0) { mg = (double)gsum_s / (double)gsum_n; mg = mg > 1.0 ? 1.0 : (mg < -1.0 ? -1.0 : mg); }
+                gilp_record<NT>(a.pf, gils_slots(lds, occp, L), (size_t)sys, k, nobs, L, ncap, pos, flg, W, S, M.field_mode != 0, mg);
+            }
         }
     };
 
@@ -441,8 +453,10 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<CP, Gi
 }
 
 // threads and dynamic LDS bytes of one system in the batch kernel; st: with the structure sums' slots, and with a copy of the
-// phase table behind them where the 160 KB leave room for it (phase_in_lds); cap: with the capture slots and the bind times
-void batch_shape(int L, int ncap, int tlen, bool st, int &NT, size_t &lds, bool *phase_in_lds = nullptr, const GilcCall *cap = nullptr) {
+// phase table behind them where the 160 KB leave room for it (phase_in_lds); cap: with the capture slots and the bind times;
+// prof_bytes: with that many bytes of profile slots
+void batch_shape(int L, int ncap, int tlen, bool st, int &NT, size_t &lds, bool *phase_in_lds = nullptr, const GilcCall *cap = nullptr,
+                 size_t prof_bytes = 0) {
     NT = ncap <= 1024 ? 64 : 256;                             // one wavefront per system while a lane owns at most 16 particles
     lds = ((size_t)2 * L + ((tlen + 2) & ~1) + ncap + (ncap & 1) + 8 + 5 * NT + 8) * sizeof(double) +
           ((size_t)3 * ncap + 16) * sizeof(int) + (size_t)((ncap + 15) & ~15) + (size_t)2 * ((L + 15) & ~15);
@@ -452,6 +466,7 @@ void batch_shape(int L, int ncap, int tlen, bool st, int &NT, size_t &lds, bool 
         if (*phase_in_lds) lds += (size_t)16 * L;
     }
     if (cap) lds = ((lds + 7) & ~(size_t)7) + (gilc_lds_slots(NT, cap->n_groups, cap->c_bins, cap->h_bins) + (size_t)ncap) * 8;
+    if (prof_bytes) lds = ((lds + 7) & ~(size_t)7) + prof_bytes;
 }
 
 // device copies of the outputs of one capture call (gilc_plan_info.output_bytes)
@@ -468,11 +483,11 @@ int64_t gils_output_bytes(const gil_params *p, int k_max, bool states, bool scal
 }
 
 // The one host driver of the batch kernel.  structure_obs: gils_run's rows (k_max modes, from observation first_obs on),
-// nullptr for gil_run_batch.  The callers have checked their required pointers.
+// nullptr for gil_run_batch; cap: gilc_run's call; prof: gilp_run's.  The callers have checked their required pointers.
 int batch_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
               const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
               int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
-              int k_max, int first_obs, double *structure_obs, const GilcCall *cap = nullptr) {
+              int k_max, int first_obs, double *structure_obs, const GilcCall *cap = nullptr, const GilpCall *prof = nullptr) {
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     if (p->L < 2 || p->L > GIL_MAX_L) return bad("L must be in [2, GIL_MAX_L]");
     if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
@@ -484,11 +499,12 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
     }
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: a run may record fewer observations than it has room for
     if (int rc = job.select_device(p->device)) return rc;
-    if (structure_obs || cap) {
+    if (structure_obs || cap || prof) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
-        const int64_t work = cap ? (cap->n_groups > 0 ? (int64_t)L * 4 : 0) : (int64_t)L * 16,
-                      outb = cap ? gilc_output_bytes(p, *cap, pos_obs || sigma_obs || flags_obs)
+        const int64_t work = prof ? (int64_t)S * 4 : cap ? (cap->n_groups > 0 ? (int64_t)L * 4 : 0) : (int64_t)L * 16,
+                      outb = prof ? gilp_output_bytes(p, prof->n_groups, prof->n_bins, pos_obs || sigma_obs || flags_obs, prof->profile_obs != nullptr)
+                             : cap ? gilc_output_bytes(p, *cap, pos_obs || sigma_obs || flags_obs)
                                  : gils_output_bytes(p, k_max, pos_obs || sigma_obs || flags_obs, scalars_obs != nullptr);
         if ((uint64_t)(work + outb) > (uint64_t)free_b)
             return bad("the batch needs " + std::to_string(work) + " bytes of work memory and " + std::to_string(outb) +
@@ -497,9 +513,9 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
 
     std::vector<double> table; int tlen = 0, q = 0;
     weight_table(p->sigma_grid, L, p->K, p->periodic != 0, table, tlen, q);
-    GilcBatchArgs a{};
+    GilpBatchArgs a{};
     int NT; size_t lds; bool phase_in_lds = false;
-    batch_shape(L, ncap, tlen, structure_obs != nullptr, NT, lds, &phase_in_lds, cap);
+    batch_shape(L, ncap, tlen, structure_obs != nullptr, NT, lds, &phase_in_lds, cap, prof ? gilp_lds_bytes(prof->n_bins, prof->want_field != 0) : 0);
     a.p = *p; a.tlen = tlen; a.chunk = (ncap + NT - 1) / NT;
     a.m = gil_model(p);
     const size_t SN = (size_t)S * ncap, SO = (size_t)S * p->n_obs;
@@ -532,6 +548,15 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
         WORK(cp.rows, SO * (size_t)(GILC_NFIXED + cap->n_groups + cap->c_bins));
         WORK(cp.life_hist, (size_t)S * 2 * cap->h_bins); WORK(cp.life_sums, (size_t)S * 4);
         if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, true>) : reinterpret_cast<const void *>(&gil_kernel<256, false, true>), lds)) return rc;
+    } else if (prof) {
+        GilpArgs &pa = a.pf;
+        const size_t GO = (size_t)prof->n_groups * p->n_obs;
+        pa.n_bins = prof->n_bins; pa.width = (L + prof->n_bins - 1) / prof->n_bins; pa.n_used = (L + pa.width - 1) / pa.width;
+        pa.first_obs = prof->first_obs; pa.want_field = prof->want_field;
+        if (prof->group_of_system) UP(pf.group, prof->group_of_system, (size_t)S); else WORK(pf.group, (size_t)S);   // zero-filled: group 0
+        WORK(pf.sums, GO * GILP_COLS * prof->n_bins); WORK(pf.members, GO);
+        if (prof->profile_obs) WORK(pf.rows, SO * 3 * prof->n_bins);
+        if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, false, true>) : reinterpret_cast<const void *>(&gil_kernel<256, false, false, true>), lds)) return rc;
     } else if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false>) : reinterpret_cast<const void *>(&gil_kernel<256, false>), lds)) return rc;
     if (int rc = job.create_events()) return rc;
     job.ev.start();
@@ -539,8 +564,11 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
         if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, true>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilsBatchArgs &>(a));
         else hipLaunchKernelGGL((gil_kernel<256, true>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilsBatchArgs &>(a));
     } else if (cap) {
-        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
-        else hipLaunchKernelGGL((gil_kernel<256, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
+        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilcBatchArgs &>(a));
+        else hipLaunchKernelGGL((gil_kernel<256, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilcBatchArgs &>(a));
+    } else if (prof) {
+        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
+        else hipLaunchKernelGGL((gil_kernel<256, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
     } else if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilArgs &>(a));
     else hipLaunchKernelGGL((gil_kernel<256, false>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilArgs &>(a));
     job.ev.stop();
@@ -553,6 +581,12 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
         if (int rc = job.download(cap->capture_obs, a.cp.rows, SO * (size_t)(GILC_NFIXED + cap->n_groups + cap->c_bins) * 8, "capture_obs")) return rc;
         if (int rc = job.download(cap->life_hist, a.cp.life_hist, (size_t)S * 2 * cap->h_bins * 8, "life_hist")) return rc;
         if (int rc = job.download(cap->life_sums, a.cp.life_sums, (size_t)S * 4 * 8, "life_sums")) return rc;
+    }
+    if (prof) {
+        const size_t GO = (size_t)prof->n_groups * p->n_obs;
+        if (int rc = job.download(prof->ensemble_sums, a.pf.sums, GO * GILP_COLS * prof->n_bins * 8, "ensemble_sums")) return rc;
+        if (int rc = job.download(prof->members, a.pf.members, GO * 4, "members")) return rc;
+        if (int rc = job.download(prof->profile_obs, a.pf.rows, SO * 3 * prof->n_bins * 4, "profile_obs")) return rc;
     }
     return GIL_OK;
 }
@@ -633,9 +667,81 @@ int gilc_decide(const char *who, const gil_params *p, const GilcCall &c, bool st
     return GIL_OK;
 }
 
+std::string g_gilp_err;
+
+// the checks gilp_plan and gilp_run share, and the shape: 0 with `info` filled, or GIL_ERR_ARG with the text in g_gilp_err
+int gilp_decide(const char *who, const gil_params *p, const GilpCall &c, bool states, gilp_plan_info &info) {
+    auto bad = [&](const std::string &m) { g_gilp_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    if (p->L < 2) return bad("L must be at least 2");
+    if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
+    const int max_bins = std::min(p->L, GILP_MAX_BINS);
+    if (c.n_bins < 1 || c.n_bins > max_bins) return bad("n_bins = " + std::to_string(c.n_bins) + " is outside [1, min(L, GILP_MAX_BINS) = " + std::to_string(max_bins) + "]");
+    if (c.n_groups < 1 || c.n_groups > GILP_MAX_GROUPS) return bad("n_groups = " + std::to_string(c.n_groups) + " is outside [1, " + std::to_string(GILP_MAX_GROUPS) + "]");
+    if (c.first_obs < 0 || c.first_obs > p->n_obs) return bad("first_obs = " + std::to_string(c.first_obs) + " is outside [0, n_obs = " + std::to_string(p->n_obs) + "]");
+    if (c.want_field != 0 && c.want_field != 1) return bad("want_field = " + std::to_string(c.want_field) + " is neither 0 nor 1");
+    if (c.want_field && (int64_t)p->L * p->n_systems >= (1ll << 31))
+        return bad("want_field with L * n_systems = " + std::to_string((int64_t)p->L * p->n_systems) + " >= 2^31: the fixed-point field sum could overflow 64 bits");
+    if (c.group_of_system)
+        for (int s = 0; s < p->n_systems; ++s) {
+            const int g = c.group_of_system[s];
+            if (g < 0 || g >= c.n_groups) return bad("group id " + std::to_string(g) + " of system " + std::to_string(s) + " is outside [0, n_groups = " + std::to_string(c.n_groups) + ")");
+        }
+    info = gilp_plan_info{};
+    info.bin_width = (p->L + c.n_bins - 1) / c.n_bins;
+    info.n_bins_used = (p->L + info.bin_width - 1) / info.bin_width;
+    info.output_bytes = gilp_output_bytes(p, c.n_groups, c.n_bins, states, c.profile_obs != nullptr);
+    info.shape = GILS_SHAPE_LARGE;
+    const size_t prof_lds = gilp_lds_bytes(c.n_bins, c.want_field != 0);
+    if (p->L <= GIL_MAX_L && p->n_cap <= GIL_MAX_N) {
+        if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
+        std::vector<double> table; int tlen = 0, q = 0, NT = 0; size_t lds = 0;
+        weight_table(p->sigma_grid, p->L, p->K, p->periodic != 0, table, tlen, q);
+        batch_shape(p->L, p->n_cap, tlen, false, NT, lds, nullptr, nullptr, prof_lds);
+        if (lds <= 160 * 1024) { info.shape = GILS_SHAPE_BATCH; info.threads = NT; info.lds_bytes = (int32_t)lds; info.work_bytes = (int64_t)p->n_systems * 4; }
+    }
+    if (info.shape == GILS_SHAPE_LARGE) {
+        int32_t lds = 0; int64_t work = 0;
+        if (int rc = gilp_large_plan(who, g_gilp_err, p, (int32_t)prof_lds, &lds, &work)) return rc;
+        info.threads = 1024; info.lds_bytes = lds; info.work_bytes = work + (int64_t)p->n_systems * 4;
+    }
+    if (info.work_bytes + info.output_bytes > (1ll << 38))
+        return bad("the batch needs " + std::to_string(info.work_bytes) + " bytes of work memory and " + std::to_string(info.output_bytes) +
+                   " bytes of outputs, more than the " + std::to_string(1ll << 38) + " bytes a plan accepts");
+    return GIL_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+const char *gilp_last_error(void) { return g_gilp_err.c_str(); }
+
+int gilp_plan(const gil_params *p, int32_t n_bins, int32_t n_groups, int32_t first_obs, int32_t want_field, int32_t want_states,
+              int32_t want_per_system, gilp_plan_info *out) {
+    if (!p || !out) { g_gilp_err = "gilp_plan: null argument"; return GIL_ERR_ARG; }
+    int32_t some = 0;                                          // a plan has no buffers: only whether the per-system rows are wanted
+    const GilpCall c{nullptr, n_groups, n_bins, first_obs, want_field, nullptr, nullptr, want_per_system ? &some : nullptr};
+    gilp_plan_info info;
+    if (int rc = gilp_decide("gilp_plan", p, c, want_states != 0, info)) return rc;
+    *out = info;
+    return GIL_OK;
+}
+
+int gilp_run(const gil_params *p, int32_t n_bins, int32_t first_obs, int32_t want_field, const int32_t *group_of_system, int32_t n_groups,
+             const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0, const double *uniforms,
+             int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
+             int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, int64_t *ensemble_sums, int32_t *members,
+             int32_t *profile_obs, double *kernel_ms) {
+    if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !ensemble_sums || !members) { g_gilp_err = "gilp_run: null argument"; return GIL_ERR_ARG; }
+    const GilpCall c{group_of_system, n_groups, n_bins, first_obs, want_field, ensemble_sums, members, profile_obs};
+    gilp_plan_info info;
+    if (int rc = gilp_decide("gilp_run", p, c, pos_obs || sigma_obs || flags_obs, info)) return rc;
+    if (info.shape == GILS_SHAPE_BATCH)
+        return batch_run("gilp_run", g_gilp_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
+                         n_recorded, n_events, t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, nullptr, &c);
+    return gilp_large_run("gilp_run", g_gilp_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
+                          n_recorded, n_events, t_final, exits, n_exits, kernel_ms, &c);
+}
 
 const char *gilc_last_error(void) { return g_gilc_err.c_str(); }
 

@@ -6,7 +6,9 @@ The two outer sweeps of the other drivers are here too: `sweep_over_sigmas` (int
 one batched handle per sigma / per particle number (the weight table and the state capacity differ), all (beta, run)
 pairs inside it.  `sweep_betas_for_structures` / `sweep_beta_structure_ensemble` are the pattern study's drivers
 (PARTICLE_solver_BIOLOGY_local_structure.py:105-193), all (beta, run) pairs in one launch, the per-run observables from sums
-taken on the GPU.  `capture_study` is the anchor-capture study (PARTICLE_solver_CLASS.py:766-976) as an ensemble in one launch."""
+taken on the GPU.  `capture_study` is the anchor-capture study (PARTICLE_solver_CLASS.py:766-976) as an ensemble in one launch.
+`profile_sweep` gives the ensemble density and field profiles per beta (the means over runs of rho_plus_list, rho_minus_list,
+m_local_list, PARTICLE_solver_CLASS.py:205-213), all (beta, run) pairs in one launch and summed over the runs on the GPU."""
 from __future__ import annotations
 
 import warnings
@@ -217,3 +219,34 @@ def capture_study(ps_kwargs, init_kwargs, n_runs, run_kwargs, rng_seeds=None, on
         res["life_hist_sum"] = np.sum([r["life_hist"] for r in rows], axis=0)
         res["life_edges"] = rows[0]["life_edges"]
     return res
+
+
+def profile_sweep(beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwargs, n_bins, rng_seeds=None, want_field=False,
+                  on_device=True):
+    """Space-time profiles per beta under the exact dynamics: {beta: observables.DeviceProfiles.result()} -- per observation and
+    bin the mean and standard error over the runs of the plus, minus, total and signed counts, the reference's densities
+    `rho_plus`, `rho_minus`, `rho_total` (count / (N bin_sites dx)) and, with `want_field`, the mean field `field_mean`.  All
+    (beta, run) pairs run in ONE launch, group = beta index.  `run_kwargs` holds T and obs_dt; `rng_seeds[b][r]` seeds the
+    initial condition of run r at beta b.  Needs k_exit = 0 and the same N for the runs of a beta.
+
+    on_device=True (gillespie.run_batched_exact_profiles): the event loop adds every run's bin counts to its beta's sums, and
+    [betas][observations][7][n_bins] integers leave the GPU.  on_device=False (gillespie.run_batched_exact +
+    observables.profile_observables): the same keys from the full state outputs, a bincount per run and observation on the host."""
+    from . import gillespie
+    ps_kwargs, init_kwargs, run_kwargs = dict(ps_kwargs or {}), dict(init_kwargs or {}), dict(run_kwargs or {})
+    unknown = set(run_kwargs) - {"T", "obs_dt"}
+    if unknown:
+        raise ValueError(f"run_kwargs may hold T and obs_dt; got {sorted(unknown)}")
+    systems, owner = [], []
+    for bi, beta in enumerate(beta_values):
+        for r in range(n_runs_per_beta):
+            rng = None if rng_seeds is None else np.random.default_rng(int(rng_seeds[bi][r]))
+            systems.append(ParticleSystem(beta=beta, rng=rng, **ps_kwargs, **init_kwargs))
+            owner.append(bi)
+    if on_device:
+        rows = gillespie.run_batched_exact_profiles(systems, n_bins=n_bins, groups=owner, want_field=want_field, **run_kwargs)
+    else:
+        outs = gillespie.run_batched_exact(systems, want_m_local=want_field, **run_kwargs)
+        rows = [observables.profile_observables([o for o, g in zip(outs, owner) if g == bi], n_bins, want_field, dx=systems[0].dx)
+                for bi in range(len(beta_values))]
+    return {beta: rows[bi] for bi, beta in enumerate(beta_values)}

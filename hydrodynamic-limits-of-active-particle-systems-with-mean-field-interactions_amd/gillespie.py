@@ -4,7 +4,8 @@ PARTICLE_solver_CLASS.py:450-558), one persistent workgroup per system.  `run_ba
 result dictionaries; `sweep` statistics can be taken from the scalar sums without the M x L arrays (`scalars_only=True`),
 and the structure observables from sums the loop takes at every observation (`run_batched_exact_structure`,
 include/gillespie_structure.h); the anchor-capture study's cluster, lifetime and exit statistics likewise
-(`run_batched_exact_capture`, include/gillespie_capture.h).
+(`run_batched_exact_capture`, include/gillespie_capture.h); the ensemble density and field profiles of many runs
+(`run_batched_exact_profiles`, include/gillespie_profile.h) are summed over the runs on the device.
 
 Differences to the reference: randomness is Philox4x32-10 keyed by `seed` (the reference consumes a NumPy Generator), so
 trajectories agree in distribution, not draw for draw; `m_local_list[k]` is the field of the observed state (the
@@ -51,6 +52,14 @@ class GilcPlanInfo(C.Structure):
                 ("work_bytes", C.c_int64), ("output_bytes", C.c_int64)]
 
 
+class GilpPlanInfo(C.Structure):
+    """struct gilp_plan_info of include/gillespie_profile.h, field for field."""
+    _fields_ = [("shape", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32), ("bin_width", C.c_int32),
+                ("n_bins_used", C.c_int32), ("reserved", C.c_int32), ("work_bytes", C.c_int64), ("output_bytes", C.c_int64)]
+
+
+GILP_NCOLS, GILP_MAX_BINS, GILP_MAX_GROUPS = 7, 1024, 4096
+PROFILE_COLUMNS = ("n_plus", "n_minus", "n_bound", "n_plus2", "n_minus2", "n_plus_minus", "field")
 GILC_NFIXED = 9
 CAPTURE_COLUMNS = ("n", "n_bound", "binds", "unbinds", "exits", "occupied_sites", "n_clusters", "largest_cluster", "sum_size2")
 
@@ -80,6 +89,13 @@ def _lib():
             lib.gilc_plan.argtypes = [C.POINTER(GilParams)] + [C.c_int32] * 5 + [C.POINTER(GilcPlanInfo)]
             lib.gilc_run.restype = C.c_int
             lib.gilc_run.argtypes = ([C.POINTER(GilParams), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32] +
+                                     [C.c_void_p] * 17 + [C.POINTER(C.c_double)])
+        if hasattr(lib, "gilp_run"):           # likewise: no profile entry points in a build from before them
+            lib.gilp_last_error.restype, lib.gilp_last_error.argtypes = C.c_char_p, []
+            lib.gilp_plan.restype = C.c_int
+            lib.gilp_plan.argtypes = [C.POINTER(GilParams)] + [C.c_int32] * 6 + [C.POINTER(GilpPlanInfo)]
+            lib.gilp_run.restype = C.c_int
+            lib.gilp_run.argtypes = ([C.POINTER(GilParams), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] +
                                      [C.c_void_p] * 17 + [C.POINTER(C.c_double)])
         lib._gil_ready = True
     return lib
@@ -178,17 +194,54 @@ def plan_capture(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, n_group
     return {k: int(getattr(info, k)) for k, _ in GilcPlanInfo._fields_}
 
 
+def run_profiles_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
+                     minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
+                     anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
+                     block_table=None, device=0, flip_table=None, n_bins=None, first_obs=0, want_field=False, group_of_system=None,
+                     n_groups=None, per_system=False, n_cap=None):
+    """`run_raw` with the bin counts of every observation from `first_obs` on summed over the systems of a group inside the
+    event loop (gilp_run of include/gillespie_profile.h); the library picks the kernel as for `run_structure_raw`.
+    `n_bins=None`: min(L, 1024).  `group_of_system` [systems]: the group a system adds to, None: all to group 0;
+    `n_groups=None`: the largest id + 1.  The dictionary of `run_raw` plus
+      `ensemble_sums` [groups][observations][7][n_bins] int64: PROFILE_COLUMNS (sums over the group's members of n+, n-, n_bound,
+                      n+^2, n-^2, n+ n- per bin, and of the bin's field sum in 2^-32 fixed point when `want_field`);
+      `members`       [groups][observations] int32: the systems of the group that recorded the observation;
+      `profile_obs`   [systems][observations][3][n_bins] int32 when `per_system`: one system's own n+, n-, n_bound;
+      `bin_width`, `n_bins_used`: the sites of a bin (the last used one may hold fewer) and the bins that hold sites."""
+    n_bins = min(int(L), GILP_MAX_BINS) if n_bins is None else int(n_bins)
+    if n_groups is None:
+        n_groups = 1 if group_of_system is None else int(max(0, np.max(group_of_system))) + 1
+    return _run_batch_entry("gilp_run", **locals())
+
+
+def plan_profiles(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, n_bins, n_groups=1, first_obs=0, want_field=False,
+                  want_states=True, per_system=False):
+    """gilp_plan: which kernel `run_profiles_raw` would use (shape 0: systems in LDS, 1: large systems), its threads per system,
+    LDS, the bin width and the bins that hold sites, work and output bytes, by host arithmetic; no device needed.  Refuses what
+    the run would refuse on these numbers."""
+    lib = _lib()
+    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), sigma_grid=float(sigma_grid), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
+    info = GilpPlanInfo()
+    rc = lib.gilp_plan(C.byref(par), int(n_bins), int(n_groups), int(first_obs), int(want_field), int(bool(want_states)),
+                       int(bool(per_system)), C.byref(info))
+    if rc != 0:
+        raise capi.ApsError(rc, lib.gilp_last_error().decode())
+    return {k: int(getattr(info, k)) for k, _ in GilpPlanInfo._fields_ if k != "reserved"}
+
+
 def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed,
                      minus_anchor, immobilize, suppress_flip, crowding, k_on, k_off, k_exit, anchor_mask, uniforms, max_events,
                      want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table, k_max=None, first_obs=0,
-                     group_of_site=None, n_groups=0, c_bins=0, h_bins=0, h_dt=0.0, n_cap=None):
+                     group_of_site=None, n_groups=0, c_bins=0, h_bins=0, h_dt=0.0, n_cap=None, n_bins=0, want_field=False,
+                     group_of_system=None, per_system=False):
     """The batch entry points take the same arguments: gil_run_batch (systems in LDS), gilm_run (large systems), gils_run
     (either, with the structure sums: k_max, first_obs) and gilc_run (either, with the capture statistics: group_of_site,
-    n_groups, c_bins, h_bins, h_dt, first_obs)."""
+    n_groups, c_bins, h_bins, h_dt, first_obs); gilp_run (either, with the ensemble profiles: n_bins, first_obs, want_field,
+    group_of_system, n_groups, per_system)."""
     lib = _lib()
     call = getattr(lib, entry)
     last_error = getattr(lib, {"gil_run_batch": "gil_last_error", "gilm_run": "gilm_last_error", "gils_run": "gils_last_error",
-                               "gilc_run": "gilc_last_error"}[entry])
+                               "gilc_run": "gilc_last_error", "gilp_run": "gilp_last_error"}[entry])
     S = len(states)
     betas = np.ascontiguousarray(np.broadcast_to(np.asarray(betas, dtype=np.float64), (S,)))
     ncap = max(1, max(len(st[0]) for st in states))
@@ -230,7 +283,7 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     ms = C.c_double()
     args = [_p(n0), _p(pos0), _p(sg0), _p(bd0), _p(uniforms), _p(pos_obs), _p(sg_obs), _p(fl_obs), _p(scal), _p(n_rec), _p(n_ev),
             _p(t_fin), _p(exits), _p(n_exit)]
-    rows = capture = None
+    rows = capture = sums = None
     if entry == "gils_run":
         rows = np.zeros((S, M, 4 + 2 * max(int(k_max), 0)))
         rc = call(C.byref(par), int(k_max), int(first_obs), *args, _p(rows), C.byref(ms))
@@ -242,6 +295,15 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
         life_hist, life_sums = np.zeros((S, 2, max(int(h_bins), 1)), np.int64), np.zeros((S, 2, 2))
         rc = call(C.byref(par), _p(groups), int(n_groups), int(c_bins), int(h_bins), float(h_dt), int(first_obs), *args,
                   _p(capture), _p(life_hist), _p(life_sums), C.byref(ms))
+    elif entry == "gilp_run":
+        groups = None if group_of_system is None else np.ascontiguousarray(group_of_system, dtype=np.int32)
+        if groups is not None and groups.shape != (S,):
+            raise ValueError("group_of_system must have one entry per system")
+        G, B = max(int(n_groups), 1), max(int(n_bins), 1)
+        sums, members = np.zeros((G, M, GILP_NCOLS, B), np.int64), np.zeros((G, M), np.int32)
+        prof = np.zeros((S, M, 3, B), np.int32) if per_system else None
+        rc = call(C.byref(par), int(n_bins), int(first_obs), int(want_field), _p(groups), int(n_groups), *args, _p(sums), _p(members),
+                  _p(prof), C.byref(ms))
     else:
         rc = call(C.byref(par), *args, C.byref(ms))
     if rc != 0:
@@ -252,6 +314,9 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
         out["structure"] = rows
     if capture is not None:
         out.update(capture=capture, life_hist=life_hist, life_sums=life_sums)
+    if sums is not None:
+        width = -(-int(L) // int(n_bins))
+        out.update(ensemble_sums=sums, members=members, profile_obs=prof, bin_width=width, n_bins_used=-(-int(L) // width))
     return out
 
 
@@ -445,6 +510,50 @@ def run_batched_exact_capture(systems, T=10.0, obs_dt=0.01, c_bins=16, h_bins=40
         ps.n_events = int(r["n_events"][s])
     first.kernel_ms = r["kernel_ms"]
     return rows
+
+
+def run_batched_exact_profiles(systems, T=10.0, obs_dt=0.01, n_bins=None, groups=None, first_obs=0, want_field=False,
+                               per_system=False, uniforms=None):
+    """The ensemble profiles <rho+(x, t)>, <rho-(x, t)> and <m(x, t)> of many ParticleSystem objects under the exact dynamics
+    (the means over runs of the reference's rho_plus_list, rho_minus_list, m_local_list, PARTICLE_solver_CLASS.py:205-213,
+    :517-536), coarse-grained to `n_bins` bins of sites and summed over the runs of a group inside the event loop: no state array
+    leaves the GPU, and what does is [groups][observations][7][n_bins].  `groups[s]` is the group system s adds to (None: one
+    group).  Returns one dict per group, in the order of the group ids (observables.DeviceProfiles.result); `per_system=True`
+    adds each member's own counts as `profile_obs` [members][observations][3][n_bins] (single-run heat maps at n_bins = L)."""
+    from . import observables
+    from .particle_system import _SHAPE_ATTRS
+    first = systems[0]
+    for ps in systems[1:]:
+        for k in _SHAPE_ATTRS:
+            if getattr(ps, k) != getattr(first, k):
+                raise ValueError(f"run_batched_exact_profiles: systems differ in {k}")
+    inits = [ps.init_particles() for ps in systems]
+    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+    times_obs = np.arange(0.0, T, obs_dt)
+    L = first.L
+    n_bins = min(L, GILP_MAX_BINS) if n_bins is None else int(n_bins)
+    owner = np.zeros(len(systems), np.int32) if groups is None else np.asarray(groups, dtype=np.int32)
+    n_groups = int(owner.max()) + 1 if owner.size else 1
+    r = run_profiles_raw(L=L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
+                         rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs,
+                         T=T, seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
+                         suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
+                         k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms,
+                         want_states=False, device=first.device, flip_table=first.flip_table(), n_bins=n_bins,
+                         first_obs=first_obs, want_field=want_field, group_of_system=owner, n_groups=n_groups, per_system=per_system)
+    out = []
+    for g in range(n_groups):
+        mine = np.flatnonzero(owner == g)
+        prof = observables.DeviceProfiles(times_obs, L, first.dx, n_bins, r["ensemble_sums"][g], r["members"][g],
+                                          n_particles=[int(r["n0"][s]) for s in mine], k_exit=first.k_exit, want_field=want_field,
+                                          first_obs=first_obs).result()
+        if per_system:
+            prof["profile_obs"] = r["profile_obs"][mine]
+        out.append(prof)
+    for s, ps in enumerate(systems):
+        ps.n_events = int(r["n_events"][s])
+    first.kernel_ms = r["kernel_ms"]
+    return out
 
 
 def run_large_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, beta, state, times_obs, T, seed=0,

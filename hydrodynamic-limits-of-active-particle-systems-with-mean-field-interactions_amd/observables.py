@@ -350,3 +350,113 @@ class DeviceCapture:
             var = np.where(count > 0, sums[:, 1] / count - mean * mean, np.nan)
         res.update(life_hist=hist.copy(), life_edges=self.h_dt * np.arange(hist.shape[1] + 1), life_count=count, life_mean=mean, life_var=var)
         return res
+
+
+# ------------------------------------------------------------------------------------------------ ensemble profiles
+def profile_bins(L, n_bins):
+    """The bin rule of gilp_run and aps_observe_bins: (width, bins that hold sites, sites per bin [n_bins])."""
+    L, n_bins = int(L), int(n_bins)
+    width = -(-L // n_bins)
+    used = -(-L // width)
+    sites = np.zeros(n_bins, np.int64)
+    sites[:used] = width
+    sites[used - 1] = L - (used - 1) * width
+    return width, used, sites
+
+
+class DeviceProfiles:
+    """The ensemble profiles of one group from what gilp_run returns for it (include/gillespie_profile.h): `ensemble_sums`
+    [M][7][n_bins] (sums over the members of n+, n-, n_bound, n+^2, n-^2, n+ n- per bin, and of the field in 2^-32 fixed point)
+    and `members` [M].  `result()` gives, per observation and bin,
+      `plus_mean`, `minus_mean`, `total_mean`, `signed_mean` (n+ - n-) and their `_se` (standard error over the members, ddof = 1;
+          the variances of total and signed count take the cross column: var+ + var- +/- 2 cov), `bound_mean` (the device takes
+          no second moment of the bound count, so it has no `_se`),
+      `field_mean` with the field: the mean over members and over the bin's sites of m(x),
+      `rho_plus`, `rho_minus`, `rho_total` and their `_se`: the densities in the reference's normalisation count / (N bin_sites
+          dx) (PARTICLE_solver_CLASS.py:205-213), the ensemble means of rho_plus_list, rho_minus_list coarse-grained to the bins,
+      `times_obs`, `members`, `bin_sites` [n_bins], `bin_width`, `n_bins_used`.
+    Observations no member recorded (and those before `first_obs`) are nan; a standard error needs two members.
+
+    The reference divides each run by its current particle number, which a sum over runs cannot reproduce: the densities need
+    all members to start with the same N and k_exit = 0, anything else is a ValueError."""
+
+    def __init__(self, times_obs, L, dx, n_bins, ensemble_sums, members, n_particles, k_exit=0.0, want_field=False, first_obs=0):
+        self.times, self.L, self.dx, self.n_bins = np.asarray(times_obs, dtype=float), int(L), float(dx), int(n_bins)
+        self.sums, self.members = np.asarray(ensemble_sums, dtype=np.int64), np.asarray(members, dtype=np.int64)
+        if self.sums.shape != (len(self.times), 7, self.n_bins) or self.members.shape != (len(self.times),):
+            raise ValueError("ensemble_sums must be [observations][7][n_bins] and members [observations]")
+        ns = {int(n) for n in np.atleast_1d(n_particles)}
+        if len(ns) != 1:
+            raise ValueError(f"the members of a group must start with the same particle number, got {sorted(ns)}")
+        if k_exit:
+            raise ValueError("the profile densities need k_exit = 0: the reference divides every run by its current particle number")
+        self.N, self.want_field, self.first_obs = ns.pop(), bool(want_field), int(first_obs)
+        self.width, self.used, self.bin_sites = profile_bins(self.L, self.n_bins)
+
+    @staticmethod
+    def _moments(n, s1, s2):
+        """mean and standard error (ddof = 1) from n, sum x, sum x^2; the variance's numerator in exact integers"""
+        n = n[:, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = np.where(n > 0, s1 / np.maximum(n, 1), np.nan)
+            var = np.where(n > 1, (n * s2 - s1 * s1) / np.maximum(n * (n - 1), 1).astype(float), np.nan)
+            return mean, np.sqrt(var / np.maximum(n, 1))
+
+    def result(self):
+        n, s = self.members, self.sums
+        p1, m1, b1, p2, m2, pm = (s[:, j, :] for j in range(6))
+        res = {"times_obs": self.times.copy(), "members": n.copy(), "bin_sites": self.bin_sites.copy(), "bin_width": self.width,
+               "n_bins_used": self.used}
+        res["plus_mean"], res["plus_se"] = self._moments(n, p1, p2)
+        res["minus_mean"], res["minus_se"] = self._moments(n, m1, m2)
+        res["total_mean"], res["total_se"] = self._moments(n, p1 + m1, p2 + m2 + 2 * pm)
+        res["signed_mean"], res["signed_se"] = self._moments(n, p1 - m1, p2 + m2 - 2 * pm)
+        res["bound_mean"] = self._moments(n, b1, b1)[0]
+        sites = np.where(self.bin_sites > 0, self.bin_sites, 1).astype(float)
+        if self.want_field:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                res["field_mean"] = np.where(n[:, None] > 0, s[:, 6, :] / 4294967296.0 / np.maximum(n, 1)[:, None] / sites, np.nan)
+        norm = self.N * sites * self.dx
+        for src, dst in (("plus", "rho_plus"), ("minus", "rho_minus"), ("total", "rho_total")):
+            res[dst], res[dst + "_se"] = res[src + "_mean"] / norm, res[src + "_se"] / norm
+        return res
+
+
+def profile_sums(outs, n_bins, want_field=False, first_obs=0):
+    """What gilp_run would return for ONE group made of the runs `outs` (full outputs of gillespie.run_batched_exact): the
+    integer `ensemble_sums` [M][7][n_bins], `members` [M] and the per-run counts [runs][M][3][n_bins], by bincount on the host.
+    The field column sums llrint(m_local_list * 2^32) over the bin's sites."""
+    M, L = np.asarray(outs[0]["total_list"]).shape
+    width, used, _ = profile_bins(L, n_bins)
+    sums, members, rows = np.zeros((M, 7, n_bins), np.int64), np.zeros(M, np.int64), np.zeros((len(outs), M, 3, n_bins), np.int64)
+    for r, out in enumerate(outs):
+        for k in range(first_obs, M):
+            if out["pos_list"][k] is None:
+                continue                                           # the run ended before this observation
+            pos = np.asarray(out["pos_list"][k], dtype=np.int64)
+            # count / (N dx) per site, and sum(total) = 1 / dx: the counts come back as integers
+            scale = pos.size / max(float(np.sum(out["total_list"][k])), 1e-300)
+            cp = np.rint(np.asarray(out["rho_p_list"][k]) * scale).astype(np.int64)
+            cm = np.rint(np.asarray(out["rho_m_list"][k]) * scale).astype(np.int64)
+            cb = np.bincount(pos[np.asarray(out["bound_list"][k], dtype=bool)], minlength=L)
+            b = np.arange(L) // width
+            np_, nm, nd = (np.bincount(b, weights=c, minlength=n_bins).astype(np.int64) for c in (cp, cm, cb))
+            rows[r, k] = np_, nm, nd
+            sums[k, :6] += np.stack([np_, nm, nd, np_ * np_, nm * nm, np_ * nm])
+            if want_field:
+                q = np.rint(np.asarray(out["m_local_list"][k], dtype=float) * 4294967296.0).astype(np.int64)
+                np.add.at(sums[k, 6], b, q)
+            members[k] += 1
+    return sums, members, rows
+
+
+def profile_observables(outs, n_bins, want_field=False, first_obs=0, dx=None):
+    """The keys of `DeviceProfiles.result` for one group from the full outputs of its runs (gillespie.run_batched_exact): a
+    bincount per run and observation on the host.  `dx=None`: read off the outputs (the site densities of a run add up to 1 / dx)."""
+    first = outs[0]
+    M, L = np.asarray(first["total_list"]).shape
+    if dx is None:
+        dx = 1.0 / float(np.sum(first["total_list"][0]))
+    sums, members, _ = profile_sums(outs, n_bins, want_field, first_obs)
+    return DeviceProfiles(first["times_obs"], L, dx, n_bins, sums, members, [o["particle_count_list"][0] for o in outs],
+                          0.0, want_field, first_obs).result()
