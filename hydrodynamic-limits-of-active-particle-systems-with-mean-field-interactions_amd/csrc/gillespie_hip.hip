@@ -27,11 +27,13 @@
 #include "gillespie_structure.h"
 #include "gillespie_capture.h"
 #include "gillespie_profile.h"
+#include "gillespie_mixed.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"           // model, initial-state check, the driver of the one-shot entry points
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiations only)
 #include "gillespie_capture.hpp"          // anchor capture and cluster statistics (capture instantiations only)
 #include "gillespie_profile.hpp"          // ensemble density and field profiles (profile instantiations only)
+#include "gillespie_mixed.hpp"            // a variant per system: table, blocking table, slots, Philox key (mixed instantiations only)
 
 namespace {
 
@@ -68,6 +70,7 @@ __device__ inline long long wg_sum_ll(long long v, long long *red) {
 struct GilsBatchArgs : GilArgs { GilsArgs st; };            // arguments of the structure instantiations
 struct GilcBatchArgs : GilsBatchArgs { GilcArgs cp; };      // arguments of the capture instantiations
 struct GilpBatchArgs : GilcBatchArgs { GilpArgs pf; };      // arguments of the profile instantiations (the driver's one struct)
+struct GilxBatchArgs : GilArgs { GilxArgs mx; };            // arguments of the mixed instantiations (gilx_run's driver)
 
 // the structure sums' slots: behind the loop's own LDS (which ends with the plus-occupancy bytes), at the next multiple of 8
 __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L) {
@@ -80,13 +83,24 @@ __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L)
 // kernels without it are the code they were before it existed.
 // CP = anchor capture and cluster statistics (gillespie_capture.hpp), likewise; not combined with ST.
 // PF = ensemble density and field profiles (gillespie_profile.hpp), likewise; not combined with ST or CP.
-template <int NT, bool ST, bool CP = false, bool PF = false>
-__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, GilpBatchArgs, std::conditional_t<CP, GilcBatchArgs, std::conditional_t<ST, GilsBatchArgs, GilArgs>>> a) {
+// MX = a mixed batch (gillespie_mixed.hpp): the system of a workgroup comes from a launch order, and the weight table, the
+// blocking table, the slot count and the Philox key are the system's own; likewise; not combined with ST, CP or PF.  In such a
+// launch a.tlen is the longest table's length (the LDS layout is the launch's).
+template <int NT, bool ST, bool CP = false, bool PF = false, bool MX = false>
+__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, GilxBatchArgs, std::conditional_t<PF, GilpBatchArgs, std::conditional_t<CP, GilcBatchArgs, std::conditional_t<ST, GilsBatchArgs, GilArgs>>>> a) {
     static_assert(!(ST && CP), "the capture launches take no structure sums");
     static_assert(!(PF && (ST || CP)), "the profile launches take no structure sums and no capture statistics");
+    static_assert(!(MX && (ST || CP || PF)), "the mixed launches take the scalar sums and the states only");
     extern __shared__ double lds[];
     const Model &M = a.m;
-    const int L = M.L, K = M.K, t = threadIdx.x, sys = blockIdx.x, ncap = a.p.n_cap, nobs = a.p.n_obs;
+    const GilxView vw = gilx_view<MX, NT>(a);                  // empty without MX
+    const int L = M.L, K = M.K, t = threadIdx.x, sys = MX ? vw.sys : blockIdx.x, ncap = a.p.n_cap, nobs = a.p.n_obs;
+// the launch's values, read where they are used as before MX existed, or with MX the system's own (MX is a constant: one arm is compiled)
+#define GX_TLEN (MX ? vw.tlen : a.tlen)
+#define GX_FIELD (MX ? vw.field_mode : M.field_mode)
+#define GX_SLOTS (MX ? vw.nslots : ncap)
+#define GX_CHUNK (MX ? vw.chunk : a.chunk)
+#define GX_BLOCK (MX ? vw.block_table : a.block_table)
     double *W = lds, *S = W + L, *tab = S + L, *rate = tab + ((a.tlen + 2) & ~1), *red = rate + ncap + (ncap & 1);
     double *tinc = red + 8;                                   // [NT] inclusive scan of the threads' rate sums
     double *draws = tinc + NT;                                // [NT][4] -log1p(-u0), u1, u2, u3 of the next NT events
@@ -101,9 +115,9 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
     const double beta = a.beta[sys];
     const int n_init = a.n0[sys];
     // ---- load the system
-    for (int i = t; i <= a.tlen; i += NT) tab[i] = a.table[i];
+    for (int i = t; i <= GX_TLEN; i += NT) tab[i] = (MX ? vw.table : a.table)[i];
     for (int x = t; x < L; x += NT) { occ[x] = 0; occp[x] = 0; }
-    for (int i = t; i < ncap; i += NT) {
+    for (int i = t; i < GX_SLOTS; i += NT) {
         const bool live = i < n_init;
         pos[i] = live ? a.pos0[(size_t)sys * ncap + i] : 0;
         flg[i] = live ? (uint8_t)(F_ALIVE | (a.sigma0[(size_t)sys * ncap + i] > 0 ? F_PLUS : 0) |
@@ -126,16 +140,16 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
     // field from scratch: W(x) = sum_j w(x, p_j), S(x) = sum_j sigma_j w(x, p_j)
     for (int x = t; x < L; x += NT) {
         double w = 0.0, s = 0.0;
-        if (M.field_mode)
+        if (GX_FIELD)
             for (int j = 0; j < n_init; ++j) {
-                const double g = site_weight(M, tab, a.tlen, x, pos[j]);
+                const double g = site_weight(M, tab, GX_TLEN, x, pos[j]);
                 w += g; s += (flg[j] & F_PLUS) ? g : -g;
             }
         W[x] = w; S[x] = s;
     }
     __syncthreads();
     long long gsum_s = 0, gsum_n = 0;                          // global-mean mode: sum of spins, particles alive
-    if (!M.field_mode) {
+    if (!GX_FIELD) {
         long long ls = 0, ln = 0;
         for (int i = t; i < n_init; i += NT) { ls += (flg[i] & F_PLUS) ? 1 : -1; ln += 1; }
         gsum_s = wg_sum_ll<NT>(ls, redl); gsum_n = wg_sum_ll<NT>(ln, redl);
@@ -143,14 +157,14 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
     double tnow = 0.0;
     long long n_ev = 0;
     int k_obs = 0, n_exit = 0;
-    const int c0 = t * a.chunk, c1 = min(ncap, c0 + a.chunk);
+    const int c0 = t * GX_CHUNK, c1 = min(GX_SLOTS, c0 + GX_CHUNK);
 
     auto record = [&](int k) {                                 // observation k: state and scalar sums (ref :517-536)
         const size_t o = ((size_t)sys * nobs + k) * ncap;
         long long v[GIL_NSCALARS] = {0, 0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0};
-        if (k == a.p.ref_obs) for (int i = t; i < ncap; i += NT) ref[i] = (flg[i] & F_ALIVE) ? pos[i] : -1;
+        if (k == a.p.ref_obs) for (int i = t; i < GX_SLOTS; i += NT) ref[i] = (flg[i] & F_ALIVE) ? pos[i] : -1;
         __syncthreads();
-        for (int i = t; i < ncap; i += NT) {
+        for (int i = t; i < GX_SLOTS; i += NT) {
             const uint8_t f = flg[i];
             if (a.pos_obs) a.pos_obs[o + i] = pos[i];
             if (a.sigma_obs) a.sigma_obs[o + i] = (f & F_PLUS) ? 1 : -1;
@@ -162,7 +176,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
             if ((f & F_PLUS) && p < L - 1) {
                 v[GS_ATTEMPT] += 1;
                 const int cp = occp[p + 1], cm = occ[p + 1] - occp[p + 1];
-                v[GS_BLOCKED] += a.block_table ? a.block_table[cp * (K + 1) + cm] : (cp + cm >= 1);
+                v[GS_BLOCKED] += GX_BLOCK ? GX_BLOCK[cp * (K + 1) + cm] : (cp + cm >= 1);
             }
             if (ref[i] >= 0) { const long long d = (long long)p - ref[i]; v[GS_DISP] += d; v[GS_DISP2] += d * d; v[GS_NDISP] += 1; }
         }
@@ -177,7 +191,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
         for (int w = 1; w < NT / 64; ++w) mx = max(mx, redl[4 + w]);
         if (a.front_lo && mx >= 0) {
             const int lo = a.front_lo[mx];
-            for (int i = t; i < ncap; i += NT) if ((flg[i] & F_ALIVE) && pos[i] >= lo) v[GS_FRONT] += 1;
+            for (int i = t; i < GX_SLOTS; i += NT) if ((flg[i] & F_ALIVE) && pos[i] >= lo) v[GS_FRONT] += 1;
         }
         for (int q = 0; q < GIL_NSCALARS; ++q) {
             if (q == GS_MAXPOS || q == GS_EVENTS) continue;
@@ -226,7 +240,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
     long long ev_base = 0;                                     // first event of the block of draws held in LDS
     bool dirty_all = true;                                     // first event: every rate is evaluated
     int dirty_a = 0, dirty_b = 0;
-    const int dirty_reach = (M.field_mode ? a.tlen - 1 : 0) + 1;
+    const int dirty_reach = (GX_FIELD ? GX_TLEN - 1 : 0) + 1;
     while (tnow < a.p.T && k_obs < nobs && n_ev < a.p.max_events) {
         // ---- A: rates (ref :254-352).  The reference recomputes every particle's rates before every event; here only
         // the particles whose inputs the last event changed are re-evaluated (field within the table's reach of the
@@ -235,7 +249,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
         //     expensive rate evaluation then runs once over the compacted list, a lane per listed particle)
         int nwork = 0;
         if (NT == 64) {                                        // one wavefront: ballot + mbcnt compaction, no LDS counter
-            for (int k = 0; k < a.chunk; ++k) {
+            for (int k = 0; k < GX_CHUNK; ++k) {
                 const int i = c0 + k;
                 bool redo = i < c1 && (flg[i] & F_ALIVE);      // the rate of a particle that left was zeroed when it left
                 if (redo && !dirty_all) {
@@ -270,7 +284,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
             const int i = work[j], p = pos[i];
             const uint8_t f = flg[i];
             double w, s;
-            if (M.field_mode) { w = W[p]; s = S[p]; } else { w = (double)gsum_n; s = (double)gsum_s; }
+            if (GX_FIELD) { w = W[p]; s = S[p]; } else { w = (double)gsum_n; s = (double)gsum_s; }
             double mloc = 0.0;
             if (w > 0.0) { mloc = s / w; mloc = mloc > 1.0 ? 1.0 : (mloc < -1.0 ? -1.0 : mloc); }
             int l = p - 1, rr = p + 1;
@@ -307,8 +321,8 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
                 u0 = in ? src[0] : 0.0; u1 = in ? src[1] : 0.0; u2 = in ? src[2] : 0.0; u3 = in ? src[3] : 0.0;
             } else {
                 uint32_t x[4], y[4];
-                philox4x32_10((uint32_t)evn, (uint32_t)(evn >> 32), (uint32_t)sys, 0x47494C31u, M.seed_lo, M.seed_hi, x);
-                philox4x32_10((uint32_t)evn, (uint32_t)(evn >> 32), (uint32_t)sys, 0x47494C32u, M.seed_lo, M.seed_hi, y);
+                philox4x32_10((uint32_t)evn, (uint32_t)(evn >> 32), MX ? vw.stream : (uint32_t)sys, 0x47494C31u, MX ? vw.seed_lo : M.seed_lo, MX ? vw.seed_hi : M.seed_hi, x);
+                philox4x32_10((uint32_t)evn, (uint32_t)(evn >> 32), MX ? vw.stream : (uint32_t)sys, 0x47494C32u, MX ? vw.seed_lo : M.seed_lo, MX ? vw.seed_hi : M.seed_hi, y);
                 u0 = ((double)(x[0] >> 5) * 67108864.0 + (double)(x[1] >> 6)) * 0x1.0p-53;
                 u1 = ((double)(x[2] >> 5) * 67108864.0 + (double)(x[3] >> 6)) * 0x1.0p-53;
                 u2 = ((double)(y[0] >> 5) * 67108864.0 + (double)(y[1] >> 6)) * 0x1.0p-53;
@@ -352,7 +366,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
             uint8_t f = flg[i];
             const bool plus = (f & F_PLUS) != 0;
             double w, s;
-            if (M.field_mode) { w = W[p]; s = S[p]; } else { w = (double)gsum_n; s = (double)gsum_s; }
+            if (GX_FIELD) { w = W[p]; s = S[p]; } else { w = (double)gsum_n; s = (double)gsum_s; }
             double mloc = 0.0;
             if (w > 0.0) { mloc = s / w; mloc = mloc > 1.0 ? 1.0 : (mloc < -1.0 ? -1.0 : mloc); }
             int l = p - 1, rr = p + 1;
@@ -406,12 +420,12 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
         // whose rates must be re-evaluated before the next event: everybody when the global mean moved, otherwise the
         // particles within the table's reach (+1 site for the occupancy of neighbours) of the event's sites
         dirty_a = p_old; dirty_b = p_new;
-        dirty_all = !M.field_mode && (kind == 2 || kind == 3);
-        if (!M.field_mode) {
+        dirty_all = !GX_FIELD && (kind == 2 || kind == 3);
+        if (!GX_FIELD) {
             if (kind == 2) gsum_s -= 2 * sg;
             else if (kind == 3) { gsum_s -= sg; gsum_n -= 1; }
         } else if (kind != 0) {
-            const int Rt = a.tlen - 1;
+            const int Rt = GX_TLEN - 1;
             const int centre = kind == 1 ? min(p_old, p_new) : p_old, span = kind == 1 ? 1 : 0;
             const bool wrap1 = kind == 1 && M.periodic && (p_old - p_new > 1 || p_new - p_old > 1);   // hop across the seam
             int lo = centre - Rt, len = 2 * Rt + 1 + span;
@@ -420,9 +434,9 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
                 int x = lo + k;
                 if (M.periodic) { x %= L; if (x < 0) x += L; }
                 else if (x < 0 || x >= L) continue;
-                const double g0 = site_weight(M, tab, a.tlen, x, p_old);
+                const double g0 = site_weight(M, tab, GX_TLEN, x, p_old);
                 if (kind == 1) {
-                    const double g1 = site_weight(M, tab, a.tlen, x, p_new), d = g1 - g0;      // exact on the weight grid
+                    const double g1 = site_weight(M, tab, GX_TLEN, x, p_new), d = g1 - g0;      // exact on the weight grid
                     W[x] += d; S[x] += sg > 0 ? d : -d;
                 } else if (kind == 2) {
                     S[x] -= sg > 0 ? 2.0 * g0 : -2.0 * g0;
@@ -451,6 +465,11 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<PF, Gi
         if (a.n_exits) a.n_exits[sys] = n_exit;
     }
 }
+#undef GX_TLEN
+#undef GX_FIELD
+#undef GX_SLOTS
+#undef GX_CHUNK
+#undef GX_BLOCK
 
 // threads and dynamic LDS bytes of one system in the batch kernel; st: with the structure sums' slots, and with a copy of the
 // phase table behind them where the 160 KB leave room for it (phase_in_lds); cap: with the capture slots and the bind times;
@@ -710,9 +729,138 @@ int gilp_decide(const char *who, const gil_params *p, const GilpCall &c, bool st
     return GIL_OK;
 }
 
+std::string g_gilx_err;
+
+// the V weight tables of a mixed batch, back to back, each as weight_table gives it for that sigma_grid alone
+struct GilxTables { std::vector<double> table; std::vector<GilxVariant> var; int max_tlen = 0; };
+
+// the checks gilx_plan and gilx_run share, the tables and the shape: 0 with `info` and `tb` filled, or GIL_ERR_ARG with the
+// text in g_gilx_err
+int gilx_decide(const char *who, const gil_params *p, const gilx_variants *v, bool states, gilx_plan_info &info, GilxTables &tb) {
+    auto bad = [&](const std::string &m) { g_gilx_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    if (p->L < 2) return bad("L must be at least 2");
+    if (p->L > GIL_MAX_L)
+        return bad("L = " + std::to_string(p->L) + " is beyond GIL_MAX_L = " + std::to_string(GIL_MAX_L) + ": the large-system shape takes no mixed batches");
+    if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
+    if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
+    if (p->n_cap > GIL_MAX_N)
+        return bad("n_cap = " + std::to_string(p->n_cap) + " is beyond GIL_MAX_N = " + std::to_string(GIL_MAX_N) + ": the large-system shape takes no mixed batches");
+    const int V = v->n_variants, S = p->n_systems;
+    if (V < 1 || V > GILX_MAX_VARIANTS) return bad("n_variants = " + std::to_string(V) + " is outside [1, " + std::to_string(GILX_MAX_VARIANTS) + "]");
+    if (!v->sigma_grid) return bad("null sigma_grid");
+    for (int i = 0; i < V; ++i)
+        if (!std::isfinite(v->sigma_grid[i]) || v->sigma_grid[i] < 0.0)
+            return bad("sigma_grid = " + std::to_string(v->sigma_grid[i]) + " of variant " + std::to_string(i) + " must be finite and not negative");
+    if (v->variant_of_system)
+        for (int s = 0; s < S; ++s) {
+            const int i = v->variant_of_system[s];
+            if (i < 0 || i >= V) return bad("variant index " + std::to_string(i) + " of system " + std::to_string(s) + " is outside [0, n_variants = " + std::to_string(V) + ")");
+        }
+    if (v->order) {
+        std::vector<uint8_t> seen((size_t)S, 0);
+        for (int b = 0; b < S; ++b) {
+            const int s = v->order[b];
+            if (s < 0 || s >= S) return bad("order is not a permutation: order[" + std::to_string(b) + "] = " + std::to_string(s) + " is outside [0, n_systems = " + std::to_string(S) + ")");
+            if (seen[(size_t)s]++) return bad("order is not a permutation: system " + std::to_string(s) + " appears twice (second time at " + std::to_string(b) + ")");
+        }
+    }
+    tb = GilxTables{};
+    tb.var.resize((size_t)V);
+    std::vector<double> one;
+    for (int i = 0; i < V; ++i) {
+        int tlen = 0, q = 0;
+        weight_table(v->sigma_grid[i], p->L, p->K, p->periodic != 0, one, tlen, q);
+        tb.var[(size_t)i] = GilxVariant{(int32_t)tb.table.size(), tlen, v->sigma_grid[i] > 0.0 ? 1 : 0, 0};
+        tb.table.insert(tb.table.end(), one.begin(), one.end());   // tlen taps and the closing zero
+        tb.max_tlen = std::max(tb.max_tlen, tlen);
+    }
+    int NT = 0; size_t lds = 0;
+    batch_shape(p->L, p->n_cap, tb.max_tlen, false, NT, lds);
+    if (lds > 160 * 1024)
+        return bad("the launch needs " + std::to_string(lds) + " bytes of LDS per system (L = " + std::to_string(p->L) + ", n_cap = " + std::to_string(p->n_cap) +
+                   ", longest table " + std::to_string(tb.max_tlen) + "), more than the " + std::to_string(160 * 1024) + " bytes (160 KB) of a workgroup");
+    info = gilx_plan_info{};
+    info.threads = NT; info.lds_bytes = (int32_t)lds; info.max_tlen = tb.max_tlen; info.systems_per_cu = (int32_t)((size_t)160 * 1024 / lds);
+    info.table_doubles = (int64_t)tb.table.size();
+    const int64_t O = p->n_obs, N = p->n_cap;
+    info.output_bytes = (int64_t)S * ((states ? O * N * 6 : 0) + O * GIL_NSCALARS * 8 + N * 24 + 24);
+    return GIL_OK;
+}
+
+// gilx_run's driver: batch_run for a launch of the mixed instantiations
+int mixed_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
+              const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
+              int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
+    const char *who = "gilx_run";
+    std::string &err = g_gilx_err;
+    auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    gilx_plan_info info; GilxTables tb;
+    if (int rc = gilx_decide(who, p, v, pos_obs || sigma_obs || flags_obs, info, tb)) return rc;
+    const int S = p->n_systems, L = p->L, ncap = p->n_cap, V = v->n_variants, NT = info.threads;
+    for (int s = 0; s < S; ++s) {
+        if (n0[s] < 0 || n0[s] > ncap) return bad("n0 = " + std::to_string(n0[s]) + " of system " + std::to_string(s) + " is outside [0, n_cap = " + std::to_string(ncap) + "]");
+        if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * ncap, sigma0 + (size_t)s * ncap)) return bad(why);
+    }
+    std::vector<int32_t> order((size_t)S), stream((size_t)S);
+    std::vector<uint64_t> seed((size_t)S);
+    for (int s = 0; s < S; ++s) { order[(size_t)s] = v->order ? v->order[s] : s; stream[(size_t)s] = v->stream ? v->stream[s] : s; seed[(size_t)s] = v->seed ? v->seed[s] : p->seed; }
+    if (!v->order) std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return n0[x] > n0[y]; });   // long systems first
+    OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: slots beyond n0 and rows never reached stay zero
+    if (int rc = job.select_device(p->device)) return rc;
+    GilxBatchArgs a{};
+    a.p = *p; a.p.sigma_grid = 0.0; a.p.block_table = nullptr;
+    a.tlen = tb.max_tlen; a.chunk = (ncap + NT - 1) / NT;        // the layout's table length; the kernel takes every system's own chunk
+    a.m = gil_model(p);
+    const size_t lds = (size_t)info.lds_bytes, SN = (size_t)S * ncap, SO = (size_t)S * p->n_obs, KK = (size_t)(p->K + 1) * (p->K + 1);
+    UP(beta, p->beta, (size_t)S); UP(table, tb.table.data(), tb.table.size()); UP(times, p->times_obs, (size_t)p->n_obs);
+    UP(n0, n0, (size_t)S); UP(pos0, pos0, SN); UP(sigma0, sigma0, SN);
+    if (bound0) UP(bound0, bound0, SN);
+    if (p->anchor_mask) UP(anchor, p->anchor_mask, (size_t)L);
+    if (p->front_lo) UP(front_lo, p->front_lo, (size_t)L);
+    if (v->block_table) { UP(block_table, v->block_table, (size_t)V * KK); a.mx.has_block = 1; }
+    UP(mx.order, order.data(), (size_t)S); UP(mx.variant_of_system, v->variant_of_system, (size_t)S); UP(mx.variants, tb.var.data(), (size_t)V);
+    UP(mx.seed, seed.data(), (size_t)S); UP(mx.stream, stream.data(), (size_t)S);
+    if (int rc = gil_upload_flip_table(job, p, a.m)) return rc;
+    if (uniforms) UP(uniforms, uniforms, (size_t)S * p->max_events * 4);
+    OUT(pos_obs, pos_obs, SO * ncap); OUT(sigma_obs, sigma_obs, SO * ncap); OUT(flags_obs, flags_obs, SO * ncap);
+    OUT(scalars, scalars_obs, SO * GIL_NSCALARS);
+    OUT(n_recorded, n_recorded, (size_t)S); OUT(t_final, t_final, (size_t)S); OUT(exits, exits, SN * 3); OUT(n_exits, n_exits, (size_t)S);
+    OUT(n_events, n_events, (size_t)S);
+    if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, false, false, true>)
+                                              : reinterpret_cast<const void *>(&gil_kernel<256, false, false, false, true>), lds)) return rc;
+    if (int rc = job.create_events()) return rc;
+    job.ev.start();
+    if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
+    else hipLaunchKernelGGL((gil_kernel<256, false, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
+    job.ev.stop();
+    if (int rc = job.finish(hipGetLastError(), "gil_kernel (mixed)", kernel_ms)) return rc;
+    DOWN(pos_obs, pos_obs, SO * ncap * 4); DOWN(sigma_obs, sigma_obs, SO * ncap); DOWN(flags_obs, flags_obs, SO * ncap);
+    DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8); DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8);
+    DOWN(t_final, t_final, (size_t)S * 8); DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
+    return GIL_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+const char *gilx_last_error(void) { return g_gilx_err.c_str(); }
+
+int gilx_plan(const gil_params *p, const gilx_variants *v, int32_t want_states, gilx_plan_info *out) {
+    if (!p || !v || !out) { g_gilx_err = "gilx_plan: null argument"; return GIL_ERR_ARG; }
+    gilx_plan_info info; GilxTables tb;
+    if (int rc = gilx_decide("gilx_plan", p, v, want_states != 0, info, tb)) return rc;
+    *out = info;
+    return GIL_OK;
+}
+
+int gilx_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
+             const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+             int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
+    if (!p || !v || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !v->variant_of_system) { g_gilx_err = "gilx_run: null argument"; return GIL_ERR_ARG; }
+    return mixed_run(p, v, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final,
+                     exits, n_exits, kernel_ms);
+}
 
 const char *gilp_last_error(void) { return g_gilp_err.c_str(); }
 

@@ -4,7 +4,8 @@ together as independent ensembles of one GPU handle, and the per-run observables
 The two outer sweeps of the other drivers are here too: `sweep_over_sigmas` (interaction range,
 ..._sweep_beta_2.py:1030-1075) and `sweep_over_densities` (particle number x beta, ..._double_sweep.py:851-861) --
 one batched handle per sigma / per particle number (the weight table and the state capacity differ), all (beta, run)
-pairs inside it.  `sweep_betas_for_structures` / `sweep_beta_structure_ensemble` are the pattern study's drivers
+pairs inside it; under the exact dynamics `one_launch=True` puts the whole sweep into ONE mixed launch of the event loop
+(include/gillespie_mixed.h: a weight table and a blocking table per system).  `sweep_betas_for_structures` / `sweep_beta_structure_ensemble` are the pattern study's drivers
 (PARTICLE_solver_BIOLOGY_local_structure.py:105-193), all (beta, run) pairs in one launch, the per-run observables from sums
 taken on the GPU.  `capture_study` is the anchor-capture study (PARTICLE_solver_CLASS.py:766-976) as an ensemble in one launch.
 `profile_sweep` gives the ensemble density and field profiles per beta (the means over runs of rho_plus_list, rho_minus_list,
@@ -57,6 +58,14 @@ def sweep_over_betas(beta_values, n_runs_per_beta=10, ps_kwargs=None, init_kwarg
     else:
         outs = run_batched(systems, **run_kwargs)
         rows = [observables.run_observables(out, ps.L, ps.dx) for ps, out in zip(systems, outs)]
+    out = _beta_statistics(rows, owner, beta_values)
+    if keep_outputs:
+        out["outs"] = outs
+    return out
+
+
+def _beta_statistics(rows, owner, beta_values):
+    """The per-beta reduction of sweep_over_betas over the per-run rows; owner[i] is the beta index of rows[i]."""
     res = {k: [] for k in ("means", "stds", "ses", "D_means", "D_ses", "m_means", "m_stds", "m_ses", "rho_means", "rho_ses",
                            "block_means", "block_ses", "raw_by_beta")}
     for bi in range(len(beta_values)):
@@ -67,9 +76,41 @@ def sweep_over_betas(beta_values, n_runs_per_beta=10, ps_kwargs=None, init_kwarg
             res[dst].append(st[src])
     out = {k: (np.array(v) if k != "raw_by_beta" else v) for k, v in res.items()}
     out["beta_values"] = np.asarray(beta_values, dtype=float)
-    if keep_outputs:
-        out["outs"] = outs
     return out
+
+
+def _sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_kwargs, rng_seeds, on_device, dynamics):
+    """One sweep_over_betas per case = (ps_kwargs, init_kwargs), all cases in ONE mixed launch of the exact event loop
+    (gillespie.run_batched_exact_statistics_mixed / run_batched_exact_mixed).  The systems are built in the order of the host
+    loop, and every case is a group of the launch: its systems draw what the case's own launch draws.  Returns the list of the
+    per-case sweep dictionaries.  ValueError where no mixed launch exists: the fixed-dt stepper, a large shape (L > 4096 or
+    N > 2048), a launch over the 160 KB of LDS."""
+    from . import gillespie
+    run_kwargs = dict(run_kwargs or {})
+    for ps_kwargs, _ in cases:
+        d = dynamics
+        if d is None:
+            d = "sync" if (ps_kwargs.get("dt") is not None or ps_kwargs.get("mode") == "sync") else "exact"
+        if d not in ("sync", "exact"):
+            raise ValueError("dynamics must be 'sync' or 'exact'")
+        if d != "exact":
+            raise ValueError(f"{who}: one_launch=True needs the exact dynamics; the fixed-dt stepper has no mixed launch")
+    systems, group, owner = [], [], []
+    for ci, (ps_kwargs, init_kwargs) in enumerate(cases):
+        for bi, beta in enumerate(beta_values):
+            for r in range(n_runs_per_beta):
+                rng = None if rng_seeds is None else np.random.default_rng(int(rng_seeds[bi][r]))
+                systems.append(ParticleSystem(beta=beta, rng=rng, **ps_kwargs, **init_kwargs))
+                group.append(ci)
+                owner.append(bi)
+    if on_device:
+        slim = {k: v for k, v in run_kwargs.items() if k in ("T", "obs_dt")}
+        rows = gillespie.run_batched_exact_statistics_mixed(systems, groups=group, **slim)
+    else:
+        outs = gillespie.run_batched_exact_mixed(systems, want_m_local=False, groups=group, **run_kwargs)
+        rows = [observables.run_observables(out, ps.L, ps.dx) for ps, out in zip(systems, outs)]
+    per = len(beta_values) * n_runs_per_beta
+    return [_beta_statistics(rows[ci * per:(ci + 1) * per], owner[ci * per:(ci + 1) * per], beta_values) for ci in range(len(cases))]
 
 
 def sweep_beta_ensemble(beta, n_runs=10, ps_kwargs=None, init_kwargs=None, run_kwargs=None, rng_seeds=None):
@@ -83,33 +124,47 @@ def sweep_beta_ensemble(beta, n_runs=10, ps_kwargs=None, init_kwargs=None, run_k
 
 
 def sweep_over_sigmas(sigma_values, beta_values, n_runs_per_beta=5, ps_kwargs=None, init_kwargs=None, run_kwargs=None,
-                      rng_seeds=None, on_device=False, dynamics=None):
+                      rng_seeds=None, on_device=False, dynamics=None, one_launch=False):
     """The sigma sweep of PARTICLE_solver_BIOLOGY_EXCLUSION_sweep_beta_2.py:1030-1075: for every interaction range
     `local_kernel_sigma` a whole beta sweep (one GPU handle per sigma: the weight table changes; sigma = 0 selects the global
     mean field, sigma wider than the box the folded table).  Returns {sigma: {"beta", "v_mean", "v_se", "D_mean", "D_se",
-    "ps_kwargs"}} like the reference (which also writes one .npz per sigma; saving is left to the caller)."""
+    "ps_kwargs"}} like the reference (which also writes one .npz per sigma; saving is left to the caller).
+    `one_launch=True` (exact dynamics only): all (sigma, beta, run) systems in one mixed launch, with the draws and hence the
+    numbers of the loop over sigma; ValueError for the fixed-dt stepper, a large shape or a launch over the LDS limit."""
     results = {}
-    for sigma in sigma_values:
-        kw = dict(ps_kwargs or {}, local_kernel_sigma=float(sigma))
-        r = sweep_over_betas(beta_values, n_runs_per_beta, kw, init_kwargs, run_kwargs, rng_seeds, on_device=on_device, dynamics=dynamics)
+    kws = [dict(ps_kwargs or {}, local_kernel_sigma=float(sigma)) for sigma in sigma_values]
+    if one_launch:
+        sweeps = _sweeps_in_one_launch("sweep_over_sigmas", [(kw, dict(init_kwargs or {})) for kw in kws], beta_values, n_runs_per_beta,
+                                       run_kwargs, rng_seeds, on_device, dynamics)
+    for si, (sigma, kw) in enumerate(zip(sigma_values, kws)):
+        r = sweeps[si] if one_launch else sweep_over_betas(beta_values, n_runs_per_beta, kw, init_kwargs, run_kwargs, rng_seeds,
+                                                           on_device=on_device, dynamics=dynamics)
         results[sigma] = {"beta": np.asarray(beta_values, dtype=float), "v_mean": r["means"], "v_se": r["ses"], "D_mean": r["D_means"],
                           "D_se": r["D_ses"], "m_mean": r["m_means"], "block_mean": r["block_means"], "ps_kwargs": kw}
     return results
 
 
 def sweep_over_densities(n_part_values, beta_values, n_runs_per_beta=4, ps_kwargs=None, init_kwargs=None, run_kwargs=None,
-                         rng_seeds=None, on_device=False, dynamics=None):
+                         rng_seeds=None, on_device=False, dynamics=None, one_launch=False):
     """The density x beta double sweep of PARTICLE_solver_BIOLOGY_EXCLUSION_double_sweep.py:851-861
     (`list_N_part = np.linspace(50, 950, 19)`: N arrives as a float there and is used as an integer): one batched beta sweep
     per particle number.  Returns a list of the per-N sweep dictionaries (keys of `sweep_over_betas`) with "N_part" added;
     the reference's fit of the blocking coefficients f, g to them (`rho_model`, :290-317) is closed-form SciPy on these
-    numbers and stays with the caller."""
+    numbers and stays with the caller.
+    `one_launch=True` (exact dynamics only): all (N, beta, run) systems in one mixed launch, each counted with the blocking
+    table of its own particle number, with the draws and hence the numbers of the loop over N; ValueError for the fixed-dt
+    stepper, a large shape or a launch over the LDS limit."""
     out = []
     for n_part in n_part_values:
         if float(n_part) != int(n_part):
             raise ValueError("particle numbers must be integral")
-        ik = dict(init_kwargs or {}, N=int(n_part))
-        r = sweep_over_betas(beta_values, n_runs_per_beta, ps_kwargs, ik, run_kwargs, rng_seeds, on_device=on_device, dynamics=dynamics)
+    iks = [dict(init_kwargs or {}, N=int(n_part)) for n_part in n_part_values]
+    if one_launch:
+        sweeps = _sweeps_in_one_launch("sweep_over_densities", [(dict(ps_kwargs or {}), ik) for ik in iks], beta_values, n_runs_per_beta,
+                                       run_kwargs, rng_seeds, on_device, dynamics)
+    for ni, (n_part, ik) in enumerate(zip(n_part_values, iks)):
+        r = sweeps[ni] if one_launch else sweep_over_betas(beta_values, n_runs_per_beta, ps_kwargs, ik, run_kwargs, rng_seeds,
+                                                           on_device=on_device, dynamics=dynamics)
         r["N_part"] = int(n_part)
         out.append(r)
     return out

@@ -5,7 +5,9 @@ result dictionaries; `sweep` statistics can be taken from the scalar sums withou
 and the structure observables from sums the loop takes at every observation (`run_batched_exact_structure`,
 include/gillespie_structure.h); the anchor-capture study's cluster, lifetime and exit statistics likewise
 (`run_batched_exact_capture`, include/gillespie_capture.h); the ensemble density and field profiles of many runs
-(`run_batched_exact_profiles`, include/gillespie_profile.h) are summed over the runs on the device.
+(`run_batched_exact_profiles`, include/gillespie_profile.h) are summed over the runs on the device.  Systems that differ in
+the interaction range or in the blocking threshold of their particle number share ONE launch as a mixed batch
+(`run_batched_exact_mixed`, `run_batched_exact_statistics_mixed`, include/gillespie_mixed.h).
 
 Differences to the reference: randomness is Philox4x32-10 keyed by `seed` (the reference consumes a NumPy Generator), so
 trajectories agree in distribution, not draw for draw; `m_local_list[k]` is the field of the observed state (the
@@ -58,6 +60,20 @@ class GilpPlanInfo(C.Structure):
                 ("n_bins_used", C.c_int32), ("reserved", C.c_int32), ("work_bytes", C.c_int64), ("output_bytes", C.c_int64)]
 
 
+class GilxVariants(C.Structure):
+    """struct gilx_variants of include/gillespie_mixed.h, field for field."""
+    _fields_ = [("n_variants", C.c_int32), ("reserved", C.c_int32), ("sigma_grid", C.c_void_p), ("block_table", C.c_void_p),
+                ("variant_of_system", C.c_void_p), ("seed", C.c_void_p), ("stream", C.c_void_p), ("order", C.c_void_p)]
+
+
+class GilxPlanInfo(C.Structure):
+    """struct gilx_plan_info of include/gillespie_mixed.h, field for field."""
+    _fields_ = [("threads", C.c_int32), ("lds_bytes", C.c_int32), ("max_tlen", C.c_int32), ("systems_per_cu", C.c_int32),
+                ("table_doubles", C.c_int64), ("output_bytes", C.c_int64)]
+
+
+GILX_MAX_VARIANTS = 4096
+GILX_LDS_LIMIT = 160 * 1024     # bytes of LDS a workgroup can have: what a mixed launch must fit
 GILP_NCOLS, GILP_MAX_BINS, GILP_MAX_GROUPS = 7, 1024, 4096
 PROFILE_COLUMNS = ("n_plus", "n_minus", "n_bound", "n_plus2", "n_minus2", "n_plus_minus", "field")
 GILC_NFIXED = 9
@@ -97,6 +113,12 @@ def _lib():
             lib.gilp_run.restype = C.c_int
             lib.gilp_run.argtypes = ([C.POINTER(GilParams), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] +
                                      [C.c_void_p] * 17 + [C.POINTER(C.c_double)])
+        if hasattr(lib, "gilx_run"):           # likewise: no mixed batches in a build from before them
+            lib.gilx_last_error.restype, lib.gilx_last_error.argtypes = C.c_char_p, []
+            lib.gilx_plan.restype = C.c_int
+            lib.gilx_plan.argtypes = [C.POINTER(GilParams), C.POINTER(GilxVariants), C.c_int32, C.POINTER(GilxPlanInfo)]
+            lib.gilx_run.restype = C.c_int
+            lib.gilx_run.argtypes = [C.POINTER(GilParams), C.POINTER(GilxVariants)] + [C.c_void_p] * 14 + [C.POINTER(C.c_double)]
         lib._gil_ready = True
     return lib
 
@@ -229,19 +251,79 @@ def plan_profiles(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, n_bins
     return {k: int(getattr(info, k)) for k, _ in GilpPlanInfo._fields_ if k != "reserved"}
 
 
+def _mixed_descriptor(S, K, sigma_grids, variant_of_system, block_tables=None, seeds=None, streams=None, order=None):
+    """struct gilx_variants for S systems, and the arrays it points to (keep them alive for the call)."""
+    sg = np.ascontiguousarray(sigma_grids, dtype=np.float64).reshape(-1)
+    V = len(sg)
+    keep = [sg]
+
+    def per_system(a, dtype, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.shape != (S,):
+            raise ValueError(f"{name} must have one entry per system")
+        keep.append(a)
+        return _p(a).value
+
+    bt = None
+    if block_tables is not None:
+        bt = np.ascontiguousarray(block_tables, dtype=np.uint8)
+        if bt.shape != (V, K + 1, K + 1):
+            raise ValueError("block_tables must be [variants][K + 1][K + 1]")
+        keep.append(bt)
+    if seeds is not None:
+        seeds = [int(x) & (2 ** 64 - 1) for x in seeds]
+    desc = GilxVariants(n_variants=V, sigma_grid=_p(sg).value, block_table=None if bt is None else _p(bt).value,
+                        variant_of_system=per_system(variant_of_system, np.int32, "variant_of_system"),
+                        seed=per_system(seeds, np.uint64, "seeds"), stream=per_system(streams, np.int32, "streams"),
+                        order=per_system(order, np.int32, "order"))
+    return desc, keep
+
+
+def plan_mixed(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs, variant_of_system=None, order=None, want_states=True):
+    """gilx_plan: what a mixed launch (`run_mixed_raw`) would use -- threads per system, LDS of a workgroup (the longest table of
+    the batch), that table's length, the doubles of all tables, systems per CU by LDS and the output bytes -- by host arithmetic;
+    no device needed.  Refuses what the run would refuse on these numbers."""
+    lib = _lib()
+    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
+    desc, keep = _mixed_descriptor(int(n_systems), int(K), sigma_grids, variant_of_system, order=order)
+    info = GilxPlanInfo()
+    rc = lib.gilx_plan(C.byref(par), C.byref(desc), int(bool(want_states)), C.byref(info))
+    if rc != 0:
+        raise capi.ApsError(rc, lib.gilx_last_error().decode())
+    return {k: int(getattr(info, k)) for k, _ in GilxPlanInfo._fields_}
+
+
+def run_mixed_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
+                  minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
+                  anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
+                  block_tables=None, device=0, flip_table=None, seeds=None, streams=None, order=None, n_cap=None):
+    """`run_raw` for a MIXED batch (gilx_run of include/gillespie_mixed.h): system s runs with the interaction range
+    `sigma_grids[variant_of_system[s]]` and the blocking table `block_tables[variant_of_system[s]]` ([variants][K + 1][K + 1], or
+    None), all systems in one launch.  `seeds[s]`, `streams[s]`: Philox key and system index of system s (None: `seed` and s), so
+    that a system can draw what it would draw in a `run_raw` launch of its own group.  `order`: the system each workgroup takes,
+    a permutation (None: falling particle number).  Same dictionary as `run_raw`; the slots at and beyond a system's own particle
+    number are zero in `pos`, `sigma` and `flags`."""
+    kw = dict(locals())
+    mixed = {k: kw.pop(k) for k in ("sigma_grids", "variant_of_system", "block_tables", "seeds", "streams", "order")}
+    return _run_batch_entry("gilx_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
+
+
 def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed,
                      minus_anchor, immobilize, suppress_flip, crowding, k_on, k_off, k_exit, anchor_mask, uniforms, max_events,
                      want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table, k_max=None, first_obs=0,
                      group_of_site=None, n_groups=0, c_bins=0, h_bins=0, h_dt=0.0, n_cap=None, n_bins=0, want_field=False,
-                     group_of_system=None, per_system=False):
+                     group_of_system=None, per_system=False, mixed=None):
     """The batch entry points take the same arguments: gil_run_batch (systems in LDS), gilm_run (large systems), gils_run
     (either, with the structure sums: k_max, first_obs) and gilc_run (either, with the capture statistics: group_of_site,
     n_groups, c_bins, h_bins, h_dt, first_obs); gilp_run (either, with the ensemble profiles: n_bins, first_obs, want_field,
-    group_of_system, n_groups, per_system)."""
+    group_of_system, n_groups, per_system); gilx_run (systems in LDS, a variant per system: `mixed`, the keywords of
+    _mixed_descriptor)."""
     lib = _lib()
     call = getattr(lib, entry)
     last_error = getattr(lib, {"gil_run_batch": "gil_last_error", "gilm_run": "gilm_last_error", "gils_run": "gils_last_error",
-                               "gilc_run": "gilc_last_error", "gilp_run": "gilp_last_error"}[entry])
+                               "gilc_run": "gilc_last_error", "gilp_run": "gilp_last_error", "gilx_run": "gilx_last_error"}[entry])
     S = len(states)
     betas = np.ascontiguousarray(np.broadcast_to(np.asarray(betas, dtype=np.float64), (S,)))
     ncap = max(1, max(len(st[0]) for st in states))
@@ -304,6 +386,11 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
         prof = np.zeros((S, M, 3, B), np.int32) if per_system else None
         rc = call(C.byref(par), int(n_bins), int(first_obs), int(want_field), _p(groups), int(n_groups), *args, _p(sums), _p(members),
                   _p(prof), C.byref(ms))
+    elif entry == "gilx_run":
+        desc, keep = _mixed_descriptor(S, int(K), **mixed)
+        if desc.variant_of_system is None:
+            raise ValueError("variant_of_system must have one entry per system")
+        rc = call(C.byref(par), C.byref(desc), *args, C.byref(ms))
     else:
         rc = call(C.byref(par), *args, C.byref(ms))
     if rc != 0:
@@ -345,6 +432,15 @@ def run_batched_exact(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var
             suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
             k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms, device=first.device,
             flip_table=first.flip_table())
+    outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
+    first.kernel_ms = r["kernel_ms"]
+    return outs
+
+
+def _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local):
+    """The reference's result dictionaries (:542-557) from the raw outputs `r` of a launch with states."""
+    from .particle_system import ParticleSystem
+    M, L, dx = len(times_obs), systems[0].L, systems[0].dx
     outs = []
     for s, ps in enumerate(systems):
         n0 = int(r["n0"][s])
@@ -374,7 +470,6 @@ def run_batched_exact(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var
                      "total_list": total, "particle_count_list": count, "bound_list": bound_list, "m_local_list": m_loc,
                      "m_global": m_glob, "rho_hat_complex": hat, "fft_amp_list": amp, "var_list": var,
                      "exit_times": [float(t) for t in ex[:, 0]], "exit_positions": [int(x) for x in ex[:, 1]]})
-    first.kernel_ms = r["kernel_ms"]
     return outs
 
 
@@ -408,6 +503,15 @@ def run_batched_exact_statistics(systems, T=10.0, obs_dt=0.01):
             suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
             k_off=first.k_off, k_exit=0.0, anchor_mask=first.is_anchor_site, want_states=False, x_wall=acc0.x_wall,
             ref_obs=acc0.start, front_lo=front_lo, block_table=tables[0], device=first.device, flip_table=first.flip_table())
+    rows = _statistics_rows(systems, r, times_obs)
+    first.kernel_ms = r["kernel_ms"]
+    return rows
+
+
+def _statistics_rows(systems, r, times_obs):
+    """The DeviceObservables rows from the scalar sums of the raw outputs `r`."""
+    from . import observables
+    first = systems[0]
     rows = []
     for s, ps in enumerate(systems):
         if int(r["n_recorded"][s]) < len(times_obs):
@@ -418,7 +522,109 @@ def run_batched_exact_statistics(systems, T=10.0, obs_dt=0.01):
             acc.add(k, sums, sums["n_front"] if k >= acc.start and sums["max_pos"] >= 0 else None)
         rows.append(acc.result())
         ps.n_events = int(r["n_events"][s])
-    first.kernel_ms = r["kernel_ms"]
+    return rows
+
+
+def mixed_variants(sigma_grids, block_tables=None):
+    """The variants of a mixed batch: the distinct pairs of a system's sigma_grid and the bytes of its blocking table.  Returns
+    (`sigma_grids` [V], `block_tables` [V][...] or None, `variant_of_system` [S]), the variants in the order of their first
+    system.  Two interaction ranges are one variant only when they are the same number: whether their weight tables happen to
+    have the same taps is not looked at."""
+    index, sig, tabs, owner = {}, [], [], []
+    for s, sg in enumerate(sigma_grids):
+        tab = None if block_tables is None else np.ascontiguousarray(block_tables[s], dtype=np.uint8)
+        key = (float(sg), None if tab is None else tab.tobytes())
+        if key not in index:
+            index[key] = len(sig)
+            sig.append(float(sg))
+            tabs.append(tab)
+        owner.append(index[key])
+    return np.array(sig), (None if block_tables is None else np.stack(tabs)), np.array(owner, np.int32)
+
+
+def mixed_keys(systems, groups=None):
+    """Philox key and system index of every system of a mixed batch.  `groups[s]` is the group of system s, a group being what one
+    `run_raw` launch of the host loop would hold: the key is the seed of the group's FIRST system (its `seed`, or a number drawn
+    from its rng -- call this after the initial states were drawn, as the per-group functions do) and the index is the place
+    within the group.  None: one group."""
+    groups = [0] * len(systems) if groups is None else [int(g) for g in groups]
+    if len(groups) != len(systems):
+        raise ValueError("groups must have one entry per system")
+    key, count, seeds, streams = {}, {}, [], []
+    for ps, g in zip(systems, groups):
+        if g not in key:
+            key[g] = ps.seed if ps.seed is not None else int(ps.rng.random() * 2.0 ** 53)
+            count[g] = 0
+        seeds.append(int(key[g]))
+        streams.append(count[g])
+        count[g] += 1
+    return seeds, streams
+
+
+def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, order=None):
+    """The one launch behind run_batched_exact_mixed and run_batched_exact_statistics_mixed: checks, initial states, variants,
+    keys, gilx_run.  Returns (raw outputs, times_obs)."""
+    from . import observables
+    from .particle_system import _SHAPE_ATTRS
+    first = systems[0]
+    for ps in systems[1:]:
+        for k in _SHAPE_ATTRS:
+            if k != "local_kernel_sigma" and getattr(ps, k) != getattr(first, k):
+                raise ValueError(f"{who}: systems differ in {k}")
+        if not np.array_equal(ps.is_anchor_site, first.is_anchor_site):
+            raise ValueError(f"{who}: systems differ in their anchor sites")
+        if (ps.flip_table() is None) != (first.flip_table() is None) or (ps.flip_table() is not None and not np.array_equal(ps.flip_table(), first.flip_table())):
+            raise ValueError(f"{who}: systems differ in flip_rate_fn")
+    if statistics and first.k_exit:
+        raise ValueError(f"{who} needs k_exit = 0")
+    inits = [ps.init_particles() for ps in systems]
+    n_cap = max(1, max(len(p) for p, _ in inits))
+    if first.L > GIL_MAX_L or n_cap > GIL_MAX_N:
+        raise ValueError(f"{who}: L = {first.L}, N = {n_cap} is a large shape (beyond L = {GIL_MAX_L}, N = {GIL_MAX_N}); "
+                         "the large-system kernel takes no mixed batches")
+    seeds, streams = mixed_keys(systems, groups)
+    times_obs = np.arange(0.0, T, obs_dt)
+    kw = {}
+    tables = None
+    if statistics:
+        acc0 = observables.DeviceObservables(times_obs, first.L, first.dx, first.K)
+        tables = [acc0.block_table(len(p)) for p, _ in inits]  # the blocking threshold depends on the particle number
+        kw = dict(want_states=False, x_wall=acc0.x_wall, ref_obs=acc0.start,
+                  front_lo=np.array([acc0.front_range(s)[0] for s in range(first.L)], np.int32))
+    sig, tabs, owner = mixed_variants([ps._sigma_grid for ps in systems], tables)
+    plan = plan_mixed(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems), n_cap=n_cap,
+                      n_obs=len(times_obs), variant_of_system=owner, want_states=not statistics)
+    if plan["lds_bytes"] > GILX_LDS_LIMIT:
+        raise ValueError(f"{who}: the launch needs {plan['lds_bytes']} bytes of LDS per system, over the limit of {GILX_LDS_LIMIT} bytes")
+    r = run_mixed_raw(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, variant_of_system=owner, block_tables=tabs,
+                      rate_diffusion=first.rate_diffusion, rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems],
+                      states=inits, times_obs=times_obs, T=T, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
+                      suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
+                      k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms, device=first.device,
+                      flip_table=first.flip_table(), seeds=seeds, streams=streams, order=order, **kw)
+    r["plan"] = plan
+    return r, times_obs
+
+
+def run_batched_exact_mixed(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False, uniforms=None, want_m_local=True,
+                            groups=None, order=None):
+    """`run_batched_exact` for systems that may ALSO differ in `local_kernel_sigma`: one mixed launch (include/gillespie_mixed.h).
+    Every other attribute the batched functions compare, the anchor sites and the flip table must agree.  `groups[s]`: the group
+    of system s; its systems draw what `run_batched_exact` on the group alone draws (`mixed_keys`).  Returns the list of the
+    reference's result dictionaries, one per system."""
+    r, times_obs = _mixed_launch("run_batched_exact_mixed", systems, T, obs_dt, groups, False, uniforms, order)
+    outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
+    systems[0].kernel_ms = r["kernel_ms"]
+    return outs
+
+
+def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None, order=None):
+    """`run_batched_exact_statistics` for systems that may also differ in `local_kernel_sigma` and whose particle numbers may give
+    different blocking thresholds: every system is counted with the blocking table of its own particle number, in one mixed
+    launch.  `groups` as in run_batched_exact_mixed.  Returns the DeviceObservables rows, one per system."""
+    r, times_obs = _mixed_launch("run_batched_exact_statistics_mixed", systems, T, obs_dt, groups, True, None, order)
+    rows = _statistics_rows(systems, r, times_obs)
+    systems[0].kernel_ms = r["kernel_ms"]
     return rows
 
 
