@@ -28,12 +28,14 @@
 #include "gillespie_capture.h"
 #include "gillespie_profile.h"
 #include "gillespie_mixed.h"
+#include "gillespie_mixed_structure.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"           // model, initial-state check, the driver of the one-shot entry points
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiations only)
 #include "gillespie_capture.hpp"          // anchor capture and cluster statistics (capture instantiations only)
 #include "gillespie_profile.hpp"          // ensemble density and field profiles (profile instantiations only)
 #include "gillespie_mixed.hpp"            // a variant per system: table, blocking table, slots, Philox key (mixed instantiations only)
+#include "gillespie_window.hpp"           // the window sums of the structure rows (mixed structure instantiations only)
 
 namespace {
 
@@ -71,6 +73,7 @@ struct GilsBatchArgs : GilArgs { GilsArgs st; };            // arguments of the 
 struct GilcBatchArgs : GilsBatchArgs { GilcArgs cp; };      // arguments of the capture instantiations
 struct GilpBatchArgs : GilcBatchArgs { GilpArgs pf; };      // arguments of the profile instantiations (the driver's one struct)
 struct GilxBatchArgs : GilArgs { GilxArgs mx; };            // arguments of the mixed instantiations (gilx_run's driver)
+struct GilxsBatchArgs : GilxBatchArgs { GilsArgs st; GilwArgs wn; };   // arguments of the mixed structure instantiations (gilxs_run's)
 
 // the structure sums' slots: behind the loop's own LDS (which ends with the plus-occupancy bytes), at the next multiple of 8
 __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L) {
@@ -85,12 +88,13 @@ __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L)
 // PF = ensemble density and field profiles (gillespie_profile.hpp), likewise; not combined with ST or CP.
 // MX = a mixed batch (gillespie_mixed.hpp): the system of a workgroup comes from a launch order, and the weight table, the
 // blocking table, the slot count and the Philox key are the system's own; likewise; not combined with ST, CP or PF.  In such a
-// launch a.tlen is the longest table's length (the LDS layout is the launch's).
+// launch a.tlen is the longest table's length (the LDS layout is the launch's).  MX with ST: the structure sums of a mixed launch,
+// with the window reduction of gillespie_window.hpp; the rows themselves are optional there.
 template <int NT, bool ST, bool CP = false, bool PF = false, bool MX = false>
-__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, GilxBatchArgs, std::conditional_t<PF, GilpBatchArgs, std::conditional_t<CP, GilcBatchArgs, std::conditional_t<ST, GilsBatchArgs, GilArgs>>>> a) {
+__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, std::conditional_t<ST, GilxsBatchArgs, GilxBatchArgs>, std::conditional_t<PF, GilpBatchArgs, std::conditional_t<CP, GilcBatchArgs, std::conditional_t<ST, GilsBatchArgs, GilArgs>>>> a) {
     static_assert(!(ST && CP), "the capture launches take no structure sums");
     static_assert(!(PF && (ST || CP)), "the profile launches take no structure sums and no capture statistics");
-    static_assert(!(MX && (ST || CP || PF)), "the mixed launches take the scalar sums and the states only");
+    static_assert(!(MX && (CP || PF)), "the mixed launches take no capture statistics and no profiles");
     extern __shared__ double lds[];
     const Model &M = a.m;
     const GilxView vw = gilx_view<MX, NT>(a);                  // empty without MX
@@ -157,6 +161,9 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, Gi
     double tnow = 0.0;
     long long n_ev = 0;
     int k_obs = 0, n_exit = 0;
+    // MX with ST only: observations the window took, and empty ones it met.  The other instantiations never read them, so
+    // they cost no register there (their assembly is the parent's)
+    [[maybe_unused]] int n_win = 0, n_emp = 0;
     const int c0 = t * GX_CHUNK, c1 = min(GX_SLOTS, c0 + GX_CHUNK);
 
     auto record = [&](int k) {                                 // observation k: state and scalar sums (ref :517-536)
@@ -205,13 +212,24 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, Gi
         __syncthreads();
         if constexpr (ST) {
             const GilsArgs &sa = a.st;
-            if (k >= sa.first_obs) {
+            if (MX || k >= sa.first_obs) {                     // MX: the four site sums of every observation (the head rows)
                 double mg = 0.0;                               // global-mean mode: the one value of every site (ref :219-221)
-                if (!M.field_mode && gsum_n > 0) { mg = (double)gsum_s / (double)gsum_n; mg = mg > 1.0 ? 1.0 : (mg < -1.0 ? -1.0 : mg); }
-                double *row = sa.rows + ((size_t)sys * nobs + k) * (size_t)(4 + 2 * sa.k_max), *red = gils_slots(lds, occp, L);
-                // two calls: the gathers of the first are LDS reads, of the second global loads
-                if (sa.phase_in_lds) gils_record_row<NT>(row, sa.k_max, L, ncap, pos, flg, occ, W, S, M.field_mode != 0, mg, red + gils_lds_doubles(NT), red, work);
-                else gils_record_row<NT>(row, sa.k_max, L, ncap, pos, flg, occ, W, S, M.field_mode != 0, mg, sa.phase, red, work);
+                if (!GX_FIELD && gsum_n > 0) { mg = (double)gsum_s / (double)gsum_n; mg = mg > 1.0 ? 1.0 : (mg < -1.0 ? -1.0 : mg); }
+                if constexpr (MX) {
+                    double *red = gils_slots(lds, occp, L);
+                    const bool in = k >= sa.first_obs;         // Fourier work from first_obs on only: before it, no modes
+                    const int kk = in ? sa.k_max : 0;
+                    double *row = in && sa.rows ? sa.rows + ((size_t)sys * nobs + k) * (size_t)(4 + 2 * sa.k_max) : nullptr;
+                    const GilwSink sink{a.wn.head + ((size_t)sys * nobs + k) * 4, a.wn.window + (size_t)sys * 3 * sa.k_max, n_win == 0};
+                    if (sa.phase_in_lds) gils_record_row<NT>(row, kk, L, GX_SLOTS, pos, flg, occ, W, S, GX_FIELD != 0, mg, red + gils_lds_doubles(NT), red, work, sink);
+                    else gils_record_row<NT>(row, kk, L, GX_SLOTS, pos, flg, occ, W, S, GX_FIELD != 0, mg, sa.phase, red, work, sink);
+                    if (in) { if (gilw_live<NT>(red) > 0.0) n_win += 1; else n_emp += 1; }   // red: next written behind a barrier of the next observation
+                } else {
+                    double *row = sa.rows + ((size_t)sys * nobs + k) * (size_t)(4 + 2 * sa.k_max), *red = gils_slots(lds, occp, L);
+                    // two calls: the gathers of the first are LDS reads, of the second global loads
+                    if (sa.phase_in_lds) gils_record_row<NT>(row, sa.k_max, L, GX_SLOTS, pos, flg, occ, W, S, GX_FIELD != 0, mg, red + gils_lds_doubles(NT), red, work);
+                    else gils_record_row<NT>(row, sa.k_max, L, GX_SLOTS, pos, flg, occ, W, S, GX_FIELD != 0, mg, sa.phase, red, work);
+                }
             }
         }
         if constexpr (CP) {
@@ -463,6 +481,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, Gi
         if (a.n_events) a.n_events[sys] = n_ev;
         if (a.t_final) a.t_final[sys] = tnow;
         if (a.n_exits) a.n_exits[sys] = n_exit;
+        if constexpr (MX && ST) { a.wn.n_window[sys] = n_win; a.wn.n_empty[sys] = n_emp; }
     }
 }
 #undef GX_TLEN
@@ -736,8 +755,9 @@ struct GilxTables { std::vector<double> table; std::vector<GilxVariant> var; int
 
 // the checks gilx_plan and gilx_run share, the tables and the shape: 0 with `info` and `tb` filled, or GIL_ERR_ARG with the
 // text in g_gilx_err
-int gilx_decide(const char *who, const gil_params *p, const gilx_variants *v, bool states, gilx_plan_info &info, GilxTables &tb) {
-    auto bad = [&](const std::string &m) { g_gilx_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+int gilx_decide(const char *who, const gil_params *p, const gilx_variants *v, bool states, gilx_plan_info &info, GilxTables &tb,
+                std::string &err = g_gilx_err) {
+    auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     if (p->L < 2) return bad("L must be at least 2");
     if (p->L > GIL_MAX_L)
         return bad("L = " + std::to_string(p->L) + " is beyond GIL_MAX_L = " + std::to_string(GIL_MAX_L) + ": the large-system shape takes no mixed batches");
@@ -787,15 +807,53 @@ int gilx_decide(const char *who, const gil_params *p, const gilx_variants *v, bo
     return GIL_OK;
 }
 
-// gilx_run's driver: batch_run for a launch of the mixed instantiations
+std::string g_gilxs_err;
+
+// what gilxs_run adds to gilx_run: the structure sums (rows optional) and their window reduction
+struct GilxsCall { int k_max, first_obs; double *structure_obs, *head_obs, *window; int32_t *n_window, *n_empty; };
+
+// the checks gilxs_plan and gilxs_run share, the tables and the shape: 0 with `info` and `tb` filled, or GIL_ERR_ARG with the
+// text in g_gilxs_err.  gilx_decide's refusals first, then gils_decide's.
+int gilxs_decide(const char *who, const gil_params *p, const gilx_variants *v, int k_max, int first_obs, bool states, bool rows,
+                 gilxs_plan_info &info, GilxTables &tb) {
+    auto bad = [&](const std::string &m) { g_gilxs_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    gilx_plan_info xi;
+    if (int rc = gilx_decide(who, p, v, states, xi, tb, g_gilxs_err)) return rc;
+    const int max_k = std::min(p->L, GILS_MAX_K);
+    if (k_max < 1 || k_max > max_k) return bad("k_max = " + std::to_string(k_max) + " is outside [1, min(L, GILS_MAX_K) = " + std::to_string(max_k) + "]");
+    if (first_obs < 0 || first_obs > p->n_obs) return bad("first_obs = " + std::to_string(first_obs) + " is outside [0, n_obs = " + std::to_string(p->n_obs) + "]");
+    int NT = 0; size_t lds = 0; bool phase_in_lds = false;
+    batch_shape(p->L, p->n_cap, tb.max_tlen, true, NT, lds, &phase_in_lds);
+    if (lds > 160 * 1024)
+        return bad("the launch needs " + std::to_string(lds) + " bytes of LDS per system with the structure sums (L = " + std::to_string(p->L) +
+                   ", n_cap = " + std::to_string(p->n_cap) + ", longest table " + std::to_string(tb.max_tlen) + "), more than the " +
+                   std::to_string(160 * 1024) + " bytes (160 KB) of a workgroup");
+    info = gilxs_plan_info{};
+    info.threads = NT; info.lds_bytes = (int32_t)lds; info.phase_in_lds = phase_in_lds ? 1 : 0; info.max_tlen = tb.max_tlen;
+    info.systems_per_cu = (int32_t)((size_t)160 * 1024 / lds); info.row_len = 4 + 2 * k_max;
+    info.work_bytes = (int64_t)p->L * 16;
+    const int64_t S = p->n_systems, O = p->n_obs;
+    info.output_bytes = xi.output_bytes + S * (O * 32 + (int64_t)k_max * 24 + 8) + (rows ? S * O * info.row_len * 8 : 0);
+    if (info.work_bytes + info.output_bytes > (1ll << 38))
+        return bad("the batch needs " + std::to_string(info.work_bytes) + " bytes of work memory and " + std::to_string(info.output_bytes) +
+                   " bytes of outputs, more than the " + std::to_string(1ll << 38) + " bytes a plan accepts");
+    return GIL_OK;
+}
+
+// gilx_run's driver: batch_run for a launch of the mixed instantiations; xs: gilxs_run's call, with the structure sums
 int mixed_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
               const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
-              int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
-    const char *who = "gilx_run";
-    std::string &err = g_gilx_err;
+              int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms, const GilxsCall *xs = nullptr) {
+    const char *who = xs ? "gilxs_run" : "gilx_run";
+    std::string &err = xs ? g_gilxs_err : g_gilx_err;
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilx_plan_info info; GilxTables tb;
-    if (int rc = gilx_decide(who, p, v, pos_obs || sigma_obs || flags_obs, info, tb)) return rc;
+    gilxs_plan_info sinfo{};
+    if (xs) {
+        if (int rc = gilxs_decide(who, p, v, xs->k_max, xs->first_obs, pos_obs || sigma_obs || flags_obs, xs->structure_obs != nullptr, sinfo, tb)) return rc;
+        info = gilx_plan_info{};
+        info.threads = sinfo.threads; info.lds_bytes = sinfo.lds_bytes;
+    } else if (int rc = gilx_decide(who, p, v, pos_obs || sigma_obs || flags_obs, info, tb)) return rc;
     const int S = p->n_systems, L = p->L, ncap = p->n_cap, V = v->n_variants, NT = info.threads;
     for (int s = 0; s < S; ++s) {
         if (n0[s] < 0 || n0[s] > ncap) return bad("n0 = " + std::to_string(n0[s]) + " of system " + std::to_string(s) + " is outside [0, n_cap = " + std::to_string(ncap) + "]");
@@ -807,7 +865,14 @@ int mixed_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, co
     if (!v->order) std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return n0[x] > n0[y]; });   // long systems first
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: slots beyond n0 and rows never reached stay zero
     if (int rc = job.select_device(p->device)) return rc;
-    GilxBatchArgs a{};
+    if (xs) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
+        if ((uint64_t)(sinfo.work_bytes + sinfo.output_bytes) > (uint64_t)free_b)
+            return bad("the batch needs " + std::to_string(sinfo.work_bytes) + " bytes of work memory and " + std::to_string(sinfo.output_bytes) +
+                       " bytes of outputs, the device has " + std::to_string(free_b) + " bytes free");
+    }
+    GilxsBatchArgs a{};
     a.p = *p; a.p.sigma_grid = 0.0; a.p.block_table = nullptr;
     a.tlen = tb.max_tlen; a.chunk = (ncap + NT - 1) / NT;        // the layout's table length; the kernel takes every system's own chunk
     a.m = gil_model(p);
@@ -826,17 +891,38 @@ int mixed_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, co
     OUT(scalars, scalars_obs, SO * GIL_NSCALARS);
     OUT(n_recorded, n_recorded, (size_t)S); OUT(t_final, t_final, (size_t)S); OUT(exits, exits, SN * 3); OUT(n_exits, n_exits, (size_t)S);
     OUT(n_events, n_events, (size_t)S);
-    if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, false, false, true>)
-                                              : reinterpret_cast<const void *>(&gil_kernel<256, false, false, false, true>), lds)) return rc;
+    const size_t row = xs ? 4 + 2 * (size_t)xs->k_max : 0;
+    if (xs) {
+        GilsArgs &sa = a.st;
+        double *phase = nullptr;
+        if (xs->structure_obs) if (int rc = job.alloc(&sa.rows, SO * row, "structure_obs")) return rc;
+        if (int rc = job.alloc(&phase, (size_t)2 * L, "phase")) return rc;
+        sa.phase = phase; sa.k_max = xs->k_max; sa.first_obs = xs->first_obs; sa.phase_in_lds = sinfo.phase_in_lds;
+        WORK(wn.head, SO * 4); WORK(wn.window, (size_t)S * 3 * xs->k_max); WORK(wn.n_window, (size_t)S); WORK(wn.n_empty, (size_t)S);
+        if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, true, false, false, true>)
+                                                  : reinterpret_cast<const void *>(&gil_kernel<256, true, false, false, true>), lds)) return rc;
+        hipLaunchKernelGGL(gils_phase_table, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, nullptr, phase, L);
+    } else if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, false, false, true>)
+                                                     : reinterpret_cast<const void *>(&gil_kernel<256, false, false, false, true>), lds)) return rc;
     if (int rc = job.create_events()) return rc;
     job.ev.start();
-    if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
-    else hipLaunchKernelGGL((gil_kernel<256, false, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
+    if (xs) {
+        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, true, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
+        else hipLaunchKernelGGL((gil_kernel<256, true, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
+    } else if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilxBatchArgs &>(a));
+    else hipLaunchKernelGGL((gil_kernel<256, false, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilxBatchArgs &>(a));
     job.ev.stop();
     if (int rc = job.finish(hipGetLastError(), "gil_kernel (mixed)", kernel_ms)) return rc;
     DOWN(pos_obs, pos_obs, SO * ncap * 4); DOWN(sigma_obs, sigma_obs, SO * ncap); DOWN(flags_obs, flags_obs, SO * ncap);
     DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8); DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8);
     DOWN(t_final, t_final, (size_t)S * 8); DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
+    if (xs) {
+        if (xs->structure_obs) if (int rc = job.download(xs->structure_obs, a.st.rows, SO * row * 8, "structure_obs")) return rc;
+        if (int rc = job.download(xs->head_obs, a.wn.head, SO * 4 * 8, "head_obs")) return rc;
+        if (int rc = job.download(xs->window, a.wn.window, (size_t)S * 3 * xs->k_max * 8, "window")) return rc;
+        if (int rc = job.download(xs->n_window, a.wn.n_window, (size_t)S * 4, "n_window")) return rc;
+        if (int rc = job.download(xs->n_empty, a.wn.n_empty, (size_t)S * 4, "n_empty")) return rc;
+    }
     return GIL_OK;
 }
 
@@ -860,6 +946,30 @@ int gilx_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, con
     if (!p || !v || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !v->variant_of_system) { g_gilx_err = "gilx_run: null argument"; return GIL_ERR_ARG; }
     return mixed_run(p, v, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final,
                      exits, n_exits, kernel_ms);
+}
+
+const char *gilxs_last_error(void) { return g_gilxs_err.c_str(); }
+
+int gilxs_plan(const gil_params *p, const gilx_variants *v, int32_t k_max, int32_t first_obs, int32_t want_states, int32_t want_rows,
+               gilxs_plan_info *out) {
+    if (!p || !v || !out) { g_gilxs_err = "gilxs_plan: null argument"; return GIL_ERR_ARG; }
+    gilxs_plan_info info; GilxTables tb;
+    if (int rc = gilxs_decide("gilxs_plan", p, v, k_max, first_obs, want_states != 0, want_rows != 0, info, tb)) return rc;
+    *out = info;
+    return GIL_OK;
+}
+
+int gilxs_run(const gil_params *p, const gilx_variants *v, int32_t k_max, int32_t first_obs,
+              const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0, const double *uniforms,
+              int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
+              int64_t *n_events, double *t_final, double *exits, int32_t *n_exits,
+              double *structure_obs, double *head_obs, double *window, int32_t *n_window, int32_t *n_empty, double *kernel_ms) {
+    if (!p || !v || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !v->variant_of_system || !head_obs || !window || !n_window || !n_empty) {
+        g_gilxs_err = "gilxs_run: null argument"; return GIL_ERR_ARG;
+    }
+    const GilxsCall xs{k_max, first_obs, structure_obs, head_obs, window, n_window, n_empty};
+    return mixed_run(p, v, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final,
+                     exits, n_exits, kernel_ms, &xs);
 }
 
 const char *gilp_last_error(void) { return g_gilp_err.c_str(); }

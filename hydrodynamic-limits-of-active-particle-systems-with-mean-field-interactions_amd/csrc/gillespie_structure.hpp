@@ -54,13 +54,18 @@ __device__ __forceinline__ int gils_phase_index(int k, int p, int L, double inv_
     return r >= L ? r - L : r;
 }
 
+// The default of gils_record_row's last argument: the sums go to the row and nowhere else.
+struct GilsNoSink { static constexpr bool active = false; };
+
 // Every thread of the workgroup calls it (it holds barriers).  occ: particles per site; W, S: the smoothed histograms
 // (field_mode) or unused, when every site carries m_global; red: gils_lds_doubles(NT) doubles of LDS; step: ncap ints
 // of scratch (the loop's work list, which every event rebuilds from nothing).
-template <int NT, typename Occ>
+// sink: a second destination for the sums (gillespie_window.hpp); with an active sink `row` may be null (no row is stored) and
+// k_max may be 0 (the four site sums only).  Without one, the callers' code is what it was before the argument existed.
+template <int NT, typename Occ, class Sink = GilsNoSink>
 __device__ inline void gils_record_row(double *row, int k_max, int L, int ncap, const int *pos, const uint8_t *flg, const Occ *occ,
                                        const double *W, const double *S, bool field_mode, double m_global, const double *phase,
-                                       double *red, int *step) {
+                                       double *red, int *step, const Sink &sink = Sink{}) {
     constexpr int NW = NT / 64;
     const int t = threadIdx.x;
     // ---- the four sums over sites: m(x) = clip(S / W) where W > 0, the expression of the rate evaluation
@@ -88,7 +93,14 @@ __device__ inline void gils_record_row(double *row, int k_max, int L, int ncap, 
         double s = red[t];
 #pragma unroll
         for (int w = 1; w < NW; ++w) s += red[4 * w + t];
-        row[t] = s;
+        if constexpr (!Sink::active) row[t] = s;
+        else { if (row) row[t] = s; sink.site_sum(t, s); }
+    }
+    double n_live = 0.0;                                       // an active sink divides by it: entry 0, summed in the same order
+    if constexpr (Sink::active) {
+        n_live = red[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) n_live += red[4 * w];
     }
     // ---- Fourier sums: thread = (mode within a pass, slice of the particle slots).  A thread keeps the sums of PT modes,
     // kw apart, in registers while it walks the slots: the phase index of the first comes from one product per slot, the
@@ -136,9 +148,20 @@ __device__ inline void gils_record_row(double *row, int k_max, int L, int ncap, 
         for (int q = 0; q < PT; ++q) {
             const int k = kb + q * kw;
             if (g == 0 && k < kk) {
-                row[4 + 2 * k] = re[q]; row[5 + 2 * k] = im[q];
-                const int kc = L - k;                          // kc >= kk unless kc == k: no other thread writes it
-                if (k > 0 && kc != k && kc < k_max) { row[4 + 2 * kc] = re[q]; row[5 + 2 * kc] = -im[q]; }
+                if constexpr (!Sink::active) {
+                    row[4 + 2 * k] = re[q]; row[5 + 2 * k] = im[q];
+                    const int kc = L - k;                      // kc >= kk unless kc == k: no other thread writes it
+                    if (k > 0 && kc != k && kc < k_max) { row[4 + 2 * kc] = re[q]; row[5 + 2 * kc] = -im[q]; }
+                } else {                                       // the same stores where there is a row, and the sink's
+                    const int kc = L - k;
+                    const bool conj = k > 0 && kc != k && kc < k_max;
+                    if (row) {
+                        row[4 + 2 * k] = re[q]; row[5 + 2 * k] = im[q];
+                        if (conj) { row[4 + 2 * kc] = re[q]; row[5 + 2 * kc] = -im[q]; }
+                    }
+                    sink.mode(k, re[q], im[q], n_live);
+                    if (conj) sink.mode(kc, re[q], im[q], n_live);
+                }
             }
         }
     }

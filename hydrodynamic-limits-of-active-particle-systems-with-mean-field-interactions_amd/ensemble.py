@@ -7,7 +7,8 @@ one batched handle per sigma / per particle number (the weight table and the sta
 pairs inside it; under the exact dynamics `one_launch=True` puts the whole sweep into ONE mixed launch of the event loop
 (include/gillespie_mixed.h: a weight table and a blocking table per system).  `sweep_betas_for_structures` / `sweep_beta_structure_ensemble` are the pattern study's drivers
 (PARTICLE_solver_BIOLOGY_local_structure.py:105-193), all (beta, run) pairs in one launch, the per-run observables from sums
-taken on the GPU.  `capture_study` is the anchor-capture study (PARTICLE_solver_CLASS.py:766-976) as an ensemble in one launch.
+taken on the GPU; `sweep_sigmas_for_structures` is that study over the interaction range, all (sigma, beta, run) systems in one mixed
+launch with the window reduction on the device (include/gillespie_mixed_structure.h).  `capture_study` is the anchor-capture study (PARTICLE_solver_CLASS.py:766-976) as an ensemble in one launch.
 `profile_sweep` gives the ensemble density and field profiles per beta (the means over runs of rho_plus_list, rho_minus_list,
 m_local_list, PARTICLE_solver_CLASS.py:205-213), all (beta, run) pairs in one launch and summed over the runs on the GPU."""
 from __future__ import annotations
@@ -217,6 +218,71 @@ def sweep_betas_for_structures(beta_values, n_runs_per_beta, ps_kwargs, init_kwa
         from .particle_system import run_batched_structure
         rows = run_batched_structure(systems, start_fraction=start_fraction, k_max=k_max, **slim)
     return {beta: structure_ensemble_statistics([row for row, o in zip(rows, owner) if o == bi]) for bi, beta in enumerate(beta_values)}
+
+
+def sweep_sigmas_for_structures(sigma_values, beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwargs, start_fraction=0.5,
+                                k_max=None, rng_seeds=None, one_launch=True, return_series=False):
+    """The pattern study over the interaction range: for every `local_kernel_sigma` of `sigma_values` the structure sweep of
+    sweep_betas_for_structures -- the particle counterpart of pde.sweep_over_kernel_sigmas and of the reference's
+    IMEX_PDE_solver_run_sweep_magn*.py.  Returns {sigma: {beta: structure_ensemble_statistics(...)}}.
+    `one_launch=True`: all (sigma, beta, run) systems in ONE mixed launch of the exact event loop that takes the structure sums
+    and reduces them over the window on the device (gillespie.run_batched_exact_structure_mixed): nothing of size observations x
+    modes leaves the GPU.  The systems are built in the order of the host loop over sigma and every sigma is a group of the
+    launch, so each sigma draws what its own launch draws.  `one_launch=False` is that host loop, one launch per sigma
+    (gillespie.run_batched_exact_structure).
+    `return_series=True`: returns (results, series) with series[sigma][beta] = {"times_obs", "m_abs_series", "var_series"}, the
+    means over the runs of |m|(t) and var(total)(t): the arrays the PDE width sweep records per width.
+    Exact dynamics only: ValueError for the fixed-dt stepper (`dt` or `mode="sync"` in ps_kwargs) and, with one_launch, for a
+    large shape (L > 4096 or N > 2048), neither of which has a mixed launch -- raised here before any system is built where the
+    numbers are known (L, and N of init="fixed"), and by the launch's own check once a Poisson initial state is drawn; `run_kwargs` may hold T, obs_dt, record_fft, record_var."""
+    from . import gillespie
+    who = "sweep_sigmas_for_structures"
+    ps_kwargs, init_kwargs, run_kwargs = dict(ps_kwargs or {}), dict(init_kwargs or {}), dict(run_kwargs or {})
+    if ps_kwargs.get("dt") is not None or ps_kwargs.get("mode") == "sync":
+        raise ValueError(f"{who} needs the exact dynamics; the fixed-dt stepper has no mixed launch")
+    unknown = set(run_kwargs) - {"T", "obs_dt", "record_fft", "record_var"}
+    if unknown:
+        raise ValueError(f"run_kwargs may hold T, obs_dt, record_fft, record_var; got {sorted(unknown)}")
+    slim = {k: v for k, v in run_kwargs.items() if k in ("T", "obs_dt")}
+    L = int(ps_kwargs["L"])
+    n_fixed = int(init_kwargs.get("N", 1000)) if init_kwargs.get("init", "fixed") == "fixed" else 0   # poisson: _mixed_launch raises the same ValueError once the states are drawn
+    if one_launch and (L > gillespie.GIL_MAX_L or n_fixed > gillespie.GIL_MAX_N):
+        raise ValueError(f"{who}: L = {L}, N = {n_fixed} is a large shape (beyond L = {gillespie.GIL_MAX_L}, "
+                         f"N = {gillespie.GIL_MAX_N}); the large-system kernel takes no mixed batches")
+    systems, group, owner = [], [], []
+    for si, sigma in enumerate(sigma_values):
+        for bi, beta in enumerate(beta_values):
+            for r in range(n_runs_per_beta):
+                rng = None if rng_seeds is None else np.random.default_rng(int(rng_seeds[bi][r]))
+                systems.append(ParticleSystem(beta=beta, rng=rng, **dict(ps_kwargs, local_kernel_sigma=float(sigma)), **init_kwargs))
+                group.append(si)
+                owner.append(bi)
+    per = len(beta_values) * n_runs_per_beta
+    if one_launch:
+        rows = gillespie.run_batched_exact_structure_mixed(systems, start_fraction=start_fraction, k_max=k_max, groups=group,
+                                                           reduce="device", return_series=return_series, **slim)
+    else:
+        rows = []
+        for si in range(len(sigma_values)):
+            mine = systems[si * per:(si + 1) * per]
+            if return_series:                  # the series need the head rows: the mixed entry point, one sigma per launch
+                rows += gillespie.run_batched_exact_structure_mixed(mine, start_fraction=start_fraction, k_max=k_max, reduce="rows",
+                                                                    return_series=True, **slim)
+            else:
+                rows += gillespie.run_batched_exact_structure(mine, start_fraction=start_fraction, k_max=k_max, **slim)
+    results, series = {}, {}
+    for si, sigma in enumerate(sigma_values):
+        mine, own = rows[si * per:(si + 1) * per], owner[si * per:(si + 1) * per]
+        by_beta = [[row for row, o in zip(mine, own) if o == bi] for bi in range(len(beta_values))]
+        if return_series:
+            series[sigma] = {beta: {"times_obs": sel[0]["times_obs"].copy(),
+                                    "m_abs_series": np.mean([np.abs(row["m_series"]) for row in sel], axis=0),
+                                    "var_series": np.mean([row["var_series"] for row in sel], axis=0)}
+                             for beta, sel in zip(beta_values, by_beta)}
+            by_beta = [[{k: v for k, v in row.items() if k not in ("times_obs", "m_series", "var_series", "fft_amp_series")} for row in sel]
+                       for sel in by_beta]
+        results[sigma] = {beta: structure_ensemble_statistics(sel) for beta, sel in zip(beta_values, by_beta)}
+    return (results, series) if return_series else results
 
 
 def sweep_beta_structure_ensemble(beta, n_runs, ps_kwargs, init_kwargs, run_kwargs, start_fraction=0.5, k_max=None, rng_seeds=None,

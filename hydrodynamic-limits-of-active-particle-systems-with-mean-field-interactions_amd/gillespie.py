@@ -7,7 +7,9 @@ include/gillespie_structure.h); the anchor-capture study's cluster, lifetime and
 (`run_batched_exact_capture`, include/gillespie_capture.h); the ensemble density and field profiles of many runs
 (`run_batched_exact_profiles`, include/gillespie_profile.h) are summed over the runs on the device.  Systems that differ in
 the interaction range or in the blocking threshold of their particle number share ONE launch as a mixed batch
-(`run_batched_exact_mixed`, `run_batched_exact_statistics_mixed`, include/gillespie_mixed.h).
+(`run_batched_exact_mixed`, `run_batched_exact_statistics_mixed`, include/gillespie_mixed.h); the structure observables of such a batch come from sums the
+mixed launch takes and reduces over the window on the device (`run_batched_exact_structure_mixed`,
+include/gillespie_mixed_structure.h).
 
 Differences to the reference: randomness is Philox4x32-10 keyed by `seed` (the reference consumes a NumPy Generator), so
 trajectories agree in distribution, not draw for draw; `m_local_list[k]` is the field of the observed state (the
@@ -119,6 +121,8 @@ def _lib():
             lib.gilx_plan.argtypes = [C.POINTER(GilParams), C.POINTER(GilxVariants), C.c_int32, C.POINTER(GilxPlanInfo)]
             lib.gilx_run.restype = C.c_int
             lib.gilx_run.argtypes = [C.POINTER(GilParams), C.POINTER(GilxVariants)] + [C.c_void_p] * 14 + [C.POINTER(C.c_double)]
+        if hasattr(lib, "gilxs_run"):          # likewise: no mixed structure launches in a build from before them
+            capi.declare_mixed_structure(lib, C.POINTER(GilParams), C.POINTER(GilxVariants))
         lib._gil_ready = True
     return lib
 
@@ -310,11 +314,48 @@ def run_mixed_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffus
     return _run_batch_entry("gilx_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
 
 
+def plan_mixed_structure(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs, k_max, first_obs=0, variant_of_system=None,
+                         order=None, want_states=True, want_rows=True):
+    """gilxs_plan: what a mixed launch with the structure sums (`run_mixed_structure_raw`) would use -- threads per system, LDS of
+    a workgroup (with the sums' slots and, where it fits, the phase table), the longest table's length, systems per CU by LDS, the
+    row length, work and output bytes -- by host arithmetic; no device needed.  Refuses what the run would refuse on these
+    numbers.  Without rows and states the output bytes do not grow with n_obs * k_max."""
+    lib = _lib()
+    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
+    desc, keep = _mixed_descriptor(int(n_systems), int(K), sigma_grids, variant_of_system, order=order)
+    info = capi.GilxsPlanInfo()
+    rc = lib.gilxs_plan(C.byref(par), C.byref(desc), int(k_max), int(first_obs), int(bool(want_states)), int(bool(want_rows)), C.byref(info))
+    if rc != 0:
+        raise capi.ApsError(rc, lib.gilxs_last_error().decode())
+    return {k: int(getattr(info, k)) for k, _ in capi.GilxsPlanInfo._fields_}
+
+
+def run_mixed_structure_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs, T,
+                            seed=0, minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0,
+                            k_exit=0.0, anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1,
+                            front_lo=None, block_tables=None, device=0, flip_table=None, seeds=None, streams=None, order=None,
+                            n_cap=None, k_max=None, first_obs=0, want_rows=True):
+    """`run_mixed_raw` with the structure sums of `run_structure_raw` taken in the same launch, every system with its own table
+    and field mode, and reduced over the window of observations on the device (gilxs_run of
+    include/gillespie_mixed_structure.h).  The dictionary of `run_mixed_raw` plus
+      `head`      [systems][observations][4]: n, sum occ^2, sum m, sum m^2 of every recorded observation (row entries 0..3);
+      `window`    [systems][k_max][3]: per mode a0, sum d, sum d^2 over the recorded observations from `first_obs` on that had a
+                  live particle, d = a - a0, a = sqrt(re^2 + im^2) / n (observables.DeviceStructureWindow);
+      `n_window`, `n_empty` [systems]: observations accumulated, and window observations without a live particle;
+      `structure` [systems][observations][4 + 2 k_max] when `want_rows`, as `run_structure_raw` (None otherwise: no row is stored);
+      `bytes_back`: the bytes of the output arrays the call copied back.
+    One variant is the uniform batch.  `k_max=None`: all L modes (at most 4096)."""
+    k_max = min(int(L), 4096) if k_max is None else int(k_max)
+    kw = dict(locals())
+    mixed = {k: kw.pop(k) for k in ("sigma_grids", "variant_of_system", "block_tables", "seeds", "streams", "order")}
+    return _run_batch_entry("gilxs_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
+
+
 def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed,
                      minus_anchor, immobilize, suppress_flip, crowding, k_on, k_off, k_exit, anchor_mask, uniforms, max_events,
                      want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table, k_max=None, first_obs=0,
                      group_of_site=None, n_groups=0, c_bins=0, h_bins=0, h_dt=0.0, n_cap=None, n_bins=0, want_field=False,
-                     group_of_system=None, per_system=False, mixed=None):
+                     group_of_system=None, per_system=False, mixed=None, want_rows=True):
     """The batch entry points take the same arguments: gil_run_batch (systems in LDS), gilm_run (large systems), gils_run
     (either, with the structure sums: k_max, first_obs) and gilc_run (either, with the capture statistics: group_of_site,
     n_groups, c_bins, h_bins, h_dt, first_obs); gilp_run (either, with the ensemble profiles: n_bins, first_obs, want_field,
@@ -323,7 +364,7 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     lib = _lib()
     call = getattr(lib, entry)
     last_error = getattr(lib, {"gil_run_batch": "gil_last_error", "gilm_run": "gilm_last_error", "gils_run": "gils_last_error",
-                               "gilc_run": "gilc_last_error", "gilp_run": "gilp_last_error", "gilx_run": "gilx_last_error"}[entry])
+                               "gilc_run": "gilc_last_error", "gilp_run": "gilp_last_error", "gilx_run": "gilx_last_error", "gilxs_run": "gilxs_last_error"}[entry])
     S = len(states)
     betas = np.ascontiguousarray(np.broadcast_to(np.asarray(betas, dtype=np.float64), (S,)))
     ncap = max(1, max(len(st[0]) for st in states))
@@ -365,7 +406,7 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     ms = C.c_double()
     args = [_p(n0), _p(pos0), _p(sg0), _p(bd0), _p(uniforms), _p(pos_obs), _p(sg_obs), _p(fl_obs), _p(scal), _p(n_rec), _p(n_ev),
             _p(t_fin), _p(exits), _p(n_exit)]
-    rows = capture = sums = None
+    rows = capture = sums = head = None
     if entry == "gils_run":
         rows = np.zeros((S, M, 4 + 2 * max(int(k_max), 0)))
         rc = call(C.byref(par), int(k_max), int(first_obs), *args, _p(rows), C.byref(ms))
@@ -391,6 +432,16 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
         if desc.variant_of_system is None:
             raise ValueError("variant_of_system must have one entry per system")
         rc = call(C.byref(par), C.byref(desc), *args, C.byref(ms))
+    elif entry == "gilxs_run":
+        desc, keep = _mixed_descriptor(S, int(K), **mixed)
+        if desc.variant_of_system is None:
+            raise ValueError("variant_of_system must have one entry per system")
+        kk = max(int(k_max), 0)
+        rows = np.zeros((S, M, 4 + 2 * kk)) if want_rows else None
+        head, window = np.zeros((S, M, 4)), np.zeros((S, kk, 3))          # gilxs_run refuses k_max < 1
+        n_window, n_empty = np.zeros(S, np.int32), np.zeros(S, np.int32)
+        rc = call(C.byref(par), C.byref(desc), int(k_max), int(first_obs), *args, _p(rows), _p(head), _p(window), _p(n_window), _p(n_empty),
+                  C.byref(ms))
     else:
         rc = call(C.byref(par), *args, C.byref(ms))
     if rc != 0:
@@ -399,6 +450,10 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
                exits=exits, n_exits=n_exit, n0=n0, kernel_ms=ms.value)
     if rows is not None:
         out["structure"] = rows
+    if head is not None:
+        back = [pos_obs, sg_obs, fl_obs, scal, n_rec, n_ev, t_fin, exits, n_exit, rows, head, window, n_window, n_empty]
+        out.update(structure=rows, head=head, window=window, n_window=n_window, n_empty=n_empty,
+                   bytes_back=int(sum(x.nbytes for x in back if x is not None)))
     if capture is not None:
         out.update(capture=capture, life_hist=life_hist, life_sums=life_sums)
     if sums is not None:
@@ -561,9 +616,10 @@ def mixed_keys(systems, groups=None):
     return seeds, streams
 
 
-def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, order=None):
+def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, order=None, structure=None):
     """The one launch behind run_batched_exact_mixed and run_batched_exact_statistics_mixed: checks, initial states, variants,
-    keys, gilx_run.  Returns (raw outputs, times_obs)."""
+    keys, gilx_run.  `structure` = (k_max or None, start_fraction, want_rows, all_observations): the launch behind
+    run_batched_exact_structure_mixed instead, gilxs_run without states.  Returns (raw outputs, times_obs)."""
     from . import observables
     from .particle_system import _SHAPE_ATTRS
     first = systems[0]
@@ -592,16 +648,26 @@ def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, or
         kw = dict(want_states=False, x_wall=acc0.x_wall, ref_obs=acc0.start,
                   front_lo=np.array([acc0.front_range(s)[0] for s in range(first.L)], np.int32))
     sig, tabs, owner = mixed_variants([ps._sigma_grid for ps in systems], tables)
-    plan = plan_mixed(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems), n_cap=n_cap,
-                      n_obs=len(times_obs), variant_of_system=owner, want_states=not statistics)
+    run_fn = run_mixed_raw
+    if structure is not None:
+        k_max, start_fraction, want_rows, all_obs = structure
+        kk = first.L if k_max is None else min(int(k_max), first.L)
+        first_obs = 0 if all_obs else int(start_fraction * len(times_obs))
+        kw = dict(want_states=False, k_max=kk, first_obs=first_obs, want_rows=want_rows)
+        run_fn = run_mixed_structure_raw
+        plan = plan_mixed_structure(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems), n_cap=n_cap,
+                                    n_obs=len(times_obs), variant_of_system=owner, **kw)
+    else:
+        plan = plan_mixed(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems), n_cap=n_cap,
+                          n_obs=len(times_obs), variant_of_system=owner, want_states=not statistics)
     if plan["lds_bytes"] > GILX_LDS_LIMIT:
         raise ValueError(f"{who}: the launch needs {plan['lds_bytes']} bytes of LDS per system, over the limit of {GILX_LDS_LIMIT} bytes")
-    r = run_mixed_raw(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, variant_of_system=owner, block_tables=tabs,
-                      rate_diffusion=first.rate_diffusion, rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems],
-                      states=inits, times_obs=times_obs, T=T, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
-                      suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
-                      k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms, device=first.device,
-                      flip_table=first.flip_table(), seeds=seeds, streams=streams, order=order, **kw)
+    r = run_fn(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, variant_of_system=owner, block_tables=tabs,
+               rate_diffusion=first.rate_diffusion, rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems],
+               states=inits, times_obs=times_obs, T=T, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
+               suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
+               k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms, device=first.device,
+               flip_table=first.flip_table(), seeds=seeds, streams=streams, order=order, **kw)
     r["plan"] = plan
     return r, times_obs
 
@@ -626,6 +692,58 @@ def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None
     rows = _statistics_rows(systems, r, times_obs)
     systems[0].kernel_ms = r["kernel_ms"]
     return rows
+
+
+def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_max=None, groups=None, order=None,
+                                      reduce="device", return_series=False):
+    """`run_batched_exact_structure` for systems that may ALSO differ in `local_kernel_sigma` (and, like there, in beta, state and
+    particle number): one mixed launch that takes the structure sums (include/gillespie_mixed_structure.h).  The other attributes,
+    the anchor sites and the flip table must agree, as in run_batched_exact_mixed; `groups`, `order` as there (`mixed_keys`).
+    Returns one dict per system with the eight keys of observables.DeviceStructure.result.
+    `reduce="device"`: the time means and spreads come from the window sums the launch accumulates
+    (observables.DeviceStructureWindow): no row, nothing of size observations x modes, leaves the GPU.  `reduce="rows"`: the launch
+    returns the full rows and observables.DeviceStructure reduces them on the host (the cross-check route).
+    `return_series=True` adds `times_obs`, `var_series` [M] (from the head rows), `m_series` [M] = sum sigma / n (from the scalar
+    sums) and, with reduce="rows" (the sums are then taken at every observation), `fft_amp_series` [M][k_max]."""
+    from . import observables
+    if reduce not in ("device", "rows"):
+        raise ValueError("reduce must be 'device' or 'rows'")
+    rows_wanted = reduce == "rows"
+    r, times_obs = _mixed_launch("run_batched_exact_structure_mixed", systems, T, obs_dt, groups, False, None, order,
+                                 structure=(k_max, start_fraction, rows_wanted, rows_wanted and return_series))
+    first = systems[0]
+    M, L = len(times_obs), first.L
+    kk = L if k_max is None else min(int(k_max), L)
+    first_obs = 0 if (rows_wanted and return_series) else int(start_fraction * M)
+    out = []
+    for s, ps in enumerate(systems):
+        if int(r["n_recorded"][s]) < M:
+            raise RuntimeError("a system passed T before its last observation time (choose T beyond the last observation)")
+        win = observables.DeviceStructureWindow(r["head"][s], r["window"][s], r["n_window"][s], r["n_empty"][s], L, first.dx, start_fraction)
+        series = None
+        if rows_wanted:
+            acc = observables.DeviceStructure(M, L, first.dx, start_fraction, kk)
+            series = observables.DeviceStructure(M, L, first.dx, 0.0, kk) if return_series else None
+            for k in range(first_obs, M):
+                row = r["structure"][s, k]
+                acc.add(k, row[0], row[1], row[2], row[3], row[4:])
+                if series is not None:
+                    series.add(k, row[0], row[1], row[2], row[3], row[4:])
+            res = acc.result()
+        else:
+            res = win.result()
+        if return_series:
+            n, sp = r["scalars"][s, :, 0].astype(float), r["scalars"][s, :, 1].astype(float)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                m_series = np.where(n > 0, sp / n, np.nan)
+            res.update(times_obs=times_obs.copy(), var_series=win.var_series(), m_series=m_series)
+            if series is not None:
+                res["fft_amp_series"] = np.array(series.amp)
+        out.append(res)
+        ps.n_events = int(r["n_events"][s])
+    first.kernel_ms = r["kernel_ms"]
+    first.bytes_back = r["bytes_back"]
+    return out
 
 
 def run_batched_exact_structure(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_max=None, return_series=False):

@@ -248,6 +248,51 @@ class DeviceStructure:
                 "lowk_variance": float(np.mean(np.sum(amp[:, 1:cut] ** 2, axis=1)))}
 
 
+class DeviceStructureWindow:
+    """The eight observables of DeviceStructure from what a mixed structure launch reduces on the device
+    (include/gillespie_mixed_structure.h), without the rows: `head` [M][4] (n, sum c^2, sum m, sum m^2 of every observation),
+    `window` [k_max][3] (per mode a0, sum d, sum d^2 over the window, d = a - a0, a = |sum_x c_x exp(-2 pi i k x / L)| / n),
+    `n_window` observations accumulated and `n_empty` window observations without a live particle.
+
+    |fft(total)|_k = a_k / dx, so fft_mean = (a0 + sum d / M_w) / dx and, shifted sums being free of cancellation,
+    fft_std^2 = (sum d^2 - (sum d)^2 / M_w) / (M_w - 1) / dx^2; sum_t a^2 = sum d^2 + 2 a0 sum d + M_w a0^2 gives lowk_variance.
+    var_* and m_local_var come from the head rows exactly as DeviceStructure takes them from the rows.  With an empty
+    observation in the window DeviceStructure's amplitudes and var are NaN; so are they here."""
+
+    def __init__(self, head, window, n_window, n_empty, L, dx, start_fraction=0.5):
+        self.head, self.win = np.asarray(head, dtype=float), np.asarray(window, dtype=float)
+        self.M, self.L, self.dx = len(self.head), int(L), float(dx)
+        self.start = int(start_fraction * self.M)
+        self.n_window, self.n_empty = int(n_window), int(n_empty)
+
+    def var_series(self):
+        """var(total) of every observation (NaN where no particle is alive)."""
+        n, c2 = self.head[:, 0], self.head[:, 1]
+        nd = n * self.dx
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 0, (c2 / self.L - (n / self.L) ** 2) / (nd * nd), np.nan)
+
+    def result(self):
+        h = self.head[self.start:]
+        var = self.var_series()[self.start:]
+        Mw, dx = self.n_window, self.dx
+        a0, s1, s2 = self.win[:, 0], self.win[:, 1], self.win[:, 2]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            fft_mean = (a0 + s1 / Mw) / dx
+            fft_std = np.sqrt(np.maximum(s2 - s1 * s1 / Mw, 0.0) / (Mw - 1)) / dx
+            sum_a2 = (s2 + 2.0 * a0 * s1 + Mw * a0 * a0) / (dx * dx)
+        cut = min(25, len(a0))
+        lowk = float(np.sum(sum_a2[1:cut]) / Mw) if Mw else np.nan
+        if self.n_empty or Mw != len(h):           # an empty observation: DeviceStructure's NaNs
+            fft_mean, fft_std, lowk = np.full(len(a0), np.nan), np.full(len(a0), np.nan), np.nan
+        nm = self.L * len(h)
+        m1, m2 = sum(h[:, 2].tolist()), sum(h[:, 3].tolist())   # in observation order, as DeviceStructure.add
+        mean_m = m1 / nm
+        return {"var_mean": var.mean(), "var_std": var.std(ddof=1), "fft_mean": fft_mean, "fft_std": fft_std,
+                "dominant_k": int(np.argmax(fft_mean[1:]) + 1), "low_k_power": float(np.sum(fft_mean[1:cut])),
+                "m_local_var": float(m2 / nm - mean_m * mean_m), "lowk_variance": lowk}
+
+
 # ------------------------------------------------------------------------------------------------ anchor-capture study
 EXIT_POSITION_BINS = 50
 
