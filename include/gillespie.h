@@ -7,6 +7,25 @@
  * of independent systems, one persistent workgroup each, the whole system in LDS.  This is the shape of the
  * reference's sweep drivers (a serial `for beta: for run:` double loop, ..._sweep_beta.py:75-95, :895-897).
  * Plain C types, caller-allocated host buffers; 0 on success, negative on failure, gil_last_error() has the text.
+ *
+ * RANDOM NUMBERS.  Without `uniforms` every system draws from Philox4x32-10 (Salmon et al., Random123).  Event e = 0, 1, ... of
+ * a system (a 64-bit count) takes two blocks of four 32-bit words under the key (k0, k1) = (key & 0xFFFFFFFF, key >> 32):
+ *     x0..x3 = Philox(counter (e & 0xFFFFFFFF, e >> 32, stream, 0x47494C31), key)      0x47494C31 = "GIL1"
+ *     y0..y3 = Philox(counter (e & 0xFFFFFFFF, e >> 32, stream, 0x47494C32), key)      0x47494C32 = "GIL2"
+ * and forms the four numbers of the event (the columns of `uniforms`) by  u53(a, b) = ((a >> 5) * 2^26 + (b >> 6)) * 2^-53,
+ * a binary64 on the grid 2^-53 in [0, 1 - 2^-53]:
+ *     waiting time  u0 = u53(x0, x1)  (tau = -log1p(-u0) / R, finite for every u0; a table holds u0 itself)
+ *     particle      u1 = u53(x2, x3)
+ *     channel       u2 = u53(y0, y1)
+ *     left / right  u3 = u53(y2, y3)
+ * No word feeds two numbers.  Key and stream (counter word 2) per entry point:
+ *     gil_run_batch, and gils_run / gilc_run / gilp_run on the same kernel:   key = p->seed,                  stream = s
+ *     gil_run_large:                                                            key = p->seed,                  stream = 0
+ *     gilm_run, and gils_run / gilc_run / gilp_run on the large kernel:        key = (p->seed + s) mod 2^64,   stream = 0
+ *     gilx_run, gilxs_run:                                                      key = v->seed[s],               stream = v->stream[s]
+ * (s = the system's index in the batch).  The draws of 64, 256 or 1024 consecutive events are produced together, so a supplied
+ * table is read up to that many rows beyond the last event fired (rows past max_events read as 0 and are never used).
+ * oracle/philox_streams.py restates this layout on the CPU; tests/test_gpu_exact_loop_streams.py holds every entry point to it.
  */
 #ifndef GILLESPIE_H
 #define GILLESPIE_H
@@ -38,7 +57,7 @@ typedef struct gil_params {
     int32_t flip_n;             /* intervals of flip_table (0: none) */
     double sigma_grid, rate_diffusion, rate_active, k_on, k_off, k_exit;
     double T;                   /* the loop ends when t > T or after the last observation time (ref :511-538) */
-    uint64_t seed;              /* Philox key; counter = (event index, system index) */
+    uint64_t seed;              /* Philox key, both 32-bit halves used; counter = (event index lo, hi, stream, domain): RANDOM NUMBERS above */
     int64_t max_events;         /* safety bound per system (and number of rows of `uniforms` when supplied) */
     const double *beta;         /* [n_systems] */
     const uint8_t *anchor_mask; /* [L] or NULL */

@@ -7,8 +7,11 @@
  * workgroups, and the twelve scalar sums of the batch kernel are taken on the device at every observation.  No
  * workgroup waits on another: a batch with more systems than the device has compute units queues.
  *
- * Random numbers: system s uses the Philox key p->seed + s (mod 2^64) and the counters of the large-system entry point, so
- * system s of a batch is, bit for bit, the single large run with seed p->seed + s (and the same n_cap).
+ * Random numbers: system s uses the Philox key (p->seed + s) mod 2^64 -- the sum is taken in 64 bits, so it carries into the key's
+ * high word and wraps to 0 past 2^64 - 1 -- and the counters of the large-system entry point with stream 0 (counter word 2), so
+ * system s of a batch is, bit for bit, the single large run with seed p->seed + s (and the same n_cap).  Systems of one batch
+ * therefore differ in the KEY, not in the stream; two batches whose seeds are closer than their sizes share systems.  The
+ * counters, the two domain constants and the conversion to the four numbers of an event: include/gillespie.h, RANDOM NUMBERS.
  * All functions return 0 on success and a negative code on failure; gilm_last_error() gives the text.
  */
 #ifndef GILLESPIE_MANY_H

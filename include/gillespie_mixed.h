@@ -15,6 +15,12 @@
  * count, chunk = ceil(n0[s] / threads), where gil_run_batch groups by n_cap; the total rate can differ in its last bit between
  * the two when n0[s] < n_cap or the thread counts differ, and the times with it (1e-16 relative per event).
  *
+ * Random numbers: system s draws with the Philox key v->seed[s] (both 32-bit halves; NULL: p->seed for every system) and the
+ * stream v->stream[s] in counter word 2 (NULL: s), whichever workgroup takes it (`order` does not enter).  Two systems may share
+ * a stream number under different keys, or a key under different streams; the same (key, stream) pair twice gives the same
+ * numbers twice.  gilxs_run (include/gillespie_mixed_structure.h) draws the same way.  Counters, domain constants and the
+ * conversion to the four numbers of an event: include/gillespie.h, RANDOM NUMBERS.
+ *
  * Outputs are indexed by the SYSTEM, never by the workgroup, with the strides of gil_run_batch (n_cap per system).  A system's
  * loops run over its own n0[s] slots; the slots at and beyond n0[s] are zero in pos_obs, sigma_obs and flags_obs.
  * The large-system shape (gilm_run) takes no mixed batches.

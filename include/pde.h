@@ -6,6 +6,16 @@
  * systems (one workgroup each) that share every parameter except beta, the parameter the reference's sweep
  * drivers vary (IMEX_PDE_solver_run_sweep.py:26-40).  Plain C types, caller-allocated host buffers.
  * All functions return 0 on success and a negative code on failure; pde_last_error() gives the text.
+ *
+ * TRACER NOISE.  Without rand_u / rand_n, tracer i of system `sys` at step n (n = 0 .. nsteps) draws four 32-bit words
+ *     x0..x3 = Philox4x32-10(counter (n, i, sys, 0x7AC3), key (seed & 0xFFFFFFFF, seed >> 32))
+ * and forms   u = ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53            the flip decision, u < rate * dt   (rand_u[sys][n][i])
+ *             g = sqrt(-2 ln r1) * cos(2 pi r2),  r1 = (x2 + 1/2) * 2^-32,  r2 = (x3 + 1/2) * 2^-32   (rand_n[sys][n][i])
+ * -- the cosine branch of Box-Muller; r1 > 0, so g is finite (|g| < 6.8).  u and g share no word.  Every row n = 0 .. nsteps of
+ * the [nsteps + 1] axis is consumed: the tracers move once per recorded step, the last time after the final field step
+ * (ref :257-287 sits inside `for n in range(nsteps + 1)`), and a system consumes its own rows only.  The wide shape
+ * (include/pde_wide.h) and the sweep over kernel widths (include/pde_sweep.h) draw the same numbers.
+ * oracle/philox_streams.py restates this layout on the CPU; tests/test_gpu_pde_streams.py holds the three kernels to it.
  */
 #ifndef PDE_H
 #define PDE_H
@@ -39,7 +49,7 @@ typedef struct pde_params {
     int32_t convolution;        /* kernel_mode 1 on the wide shape (include/pde_wide.h): 0 direct sum, 1 spectral (include/pde_spectral.h); pde_solve_batch takes 0 only */
     int32_t reserved;
     double xlim, dt, gamma, lam, kernel_sigma;
-    uint64_t seed;              /* Philox key of the tracer noise when no random numbers are supplied */
+    uint64_t seed;              /* Philox key of the tracer noise when no random numbers are supplied (TRACER NOISE above) */
 } pde_params;
 
 const char *pde_last_error(void);

@@ -20,6 +20,7 @@
  * reference drivers' L = 1000 included.  A shape beyond that, or one whose fields would have to live in global memory
  * (L > ~2900: the ground of include/pde_wide.h), is refused with PDE_ERR_ARG and a text containing "eligible" by both
  * functions; there is no fall-back.
+ * Tracer noise: the counters, key, conversion and rows of include/pde.h (TRACER NOISE); `sys` is the system's index in the sweep.
  * All functions return 0 on success and a negative code on failure; pdek_last_error() gives the text.
  */
 #ifndef PDE_SWEEP_H

@@ -7,6 +7,7 @@
  * (the two sweeps of the implicit diffusion, the reach of the Gaussian kernel, every sum) is handed over at a kernel
  * boundary.  No workgroup waits on another.  Sums are combined from per-slab partials in a fixed order: a call repeated
  * gives the same bits, and a system's result does not depend on its place in a batch.
+ * Tracer noise: the counters, key, conversion and rows of include/pde.h (TRACER NOISE), whatever the number of slabs.
  * All functions return 0 on success and a negative code on failure; pdew_last_error() gives the text.
  */
 #ifndef PDE_WIDE_H

@@ -50,6 +50,28 @@ class TableRng:
         return v
 
 
+def oracle_event_loop(orc, pos0, sigma0, table, T, times, n_events):
+    """The reference's `while t < T` loop (PARTICLE_solver_CLASS.py:511-538) on the oracle, event by event, fed from `table`
+    through TableRng: (snaps, exits, t, ev) = the (pos, sigma, bound) recorded at every reached observation time, the exit log
+    (times, sites), the final time and the number of events fired (at most n_events)."""
+    orc.rng = TableRng(table)
+    L, N = orc.par.L, len(pos0)
+    pos, sigma, bound = pos0.copy(), sigma0.copy(), np.zeros(N, bool)
+    cp, cm = np.bincount(pos[sigma == 1], minlength=L), np.bincount(pos[sigma == -1], minlength=L)
+    snaps, exits, k, t, ev = [(pos.copy(), sigma.copy(), bound.copy())], ([], []), 1, 0.0, 0
+    while t < T and k < len(times) and ev < n_events:
+        field = orc.mean_field(cp, cm)
+        pos, sigma, bound, tau = orc.fire_event(pos, sigma, bound, field, cp, cm, t, exits)
+        ev += 1
+        t += tau
+        if t > T:
+            break
+        while k < len(times) and times[k] <= t:
+            snaps.append((pos.copy(), sigma.copy(), bound.copy()))
+            k += 1
+    return snaps, exits, t, ev
+
+
 CASES = [
     dict(tag="reflect_k1", L=200, N=90, site_capacity=1, local_kernel_sigma=0.02, rate_diffusion=0.5, rate_active=4.0, beta=1.1),
     dict(tag="periodic_k2", L=150, N=160, site_capacity=2, local_kernel_sigma=0.03, periodic=True, rate_diffusion=0.8, rate_active=3.0, beta=0.6),
@@ -75,22 +97,9 @@ def test_same_uniforms_same_trajectory(gil, case):
     orc = GillespieOracle(init="fixed", N=N, rng=init_rng, **kw)
     pos0, sigma0 = orc.init_particles()
     # ---- oracle, event by event, with the table
-    orc.rng = TableRng(table)
     L = kw["L"]
-    pos, sigma, bound = pos0.copy(), sigma0.copy(), np.zeros(N, bool)
-    cp, cm = np.bincount(pos[sigma == 1], minlength=L), np.bincount(pos[sigma == -1], minlength=L)
     times = np.arange(0.0, T, obs_dt)
-    snaps, exits, k, t, ev = [(pos.copy(), sigma.copy(), bound.copy())], ([], []), 1, 0.0, 0
-    while t < T and k < len(times) and ev < n_events:
-        field = orc.mean_field(cp, cm)
-        pos, sigma, bound, tau = orc.fire_event(pos, sigma, bound, field, cp, cm, t, exits)
-        ev += 1
-        t += tau
-        if t > T:
-            break
-        while k < len(times) and times[k] <= t:
-            snaps.append((pos.copy(), sigma.copy(), bound.copy()))
-            k += 1
+    snaps, exits, t, ev = oracle_event_loop(orc, pos0, sigma0, table, T, times, n_events)
     # ---- GPU, same table
     P = orc.par
     r = gil.run_raw(L=L, K=P.K, periodic=P.periodic, sigma_grid=P.sigma_grid if P.sigma_kernel > 0 else 0.0,
@@ -252,22 +261,9 @@ def test_large_system_kernel_same_uniforms_same_trajectory(gil, case):
     table = np.random.default_rng(zlib.crc32(tag.encode())).random((n_events, 4))
     orc = GillespieOracle(init="fixed", N=N, rng=np.random.default_rng(5), **kw)
     pos0, sigma0 = orc.init_particles()
-    orc.rng = TableRng(table)
     L = kw["L"]
-    pos, sigma, bound = pos0.copy(), sigma0.copy(), np.zeros(N, bool)
-    cp, cm = np.bincount(pos[sigma == 1], minlength=L), np.bincount(pos[sigma == -1], minlength=L)
     times = np.arange(0.0, T, obs_dt)
-    snaps, exits, k, t, ev = [(pos.copy(), sigma.copy(), bound.copy())], ([], []), 1, 0.0, 0
-    while t < T and k < len(times) and ev < n_events:
-        field = orc.mean_field(cp, cm)
-        pos, sigma, bound, tau = orc.fire_event(pos, sigma, bound, field, cp, cm, t, exits)
-        ev += 1
-        t += tau
-        if t > T:
-            break
-        while k < len(times) and times[k] <= t:
-            snaps.append((pos.copy(), sigma.copy(), bound.copy()))
-            k += 1
+    snaps, exits, t, ev = oracle_event_loop(orc, pos0, sigma0, table, T, times, n_events)
     P = orc.par
     r = gil.run_large_raw(L=L, K=P.K, periodic=P.periodic, sigma_grid=P.sigma_grid if P.sigma_kernel > 0 else 0.0,
                           rate_diffusion=P.rate_diffusion, rate_active=P.rate_active, beta=P.beta, state=(pos0, sigma0), times_obs=times,
