@@ -32,6 +32,7 @@
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiation only)
 #include "gillespie_capture.hpp"          // anchor capture and cluster statistics (capture instantiation only)
 #include "gillespie_profile.hpp"          // ensemble density and field profiles (profile instantiation only)
+#include "gillespie_resume.hpp"           // start and end state of a launch (resumable instantiation only)
 
 namespace {
 
@@ -98,6 +99,23 @@ __global__ __launch_bounds__(256) void big_field_init(const BigArgs a0) {
         for (int j = 0; j < a.n_init; ++j) {
             const double g = site_weight(a.m, a.table, a.tlen, x, a.pos0[j]);
             w += g; s += a.sigma0[j] > 0 ? g : -g;
+        }
+    a.W[x] = w; a.S[x] = s;
+}
+
+// The same from a checkpoint (resumable launch): pos0 holds every slot's site, sigma0 its spin or 0 for a slot that is not alive
+__global__ __launch_bounds__(256) void big_field_init_live(const BigArgs a0) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= a0.m.L) return;
+    BigArgs a = a0;
+    select_system(a, (size_t)blockIdx.y);
+    double w = 0.0, s = 0.0;
+    if (a.m.field_mode)
+        for (int j = 0; j < a.p.n_cap; ++j) {
+            const int sg = a.sigma0[j];
+            if (sg == 0) continue;
+            const double g = site_weight(a.m, a.table, a.tlen, x, a.pos0[j]);
+            w += g; s += sg > 0 ? g : -g;
         }
     a.W[x] = w; a.S[x] = s;
 }
@@ -202,6 +220,7 @@ __device__ inline void big_scalar_sums(const int *pos, const uint8_t *flg, int *
 struct GilsBigArgs : BigArgs { GilsArgs st; };              // arguments of the structure instantiation
 struct GilcBigArgs : GilsBigArgs { GilcArgs cp; };          // arguments of the capture instantiation
 struct GilpBigArgs : GilcBigArgs { GilpArgs pf; };          // arguments of the profile instantiation (the driver's one struct)
+struct GilrBigArgs : BigArgs { GilrArgs rs; };              // arguments of the resumable instantiation
 
 // ST = also reduce the structure sums at an observation (gillespie_structure.hpp): a compile-time property, so that the
 // kernel without it is the code it was before they existed.
@@ -209,8 +228,12 @@ struct GilpBigArgs : GilcBigArgs { GilpArgs pf; };          // arguments of the 
 // ctl[] in LDS, its bind times in global memory; the event loop holds no register for either.
 // PF = ensemble density and field profiles (gillespie_profile.hpp), likewise; not combined with ST or CP.  Its slots lie
 // behind ctl[] in LDS and are used at an observation only.
-template <bool ST, bool CP = false, bool PF = false>
-__global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<PF, GilpBigArgs, std::conditional_t<CP, GilcBigArgs, std::conditional_t<ST, GilsBigArgs, BigArgs>>> a0) {
+// RS = a resumable launch (gillespie_resume.hpp): the start state is a checkpoint (pos0 / sigma0 as big_field_init_live reads them,
+// n0 = n_cap: any slot may be alive; flags, origins, clock, event count and first row from a0.rs), likewise; combined with none
+// of the others.  The end state is the global scratch itself (pos, flg, ref), which the driver reads back.
+template <bool ST, bool CP = false, bool PF = false, bool RS = false>
+__global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<RS, GilrBigArgs, std::conditional_t<PF, GilpBigArgs, std::conditional_t<CP, GilcBigArgs, std::conditional_t<ST, GilsBigArgs, BigArgs>>>> a0) {
+    static_assert(!(RS && (ST || CP || PF)), "the resumable launch takes none of the other sums");
     static_assert(!(ST && CP), "the capture launch takes no structure sums");
     static_assert(!(PF && (ST || CP)), "the profile launch takes no structure sums and no capture statistics");
     extern __shared__ double lds[];
@@ -236,10 +259,15 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<PF
     __syncthreads();
     long long ls = 0, ln = 0;
     for (int i = t; i < N; i += BT) {
-        const bool live = i < a.n_init;
-        const int p = live ? a.pos0[i] : 0;
-        const uint8_t f = live ? (uint8_t)(F_ALIVE | (a.sigma0[i] > 0 ? F_PLUS : 0) | ((a.bound0 && a.bound0[i]) ? F_BOUND : 0)) : 0;
-        a.pos[i] = p; a.flg[i] = f; a.rate[i] = 0.0; a.ref[i] = -1;
+        bool live; int p, r0 = -1; uint8_t f;
+        if constexpr (RS) {                                    // the checkpoint's slots: departed ones stay dead, origins are kept
+            p = a.pos0[i]; f = a0.rs.flg[(size_t)blockIdx.x * N + i]; r0 = a0.rs.ref[(size_t)blockIdx.x * N + i]; live = (f & F_ALIVE) != 0;
+        } else {
+            live = i < a.n_init;
+            p = live ? a.pos0[i] : 0;
+            f = live ? (uint8_t)(F_ALIVE | (a.sigma0[i] > 0 ? F_PLUS : 0) | ((a.bound0 && a.bound0[i]) ? F_BOUND : 0)) : 0;
+        }
+        a.pos[i] = p; a.flg[i] = f; a.rate[i] = 0.0; a.ref[i] = r0;
         if (live) {
             a.slot[(size_t)p * K + atomicAdd(&a.occ[p], 1)] = i;
             if (f & F_PLUS) atomicAdd(&a.occp[p], 1);
@@ -258,7 +286,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<PF
         for (int w = 0; w < BW; ++w) { gsum_s += xl[w]; gsum_n += xl[BW + w]; }
         __syncthreads();
     }
-    for (int i = t; i < a.n_init; i += BT) a.rate[i] = big_rate(a, tab, i, gsum_s, gsum_n);
+    for (int i = t; i < a.n_init; i += BT) { if (RS && !(a.flg[i] & F_ALIVE)) continue; a.rate[i] = big_rate(a, tab, i, gsum_s, gsum_n); }
     __syncthreads();
     for (int j = wave; j < a.nblk; j += BW) {                  // block sums
         double v = 0.0;
@@ -270,6 +298,10 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<PF
     double tnow = 0.0, t_next = nobs > 1 ? a.times[1] : INFINITY;
     long long n_ev = 0, ev_base = 0;
     int k_obs = 0, n_exit = 0;
+    if constexpr (RS) {
+        tnow = a0.rs.t[blockIdx.x]; n_ev = a0.rs.n_ev[blockIdx.x]; k_obs = a0.rs.k_start[blockIdx.x];
+        ev_base = n_ev - BT;                                   // no draws held: the first iteration draws
+    }
 
     auto record = [&](int k) {                                 // observation k: state and scalar sums (ref :517-536)
         const size_t o = (size_t)k * N;
@@ -306,8 +338,15 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<PF
             }
         }
     };
-    record(0);
-    k_obs = 1;
+    if constexpr (RS) {
+        // a fresh start records row 0; a resumed one the observations the checkpoint's last event passed (in the uninterrupted
+        // run that event recorded them, with this state), unless that event passed T
+        while (k_obs < nobs && (a0.rs.fresh ? k_obs == 0 : (tnow <= a.p.T && a.times[k_obs] <= tnow))) { record(k_obs); ++k_obs; }
+        t_next = k_obs < nobs ? a.times[k_obs] : INFINITY;
+    } else {
+        record(0);
+        k_obs = 1;
+    }
     bool have_event = false, dirty_all = false;
     int ev_a = 0, ev_b = 0;
 #ifdef APS_STAMPS
@@ -622,7 +661,8 @@ int big_plan(const char *who, std::string &err, const gil_params *p, bool want_s
 int big_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
             const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
             int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
-            int k_max = 0, int first_obs = 0, double *structure_obs = nullptr, const GilcCall *cap = nullptr, const GilpCall *prof = nullptr) {
+            int k_max = 0, int first_obs = 0, double *structure_obs = nullptr, const GilcCall *cap = nullptr, const GilpCall *prof = nullptr,
+            GilrCall *rs = nullptr) {
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilm_plan_info info{};
     std::vector<double> table;
@@ -645,7 +685,17 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
         info.output_bytes = gilp_output_bytes(p, prof->n_groups, prof->n_bins, pos_obs || sigma_obs || flags_obs, prof->profile_obs != nullptr);
         if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
     }
-    for (int s = 0; s < S; ++s) {
+    // a resumable launch (rs: its start state, checked by gilr_prepare, which comes back as the end state) reads no n0 / pos0 /
+    // sigma0 / bound0: every slot's site, and its spin or 0 where it is not alive
+    std::vector<int32_t> n0_all;
+    std::vector<int8_t> spin_all;
+    if (rs) {
+        n0_all.assign((size_t)S, N);
+        spin_all.resize(rs->flg.size());
+        for (size_t q = 0; q < spin_all.size(); ++q) spin_all[q] = (rs->flg[q] & GILR_ALIVE) ? ((rs->flg[q] & GILR_PLUS) ? 1 : -1) : 0;
+        n0 = n0_all.data(); pos0 = rs->pos.data(); sigma0 = spin_all.data(); bound0 = nullptr;
+    }
+    for (int s = 0; s < S && !rs; ++s) {
         if (n0[s] < 0 || n0[s] > N) return bad("bad n_cap / n0 / n_obs / max_events");
         if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * N, sigma0 + (size_t)s * N)) return bad(why);
     }
@@ -662,7 +712,7 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
     a.p = *p; a.tlen = info.table_len; a.nblk = info.n_blocks; a.cb = (a.nblk + BT - 1) / BT;
     a.tab_in_lds = info.table_in_lds;
     a.m = gil_model(p);
-    const size_t SN = (size_t)S * N, SL = (size_t)S * L, SO = (size_t)S * p->n_obs, NIN = S == 1 ? (size_t)n0[0] : SN;
+    const size_t SN = (size_t)S * N, SL = (size_t)S * L, SO = (size_t)S * p->n_obs, NIN = S == 1 && !rs ? (size_t)n0[0] : SN;
     UP(table, table.data(), table.size()); UP(times, p->times_obs, (size_t)p->n_obs);
     UP(betas, p->beta, (size_t)S); UP(n0, n0, (size_t)S);
     UP(pos0, pos0, NIN); UP(sigma0, sigma0, NIN);
@@ -680,6 +730,7 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
     OUT(exits, exits, SN * 3); OUT(n_exits, n_exits, (size_t)S);
     const size_t lds = (size_t)info.lds_bytes;
     GilsArgs &sa = a.st;
+    GilrArgs ra{};
     if (structure_obs) {
         double *phase = nullptr;
         if (int rc = job.alloc(&sa.rows, SO * row, "structure_obs")) return rc;
@@ -702,14 +753,27 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
         WORK(pf.sums, GO * GILP_COLS * prof->n_bins); WORK(pf.members, GO);
         if (prof->profile_obs) WORK(pf.rows, SO * 3 * prof->n_bins);
         if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false, false, true>), lds)) return rc;
+    } else if (rs) {
+        ra.fresh = rs->fresh;
+        if (int rc = job.upload(&ra.ref, rs->ref.data(), SN, "checkpoint ref")) return rc;
+        if (int rc = job.upload(&ra.flg, rs->flg.data(), SN, "checkpoint flags")) return rc;
+        if (int rc = job.upload(&ra.k_start, rs->k_start.data(), (size_t)S, "checkpoint next_obs")) return rc;
+        if (int rc = job.upload(&ra.t, rs->t.data(), (size_t)S, "checkpoint t")) return rc;
+        if (int rc = job.upload(&ra.n_ev, reinterpret_cast<const long long *>(rs->n_ev.data()), (size_t)S, "checkpoint n_events")) return rc;
+        if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false, false, false, true>), lds)) return rc;
     } else if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false>), lds)) return rc;
     if (int rc = job.create_events()) return rc;
-    hipLaunchKernelGGL(big_field_init, dim3((unsigned)((L + 255) / 256), (unsigned)S), dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
+    if (rs) hipLaunchKernelGGL(big_field_init_live, dim3((unsigned)((L + 255) / 256), (unsigned)S), dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
+    else hipLaunchKernelGGL(big_field_init, dim3((unsigned)((L + 255) / 256), (unsigned)S), dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
     job.ev.start();
     if (structure_obs) hipLaunchKernelGGL(gil_big_kernel<true>, dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const GilsBigArgs &>(a));
     else if (cap) hipLaunchKernelGGL((gil_big_kernel<false, true>), dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const GilcBigArgs &>(a));
     else if (prof) hipLaunchKernelGGL((gil_big_kernel<false, false, true>), dim3((unsigned)S), dim3(BT), lds, nullptr, a);
-    else hipLaunchKernelGGL(gil_big_kernel<false>, dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const BigArgs &>(a));
+    else if (rs) {
+        GilrBigArgs b{};
+        static_cast<BigArgs &>(b) = static_cast<const BigArgs &>(a); b.rs = ra;
+        hipLaunchKernelGGL((gil_big_kernel<false, false, false, true>), dim3((unsigned)S), dim3(BT), lds, nullptr, b);
+    } else hipLaunchKernelGGL(gil_big_kernel<false>, dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const BigArgs &>(a));
     job.ev.stop();
     if (int rc = job.finish(hipGetLastError(), "gil_big_kernel", kernel_ms)) return rc;
     DOWN(pos_obs, pos_obs, SO * N * 4); DOWN(sigma_obs, sigma_obs, SO * N); DOWN(flags_obs, flags_obs, SO * N);
@@ -717,6 +781,11 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
     DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8); DOWN(t_final, t_final, (size_t)S * 8);
     DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
     if (structure_obs) if (int rc = job.download(structure_obs, sa.rows, SO * row * 8, "structure_obs")) return rc;
+    if (rs) {
+        if (int rc = job.download(rs->pos.data(), a.pos, SN * 4, "checkpoint pos")) return rc;
+        if (int rc = job.download(rs->ref.data(), a.ref, SN * 4, "checkpoint ref")) return rc;
+        if (int rc = job.download(rs->flg.data(), a.flg, SN, "checkpoint flags")) return rc;
+    }
     if (cap) {
         if (int rc = job.download(cap->capture_obs, a.cp.rows, SO * crow * 8, "capture_obs")) return rc;
         if (int rc = job.download(cap->life_hist, a.cp.life_hist, (size_t)S * 2 * cap->h_bins * 8, "life_hist")) return rc;
@@ -767,6 +836,13 @@ int gilc_large_run(const char *who, std::string &err, const gil_params *p, const
                    double *kernel_ms, const GilcCall *cap) {
     return big_run(who, err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
                    t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, cap);
+}
+
+int gilr_large_run(const char *who, std::string &err, const gil_params *p, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs,
+                   uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits,
+                   int32_t *n_exits, double *kernel_ms, GilrCall *rs) {
+    return big_run(who, err, p, nullptr, nullptr, nullptr, nullptr, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
+                   t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, nullptr, nullptr, rs);
 }
 
 int gilp_large_plan(const char *who, std::string &err, const gil_params *p, int32_t prof_lds, int32_t *lds_bytes, int64_t *work_bytes) {

@@ -29,6 +29,7 @@
 #include "gillespie_profile.h"
 #include "gillespie_mixed.h"
 #include "gillespie_mixed_structure.h"
+#include "gillespie_resume.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"           // model, initial-state check, the driver of the one-shot entry points
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiations only)
@@ -36,6 +37,7 @@
 #include "gillespie_profile.hpp"          // ensemble density and field profiles (profile instantiations only)
 #include "gillespie_mixed.hpp"            // a variant per system: table, blocking table, slots, Philox key (mixed instantiations only)
 #include "gillespie_window.hpp"           // the window sums of the structure rows (mixed structure instantiations only)
+#include "gillespie_resume.hpp"           // start and end state of a launch (resumable instantiations only)
 
 namespace {
 
@@ -74,6 +76,7 @@ struct GilcBatchArgs : GilsBatchArgs { GilcArgs cp; };      // arguments of the 
 struct GilpBatchArgs : GilcBatchArgs { GilpArgs pf; };      // arguments of the profile instantiations (the driver's one struct)
 struct GilxBatchArgs : GilArgs { GilxArgs mx; };            // arguments of the mixed instantiations (gilx_run's driver)
 struct GilxsBatchArgs : GilxBatchArgs { GilsArgs st; GilwArgs wn; };   // arguments of the mixed structure instantiations (gilxs_run's)
+struct GilrBatchArgs : GilArgs { GilrArgs rs; };            // arguments of the resumable instantiations (gilr_run's)
 
 // the structure sums' slots: behind the loop's own LDS (which ends with the plus-occupancy bytes), at the next multiple of 8
 __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L) {
@@ -90,8 +93,11 @@ __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L)
 // blocking table, the slot count and the Philox key are the system's own; likewise; not combined with ST, CP or PF.  In such a
 // launch a.tlen is the longest table's length (the LDS layout is the launch's).  MX with ST: the structure sums of a mixed launch,
 // with the window reduction of gillespie_window.hpp; the rows themselves are optional there.
-template <int NT, bool ST, bool CP = false, bool PF = false, bool MX = false>
-__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, std::conditional_t<ST, GilxsBatchArgs, GilxBatchArgs>, std::conditional_t<PF, GilpBatchArgs, std::conditional_t<CP, GilcBatchArgs, std::conditional_t<ST, GilsBatchArgs, GilArgs>>>> a) {
+// RS = a resumable launch (gillespie_resume.hpp): the start state is a checkpoint (slots may be dead, the clock, the event count
+// and the next observation are the checkpoint's) and the end state is written out; likewise; combined with none of the others.
+template <int NT, bool ST, bool CP = false, bool PF = false, bool MX = false, bool RS = false>
+__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<RS, GilrBatchArgs, std::conditional_t<MX, std::conditional_t<ST, GilxsBatchArgs, GilxBatchArgs>, std::conditional_t<PF, GilpBatchArgs, std::conditional_t<CP, GilcBatchArgs, std::conditional_t<ST, GilsBatchArgs, GilArgs>>>>> a) {
+    static_assert(!(RS && (ST || CP || PF || MX)), "the resumable launches take none of the other sums");
     static_assert(!(ST && CP), "the capture launches take no structure sums");
     static_assert(!(PF && (ST || CP)), "the profile launches take no structure sums and no capture statistics");
     static_assert(!(MX && (CP || PF)), "the mixed launches take no capture statistics and no profiles");
@@ -117,11 +123,16 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, st
     uint8_t *occ = flg + ((ncap + 15) & ~15);                 // [L] particles per site
     uint8_t *occp = occ + ((L + 15) & ~15);                   // [L] plus particles per site (blocking table)
     const double beta = a.beta[sys];
-    const int n_init = a.n0[sys];
+    const int n_init = RS ? ncap : a.n0[sys];                  // RS: any slot may be alive, the loops below ask its flags
     // ---- load the system
     for (int i = t; i <= GX_TLEN; i += NT) tab[i] = (MX ? vw.table : a.table)[i];
     for (int x = t; x < L; x += NT) { occ[x] = 0; occp[x] = 0; }
     for (int i = t; i < GX_SLOTS; i += NT) {
+        if constexpr (RS) {                                    // the checkpoint's slots: departed ones stay dead, origins are kept
+            pos[i] = a.rs.pos[(size_t)sys * ncap + i]; flg[i] = a.rs.flg[(size_t)sys * ncap + i]; ref[i] = a.rs.ref[(size_t)sys * ncap + i];
+            rate[i] = 0.0;
+            continue;
+        }
         const bool live = i < n_init;
         pos[i] = live ? a.pos0[(size_t)sys * ncap + i] : 0;
         flg[i] = live ? (uint8_t)(F_ALIVE | (a.sigma0[(size_t)sys * ncap + i] > 0 ? F_PLUS : 0) |
@@ -140,12 +151,13 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, st
         gilc_init<NT>(cs, a.cp, cs.tbind, ncap);
     }
     __syncthreads();
-    if (t == 0) for (int i = 0; i < n_init; ++i) { occ[pos[i]]++; if (flg[i] & F_PLUS) occp[pos[i]]++; }
+    if (t == 0) for (int i = 0; i < n_init; ++i) { if (RS && !(flg[i] & F_ALIVE)) continue; occ[pos[i]]++; if (flg[i] & F_PLUS) occp[pos[i]]++; }
     // field from scratch: W(x) = sum_j w(x, p_j), S(x) = sum_j sigma_j w(x, p_j)
     for (int x = t; x < L; x += NT) {
         double w = 0.0, s = 0.0;
         if (GX_FIELD)
             for (int j = 0; j < n_init; ++j) {
+                if (RS && !(flg[j] & F_ALIVE)) continue;
                 const double g = site_weight(M, tab, GX_TLEN, x, pos[j]);
                 w += g; s += (flg[j] & F_PLUS) ? g : -g;
             }
@@ -155,7 +167,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, st
     long long gsum_s = 0, gsum_n = 0;                          // global-mean mode: sum of spins, particles alive
     if (!GX_FIELD) {
         long long ls = 0, ln = 0;
-        for (int i = t; i < n_init; i += NT) { ls += (flg[i] & F_PLUS) ? 1 : -1; ln += 1; }
+        for (int i = t; i < n_init; i += NT) { if (RS && !(flg[i] & F_ALIVE)) continue; ls += (flg[i] & F_PLUS) ? 1 : -1; ln += 1; }
         gsum_s = wg_sum_ll<NT>(ls, redl); gsum_n = wg_sum_ll<NT>(ln, redl);
     }
     double tnow = 0.0;
@@ -246,16 +258,25 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, st
         }
     };
 
-    record(0);                                                 // ref :489-508
-    k_obs = 1;
-    double t_next = nobs > 1 ? a.times[1] : INFINITY;          // next observation time (kept in a register: no load per event)
+    double t_next;                                             // next observation time (kept in a register: no load per event)
+    if constexpr (RS) {
+        // a fresh start records row 0; a resumed one the observations the checkpoint's last event passed (in the uninterrupted
+        // run that event recorded them, with this state), unless that event passed T
+        tnow = a.rs.t[sys]; n_ev = a.rs.n_ev[sys]; k_obs = a.rs.k_start[sys];
+        while (k_obs < nobs && (a.rs.fresh ? k_obs == 0 : (tnow <= a.p.T && a.times[k_obs] <= tnow))) { record(k_obs); ++k_obs; }
+        t_next = k_obs < nobs ? a.times[k_obs] : INFINITY;
+    } else {
+        record(0);                                             // ref :489-508
+        k_obs = 1;
+        t_next = nobs > 1 ? a.times[1] : INFINITY;
+    }
 #ifdef APS_STAMPS
     unsigned long long st[5] = {0, 0, 0, 0, 0}, s0 = __builtin_amdgcn_s_memtime();
 #define GSTAMP(k) { const unsigned long long s1_ = __builtin_amdgcn_s_memtime(); st[k] += s1_ - s0; s0 = s1_; }
 #else
 #define GSTAMP(k)
 #endif
-    long long ev_base = 0;                                     // first event of the block of draws held in LDS
+    long long ev_base = RS ? n_ev - NT : 0;                    // first event of the block of draws held in LDS (RS: none held, the first iteration draws)
     bool dirty_all = true;                                     // first event: every rate is evaluated
     int dirty_a = 0, dirty_b = 0;
     const int dirty_reach = (GX_FIELD ? GX_TLEN - 1 : 0) + 1;
@@ -476,6 +497,12 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<MX, st
     if (t == 0 && sys == 0 && a.exits) for (int k = 0; k < 5; ++k) a.exits[k] = (double)st[k];   // diagnostic build only
 #endif
     if constexpr (CP) gilc_flush<NT>(gilc_lds(gils_slots(lds, occp, L), a.cp, NT / 64), a.cp, (size_t)sys);
+    if constexpr (RS) {                                        // the end state: a resumed launch continues this trajectory
+        __syncthreads();
+        for (int i = t; i < ncap; i += NT) {
+            a.rs.pos_out[(size_t)sys * ncap + i] = pos[i]; a.rs.flg_out[(size_t)sys * ncap + i] = flg[i]; a.rs.ref_out[(size_t)sys * ncap + i] = ref[i];
+        }
+    }
     if (t == 0) {
         if (a.n_recorded) a.n_recorded[sys] = k_obs;
         if (a.n_events) a.n_events[sys] = n_ev;
@@ -521,17 +548,19 @@ int64_t gils_output_bytes(const gil_params *p, int k_max, bool states, bool scal
 }
 
 // The one host driver of the batch kernel.  structure_obs: gils_run's rows (k_max modes, from observation first_obs on),
-// nullptr for gil_run_batch; cap: gilc_run's call; prof: gilp_run's.  The callers have checked their required pointers.
+// nullptr for gil_run_batch; cap: gilc_run's call; prof: gilp_run's; rs: gilr_run's start state (checked by gilr_prepare; n0, pos0,
+// sigma0 and bound0 are not read then), which comes back as the end state.  The callers have checked their required pointers.
 int batch_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
               const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
               int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
-              int k_max, int first_obs, double *structure_obs, const GilcCall *cap = nullptr, const GilpCall *prof = nullptr) {
+              int k_max, int first_obs, double *structure_obs, const GilcCall *cap = nullptr, const GilpCall *prof = nullptr,
+              GilrCall *rs = nullptr) {
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     if (p->L < 2 || p->L > GIL_MAX_L) return bad("L must be in [2, GIL_MAX_L]");
     if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
     if (p->n_systems < 1 || p->n_cap < 1 || p->n_cap > GIL_MAX_N || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
     const int S = p->n_systems, L = p->L, ncap = p->n_cap;
-    for (int s = 0; s < S; ++s) {
+    for (int s = 0; s < S && !rs; ++s) {
         if (n0[s] < 0 || n0[s] > ncap) return bad("n0 outside [0, n_cap]");
         if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * ncap, sigma0 + (size_t)s * ncap)) return bad(why);
     }
@@ -558,8 +587,8 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
     a.m = gil_model(p);
     const size_t SN = (size_t)S * ncap, SO = (size_t)S * p->n_obs;
     UP(beta, p->beta, (size_t)S); UP(table, table.data(), table.size()); UP(times, p->times_obs, (size_t)p->n_obs);
-    UP(n0, n0, (size_t)S); UP(pos0, pos0, SN); UP(sigma0, sigma0, SN);
-    if (bound0) UP(bound0, bound0, SN);
+    if (!rs) { UP(n0, n0, (size_t)S); UP(pos0, pos0, SN); UP(sigma0, sigma0, SN); }
+    if (!rs && bound0) UP(bound0, bound0, SN);
     if (p->anchor_mask) UP(anchor, p->anchor_mask, (size_t)L);
     if (p->front_lo) UP(front_lo, p->front_lo, (size_t)L);
     if (p->block_table) UP(block_table, p->block_table, (size_t)(p->K + 1) * (p->K + 1));
@@ -572,6 +601,7 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
     if (lds > 160 * 1024) return bad("system does not fit the 160 KB of LDS");
     const size_t row = 4 + 2 * (size_t)k_max;
     GilsArgs &sa = a.st;
+    GilrArgs ra{};
     if (structure_obs) {
         double *phase = nullptr;
         if (int rc = job.alloc(&sa.rows, SO * row, "structure_obs")) return rc;
@@ -595,6 +625,18 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
         WORK(pf.sums, GO * GILP_COLS * prof->n_bins); WORK(pf.members, GO);
         if (prof->profile_obs) WORK(pf.rows, SO * 3 * prof->n_bins);
         if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, false, true>) : reinterpret_cast<const void *>(&gil_kernel<256, false, false, true>), lds)) return rc;
+    } else if (rs) {
+        ra.fresh = rs->fresh;
+        if (int rc = job.upload(&ra.pos, rs->pos.data(), SN, "checkpoint pos")) return rc;
+        if (int rc = job.upload(&ra.ref, rs->ref.data(), SN, "checkpoint ref")) return rc;
+        if (int rc = job.upload(&ra.flg, rs->flg.data(), SN, "checkpoint flags")) return rc;
+        if (int rc = job.upload(&ra.k_start, rs->k_start.data(), (size_t)S, "checkpoint next_obs")) return rc;
+        if (int rc = job.upload(&ra.t, rs->t.data(), (size_t)S, "checkpoint t")) return rc;
+        if (int rc = job.upload(&ra.n_ev, reinterpret_cast<const long long *>(rs->n_ev.data()), (size_t)S, "checkpoint n_events")) return rc;
+        if (int rc = job.alloc(&ra.pos_out, SN, "checkpoint pos")) return rc;
+        if (int rc = job.alloc(&ra.ref_out, SN, "checkpoint ref")) return rc;
+        if (int rc = job.alloc(&ra.flg_out, SN, "checkpoint flags")) return rc;
+        if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, false, false, false, true>) : reinterpret_cast<const void *>(&gil_kernel<256, false, false, false, false, true>), lds)) return rc;
     } else if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false>) : reinterpret_cast<const void *>(&gil_kernel<256, false>), lds)) return rc;
     if (int rc = job.create_events()) return rc;
     job.ev.start();
@@ -607,6 +649,11 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
     } else if (prof) {
         if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
         else hipLaunchKernelGGL((gil_kernel<256, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
+    } else if (rs) {
+        GilrBatchArgs b{};
+        static_cast<GilArgs &>(b) = static_cast<const GilArgs &>(a); b.rs = ra;
+        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, false, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, b);
+        else hipLaunchKernelGGL((gil_kernel<256, false, false, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, b);
     } else if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilArgs &>(a));
     else hipLaunchKernelGGL((gil_kernel<256, false>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilArgs &>(a));
     job.ev.stop();
@@ -615,6 +662,11 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
     DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8); DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8);
     DOWN(t_final, t_final, (size_t)S * 8); DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
     if (structure_obs) if (int rc = job.download(structure_obs, sa.rows, SO * row * 8, "structure_obs")) return rc;
+    if (rs) {
+        if (int rc = job.download(rs->pos.data(), ra.pos_out, SN * 4, "checkpoint pos")) return rc;
+        if (int rc = job.download(rs->ref.data(), ra.ref_out, SN * 4, "checkpoint ref")) return rc;
+        if (int rc = job.download(rs->flg.data(), ra.flg_out, SN, "checkpoint flags")) return rc;
+    }
     if (cap) {
         if (int rc = job.download(cap->capture_obs, a.cp.rows, SO * (size_t)(GILC_NFIXED + cap->n_groups + cap->c_bins) * 8, "capture_obs")) return rc;
         if (int rc = job.download(cap->life_hist, a.cp.life_hist, (size_t)S * 2 * cap->h_bins * 8, "life_hist")) return rc;
@@ -625,6 +677,42 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
         if (int rc = job.download(prof->ensemble_sums, a.pf.sums, GO * GILP_COLS * prof->n_bins * 8, "ensemble_sums")) return rc;
         if (int rc = job.download(prof->members, a.pf.members, GO * 4, "members")) return rc;
         if (int rc = job.download(prof->profile_obs, a.pf.rows, SO * 3 * prof->n_bins * 4, "profile_obs")) return rc;
+    }
+    return GIL_OK;
+}
+
+std::string g_gilr_err;
+
+// gilr_run and gilrm_run: the start state is checked and laid out here, the launch is the shape's own driver
+int gilr_drive(bool large, const char *who, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
+               const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+               int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
+               int32_t obs_first, const gil_checkpoint *from, gil_checkpoint *to) {
+    auto bad = [&](const std::string &m) { g_gilr_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    if (!p || !p->beta || !p->times_obs || (!from && (!n0 || !pos0 || !sigma0))) return bad("null argument");
+    if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0 || p->L < 2 || p->K < 1) return bad("bad n_systems / n_cap / n_obs / max_events / L / K");
+    if (large && p->n_systems > GILM_MAX_SYSTEMS) return bad("n_systems must be in [1, GILM_MAX_SYSTEMS]");
+    const size_t S = (size_t)p->n_systems, N = (size_t)p->n_cap;
+    for (size_t s = 0; s < S && !from; ++s) {
+        if (n0[s] < 0 || n0[s] > p->n_cap) return bad("n0 outside [0, n_cap]");
+        if (const char *why = gil_check_state(p, n0[s], pos0 + s * N, sigma0 + s * N)) return bad(why);
+    }
+    GilrCall call;
+    const std::string why = gilr_prepare(p, n0, pos0, sigma0, bound0, obs_first, from, to, call);
+    if (!why.empty()) return bad(why);
+    std::vector<int32_t> nrec(S, 0);                           // the checkpoint needs these three whether or not the caller wants them
+    std::vector<int64_t> nev(S, 0);
+    std::vector<double> tfin(S, 0.0);
+    const int rc = large ? gilr_large_run(who, g_gilr_err, p, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, nrec.data(), nev.data(),
+                                          tfin.data(), exits, n_exits, kernel_ms, &call)
+                         : batch_run(who, g_gilr_err, p, nullptr, nullptr, nullptr, nullptr, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
+                                     nrec.data(), nev.data(), tfin.data(), exits, n_exits, kernel_ms, 0, 0, nullptr, nullptr, nullptr, &call);
+    if (rc) return rc;
+    gilr_finish(p, call, nrec.data(), nev.data(), tfin.data());
+    for (size_t s = 0; s < S; ++s) {
+        if (n_recorded) n_recorded[s] = nrec[s];
+        if (n_events) n_events[s] = nev[s];
+        if (t_final) t_final[s] = tfin[s];
     }
     return GIL_OK;
 }
@@ -1036,6 +1124,24 @@ int gil_run_batch(const gil_params *p, const int32_t *n0, const int32_t *pos0, c
     if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs) { g_gil_err = "gil_run_batch: null argument"; return GIL_ERR_ARG; }
     return batch_run("gil_run_batch", g_gil_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
                      n_recorded, n_events, t_final, exits, n_exits, kernel_ms, 0, 0, nullptr);
+}
+
+const char *gilr_last_error(void) { return g_gilr_err.c_str(); }
+
+int gilr_run(const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
+             const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+             int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
+             int32_t obs_first, const gil_checkpoint *from, gil_checkpoint *to) {
+    return gilr_drive(false, "gilr_run", p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded,
+                      n_events, t_final, exits, n_exits, kernel_ms, obs_first, from, to);
+}
+
+int gilrm_run(const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
+              const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+              int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
+              int32_t obs_first, const gil_checkpoint *from, gil_checkpoint *to) {
+    return gilr_drive(true, "gilrm_run", p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded,
+                      n_events, t_final, exits, n_exits, kernel_ms, obs_first, from, to);
 }
 
 const char *gils_last_error(void) { return g_gils_err.c_str(); }

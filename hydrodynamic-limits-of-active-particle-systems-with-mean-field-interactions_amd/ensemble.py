@@ -22,7 +22,7 @@ from .particle_system import ParticleSystem, run_batched, run_batched_statistics
 
 
 def sweep_over_betas(beta_values, n_runs_per_beta=10, ps_kwargs=None, init_kwargs=None, run_kwargs=None,
-                     rng_seeds=None, keep_outputs=False, on_device=False, dynamics=None):
+                     rng_seeds=None, keep_outputs=False, on_device=False, dynamics=None, obs_per_launch=None):
     """Returns a dict with the keys the reference saves (`beta_values, means, stds, ses, D_means, D_ses, m_means,
     m_stds, m_ses, rho_means, rho_ses, block_means, block_ses`, ..._sweep_beta.py:952-968) plus `raw_by_beta`.
     `rng_seeds[b][r]` seeds the initial condition of run r at beta b (None: unseeded, like the reference).
@@ -30,10 +30,15 @@ def sweep_over_betas(beta_values, n_runs_per_beta=10, ps_kwargs=None, init_kwarg
     (run_batched_statistics; needs k_exit = 0) instead of from the M x L arrays of `run()`; `run_kwargs` may then
     only hold T and obs_dt.  `dynamics="exact"` runs the reference's event-by-event dynamics resident on the GPU
     (gillespie.run_batched_exact / run_batched_exact_statistics), `"sync"` the fixed-dt scheme; the default follows
-    ParticleSystem's: exact unless `ps_kwargs` asks for the stepper (`dt` or `mode="sync"`)."""
+    ParticleSystem's: exact unless `ps_kwargs` asks for the stepper (`dt` or `mode="sync"`).  `obs_per_launch=n` (exact
+    dynamics only): the runs as a chain of launches of at most n observations each instead of one persistent launch
+    (gillespie.run_batched_exact: the same numbers, bit for bit)."""
     ps_kwargs, init_kwargs, run_kwargs = dict(ps_kwargs or {}), dict(init_kwargs or {}), dict(run_kwargs or {})
     if dynamics is None:
         dynamics = "sync" if (ps_kwargs.get("dt") is not None or ps_kwargs.get("mode") == "sync") else "exact"
+    if obs_per_launch is not None and dynamics != "exact":
+        raise ValueError("obs_per_launch needs the exact dynamics; the fixed-dt stepper has no checkpointed launch")
+    chain = {} if obs_per_launch is None else {"obs_per_launch": obs_per_launch}
     systems, owner = [], []
     for bi, beta in enumerate(beta_values):
         for r in range(n_runs_per_beta):
@@ -49,12 +54,12 @@ def sweep_over_betas(beta_values, n_runs_per_beta=10, ps_kwargs=None, init_kwarg
         slim = {k: v for k, v in run_kwargs.items() if k in ("T", "obs_dt")}
         if dynamics == "exact":
             from .gillespie import run_batched_exact_statistics
-            rows = run_batched_exact_statistics(systems, **slim)
+            rows = run_batched_exact_statistics(systems, **slim, **chain)
         else:
             rows = run_batched_statistics(systems, **slim)
     elif dynamics == "exact":
         from .gillespie import run_batched_exact
-        outs = run_batched_exact(systems, want_m_local=False, **run_kwargs)
+        outs = run_batched_exact(systems, want_m_local=False, **run_kwargs, **chain)
         rows = [observables.run_observables(out, ps.L, ps.dx) for ps, out in zip(systems, outs)]
     else:
         outs = run_batched(systems, **run_kwargs)

@@ -17,6 +17,7 @@ reference stores the field from before the last event).  There is no CPU fallbac
 from __future__ import annotations
 
 import ctypes as C
+import json
 
 import numpy as np
 
@@ -74,6 +75,13 @@ class GilxPlanInfo(C.Structure):
                 ("table_doubles", C.c_int64), ("output_bytes", C.c_int64)]
 
 
+class GilCheckpoint(C.Structure):
+    """struct gil_checkpoint of include/gillespie_resume.h, field for field."""
+    _fields_ = [("pos", C.c_void_p), ("flags", C.c_void_p), ("ref", C.c_void_p), ("t", C.c_void_p), ("n_events", C.c_void_p),
+                ("next_obs", C.c_void_p)]
+
+
+GILR_PLUS, GILR_BOUND, GILR_ALIVE = 1, 2, 4     # bits of a checkpoint's flags
 GILX_MAX_VARIANTS = 4096
 GILX_LDS_LIMIT = 160 * 1024     # bytes of LDS a workgroup can have: what a mixed launch must fit
 GILP_NCOLS, GILP_MAX_BINS, GILP_MAX_GROUPS = 7, 1024, 4096
@@ -121,6 +129,12 @@ def _lib():
             lib.gilx_plan.argtypes = [C.POINTER(GilParams), C.POINTER(GilxVariants), C.c_int32, C.POINTER(GilxPlanInfo)]
             lib.gilx_run.restype = C.c_int
             lib.gilx_run.argtypes = [C.POINTER(GilParams), C.POINTER(GilxVariants)] + [C.c_void_p] * 14 + [C.POINTER(C.c_double)]
+        if hasattr(lib, "gilr_run"):           # likewise: no resumable launches in a build from before them
+            lib.gilr_last_error.restype, lib.gilr_last_error.argtypes = C.c_char_p, []
+            for name in ("gilr_run", "gilrm_run"):
+                getattr(lib, name).restype = C.c_int
+                getattr(lib, name).argtypes = ([C.POINTER(GilParams)] + [C.c_void_p] * 14 + [C.POINTER(C.c_double), C.c_int32,
+                                                                                           C.POINTER(GilCheckpoint), C.POINTER(GilCheckpoint)])
         if hasattr(lib, "gilxs_run"):          # likewise: no mixed structure launches in a build from before them
             capi.declare_mixed_structure(lib, C.POINTER(GilParams), C.POINTER(GilxVariants))
         lib._gil_ready = True
@@ -148,6 +162,24 @@ def run_many_large_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_activ
     with Philox key seed + s: it is the `run_large_raw` run with that seed.  `n_cap`: particle slots per system, where more
     than the largest initial state are wanted (the spare ones stay empty)."""
     return _run_batch_entry("gilm_run", **locals())
+
+
+def run_resumable_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
+                      minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
+                      anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
+                      block_table=None, device=0, flip_table=None, n_cap=None, large=False, obs_first=0, checkpoint=None):
+    """`run_raw` (large=True: `run_many_large_raw`) as one SEGMENT of a run (gilr_run / gilrm_run of include/gillespie_resume.h).
+    `times_obs` holds the absolute times of the observations obs_first, obs_first + 1, ... of the run's grid; `checkpoint` is
+    the dictionary of arrays (pos, flags, ref, t, n_events, next_obs) a previous segment returned under "checkpoint", or None
+    for a fresh start from `states` (which is not read otherwise).  `uniforms` and `max_events` count events from the run's
+    start; `ref_obs` counts within this segment; `T` is the run's.  The result also has "checkpoint" (the end state) and
+    "first_row" (per system: the first row of this segment that is its own)."""
+    kw = dict(locals())                                        # first statement: locals() are the keywords
+    return _run_batch_entry("gilrm_run" if kw.pop("large") else "gilr_run", **kw)
+
+
+CHECKPOINT_ARRAYS = (("pos", np.int32, 2), ("flags", np.uint8, 2), ("ref", np.int32, 2), ("t", np.float64, 1), ("n_events", np.int64, 1),
+                     ("next_obs", np.int32, 1))
 
 
 def plan_many_large(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, want_states=True, want_scalars=True):
@@ -355,16 +387,28 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
                      minus_anchor, immobilize, suppress_flip, crowding, k_on, k_off, k_exit, anchor_mask, uniforms, max_events,
                      want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table, k_max=None, first_obs=0,
                      group_of_site=None, n_groups=0, c_bins=0, h_bins=0, h_dt=0.0, n_cap=None, n_bins=0, want_field=False,
-                     group_of_system=None, per_system=False, mixed=None, want_rows=True):
+                     group_of_system=None, per_system=False, mixed=None, want_rows=True, obs_first=0, checkpoint=None):
     """The batch entry points take the same arguments: gil_run_batch (systems in LDS), gilm_run (large systems), gils_run
     (either, with the structure sums: k_max, first_obs) and gilc_run (either, with the capture statistics: group_of_site,
     n_groups, c_bins, h_bins, h_dt, first_obs); gilp_run (either, with the ensemble profiles: n_bins, first_obs, want_field,
     group_of_system, n_groups, per_system); gilx_run (systems in LDS, a variant per system: `mixed`, the keywords of
-    _mixed_descriptor)."""
+    _mixed_descriptor); gilr_run and gilrm_run (one segment of a run: obs_first, checkpoint)."""
     lib = _lib()
+    if entry in ("gilr_run", "gilrm_run") and not hasattr(lib, entry):
+        raise capi.ApsError(-1, f"the loaded library has no {entry} (include/gillespie_resume.h)")
     call = getattr(lib, entry)
     last_error = getattr(lib, {"gil_run_batch": "gil_last_error", "gilm_run": "gilm_last_error", "gils_run": "gils_last_error",
-                               "gilc_run": "gilc_last_error", "gilp_run": "gilp_last_error", "gilx_run": "gilx_last_error", "gilxs_run": "gilxs_last_error"}[entry])
+                               "gilc_run": "gilc_last_error", "gilp_run": "gilp_last_error", "gilx_run": "gilx_last_error", "gilxs_run": "gilxs_last_error",
+                               "gilr_run": "gilr_last_error", "gilrm_run": "gilr_last_error"}[entry])
+    ck_in = None
+    if checkpoint is not None:                                 # a resumed segment: the systems and their slots are the checkpoint's
+        ck_in = {k: np.ascontiguousarray(checkpoint[k], dtype=dt) for k, dt, _ in CHECKPOINT_ARRAYS}
+        if ck_in["pos"].ndim != 2 or any(ck_in[k].shape != ck_in["pos"].shape[:nd] for k, _, nd in CHECKPOINT_ARRAYS):
+            raise ValueError("checkpoint: pos, flags, ref must be [systems][slots], t, n_events, next_obs [systems]")
+        if n_cap is not None and int(n_cap) != ck_in["pos"].shape[1]:
+            raise ValueError("n_cap differs from the checkpoint's")
+        n_cap = ck_in["pos"].shape[1]
+        states = [((), ())] * ck_in["pos"].shape[0]
     S = len(states)
     betas = np.ascontiguousarray(np.broadcast_to(np.asarray(betas, dtype=np.float64), (S,)))
     ncap = max(1, max(len(st[0]) for st in states))
@@ -406,8 +450,13 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     ms = C.c_double()
     args = [_p(n0), _p(pos0), _p(sg0), _p(bd0), _p(uniforms), _p(pos_obs), _p(sg_obs), _p(fl_obs), _p(scal), _p(n_rec), _p(n_ev),
             _p(t_fin), _p(exits), _p(n_exit)]
-    rows = capture = sums = head = None
-    if entry == "gils_run":
+    rows = capture = sums = head = ck_out = None
+    if entry in ("gilr_run", "gilrm_run"):
+        ck_out = {k: np.zeros((S, ncap)[:nd], dt) for k, dt, nd in CHECKPOINT_ARRAYS}
+        c_in = None if ck_in is None else GilCheckpoint(**{k: _p(v).value for k, v in ck_in.items()})
+        c_out = GilCheckpoint(**{k: _p(v).value for k, v in ck_out.items()})
+        rc = call(C.byref(par), *args, C.byref(ms), int(obs_first), None if c_in is None else C.byref(c_in), C.byref(c_out))
+    elif entry == "gils_run":
         rows = np.zeros((S, M, 4 + 2 * max(int(k_max), 0)))
         rc = call(C.byref(par), int(k_max), int(first_obs), *args, _p(rows), C.byref(ms))
     elif entry == "gilc_run":
@@ -448,6 +497,11 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
         raise capi.ApsError(rc, last_error().decode())
     out = dict(pos=pos_obs, sigma=sg_obs, flags=fl_obs, scalars=scal, n_recorded=n_rec, n_events=n_ev, t_final=t_fin,
                exits=exits, n_exits=n_exit, n0=n0, kernel_ms=ms.value)
+    if ck_out is not None:
+        first_row = np.zeros(S, np.int32) if ck_in is None else np.clip(ck_in["next_obs"] - int(obs_first), 0, None).astype(np.int32)
+        if ck_in is not None:
+            first_row[ck_in["next_obs"] < int(obs_first)] = 0        # ended before this segment: n_recorded is 0 too
+        out.update(checkpoint=ck_out, first_row=first_row, obs_first=int(obs_first), n0=np.full(S, ncap, np.int32))   # any slot may be alive
     if rows is not None:
         out["structure"] = rows
     if head is not None:
@@ -462,12 +516,25 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     return out
 
 
-def run_batched_exact(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False, uniforms=None, want_m_local=True):
+def run_batched_exact(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False, uniforms=None, want_m_local=True,
+                      resume=None, obs_range=None, return_checkpoint=False, obs_per_launch=None):
     """`run()` of several ParticleSystem objects with the reference's exact event-by-event dynamics, all systems at
     once on the GPU.  They may differ in beta, rng / initial condition and particle number only.  Returns the list of
     result dictionaries (reference :542-557).  Observations the loop never reached (t passed T first, ref :515-516)
     keep the reference's pre-allocated zeros / None.  want_m_local=False leaves m_local_list zero (saves one field
-    evaluation per observation and system)."""
+    evaluation per observation and system).
+
+    A run may be cut into segments (include/gillespie_resume.h); the segments together are, bit for bit, the run in one launch.
+    The observation grid np.arange(0, T, obs_dt) and `T` are the whole run's in every segment; a segment is a range of
+    observations.  `obs_range=(k0, k1)`: record the observations k0 .. k1 - 1 only (default: from the start state's next
+    observation to the grid's end); the result dictionaries then cover those observations, and an observation the checkpoint
+    had already recorded for a system keeps the zeros / None.  `return_checkpoint=True`: return (results, Checkpoint).
+    `resume=checkpoint`: start from that state instead of `init_particles()` -- no generator is consumed, and the Philox key is
+    the checkpoint's.  The systems passed on resume supply beta, the rate constants and flip_rate_fn, which may differ from the
+    values the checkpoint was made with: that is the exact process with the parameter switched at the checkpoint's time (a
+    stopping time; the next event draws fresh numbers, so the switched process is exact).  A longer `T` extends a finished run.
+    `obs_per_launch=n`: run the range as a chain of launches of at most n observations each and return what one launch returns.
+    With none of the four keywords the run is one launch of the entry points that have no checkpoint."""
     from .particle_system import ParticleSystem, _SHAPE_ATTRS
     first = systems[0]
     for ps in systems[1:]:
@@ -475,6 +542,12 @@ def run_batched_exact(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var
             if getattr(ps, k) != getattr(first, k):
                 raise ValueError(f"run_batched_exact: systems differ in {k}")
     L, dx = first.L, first.dx
+    if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
+        r, times_obs, ck = _segmented_launches("run_batched_exact", systems, T, obs_dt, resume=resume, obs_range=obs_range,
+                                               obs_per_launch=obs_per_launch, uniforms=uniforms)
+        outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
+        first.kernel_ms = r["kernel_ms"]
+        return (outs, ck) if return_checkpoint else outs
     inits = [ps.init_particles() for ps in systems]
     seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
     times_obs = np.arange(0.0, T, obs_dt)
@@ -504,7 +577,7 @@ def _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local):
         hat = np.zeros((M, L), dtype=complex) if record_fft else None
         amp = np.zeros((M, L)) if record_fft else None
         var = np.zeros(M) if record_var else None
-        for k in range(int(r["n_recorded"][s])):
+        for k in range(int(r["first_row"][s]) if "first_row" in r else 0, int(r["n_recorded"][s])):
             fl = r["flags"][s, k, :n0]
             live = (fl & 2) != 0
             p, sg = r["pos"][s, k, :n0][live].astype(np.int64), r["sigma"][s, k, :n0][live]
@@ -528,10 +601,13 @@ def _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local):
     return outs
 
 
-def run_batched_exact_statistics(systems, T=10.0, obs_dt=0.01):
+def run_batched_exact_statistics(systems, T=10.0, obs_dt=0.01, resume=None, obs_range=None, return_checkpoint=False, obs_per_launch=None):
     """The sweep drivers' per-run observables (observables.DeviceObservables: v_eff, D_eff, mean magnetisation, front
     density, blocking probability) for many systems under the exact dynamics, from the integer sums the event-loop
-    kernel records at every observation -- no state arrays leave the GPU.  Needs k_exit = 0 like every reference sweep."""
+    kernel records at every observation -- no state arrays leave the GPU.  Needs k_exit = 0 like every reference sweep.
+    `resume`, `obs_range`, `return_checkpoint`, `obs_per_launch`: as in run_batched_exact.  The observables are those of the
+    observations of `obs_range` (the windows of DeviceObservables lie within them); `obs_per_launch` chains the launches and
+    evaluates the concatenated sums, which are the single launch's."""
     from . import observables
     from .particle_system import _SHAPE_ATTRS
     first = systems[0]
@@ -541,6 +617,15 @@ def run_batched_exact_statistics(systems, T=10.0, obs_dt=0.01):
                 raise ValueError(f"run_batched_exact_statistics: systems differ in {k}")
     if first.k_exit:
         raise ValueError("run_batched_exact_statistics needs k_exit = 0")
+    if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
+        r, times_obs, ck = _segmented_launches("run_batched_exact_statistics", systems, T, obs_dt, resume=resume, obs_range=obs_range,
+                                               obs_per_launch=obs_per_launch, statistics=True)
+        if np.any(r["first_row"] > 0):
+            raise ValueError("run_batched_exact_statistics: the checkpoint's systems stand at different observations; "
+                             "the sums need a common first observation")
+        rows = _statistics_rows(systems, r, times_obs)
+        first.kernel_ms = r["kernel_ms"]
+        return (rows, ck) if return_checkpoint else rows
     inits = [ps.init_particles() for ps in systems]
     seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
     times_obs = np.arange(0.0, T, obs_dt)
@@ -578,6 +663,150 @@ def _statistics_rows(systems, r, times_obs):
         rows.append(acc.result())
         ps.n_events = int(r["n_events"][s])
     return rows
+
+
+def _refuse_resume(who, resume):
+    """The structure, capture, profile and mixed launches carry sums of their own across a run (window sums, bind times, group
+    rows), which a Checkpoint does not hold: they cannot start from one."""
+    if resume is not None:
+        raise ValueError(f"{who} cannot resume from a checkpoint: its launch carries sums across the run that a Checkpoint does not hold "
+                         "(include/gillespie_resume.h); run_batched_exact and run_batched_exact_statistics can")
+
+
+CHECKPOINT_STREAMS = {"batch": "key = seed, stream = system index (gil_run_batch)", "large": "key = seed + system index, stream = 0 (gilm_run)"}
+_FINGERPRINT = ("L", "K", "periodic", "local_kernel_sigma", "anchor_mask", "n_systems", "n_cap", "seed", "streams", "obs_dt")
+
+
+class Checkpoint:
+    """The state of a batch of systems between two launches of the exact event loop (struct gil_checkpoint of
+    include/gillespie_resume.h): per system and slot the site (`pos`), the flags (`flags`: GILR_PLUS | GILR_BOUND | GILR_ALIVE)
+    and the origin of the displacement sums (`ref`, -1: none); per system the time after the last applied event (`t`; it may
+    exceed T, and is +inf once the total rate fell to zero), the events fired since the run's start (`n_events` = index of the
+    next event's random numbers) and the first observation not yet recorded (`next_obs`).
+
+    With it travels a fingerprint of what must not change between segments, because the layout or the random numbers depend
+    on it: L, K, periodic, local_kernel_sigma, the anchor mask, the numbers of systems and slots, the Philox key `seed`, the
+    stream convention `streams` ("batch": the kernel of systems in LDS, "large": the large-system kernel; CHECKPOINT_STREAMS)
+    and obs_dt (the observation grid).  Resuming against another value raises ValueError naming the field.  Beta, the rate
+    constants and flip_rate_fn are deliberately NOT part of it: the systems passed on resume supply them, and other values than
+    before mean the exact process with the parameter switched at the checkpoint's time."""
+
+    def __init__(self, *, pos, flags, ref, t, n_events, next_obs, L, K, periodic, local_kernel_sigma, anchor_mask, seed, streams, obs_dt):
+        for k, dt, nd in CHECKPOINT_ARRAYS:
+            setattr(self, k, np.ascontiguousarray(locals()[k], dtype=dt))
+        if self.pos.ndim != 2 or any(getattr(self, k).shape != self.pos.shape[:nd] for k, _, nd in CHECKPOINT_ARRAYS):
+            raise ValueError("Checkpoint: pos, flags, ref must be [systems][slots], t, n_events, next_obs [systems]")
+        if streams not in CHECKPOINT_STREAMS:
+            raise ValueError("Checkpoint: streams must be 'batch' or 'large'")
+        self.L, self.K, self.periodic, self.local_kernel_sigma = int(L), int(K), bool(periodic), float(local_kernel_sigma)
+        self.anchor_mask = np.zeros(self.L, np.uint8) if anchor_mask is None else (np.asarray(anchor_mask).reshape(-1) != 0).astype(np.uint8)
+        self.seed, self.streams, self.obs_dt = int(seed), str(streams), float(obs_dt)
+
+    n_systems = property(lambda self: self.pos.shape[0])
+    n_cap = property(lambda self: self.pos.shape[1])
+
+    def arrays(self):
+        """The dictionary of arrays `run_resumable_raw(checkpoint=...)` takes."""
+        return {k: getattr(self, k) for k, _, _ in CHECKPOINT_ARRAYS}
+
+    def fingerprint(self):
+        return {k: getattr(self, k) for k in _FINGERPRINT}
+
+    def require(self, **expected):
+        """ValueError naming the first fingerprint field whose value differs from `expected[field]`."""
+        mine = self.fingerprint()
+        for k in _FINGERPRINT:
+            if k not in expected:
+                continue
+            same = np.array_equal(mine[k], np.asarray(expected[k]).reshape(-1) != 0) if k == "anchor_mask" else mine[k] == expected[k]
+            if not same:
+                shown = "" if k == "anchor_mask" else f": the checkpoint has {mine[k]!r}, the resuming run {expected[k]!r}"
+                raise ValueError(f"Checkpoint: the resuming run differs from the checkpoint in {k}{shown}")
+
+    def save(self, path):
+        """One .npz: the six arrays, the anchor mask and the scalar fields of the fingerprint."""
+        meta = {k: getattr(self, k) for k in _FINGERPRINT if k not in ("anchor_mask", "n_systems", "n_cap")}
+        with open(path, "wb") as fh:
+            np.savez(fh, anchor_mask=self.anchor_mask, meta=np.array(json.dumps(meta)), **self.arrays())
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(anchor_mask=z["anchor_mask"], **{k: z[k] for k, _, _ in CHECKPOINT_ARRAYS}, **json.loads(str(z["meta"])))
+
+
+def _merge_segments(parts, k0):
+    """The raw outputs of a chain of segments as those of one launch over all their observations (row 0 = observation k0)."""
+    last = parts[-1]
+    out = {k: (None if parts[0][k] is None else np.concatenate([r[k] for r in parts], axis=1)) for k in ("pos", "sigma", "flags", "scalars")}
+    S, ncap = last["exits"].shape[:2]
+    exits, n_exits = np.zeros((S, ncap, 3)), np.zeros(S, np.int32)
+    for r in parts:                                            # the exit log of a segment holds that segment's exits
+        for s in range(S):
+            n = int(r["n_exits"][s])
+            exits[s, n_exits[s]:n_exits[s] + n] = r["exits"][s, :n]
+            n_exits[s] += n
+    n_rec = np.clip(last["checkpoint"]["next_obs"] - k0, 0, None).astype(np.int32)
+    out.update(exits=exits, n_exits=n_exits, n_recorded=n_rec, first_row=np.minimum(parts[0]["first_row"], n_rec),
+               n_events=last["n_events"], t_final=last["t_final"], n0=last["n0"], kernel_ms=float(sum(r["kernel_ms"] for r in parts)),
+               checkpoint=last["checkpoint"], launches=len(parts))
+    return out
+
+
+def _segmented_launches(who, systems, T, obs_dt, *, resume, obs_range, obs_per_launch, uniforms=None, statistics=False):
+    """The observations `obs_range` of the run (T, obs_dt) of `systems`, from `resume` or from fresh initial conditions, in
+    launches of at most `obs_per_launch` observations (gilr_run / gilrm_run): (merged raw outputs, their observation times,
+    the Checkpoint at the end)."""
+    from . import observables
+    first = systems[0]
+    times_all = np.arange(0.0, T, obs_dt)
+    M, S = len(times_all), len(systems)
+    mask = np.zeros(first.L, np.uint8) if first.is_anchor_site is None else (np.asarray(first.is_anchor_site).reshape(-1) != 0).astype(np.uint8)
+    if resume is None:
+        inits = [ps.init_particles() for ps in systems]
+        seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+        large = first.L > GIL_MAX_L or max(len(p) for p, _ in inits) > GIL_MAX_N
+        ck, k_lo, n_live = None, 0, [len(p) for p, _ in inits]
+    else:
+        if not isinstance(resume, Checkpoint):
+            raise TypeError(f"{who}: resume must be a gillespie.Checkpoint")
+        resume.require(L=first.L, K=first.K, periodic=bool(first.periodic), local_kernel_sigma=float(first.local_kernel_sigma),
+                       anchor_mask=mask, n_systems=S, obs_dt=float(obs_dt),
+                       streams="large" if (first.L > GIL_MAX_L or resume.n_cap > GIL_MAX_N) else "batch",
+                       **({} if first.seed is None else {"seed": int(first.seed)}))
+        inits, seed, large, ck = None, resume.seed, resume.streams == "large", resume.arrays()
+        k_lo, n_live = int(resume.next_obs.min()), [int(((f & GILR_ALIVE) != 0).sum()) for f in resume.flags]
+    k0, k1 = (k_lo, M) if obs_range is None else (int(obs_range[0]), int(obs_range[1]))
+    if not 0 <= k0 < k1 <= M:
+        raise ValueError(f"{who}: obs_range must be a non-empty range within the {M} observations of the run (got [{k0}, {k1}))")
+    if resume is None and k0 != 0:
+        raise ValueError(f"{who}: a run without `resume` starts at observation 0")
+    step = k1 - k0 if obs_per_launch is None else int(obs_per_launch)
+    if step < 1:
+        raise ValueError(f"{who}: obs_per_launch must be at least 1")
+    kw = dict(L=first.L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
+              rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], T=T, seed=seed, minus_anchor=first.minus_anchor,
+              immobilize=first.immobilize_when_anchored, suppress_flip=first.suppress_flip_when_bound,
+              crowding=first.crowding_suppresses_rates, k_on=first.k_on, k_off=first.k_off, k_exit=first.k_exit,
+              anchor_mask=first.is_anchor_site, uniforms=uniforms, device=first.device, flip_table=first.flip_table(), large=large)
+    ref_abs = -1
+    if statistics:                                             # the keywords of run_batched_exact_statistics' launch
+        acc0 = observables.DeviceObservables(times_all[k0:k1], first.L, first.dx, first.K)
+        tables = [acc0.block_table(n) for n in n_live]         # the blocking threshold depends on the particle number
+        if any(not np.array_equal(t, tables[0]) for t in tables[1:]):
+            raise ValueError(f"{who}: the systems' particle numbers give different blocking thresholds; run them in separate batches")
+        kw.update(k_exit=0.0, want_states=False, x_wall=acc0.x_wall, block_table=tables[0],
+                  front_lo=np.array([acc0.front_range(s)[0] for s in range(first.L)], np.int32))
+        ref_abs = k0 + acc0.start
+    parts = []
+    for a in range(k0, k1, step):
+        b = min(a + step, k1)
+        r = run_resumable_raw(states=inits, times_obs=times_all[a:b], obs_first=a, checkpoint=ck, ref_obs=ref_abs - a if a <= ref_abs < b else -1, **kw)
+        ck = r["checkpoint"]
+        parts.append(r)
+    r = _merge_segments(parts, k0)
+    return r, times_all[k0:k1], Checkpoint(L=first.L, K=first.K, periodic=first.periodic, local_kernel_sigma=first.local_kernel_sigma,
+                                           anchor_mask=mask, seed=seed, streams="large" if large else "batch", obs_dt=obs_dt, **ck)
 
 
 def mixed_variants(sigma_grids, block_tables=None):
@@ -673,21 +902,23 @@ def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, or
 
 
 def run_batched_exact_mixed(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False, uniforms=None, want_m_local=True,
-                            groups=None, order=None):
+                            groups=None, order=None, resume=None):
     """`run_batched_exact` for systems that may ALSO differ in `local_kernel_sigma`: one mixed launch (include/gillespie_mixed.h).
     Every other attribute the batched functions compare, the anchor sites and the flip table must agree.  `groups[s]`: the group
     of system s; its systems draw what `run_batched_exact` on the group alone draws (`mixed_keys`).  Returns the list of the
     reference's result dictionaries, one per system."""
+    _refuse_resume("run_batched_exact_mixed", resume)
     r, times_obs = _mixed_launch("run_batched_exact_mixed", systems, T, obs_dt, groups, False, uniforms, order)
     outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
     systems[0].kernel_ms = r["kernel_ms"]
     return outs
 
 
-def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None, order=None):
+def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None, order=None, resume=None):
     """`run_batched_exact_statistics` for systems that may also differ in `local_kernel_sigma` and whose particle numbers may give
     different blocking thresholds: every system is counted with the blocking table of its own particle number, in one mixed
     launch.  `groups` as in run_batched_exact_mixed.  Returns the DeviceObservables rows, one per system."""
+    _refuse_resume("run_batched_exact_statistics_mixed", resume)
     r, times_obs = _mixed_launch("run_batched_exact_statistics_mixed", systems, T, obs_dt, groups, True, None, order)
     rows = _statistics_rows(systems, r, times_obs)
     systems[0].kernel_ms = r["kernel_ms"]
@@ -695,7 +926,7 @@ def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None
 
 
 def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_max=None, groups=None, order=None,
-                                      reduce="device", return_series=False):
+                                      reduce="device", return_series=False, resume=None):
     """`run_batched_exact_structure` for systems that may ALSO differ in `local_kernel_sigma` (and, like there, in beta, state and
     particle number): one mixed launch that takes the structure sums (include/gillespie_mixed_structure.h).  The other attributes,
     the anchor sites and the flip table must agree, as in run_batched_exact_mixed; `groups`, `order` as there (`mixed_keys`).
@@ -705,6 +936,7 @@ def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fracti
     returns the full rows and observables.DeviceStructure reduces them on the host (the cross-check route).
     `return_series=True` adds `times_obs`, `var_series` [M] (from the head rows), `m_series` [M] = sum sigma / n (from the scalar
     sums) and, with reduce="rows" (the sums are then taken at every observation), `fft_amp_series` [M][k_max]."""
+    _refuse_resume("run_batched_exact_structure_mixed", resume)
     from . import observables
     if reduce not in ("device", "rows"):
         raise ValueError("reduce must be 'device' or 'rows'")
@@ -746,13 +978,14 @@ def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fracti
     return out
 
 
-def run_batched_exact_structure(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_max=None, return_series=False):
+def run_batched_exact_structure(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_max=None, return_series=False, resume=None):
     """The structure observables of PARTICLE_solver_BIOLOGY_local_structure.py:55-103 for many systems under the exact dynamics,
     from sums the event-loop kernel takes at every observation of the window [int(start_fraction * M), M): no state array and
     nothing of size M x L leaves the GPU.  Returns one dict per system with the reference's eight keys
     (observables.DeviceStructure.result); `k_max=None` means all L modes, as in the reference.  `return_series=True` takes the
     sums at every observation and adds `times_obs`, `fft_amp_series` [M][k_max] and `var_series` [M] (what the reference's
     time_to_pattern, :195-202, reads).  Particles may leave (k_exit > 0): n is the live count of the observation."""
+    _refuse_resume("run_batched_exact_structure", resume)
     from . import observables
     from .particle_system import _SHAPE_ATTRS
     first = systems[0]
@@ -792,7 +1025,7 @@ def run_batched_exact_structure(systems, T=10.0, obs_dt=0.01, start_fraction=0.5
     return rows
 
 
-def run_batched_exact_capture(systems, T=10.0, obs_dt=0.01, c_bins=16, h_bins=40, h_dt=None, start_fraction=0.0, uniforms=None):
+def run_batched_exact_capture(systems, T=10.0, obs_dt=0.01, c_bins=16, h_bins=40, h_dt=None, start_fraction=0.0, uniforms=None, resume=None):
     """The anchor-capture study of PARTICLE_solver_CLASS.py:766-976 (cluster sizes, bound-state lifetimes, survival curve and
     first-passage density, exit positions, cumulative exits per anchor) for many systems under the exact dynamics, from counts
     the event-loop kernel takes at every event and observation: no state array leaves the GPU.  Returns one dict per system
@@ -800,6 +1033,7 @@ def run_batched_exact_capture(systems, T=10.0, obs_dt=0.01, c_bins=16, h_bins=40
     variances).  The per-observation rows are taken from observation int(start_fraction * M) on; the series are zero before it.
     `h_dt=None`: T / h_bins.  Lifetimes are resolved to the event and follow the particle, where the reference's are quantised
     to obs_dt and, after the first exit, attributed to shifted particle ids."""
+    _refuse_resume("run_batched_exact_capture", resume)
     from . import observables
     from .particle_system import _SHAPE_ATTRS
     first = systems[0]
@@ -837,13 +1071,14 @@ def run_batched_exact_capture(systems, T=10.0, obs_dt=0.01, c_bins=16, h_bins=40
 
 
 def run_batched_exact_profiles(systems, T=10.0, obs_dt=0.01, n_bins=None, groups=None, first_obs=0, want_field=False,
-                               per_system=False, uniforms=None):
+                               per_system=False, uniforms=None, resume=None):
     """The ensemble profiles <rho+(x, t)>, <rho-(x, t)> and <m(x, t)> of many ParticleSystem objects under the exact dynamics
     (the means over runs of the reference's rho_plus_list, rho_minus_list, m_local_list, PARTICLE_solver_CLASS.py:205-213,
     :517-536), coarse-grained to `n_bins` bins of sites and summed over the runs of a group inside the event loop: no state array
     leaves the GPU, and what does is [groups][observations][7][n_bins].  `groups[s]` is the group system s adds to (None: one
     group).  Returns one dict per group, in the order of the group ids (observables.DeviceProfiles.result); `per_system=True`
     adds each member's own counts as `profile_obs` [members][observations][3][n_bins] (single-run heat maps at n_bins = L)."""
+    _refuse_resume("run_batched_exact_profiles", resume)
     from . import observables
     from .particle_system import _SHAPE_ATTRS
     first = systems[0]

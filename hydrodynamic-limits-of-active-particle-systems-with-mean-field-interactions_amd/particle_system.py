@@ -113,6 +113,7 @@ class ParticleSystem:
         self.dt = None if dt is None else float(dt)
         self.seed = seed
         self.device = int(device)
+        self.checkpoint = None                 # mode="gillespie_gpu": the state after the last run(), for continue_run()
         self.sort_by_site = bool(sort_by_site)
         self.ensemble = int(ensemble)          # Philox counter word 3 (independent streams under one seed)
         if mode is None:                       # an unchanged driver gets the reference's dynamics (ref :511-516, :358-362)
@@ -289,8 +290,26 @@ class ParticleSystem:
             return self._run_gillespie(T, obs_dt, record_fft, record_var)
         if self.mode == "gillespie_gpu":
             from .gillespie import run_batched_exact
-            return run_batched_exact([self], T=T, obs_dt=obs_dt, record_fft=record_fft, record_var=record_var)[0]
+            outs, self.checkpoint = run_batched_exact([self], T=T, obs_dt=obs_dt, record_fft=record_fft, record_var=record_var,
+                                                      return_checkpoint=True)
+            return outs[0]
         return run_batched([self], T=T, obs_dt=obs_dt, record_fft=record_fft, record_var=record_var)[0]
+
+    def continue_run(self, T, obs_dt=None, record_fft=False, record_var=False):
+        """mode="gillespie_gpu": carries the last `run()` / `continue_run()` on to a later `T` from `self.checkpoint` (a
+        gillespie.Checkpoint, which `run()` keeps) and returns the result dictionary of the NEW observations of the grid
+        np.arange(0, T, obs_dt) only; together with the earlier ones they are, bit for bit, one `run()` to the later T.  No
+        generator is consumed.  beta, the rates and flip_rate_fn are this object's current ones: changing them between the
+        calls is the exact process with the parameter switched at the checkpoint's time (gillespie.run_batched_exact)."""
+        if self.mode != "gillespie_gpu":
+            raise ValueError("continue_run needs mode='gillespie_gpu'")
+        if getattr(self, "checkpoint", None) is None:
+            raise ValueError("continue_run: no run() to continue")
+        from .gillespie import run_batched_exact
+        outs, self.checkpoint = run_batched_exact([self], T=T, obs_dt=self.checkpoint.obs_dt if obs_dt is None else obs_dt,
+                                                  record_fft=record_fft, record_var=record_var, resume=self.checkpoint,
+                                                  return_checkpoint=True)
+        return outs[0]
 
     def _run_gillespie(self, T, obs_dt, record_fft, record_var):
         """The reference's event loop as written (ref :450-558): one event per iteration, observation after the
