@@ -699,6 +699,7 @@ int big_run(const char *who, std::string &err, const gil_params *p, const int32_
         if (n0[s] < 0 || n0[s] > N) return bad("bad n_cap / n0 / n_obs / max_events");
         if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * N, sigma0 + (size_t)s * N)) return bad(why);
     }
+    if (const char *why = gil_check_flip_table(p)) return bad(why);
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: the scratch arrays start from zero
     if (int rc = job.select_device(p->device)) return rc;
     size_t free_b = 0, total_b = 0;

@@ -2,6 +2,7 @@
 // each in one workgroup's LDS) and gillespie_big_hip.hip (one large system in global memory), both of include/gillespie.h.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -35,10 +36,21 @@ inline const char *gil_check_state(const gil_params *p, int n, const int32_t *po
     return nullptr;
 }
 
+// nullptr when a caller's flip table is acceptable (or absent), else the text of the complaint: aps_set_flip_table's rules.
+// A negative or non-finite rate would make a particle's cumulative sums non-monotone on the device.  Host arithmetic only:
+// the drivers ask before they touch the device.
+inline const char *gil_check_flip_table(const gil_params *p) {
+    if (!p->flip_table) return nullptr;
+    if (p->flip_n < 1 || p->flip_n > (1 << 24)) return "flip_n must be in [1, 2^24]";
+    for (size_t i = 0, n = (size_t)2 * ((size_t)p->flip_n + 1); i < n; ++i)
+        if (!(p->flip_table[i] >= 0.0) || !std::isfinite(p->flip_table[i])) return "rates must be finite and >= 0";
+    return nullptr;
+}
+
 // a caller's flip_rate_fn, tabulated (aps_set_flip_table's layout): onto the device and into the model
 inline int gil_upload_flip_table(OneShot &job, const gil_params *p, Model &M) {
     if (!p->flip_table) return 0;
-    if (p->flip_n < 1 || p->flip_n > (1 << 24)) return job.fail(job.e_arg, std::string(job.who) + ": flip_n must be in [1, 2^24]");
+    if (const char *why = gil_check_flip_table(p)) return job.fail(job.e_arg, std::string(job.who) + ": " + why);
     if (int rc = job.upload(&M.flip_tab, p->flip_table, (size_t)2 * ((size_t)p->flip_n + 1), "flip_table")) return rc;
     M.flip_n = p->flip_n;
     return 0;

@@ -564,6 +564,7 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const int3
         if (n0[s] < 0 || n0[s] > ncap) return bad("n0 outside [0, n_cap]");
         if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * ncap, sigma0 + (size_t)s * ncap)) return bad(why);
     }
+    if (const char *why = gil_check_flip_table(p)) return bad(why);
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: a run may record fewer observations than it has room for
     if (int rc = job.select_device(p->device)) return rc;
     if (structure_obs || cap || prof) {
@@ -947,6 +948,7 @@ int mixed_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, co
         if (n0[s] < 0 || n0[s] > ncap) return bad("n0 = " + std::to_string(n0[s]) + " of system " + std::to_string(s) + " is outside [0, n_cap = " + std::to_string(ncap) + "]");
         if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * ncap, sigma0 + (size_t)s * ncap)) return bad(why);
     }
+    if (const char *why = gil_check_flip_table(p)) return bad(why);
     std::vector<int32_t> order((size_t)S), stream((size_t)S);
     std::vector<uint64_t> seed((size_t)S);
     for (int s = 0; s < S; ++s) { order[(size_t)s] = v->order ? v->order[s] : s; stream[(size_t)s] = v->stream ? v->stream[s] : s; seed[(size_t)s] = v->seed ? v->seed[s] : p->seed; }

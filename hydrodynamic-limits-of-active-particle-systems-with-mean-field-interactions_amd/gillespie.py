@@ -148,8 +148,10 @@ def _p(a):
 def run_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
             minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
             anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
-            block_table=None, device=0, flip_table=None):
-    """`states` = list of (pos, sigma[, bound]) per system.  Returns a dict of arrays with a leading system axis."""
+            block_table=None, device=0, flip_table=None, n_cap=None):
+    """`states` = list of (pos, sigma[, bound]) per system.  Returns a dict of arrays with a leading system axis.  `n_cap`:
+    particle slots per system, where more than the largest initial state are wanted (the spare ones stay empty; more than 1024
+    put a system on four wavefronts)."""
     return _run_batch_entry("gil_run_batch", **locals())       # first statement: locals() are the keywords
 
 
@@ -196,12 +198,13 @@ def plan_many_large(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, want
 def run_structure_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
                       minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
                       anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
-                      block_table=None, device=0, flip_table=None, k_max=None, first_obs=0):
+                      block_table=None, device=0, flip_table=None, k_max=None, first_obs=0, n_cap=None):
     """`run_raw` with the structure sums of every observation from `first_obs` on taken inside the event loop (gils_run of
     include/gillespie_structure.h).  The library picks the kernel: systems that fit a workgroup's LDS run as in `run_raw`,
     larger ones as in `run_many_large_raw` (system s: Philox key seed + s).  The dictionary of `run_raw` plus
     `structure` [systems][observations][4 + 2 k_max]: n, sum occ^2, sum m, sum m^2, then Re, Im of the first k_max Fourier sums
-    of the site histogram -- the arguments of observables.DeviceStructure.add.  `k_max=None`: all L modes (at most 4096)."""
+    of the site histogram -- the arguments of observables.DeviceStructure.add.  `k_max=None`: all L modes (at most 4096).
+    `n_cap`: particle slots per system, as in `run_capture_raw`."""
     k_max = min(int(L), 4096) if k_max is None else int(k_max)
     return _run_batch_entry("gils_run", **locals())
 

@@ -65,7 +65,8 @@ typedef struct gil_params {
     const int32_t *front_lo;    /* [L] or NULL: lowest site of the front window when the right-most particle sits at site s */
     const uint8_t *block_table; /* [(K+1)*(K+1)] or NULL: does a right neighbour with (plus, minus) particles block? */
     const double *flip_table;   /* [2][flip_n + 1] or NULL: a caller's flip_rate_fn tabulated over m in [-1, 1] (row 0: sigma = +1, row 1: -1),
-                                   interpolated linearly instead of exp(-beta sigma m) (ref :59-62, :261-262; aps_set_flip_table) */
+                                   interpolated linearly instead of exp(-beta sigma m) (ref :59-62, :261-262; aps_set_flip_table).
+                                   Every entry must be finite and >= 0, flip_n in [1, 2^24]: GIL_ERR_ARG otherwise, before any device call */
 } gil_params;
 
 const char *gil_last_error(void);

@@ -73,3 +73,26 @@ def test_valid_arguments_without_a_gpu(mods):
     _expect(capi, _pde(pde, 256, 1), plib.pdew_last_error, ERR_NODEVICE, "pdew_solve: no HIP device")
     _expect(capi, _gil_batch(gil, 64), glib.gil_last_error, ERR_NODEVICE, "gil_run_batch: no HIP device")
     _expect(capi, _gil_large(gil, 64), glib.gil_large_last_error, ERR_NODEVICE, "gil_run_large: no HIP device")
+
+
+@pytest.mark.parametrize("entry", [np.nan, np.inf, -np.inf, -1e-300])
+def test_flip_table_with_an_unusable_rate(mods, entry):
+    """gil_upload_flip_table holds a caller's table to aps_set_flip_table's rules, with that text behind the entry point's name,
+    before any device call: a negative rate would make a particle's cumulative sums non-monotone on the device."""
+    capi, pde, gil, plib, glib = mods
+    for row, col in ((0, 0), (1, 8), (1, 3)):                 # first entry, last entry, inside the second row
+        tab = np.ones((2, 9))
+        tab[row, col] = entry
+        _expect(capi, lambda: gil.run_raw(L=64, betas=[0.5], states=[(np.array([0]), np.array([1]))], flip_table=tab, **GIL_KW),
+                glib.gil_last_error, ERR_ARG, "gil_run_batch: rates must be finite and >= 0")
+        _expect(capi, lambda: gil.run_large_raw(L=64, beta=0.5, state=(np.array([0]), np.array([1])), flip_table=tab, **GIL_KW),
+                glib.gil_large_last_error, ERR_ARG, "gil_run_large: rates must be finite and >= 0")
+
+
+def test_flip_table_of_zeros_is_a_table(mods):
+    """Zero is a rate: the check refuses nothing that aps_set_flip_table accepts (the call gets as far as the device)."""
+    capi, pde, gil, plib, glib = mods
+    try:
+        gil.run_raw(L=64, betas=[0.5], states=[(np.array([0]), np.array([1]))], flip_table=np.zeros((2, 9)), **GIL_KW)
+    except capi.ApsError as exc:
+        assert exc.code == ERR_NODEVICE and glib.gil_last_error() == b"gil_run_batch: no HIP device"
