@@ -121,6 +121,7 @@ def load():
         "aps_set_resident_loop": (C.c_int, [vp, i32]),
         "aps_step_loop_timed": (C.c_int, [vp, i64, P(dbl), P(i64)]),
         "aps_loop_info": (C.c_int, [vp, P(i64), P(i32), C.c_char_p, i32]),
+        "aps_loop_waves": (C.c_int, [vp, P(i32)]),
         "aps_copy_bandwidth": (C.c_int, [vp, i64, i32, P(dbl)]),
         "aps_lattice_accumulate": (C.c_int, [vp, i32, vp, vp, vp, i64]),
         "aps_get_lattice": (C.c_int, [vp, i32, vp, vp, vp]),
@@ -395,6 +396,12 @@ class Handle:
         n, st, why = C.c_int64(), C.c_int32(), C.create_string_buffer(256)
         self._ck(self.lib.aps_loop_info(self._h, C.byref(n), C.byref(st), why, 256))
         return n.value, st.value, why.value.decode()
+
+    def loop_waves(self):
+        """Waves per tile of the resident loop's kernel on this handle (4 or 8); 0 while none is chosen."""
+        w = C.c_int32()
+        self._ck(self.lib.aps_loop_waves(self._h, C.byref(w)))
+        return w.value
 
     def copy_bandwidth(self, nbytes=1 << 30, reps=5):
         """GB/s (read + written) of a plain streaming copy kernel on this handle's device."""

@@ -1491,7 +1491,8 @@ struct aps_handle {
     // resident loop (tile_loop): many steps per launch while every tile of the grid is resident at once
     unsigned long long *d_xrec = nullptr;                      // [2][E][ntile][loop_rec] exchange records (8-byte granules)
     unsigned *d_abort = nullptr, *h_abort = nullptr, *h_abort_dev = nullptr;   // "a wait ran out": device word, host-mapped word and its device address
-    int loop_rec = 0, loop_drec = 0, loop_seg = 0;
+    int loop_rec = 0, loop_drec = 0, loop_seg = 0, loop_nw = 4;   // loop_nw: waves per tile of the kernel in use (4 or 8)
+    bool loop_img = true;                                      // eight waves: the instance with the image list (small boxes)
     int loop_state = -2;                                       // -2 not looked at yet, -1 gave up once (never again), 0 not eligible, 1 usable
     int loop_wanted = 1;                                       // aps_set_resident_loop
     uint32_t loop_tag = 0;                                     // tags handed out so far
@@ -2289,7 +2290,24 @@ const void *tl_kernel_f(bool periodic, int RS, bool k1) {
 #undef TL_CASE
 #undef TL_PICK
 }
-const void *tl_kernel(const aps_handle *h) {
+// eight waves per tile: binary64, one cell per site, frames of 5 to 8 rows (4 waves per SIMD: 128 VGPRs, which the halves of these
+// frames fit without scratch); img: the instance that carries the image list (reflecting walls, box comparable to the reach)
+const void *tl_kernel_wide(bool periodic, int RS, bool img) {
+#define TLW_CASE(R) case R: return periodic ? (const void *)&tile_loop<1, R, true, false, 8, false> \
+                                            : (img ? (const void *)&tile_loop<0, R, true, false, 8, true> : (const void *)&tile_loop<0, R, true, false, 8, false>);
+#ifdef APS_DEV_RS
+#if APS_DEV_RS >= 5
+    switch (RS) { TLW_CASE(APS_DEV_RS) default: return nullptr; }
+#else
+    return nullptr;
+#endif
+#else
+    switch (RS) { TLW_CASE(5) TLW_CASE(6) TLW_CASE(7) TLW_CASE(8) default: return nullptr; }
+#endif
+#undef TLW_CASE
+}
+const void *tl_kernel(const aps_handle *h, int nw) {
+    if (nw == 8) return (!h->f32 && h->p.K == 1) ? tl_kernel_wide(h->p.periodic != 0, h->ts_RS, h->loop_img) : nullptr;
     return h->f32 ? tl_kernel_f<true>(h->p.periodic != 0, h->ts_RS, h->p.K == 1) : tl_kernel_f<false>(h->p.periodic != 0, h->ts_RS, h->p.K == 1);
 }
 
@@ -2310,25 +2328,39 @@ int loop_prepare(aps_handle *h) {
 #ifdef APS_STAMPS
     return no("diagnostic build");
 #endif
-    const void *fn = tl_kernel(h);
-    if (!fn) return no("no kernel for this frame");
     // The API can promise one block more than the hardware admits (MI355X_MICROARCH.md, residency).  Measured here: with
     // 54 040 B of LDS per block the API said 3 per CU and only 2 were ever resident -- LDS is handed out in 128 granules of
-    // 1 280 B (160 KB / 128), so a block takes ceil(bytes / 1280) of them; and at most 8 blocks of 256 threads per CU.
-    // Deposit segments: the longest (of 256, 192, 128, 88 entries) that still lets the whole grid be resident.
+    // 1 280 B (160 KB / 128), so a block takes ceil(bytes / 1280) of them; and at most 32 waves per CU (8 blocks of four
+    // waves, 4 of eight).  Deposit segments: the longest (of 256, 192, 128, 88 entries; the pooled lists hold `waves` of
+    // them per class) that still lets the whole grid be resident.
     const int64_t need_per_cu = ((int64_t)h->ts_ntile * h->E + h->num_cu - 1) / h->num_cu;
+    const char *why_not = "no kernel for this frame";
+    auto fits = [&](int nw) -> bool {                          // the whole grid resident with nw waves per tile: sets loop_nw, loop_seg
+        const void *fn = tl_kernel(h, nw);
+        if (!fn) return false;
+        int seg_ok = 0;
+        size_t lds_total = 0;
+        for (int seg : {256, 192, 128, TL_SEG_MIN}) {
+            const TlLds lay = tl_lds_layout(h->tlen, h->ts_RS, h->ts_own, h->p.K, ts_wbytes(h), seg, nw);
+            if (lay.total > 160 * 1024) continue;
+            if (128 / (int)((lay.total + 1279) / 1280) >= need_per_cu) { seg_ok = seg; lds_total = lay.total; break; }
+        }
+        if (!seg_ok) { why_not = "more tiles than the device keeps resident at once (LDS)"; return false; }
+        if (lds_total > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_total) != hipSuccess) { (void)hipGetLastError(); why_not = "hipFuncSetAttribute failed"; return false; }
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nw * 64, lds_total) != hipSuccess) { (void)hipGetLastError(); why_not = "occupancy query failed"; return false; }
+        if (need_per_cu > std::min(per_cu, 32 / nw)) { why_not = "more tiles than the device keeps resident at once"; return false; }
+        h->loop_nw = nw; h->loop_seg = seg_ok;
+        return true;
+    };
+    // Eight waves per tile (tile_loop.hpp; binary64, K = 1, frames of 5 to 8 rows): the default where the geometry puts two
+    // workgroups on every CU (config 2, where it was measured) and for a frame of 8 rows, which has no binary64 kernel of four
+    // waves; APS_LOOP_WAVES=8 asks for them wherever the kernel exists (otherwise four are used), APS_LOOP_WAVES=4 never uses them.
+    h->loop_img = !h->p.periodic && !(2 * (h->tlen - 1) + 64 * h->ts_RS + h->ts_own + 4 < h->p.L);
+    bool wide = need_per_cu == 2 || !tl_kernel(h, 4);
+    if (const char *env = std::getenv("APS_LOOP_WAVES")) wide = std::atoi(env) == 8;
     h->loop_seg = 0;
-    size_t lds_total = 0;
-    for (int seg : {256, 192, 128, TL_SEG_MIN}) {
-        const TlLds lay = tl_lds_layout(h->tlen, h->ts_RS, h->ts_own, h->p.K, ts_wbytes(h), seg);
-        if (lay.total > 160 * 1024) continue;
-        if (128 / (int)((lay.total + 1279) / 1280) >= need_per_cu) { h->loop_seg = seg; lds_total = lay.total; break; }
-    }
-    if (!h->loop_seg) return no("more tiles than the device keeps resident at once (LDS)");
-    if (lds_total > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_total) != hipSuccess) { (void)hipGetLastError(); return no("hipFuncSetAttribute failed"); }
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, FU_THREADS, lds_total) != hipSuccess) { (void)hipGetLastError(); return no("occupancy query failed"); }
-    if (need_per_cu > std::min(per_cu, 8)) return no("more tiles than the device keeps resident at once");
+    if (!(wide && fits(8)) && !fits(4)) return no(why_not);
     h->loop_drec = (h->ts_dcap / 16 + 1) * 16;
     h->loop_rec = (h->loop_drec + 6 * h->p.K + 15) / 16 * 16;
     int rc;
@@ -2380,11 +2412,11 @@ int launch_tile_loop(aps_handle *h, int64_t n) {
             h->loop_stall = stall;
         }
     }
-    const void *fn = tl_kernel(h);
-    const size_t lds = tl_lds_layout(h->tlen, h->ts_RS, h->ts_own, h->p.K, ts_wbytes(h), h->loop_seg).total;
+    const void *fn = tl_kernel(h, h->loop_nw);
+    const size_t lds = tl_lds_layout(h->tlen, h->ts_RS, h->ts_own, h->p.K, ts_wbytes(h), h->loop_seg, h->loop_nw).total;
     const void *table_ptr = h->f32 ? (const void *)h->d_table_i : (const void *)h->d_table;
     void *args[] = {(void *)&la, (void *)&table_ptr};
-    const dim3 grid((unsigned)h->ts_ntile, (unsigned)h->E), block(FU_THREADS);
+    const dim3 grid((unsigned)h->ts_ntile, (unsigned)h->E), block((unsigned)h->loop_nw * 64u);
     if (h->loop_timed) {
         for (hipEvent_t &ev : h->loop_ev) if (!ev) HIP_TRY(h, hipEventCreate(&ev));
         HIP_TRY(h, hipExtLaunchKernel(fn, grid, block, args, lds, h->stream, h->loop_ev[0], h->loop_ev[1], 0));
@@ -3295,6 +3327,12 @@ int aps_loop_info(aps_handle *h, int64_t *loop_steps, int32_t *state, char *why,
     if (loop_steps) *loop_steps = h->last_loop_steps;
     if (state) *state = h->loop_state;
     if (why && why_len > 0) { std::strncpy(why, h->loop_why.c_str(), (size_t)why_len - 1); why[why_len - 1] = 0; }
+    return APS_OK;
+}
+
+int aps_loop_waves(aps_handle *h, int32_t *waves) {
+    if (!h || !waves) return APS_ERR_ARG;
+    *waves = (h->loop_state == 1 || h->loop_state == -1) ? h->loop_nw : 0;
     return APS_OK;
 }
 

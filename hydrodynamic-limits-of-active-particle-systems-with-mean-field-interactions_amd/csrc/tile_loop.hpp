@@ -21,9 +21,12 @@
 // two sets trade places).  Results are the same bits either way: the arithmetic and the random numbers are tile_step's.
 #pragma once
 
-constexpr int TL_SEG_MIN = 88;             // the four pooled deposit lists hold 4 (seg + 4) entries each; 88 at least (three workgroups per CU at config 2's 37 KB
+constexpr int TL_SEG_MIN = 88;             // the four pooled deposit lists hold NW (seg + 4) entries each (NW waves per tile); 88 at least (three workgroups per CU at config 2's 37 KB
                                            // table: <= 42 LDS granules of 1280 B), the host takes up to 256 when the residency the grid needs leaves room
-constexpr int TL_NG = 2;                   // bucket groups whose first page a wave asks for ahead of time (config 2 has two)
+constexpr int TL_QW = 4;                   // waves of a quad: the sweep deals groups of four deposits round-robin to the waves of a quad
+// bucket groups whose first page a wave asks for ahead of time: a group is 4 buckets per wave, config 2's 27 buckets are two groups
+// for four waves and one for eight
+__host__ __device__ constexpr int tl_ng(int nw) { return 8 / nw; }
 #ifndef TL_MIN_WAVES
 #define TL_MIN_WAVES 2                     /* waves per SIMD the register allocator must leave room for (tuning builds may ask for more) */
 #endif
@@ -35,7 +38,7 @@ struct LoopArgs {
     int nsteps;                            // any; the final state goes to the *_out buffers (the host swaps the two sets after an even count)
     uint32_t tag0;                         // the records written in iteration s carry the tag tag0 + s + 1 (never 0, never reused)
     int rec, drec;                         // granules per record; deposit slots of a record (a multiple of 16 above dcap)
-    int seg;                               // sizes the pooled deposit lists: 4 (seg + 4) entries per class (a multiple of 4)
+    int seg;                               // sizes the pooled deposit lists: NW (seg + 4) entries per class (a multiple of 4)
     unsigned long long *xrec;              // [2][E][ntile][rec] {tag << 32 | word}
     unsigned *abort_dev, *abort_host;      // raised by a workgroup whose wait ran out
     unsigned long long timeout_ticks;      // of the 100 MHz clock
@@ -45,12 +48,12 @@ struct LoopArgs {
 };
 
 struct TlLds { size_t seg, cells, cells2, props, occ, misc, plist, fw, fs, tab, total; };
-__host__ __device__ inline TlLds tl_lds_layout(int tlen, int RS, int own, int K, int wbytes, int seg) {
+__host__ __device__ inline TlLds tl_lds_layout(int tlen, int RS, int own, int K, int wbytes, int seg, int nw) {
     TlLds l;
     const size_t TS = 64 * (size_t)RS, ncell = (TS + 2) * K;
     auto up = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
     l.seg = 0;
-    l.cells = l.seg + (size_t)FU_WAVES * 4 * (seg + 4) * sizeof(uint32_t);
+    l.cells = l.seg + (size_t)nw * 4 * (seg + 4) * sizeof(uint32_t);
     l.cells2 = up(l.cells + ncell * 4, 8);
     l.props = up(l.cells2 + (K == 1 ? 0 : ncell * 4), 8);
     l.occ = up(l.props + TS * K, 8);
@@ -76,24 +79,111 @@ __device__ __forceinline__ unsigned long long tl_load_granule(const unsigned lon
 __device__ __forceinline__ void tl_lds_add(double *p, double v) { unsafeAtomicAdd(p, v); }       // ds_add_f64: sums are exact, the order is free
 __device__ __forceinline__ void tl_lds_add(int *p, int v) { atomicAdd(p, v); }
 
-template <int BC, int RS, bool K1, bool F32>
-// (two waves per SIMD for every instance: the loop runs with exactly two workgroups per CU where the geometry is chosen for it, and at three the
-// smaller frames spilled up to 200 bytes per lane to scratch)
-__global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const LoopArgs la, const void *__restrict__ table_v) {
+// The sweep's accumulators of one wave over its RQ rows of the frame.  Four waves (every wave sweeps all rows): one set per
+// class and the two of the image list, combined at the end.  Eight waves (a quad of waves per half of the rows, 128 VGPRs):
+// ONE working set, folded into the two totals after each class, and the image list goes into the totals directly.  All
+// sums are exact on the weight grid, so both give the same bits.
+template <int N> struct TlInt { static constexpr int value = N; };
+template <typename W, int RQ, bool FOLD> struct TlAcc;
+template <typename W, int RQ> struct TlAcc<W, RQ, false> {
+    W P[RQ], M[RQ], F[RQ], Wi[RQ], Si[RQ];
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int r = 0; r < RQ; ++r) P[r] = M[r] = F[r] = Wi[r] = Si[r] = 0;
+    }
+    __device__ __forceinline__ W (&p())[RQ] { return P; }
+    __device__ __forceinline__ W (&m())[RQ] { return M; }
+    __device__ __forceinline__ W (&f())[RQ] { return F; }
+    __device__ __forceinline__ W (&wi())[RQ] { return Wi; }
+    __device__ __forceinline__ W (&si())[RQ] { return Si; }
+    __device__ __forceinline__ void fold(int) {}
+    __device__ __forceinline__ W dw(int r) const { return (P[r] + M[r]) + Wi[r]; }           // W = P + M, S = P - M + F (+ the image deposits)
+    __device__ __forceinline__ W ds(int r) const { return ((P[r] - M[r]) + F[r]) + Si[r]; }
+};
+template <typename W, int RQ> struct TlAcc<W, RQ, true> {
+    W T[RQ], dW[RQ], dS[RQ];                                   // T is zero between two classes
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int r = 0; r < RQ; ++r) T[r] = dW[r] = dS[r] = 0;
+    }
+    __device__ __forceinline__ W (&p())[RQ] { return T; }
+    __device__ __forceinline__ W (&m())[RQ] { return T; }
+    __device__ __forceinline__ W (&f())[RQ] { return T; }
+    __device__ __forceinline__ W (&wi())[RQ] { return dW; }
+    __device__ __forceinline__ W (&si())[RQ] { return dS; }
+    __device__ __forceinline__ void fold(int cls) {
+#pragma unroll
+        for (int r = 0; r < RQ; ++r) {
+            if (cls != 2) dW[r] += T[r];
+            if (cls == 1) dS[r] -= T[r]; else dS[r] += T[r];
+            T[r] = 0;
+        }
+    }
+    __device__ __forceinline__ W dw(int r) const { return dW[r]; }
+    __device__ __forceinline__ W ds(int r) const { return dS[r]; }
+};
+
+// Eight waves, a deposit that found its pooled list full: the wave that holds it owns only half of the frame's rows, so it
+// adds the deposit to ALL rows of the field in LDS at once (nobody reads the field between barrier F and barrier B; the sums
+// are exact, the order is free).  W += w cW, S += w cS whatever the class.  IMAGE: an entry of the image list (both wall
+// images folded in, small boxes).
+template <int BC, int RS, bool F32, bool IMAGE>
+__device__ __forceinline__ void tl_one_direct(const uint32_t entry, const int x0, const int L, const int lane, const uint32_t tbase, const uint32_t tlen8,
+                                              const uint32_t L8, typename TsField<F32>::w_t *fieldW, typename TsField<F32>::w_t *fieldS) {
+    using W = typename TsField<F32>::w_t;
+    constexpr int SH = TsField<F32>::SH;
+    const uint32_t ent = (uint32_t)__builtin_amdgcn_readfirstlane((int)entry);
+    const uint32_t p8 = (ent & POS_MASK) << SH;
+    const int cw = (int)((ent >> 27) & 3u) - 1, cs = (int)(ent >> 29) - 2;
+#pragma unroll 1
+    for (int r = 0; r < RS; ++r) {
+        int s = x0 + r * 64 + lane;
+        if (BC == 1) { s %= L; if (s < 0) s += L; } else s = min(max(s, 0), L - 1);
+        const uint32_t x8 = ((uint32_t)s + TS_BIAS) << SH;
+        W w;
+        if (IMAGE) {
+            const uint32_t s8 = x8 + p8 + (1u << SH) - 2u * (TS_BIAS << SH);
+            w = ts_table_at<true, W>(nullptr, min(sad3s(x8, p8, 0u), tlen8) + tbase) + ts_table_at<true, W>(nullptr, min(min(s8, 2u * L8 - s8), tlen8) + tbase);
+        } else if (BC == 0) w = ts_table_at<true, W>(nullptr, sad3s(x8, p8, tbase));
+        else { const uint32_t d8 = sad3s(x8, p8, 0u); w = ts_table_at<true, W>(nullptr, min(min(d8, L8 - d8), tlen8) + tbase); }
+        W aw = 0, as = 0;
+        ts_acc(aw, w, cw); ts_acc(as, w, cs);
+        if (aw != 0) tl_lds_add(&fieldW[r * 64 + lane], aw);
+        if (as != 0) tl_lds_add(&fieldS[r * 64 + lane], as);
+    }
+}
+
+// Eight waves: the thread number as a value the compiler cannot follow from one iteration to the next.  Everything a lane derives from
+// it (its site, three dozen addresses of cells, records and lists) is then worked out again in every iteration, a few dozen instructions,
+// instead of being kept in registers across the sweep -- which is what sends a kernel of 128 VGPRs to scratch.  Four waves: the identity.
+template <bool FRESH> __device__ __forceinline__ int tl_fresh(int v) {
+    if constexpr (FRESH) asm volatile("" : "+v"(v));
+    return v;
+}
+
+// NW waves per tile.  4: every wave sweeps all RS rows of the frame (two waves per SIMD for every instance: the loop runs with exactly two
+// workgroups per CU where the geometry is chosen for it, and at three the smaller frames spilled up to 200 bytes per lane to scratch).
+// 8 (binary64, K = 1): waves 0-3 sweep rows 0 .. RH-1 and waves 4-7 rows RH .. RS-1, both quads drawing the same groups from the pooled
+// lists; four waves per SIMD at two workgroups per CU, hence 128 VGPRs.  IMG: the image list of small boxes is compiled in.
+template <int BC, int RS, bool K1, bool F32, int NW = 4, bool IMG = true>
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop(const LoopArgs la, const void *__restrict__ table_v) {
     using W = typename TsField<F32>::w_t;
     using WS = typename TsField<F32>::ws_t;
     constexpr int SH = TsField<F32>::SH, WB = (int)sizeof(W);
     constexpr bool TAB_LDS = true;
+    constexpr bool WIDE = NW == 8;
+    constexpr int NT = NW * 64, RH = WIDE ? (RS + 1) / 2 : RS, TL_NG = tl_ng(NW);
+    static_assert(NW == 4 || NW == 8, "four or eight waves");
     const TileArgs &a = la.a;
     const W *__restrict__ table_g = reinterpret_cast<const W *>(table_v);
-    constexpr int TS = 64 * RS, NOLD = (TS + FU_THREADS - 1) / FU_THREADS;
-    constexpr int NSLOT = 16, GB = FU_WAVES * 4;
+    constexpr int TS = 64 * RS, NOLD = (TS + NT - 1) / NT;
+    constexpr int NSLOT = 16, GB = NW * 4;
     const int SEG = la.seg;
     extern __shared__ double lds[];
     const int L = a.L, K = K1 ? 1 : a.K, OWN = a.own;
-    const TlLds lay = tl_lds_layout(a.tlen, RS, OWN, K, WB, la.seg);
+    const TlLds lay = tl_lds_layout(a.tlen, RS, OWN, K, WB, la.seg, NW);
     char *lds_c = reinterpret_cast<char *>(lds);
-    uint32_t *seg_all = reinterpret_cast<uint32_t *>(lds_c + lay.seg);          // the pooled deposit lists: [4 classes][4 (seg + 4) entries]
+    uint32_t *seg_all = reinterpret_cast<uint32_t *>(lds_c + lay.seg);          // the pooled deposit lists: [4 classes][NW (seg + 4) entries]
     uint32_t *cellL = reinterpret_cast<uint32_t *>(lds_c + lay.cells);       // [(TS + 2) K]: frame positions -1 .. TS
     uint32_t *cellN = reinterpret_cast<uint32_t *>(lds_c + lay.cells2);      // K > 1: the cells after this step
     uint8_t *propL = reinterpret_cast<uint8_t *>(lds_c + lay.props);         // [TS K]
@@ -135,7 +225,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
     {   // the table, once per call (LDS-direct loads; the global copy is followed by zeros: the padded tail comes along)
         const int nchunk = ts_table_chunks(a.tlen, RS, OWN, WB);
         const char *srct = reinterpret_cast<const char *>(table_g) + lane * 16;
-        for (int c = wave; c < nchunk; c += FU_WAVES) {
+        for (int c = wave; c < nchunk; c += NW) {
             const uint32_t m0v = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tbase + (uint32_t)c * 1024u));
             asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(m0v), "v"(srct + c * 1024) : "memory");
         }
@@ -148,7 +238,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
         return (s < 0 || s >= L) ? -1 : s;
     };
     const int ncell = (TS + 2) * K;
-    for (int c = t; c < ncell; c += FU_THREADS) {              // the frame's cells (+1 site either side) as the call finds them
+    for (int c = t; c < ncell; c += NT) {                      // the frame's cells (+1 site either side) as the call finds them
         const int s = frame_site(c / K - 1);
         const uint32_t v = cell_e[(unsigned)max(s, 0) * (unsigned)K + (unsigned)(c % K)];
         cellL[c] = s >= 0 ? v : CELL_EMPTY;
@@ -156,7 +246,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
     }
 #pragma unroll
     for (int r = 0; r < NOLD; ++r) {                           // and its field
-        const int xi = r * FU_THREADS + t;
+        const int xi = r * NT + t;
         if (xi < TS) {
             const int s = xi < nfr ? frame_site(xi) : -1;
             WS o = ws_e[(unsigned)max(s, 0)];
@@ -164,7 +254,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
             fieldW[xi] = o.x; fieldS[xi] = o.y;
         }
     }
-    for (int i = t; i < (TS * K + 3) / 4; i += FU_THREADS) reinterpret_cast<uint32_t *>(propL)[i] = 0u;
+    for (int i = t; i < (TS * K + 3) / 4; i += NT) reinterpret_cast<uint32_t *>(propL)[i] = 0u;
     // buckets (= tiles) whose deposits can reach the frame: one run of nbk buckets from b0 that may wrap around the torus
     int b0 = 0, nbk = 0;
     if (BC == 0) {
@@ -182,13 +272,15 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
         }
     }
     const bool wall = BC == 0 && ((x0c + 1 <= Rt) || (L - x1c <= Rt));
-    const bool mirror_ok = 2 * Rt + TS + OWN + 4 < L;
+    const bool mirror_ok = IMG ? 2 * Rt + TS + OWN + 4 < L : true;   // (!IMG: the host picks that instance only where this holds)
     const int sub = lane >> 4, slot = lane & (NSLOT - 1);
     const uint32_t tlen8 = (uint32_t)a.tlen << SH, L8 = (uint32_t)L << SH;
-    uint32_t x8[RS];
+    // the rows this wave sweeps: all of them, or its quad's half (an odd RS: the upper quad has one row less, x8[RH - 1] is not used there)
+    const int quad = WIDE ? wave >> 2 : 0, wq = WIDE ? wave & (TL_QW - 1) : wave, row0 = quad * RH;
+    uint32_t x8[RH];
 #pragma unroll
-    for (int r = 0; r < RS; ++r) {
-        int s = x0 + r * 64 + lane;
+    for (int r = 0; r < RH; ++r) {
+        int s = x0 + min(row0 + r, RS - 1) * 64 + lane;
         if (BC == 1) { s %= L; if (s < 0) s += L; } else s = min(max(s, 0), L - 1);
         x8[r] = ((uint32_t)s + TS_BIAS) << SH;
     }
@@ -213,12 +305,12 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
     };
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's table chunks have landed
     __syncthreads();                                           // cells staged
-    for (int i = t; i < TS + 2; i += FU_THREADS) {
+    for (int i = t; i < TS + 2; i += NT) {
         int n = 0;
         for (int k = 0; k < K; ++k) n += cellL[i * K + k] != CELL_EMPTY;
         occL[i] = (uint8_t)n;
     }
-    for (int c0 = 0; c0 < ncell; c0 += FU_THREADS) {           // uniform trip count
+    for (int c0 = 0; c0 < ncell; c0 += NT) {                   // uniform trip count
         const int c = c0 + t;
         const int pos = K1 ? c - 1 : c / K - 1, k = K1 ? 0 : c - (pos + 1) * K;
         const uint32_t cw = c < ncell ? cellL[c] : CELL_EMPTY;
@@ -238,17 +330,20 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
     unsigned long long xg[TL_NG], xh = 0;
 #pragma unroll
     for (int g = 0; g < TL_NG; ++g) xg[g] = 0;
-    const int h_side = lane >> 5, h_i = lane & 31;             // lanes 0..3K-1: left neighbour's LAST three sites; 32..: right neighbour's FIRST three
-    const int h_nb = h_side ? nb_r : nb_l;
-    const bool h_act = wave == FU_WAVES - 1 && h_i < 3 * K && h_nb >= 0;
-    auto bucket_of = [&](int j, bool &ok) -> int {
-        const int bi = j * GB + sub * FU_WAVES + wave;
+    // (lanes 0..3K-1 of the last wave: left neighbour's LAST three sites; 32..: right neighbour's FIRST three -- h_side, h_i in the loop)
+    const int lane_call = lane;
+    auto bucket_of = [&](int j, int sub, bool &ok) -> int {
+        const int bi = j * GB + sub * NW + wave;
         ok = j < ngroups && bi < nbk;
         int b = b0 + (ok ? bi : 0);
         if (b >= a.ntile) b -= a.ntile;
         return b;
     };
+    const int t_call = t;
     for (int it = 0; it < n_iter; ++it) {
+        const int t = tl_fresh<WIDE>(t_call), lane = WIDE ? t & 63 : lane_call, sub = lane >> 4, slot = lane & (NSLOT - 1);
+        const int h_side = lane >> 5, h_i = lane & 31, h_nb = h_side ? nb_r : nb_l;
+        const bool h_act = wave == NW - 1 && h_i < 3 * K && h_nb >= 0;
         const unsigned long long step = la.step0 + (unsigned long long)it;
         const uint32_t tag_in = la.tag0 + (uint32_t)it, tag_out = tag_in + 1u;
         const bool first = it == 0, last = it + 1 == la.nsteps;
@@ -296,7 +391,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
 #pragma unroll
                 for (int g = 0; g < TL_NG; ++g) {
                     bool ok;
-                    const int b = bucket_of(g, ok);
+                    const int b = bucket_of(g, sub, ok);
                     if (ok && (uint32_t)(xg[g] >> 32) != tag_in) {
                         xg[g] = tl_load_granule(rec_in + (size_t)b * la.rec + slot);
                         bad |= (uint32_t)(xg[g] >> 32) != tag_in;
@@ -311,7 +406,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
             }
             // the neighbours' boundary cells: frame positions -1, 0, 1 and own_n + 2 .. own_n + 4 -- occupancy, and the
             // particles of the four halo sites join the list
-            if (wave == FU_WAVES - 1 && !gave_up) {
+            if (wave == NW - 1 && !gave_up) {
                 const uint32_t v = h_act ? (uint32_t)xh : CELL_EMPTY;
                 const int hs = h_i / K, hk = h_i - hs * K, pos = (h_side ? own_n + 2 : -1) + hs;
                 if (h_act) cellL[(h_side ? (own_n + 3) * K : 0) + h_i] = v;
@@ -327,40 +422,42 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
         }
         TLSTAMP(0)
         // ------------------------------------------------------------ 1  deposits of the previous step -> W, S of the frame
-        W accP[RS], accM[RS], accF[RS], accWi[RS], accSi[RS];
-#pragma unroll
-        for (int r = 0; r < RS; ++r) accP[r] = accM[r] = accF[r] = accWi[r] = accSi[r] = 0;
-        // The four waves POOL the deposits of their buckets into one list per class (P, M, F; I: image terms of a small box) --
+        TlAcc<W, RS, false> acc;                               // four waves (eight: a set per quad, declared where the lists are swept)
+        if constexpr (!WIDE) acc.clear();
+        // The waves POOL the deposits of their buckets into one list per class (P, M, F; I: image terms of a small box) --
         // one packed LDS atomic per wave and round hands out the slots -- and after a barrier take whole groups of four from the
         // lists in turn: every wave sweeps the same number of groups whatever its buckets held (a wave's own ~7 buckets vary
         // by +-16 %), and a list is padded once, not once per wave.  An entry that finds its list full is swept at once by
         // the wave that holds it.
         uint32_t *shl = seg_all;                               // [4][CAP]
-        const int CAP = (FU_WAVES * 4 * (SEG + 4) / 4) & ~3;
+        const int CAP = (NW * 4 * (SEG + 4) / 4) & ~3;
         unsigned long long *shcnt = reinterpret_cast<unsigned long long *>(misc + 8 + 2 * (it & 1));   // packed list lengths: 16 bits each
         auto sweep_now = [&](unsigned long long m, const uint32_t word, const int cls) {   // overflow: one by one (never in practice)
             while (m) {
                 const int src_lane = __builtin_ctzll(m);
                 m &= m - 1;
                 const uint32_t e1 = (uint32_t)__builtin_amdgcn_readlane((int)word, src_lane);
-                if (BC == 0) {
-                    if (cls == 0) ts_one_abs<RS, 0, F32>(e1, x8, tb, accP);
-                    else if (cls == 1) ts_one_abs<RS, 0, F32>(e1, x8, tb, accM);
-                    else if (cls == 2) ts_one_abs<RS, 1, F32>(e1, x8, tb, accF);
+                if constexpr (WIDE) {                          // this wave sweeps half of the rows only: straight into the field, all rows
+                    if (IMG && cls == 3) tl_one_direct<BC, RS, F32, true>(e1, x0, L, lane, tb, tlen8, L8, fieldW, fieldS);
+                    else tl_one_direct<BC, RS, F32, false>(e1, x0, L, lane, tb, tlen8, L8, fieldW, fieldS);
+                } else if (BC == 0) {
+                    if (cls == 0) ts_one_abs<RS, 0, F32>(e1, x8, tb, acc.p());
+                    else if (cls == 1) ts_one_abs<RS, 0, F32>(e1, x8, tb, acc.m());
+                    else if (cls == 2) ts_one_abs<RS, 1, F32>(e1, x8, tb, acc.f());
                     else ts_image_group<TAB_LDS, RS, F32>(make_uint4(e1, DEP_NULL | ((uint32_t)x0c + TS_BIAS), DEP_NULL | ((uint32_t)x0c + TS_BIAS), DEP_NULL | ((uint32_t)x0c + TS_BIAS)),
-                                                          x8, tb, table_g, tlen8, L8, accWi, accSi);
+                                                          x8, tb, table_g, tlen8, L8, acc.wi(), acc.si());
                 } else {
                     const uint4 q = make_uint4(e1, DEP_NULL | ((uint32_t)null_site + TS_BIAS), DEP_NULL | ((uint32_t)null_site + TS_BIAS), DEP_NULL | ((uint32_t)null_site + TS_BIAS));
-                    if (cls == 0) ts_group<1, TAB_LDS, RS, 0, F32>(q, x8, tb, table_g, tlen8, L8, accP);
-                    else if (cls == 1) ts_group<1, TAB_LDS, RS, 0, F32>(q, x8, tb, table_g, tlen8, L8, accM);
-                    else ts_group<1, TAB_LDS, RS, 1, F32>(q, x8, tb, table_g, tlen8, L8, accF);
+                    if (cls == 0) ts_group<1, TAB_LDS, RS, 0, F32>(q, x8, tb, table_g, tlen8, L8, acc.p());
+                    else if (cls == 1) ts_group<1, TAB_LDS, RS, 0, F32>(q, x8, tb, table_g, tlen8, L8, acc.m());
+                    else ts_group<1, TAB_LDS, RS, 1, F32>(q, x8, tb, table_g, tlen8, L8, acc.f());
                 }
             }
         };
 #pragma unroll 1
         for (int j = 0; j < ngroups && !gave_up; ++j) {
             bool ok;
-            const int b = bucket_of(j, ok);
+            const int b = bucket_of(j, sub, ok);
             uint32_t cnt = 0u;
             if (first) { cnt = min(dcnt_e[(unsigned)b], (uint32_t)a.dcap); if (!ok) cnt = 0u; }   // the lists the previous launch left in the plain arrays
             const unsigned long long *rb = rec_in + (size_t)b * la.rec;                             // else: the records of the previous iteration
@@ -446,56 +543,66 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
         __syncthreads();                                       // S: the lists are complete
         TLSTAMP(9)
         if (misc[TL_ABORT]) return;                            // uniform: some wait ran out (here or in another workgroup)
-        {
+        // the lists, class by class, into the rows of this wave (RQ of them from row0 on), then into the frame's field
+        auto sweep_lists = [&](auto rq_c, auto &ac) {
+            constexpr int RQ = decltype(rq_c)::value;
+            uint32_t xq[RQ];
+#pragma unroll
+            for (int r = 0; r < RQ; ++r) xq[r] = x8[r];
             const unsigned long long tot = *shcnt;
             const int nP = min((int)(tot & 0xFFFFu), CAP), nM = min((int)((tot >> 16) & 0xFFFFu), CAP), nF = min((int)((tot >> 32) & 0xFFFFu), CAP),
                       nI = min((int)(tot >> 48), CAP);
             const uint32_t nullw = DEP_NULL | ((uint32_t)null_site + TS_BIAS);
-            int rot = wave;                                    // whole groups of four are dealt round-robin across the lists
+            int rot = wq;                                      // whole groups of four are dealt round-robin across the lists (to the waves of a quad)
 #define TL_SHARED(CLS, N, CALL4) { \
             const int ng_ = ((N) + 3) >> 2; \
             const uint4 *l4 = reinterpret_cast<const uint4 *>(shl + (CLS) * CAP); \
             int g = rot & 3; \
             uint4 q = l4[min(g, CAP / 4 - 1)]; \
-            _Pragma("unroll 1") for (; g < ng_; g += FU_WAVES) { \
-                const uint4 qn = l4[min(g + FU_WAVES, CAP / 4 - 1)]; \
+            _Pragma("unroll 1") for (; g < ng_; g += TL_QW) { \
+                const uint4 qn = l4[min(g + TL_QW, CAP / 4 - 1)]; \
                 if (4 * g + 3 >= (N)) {                        /* the list's last group: null deposits behind its end */ \
                     if (4 * g + 1 >= (N)) q.y = nullw; \
                     if (4 * g + 2 >= (N)) q.z = nullw; \
                     q.w = nullw; } \
                 CALL4; \
                 q = qn; } \
+            ac.fold(CLS); \
             rot = (rot - ng_) & 3; }
             if (BC == 1) {
-                TL_SHARED(0, nP, (ts_group<1, TAB_LDS, RS, 0, F32>(q, x8, tb, table_g, tlen8, L8, accP)))
-                TL_SHARED(1, nM, (ts_group<1, TAB_LDS, RS, 0, F32>(q, x8, tb, table_g, tlen8, L8, accM)))
-                TL_SHARED(2, nF, (ts_group<1, TAB_LDS, RS, 1, F32>(q, x8, tb, table_g, tlen8, L8, accF)))
+                TL_SHARED(0, nP, (ts_group<1, TAB_LDS, RQ, 0, F32>(q, xq, tb, table_g, tlen8, L8, ac.p())))
+                TL_SHARED(1, nM, (ts_group<1, TAB_LDS, RQ, 0, F32>(q, xq, tb, table_g, tlen8, L8, ac.m())))
+                TL_SHARED(2, nF, (ts_group<1, TAB_LDS, RQ, 1, F32>(q, xq, tb, table_g, tlen8, L8, ac.f())))
             } else {
-                TL_SHARED(0, nP, (ts_group<0, TAB_LDS, RS, 0, F32>(q, x8, tb, table_g, tlen8, L8, accP)))
-                TL_SHARED(1, nM, (ts_group<0, TAB_LDS, RS, 0, F32>(q, x8, tb, table_g, tlen8, L8, accM)))
-                TL_SHARED(2, nF, (ts_group<0, TAB_LDS, RS, 1, F32>(q, x8, tb, table_g, tlen8, L8, accF)))
+                TL_SHARED(0, nP, (ts_group<0, TAB_LDS, RQ, 0, F32>(q, xq, tb, table_g, tlen8, L8, ac.p())))
+                TL_SHARED(1, nM, (ts_group<0, TAB_LDS, RQ, 0, F32>(q, xq, tb, table_g, tlen8, L8, ac.m())))
+                TL_SHARED(2, nF, (ts_group<0, TAB_LDS, RQ, 1, F32>(q, xq, tb, table_g, tlen8, L8, ac.f())))
             }
 #undef TL_SHARED
-            if (nI) {
+            if (IMG && nI) {
                 const uint32_t nulli = DEP_NULL | ((uint32_t)x0c + TS_BIAS);
                 const uint4 *l4 = reinterpret_cast<const uint4 *>(shl + 3 * CAP);
 #pragma unroll 1
-                for (int g = rot & 3; g < (nI + 3) >> 2; g += FU_WAVES) {
+                for (int g = rot & 3; g < (nI + 3) >> 2; g += TL_QW) {
                     uint4 q = l4[g];
                     if (4 * g + 1 >= nI) q.y = nulli;
                     if (4 * g + 2 >= nI) q.z = nulli;
                     if (4 * g + 3 >= nI) q.w = nulli;
-                    ts_image_group<TAB_LDS, RS, F32>(q, x8, tb, table_g, tlen8, L8, accWi, accSi);
+                    ts_image_group<TAB_LDS, RQ, F32>(q, xq, tb, table_g, tlen8, L8, ac.wi(), ac.si());
                 }
             }
-        }
-        TLSTAMP(10)
+            TLSTAMP(10)
 #pragma unroll
-        for (int r = 0; r < RS; ++r) {                         // W = P + M, S = P - M + F (+ the image deposits), exact on the weight grid
-            const W dw = (accP[r] + accM[r]) + accWi[r], ds = ((accP[r] - accM[r]) + accF[r]) + accSi[r];
-            if (dw != 0) tl_lds_add(&fieldW[r * 64 + lane], dw);
-            if (ds != 0) tl_lds_add(&fieldS[r * 64 + lane], ds);
-        }
+            for (int r = 0; r < RQ; ++r) {                     // exact on the weight grid
+                const W dw = ac.dw(r), ds = ac.ds(r);
+                if (dw != 0) tl_lds_add(&fieldW[(row0 + r) * 64 + lane], dw);
+                if (ds != 0) tl_lds_add(&fieldS[(row0 + r) * 64 + lane], ds);
+            }
+        };
+        if constexpr (WIDE) {
+            if (quad == 0) { TlAcc<W, RH, true> ac; ac.clear(); sweep_lists(TlInt<RH>{}, ac); }
+            else { TlAcc<W, RS - RH, true> ac; ac.clear(); sweep_lists(TlInt<RS - RH>{}, ac); }
+        } else sweep_lists(TlInt<RS>{}, acc);
         TLSTAMP(11)
         __syncthreads();                                       // B: field, cells, occupancy and particle list of the frame complete
         TLSTAMP(7)
@@ -517,7 +624,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
                 }
                 propose_one(mine, rx);
             }
-            for (int j = FU_THREADS + t; j < n_part; j += FU_THREADS) {   // more than 256 particles on the frame
+            for (int j = NT + t; j < n_part; j += NT) {        // more particles on the frame than threads
                 const uint2 pc = plist[j];
                 uint32_t x[4];
                 philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), pc.y & CELL_ID, (uint32_t)(a.ens_base + e), a.seed_lo, a.seed_hi, x);
@@ -554,7 +661,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
 #pragma unroll
         for (int r = 0; r < NOLD; ++r) {
             newc[r] = CELL_EMPTY; newn[r] = 0;
-            const int xi = r * FU_THREADS + t;
+            const int xi = r * NT + t;
             if (xi < 2 || xi >= 2 + own_n || xi >= TS) continue;
             const int s = frame_site(xi);
             if constexpr (K1) {
@@ -642,7 +749,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
         int *pnext = misc + 2 + ((it + 1) & 1);
 #pragma unroll
         for (int r = 0; r < NOLD; ++r) {
-            const int xi = r * FU_THREADS + t;
+            const int xi = r * NT + t;
             const bool mine_site = !(xi < 2 || xi >= 2 + own_n || xi >= TS);
             const int io = xi - 2;
             for (int k = 0; k < K; ++k) {                      // (uniform trip count: the list's ballots)
@@ -670,7 +777,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
             const int idx = count + t;
             if (idx < (count / NSLOT + 1) * NSLOT && idx < la.drec) tl_store_granule(rec_out + idx, tag_out, DEP_NULL);
         }
-        for (int i = t; i < (TS * K + 3) / 4; i += FU_THREADS) reinterpret_cast<uint32_t *>(propL)[i] = 0u;
+        for (int i = t; i < (TS * K + 3) / 4; i += NT) reinterpret_cast<uint32_t *>(propL)[i] = 0u;
         if (t == 0) {
             misc[(it + 1) & 1] = 0;                            // the next iteration's deposit counter (this one's is still being read)
             misc[2 + (it & 1)] = 0; misc[4 + (it & 1)] = 0;    // this iteration's particle counters: used again in two iterations
@@ -685,7 +792,7 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
 #pragma unroll
             for (int g = 0; g < TL_NG; ++g) {
                 bool ok;
-                const int b = bucket_of(g, ok);
+                const int b = bucket_of(g, sub, ok);
                 xg[g] = ok ? tl_load_granule(rn + (size_t)b * la.rec + slot) : 0ull;
             }
             xh = h_act ? tl_load_granule(rn + (size_t)h_nb * la.rec + la.drec + (h_side ? 0 : 3 * K) + h_i) : 0ull;
@@ -694,8 +801,8 @@ __global__ __launch_bounds__(FU_THREADS, TL_MIN_WAVES) void tile_loop(const Loop
         __syncthreads();                                       // F: list and occupancy of the owned sites complete
     }
 #ifdef APS_LOOP_STAMPS
-    if (lane == 0 && tile < 512 && e == 0) {                   // [tile][wave][16]
-        unsigned long long *o = a.rare->stamps + ((size_t)tile * FU_WAVES + wave) * 16;
+    if (lane == 0 && tile < 2048 / NW && e == 0) {             // [tile][wave][16], as many tiles as the buffer of 8 * 4096 words holds
+        unsigned long long *o = a.rare->stamps + ((size_t)tile * NW + wave) * 16;
         for (int k = 0; k < 12; ++k) o[k] = st_acc[k];
         o[6] = __builtin_amdgcn_s_memtime() - st_begin;
         o[1] = st_acc[8] + st_acc[9] + st_acc[10] + st_acc[11];

@@ -293,9 +293,12 @@ int aps_tiles_info(aps_handle *h, int32_t *frame_sites, int32_t *owned_sites, in
  * (replaces the loop of ParticleSystem.run, PARTICLE_solver_CLASS.py:511-516, like aps_step itself).  on = 0 keeps a handle
  * on one launch per step; default 1 (used when eligible).  aps_loop_info: steps of the last aps_step call taken inside the
  * loop; state 1 usable, 0 not eligible, -1 a call gave up (the steps were repeated the ordinary way; not tried again),
- * -2 not looked at yet; `why` receives the reason when the loop is not used. */
+ * -2 not looked at yet; `why` receives the reason when the loop is not used.  aps_loop_waves: waves per tile of the loop
+ * kernel this handle uses, 4 or 8 (8: binary64, K = 1, frames of 5 to 8 rows, by default where two workgroups share every
+ * CU; the environment variable APS_LOOP_WAVES=4|8 forces the choice where the kernel exists); 0 while no kernel is chosen. */
 int aps_set_resident_loop(aps_handle *h, int32_t on);
 int aps_loop_info(aps_handle *h, int64_t *loop_steps, int32_t *state, char *why, int32_t why_len);
+int aps_loop_waves(aps_handle *h, int32_t *waves);
 /* Measurement: aps_step(nsteps) with HIP start/stop events attached to the resident loop's own dispatch; returns that
  * launch's duration and the steps it took (0 / 0.0 when the call did not use the loop). */
 int aps_step_loop_timed(aps_handle *h, int64_t nsteps, double *kernel_ms, int64_t *loop_steps);

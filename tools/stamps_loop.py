@@ -29,14 +29,15 @@ buf = np.zeros(8 * 4096, dtype=np.uint64)
 fn = h.lib.aps_debug_stamps
 fn.restype = C.c_int
 fn(h._h, buf.ctypes.data_as(C.c_void_p), C.c_int64(len(buf)))
-allw = buf.reshape(-1, 4, 16).astype(float) / steps          # [tile][wave][16]
+NW = h.loop_waves() or 4                                     # waves per tile of the kernel that ran (APS_LOOP_WAVES=4|8 forces the choice)
+allw = buf.reshape(-1, NW, 16).astype(float) / steps         # [tile][wave][16]
 idxt = np.flatnonzero(allw[:, 0, 6] > 0)
 allw = allw[idxt]
 NAMES = ((2, "barrier F + random numbers"), (0, "wait for the records"), (8, "intake (pooling)"), (9, "barrier S"), (10, "sweep"), (11, "ds_add into the field"),
          (7, "barrier B"), (3, "proposals (D)"), (4, "exclusion (E)"), (5, "hand over + ask ahead"), (6, "total"))
-print("workgroups", len(allw), "; cycles per iteration (s_memtime), per wave: mean over tiles [wave 0, 1, 2, 3]")
+print("workgroups", len(allw), f"of {NW} waves; cycles per iteration (s_memtime), per wave: mean over tiles [wave 0 .. {NW - 1}]")
 for k, name in NAMES:
-    print(f"  {name:28s} " + "  ".join(f"{allw[:, wv, k].mean():9.1f}" for wv in range(4)) + f"   | max over waves, mean over tiles {allw[:, :, k].max(axis=1).mean():9.1f}")
+    print(f"  {name:28s} " + "  ".join(f"{allw[:, wv, k].mean():9.1f}" for wv in range(NW)) + f"   | max over waves, mean over tiles {allw[:, :, k].max(axis=1).mean():9.1f}")
 st = np.zeros((len(allw), 8))
 st[:, :8] = allw[:, 0, :8]
 idx = idxt
