@@ -1,4 +1,5 @@
-// gillespie_big_hip.hip -- gil_run_large of include/gillespie.h and gilm_run of include/gillespie_many.h: the reference's
+// gillespie_big_hip.hip -- gil_run_large of include/gillespie.h, gilm_run of include/gillespie_many.h and the large shape of
+// gils_run, gilc_run, gilp_run and gilrm_run: the reference's
 // exact event loop (PARTICLE_solver_CLASS.py:511-538) for systems far too large for a workgroup's LDS (the BASELINE size:
 // N = 1e5 particles on L = 2e5 sites, where the reference manages 0.8 events/s because it recomputes the whole
 // field and all N rates before every event).  One kernel and one host driver serve both entry points: a batch is a grid
@@ -15,6 +16,8 @@
 // Event semantics, threshold order, exit handling and observation timing are those of gillespie_hip.hip (same
 // channels() device function, same draws).  Parity: same-uniforms trajectories against the oracle and against the
 // LDS-resident kernel (tests/test_gpu_gillespie.py).
+// Host side: gil_large_run takes the call record of gillespie_common.hpp (GilIo, GilExtras) and stages through its helpers; the entry
+// points of gillespie_hip.hip that fall to this shape call it and gil_large_plan.
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -22,7 +25,6 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "gillespie.h"
@@ -40,7 +42,6 @@ constexpr int BT = 1024, BW = BT / 64;      // threads, waves of the workgroup
 constexpr int PB = 256;                     // particles per rate block
 constexpr int MAX_NB = 4096;                // rate blocks (N <= 2^20)
 constexpr int TAB_LDS_MAX = 10000;          // table entries kept in LDS
-constexpr int64_t MAX_BYTES = 1ll << 38;    // work + output bytes a plan accepts without asking a device
 std::string g_big_err, g_many_err;
 enum { F_PLUS = 1, F_BOUND = 2, F_ALIVE = 4 };
 enum { GS_N = 0, GS_SPIN, GS_POS, GS_WALL, GS_MAXPOS, GS_FRONT, GS_ATTEMPT, GS_BLOCKED, GS_DISP, GS_DISP2, GS_NDISP, GS_EVENTS };
@@ -222,20 +223,26 @@ struct GilcBigArgs : GilsBigArgs { GilcArgs cp; };          // arguments of the 
 struct GilpBigArgs : GilcBigArgs { GilpArgs pf; };          // arguments of the profile instantiation (the driver's one struct)
 struct GilrBigArgs : BigArgs { GilrArgs rs; };              // arguments of the resumable instantiation
 
-// ST = also reduce the structure sums at an observation (gillespie_structure.hpp): a compile-time property, so that the
-// kernel without it is the code it was before they existed.
-// CP = anchor capture and cluster statistics (gillespie_capture.hpp), likewise; not combined with ST.  Its slots lie behind
-// ctl[] in LDS, its bind times in global memory; the event loop holds no register for either.
-// PF = ensemble density and field profiles (gillespie_profile.hpp), likewise; not combined with ST or CP.  Its slots lie
-// behind ctl[] in LDS and are used at an observation only.
-// RS = a resumable launch (gillespie_resume.hpp): the start state is a checkpoint (pos0 / sigma0 as big_field_init_live reads them,
-// n0 = n_cap: any slot may be alive; flags, origins, clock, event count and first row from a0.rs), likewise; combined with none
-// of the others.  The end state is the global scratch itself (pos, flg, ref), which the driver reads back.
-template <bool ST, bool CP = false, bool PF = false, bool RS = false>
-__global__ __launch_bounds__(BT) void gil_big_kernel(const std::conditional_t<RS, GilrBigArgs, std::conditional_t<PF, GilpBigArgs, std::conditional_t<CP, GilcBigArgs, std::conditional_t<ST, GilsBigArgs, BigArgs>>>> a0) {
-    static_assert(!(RS && (ST || CP || PF)), "the resumable launch takes none of the other sums");
-    static_assert(!(ST && CP), "the capture launch takes no structure sums");
-    static_assert(!(PF && (ST || CP)), "the profile launch takes no structure sums and no capture statistics");
+// the argument struct of each variant of the large-system kernel (it takes no mixed batches)
+template <GilKind V> struct BigKernelArgs;
+template <> struct BigKernelArgs<GilKind::Plain> { using type = BigArgs; };
+template <> struct BigKernelArgs<GilKind::Structure> { using type = GilsBigArgs; };
+template <> struct BigKernelArgs<GilKind::Capture> { using type = GilcBigArgs; };
+template <> struct BigKernelArgs<GilKind::Profile> { using type = GilpBigArgs; };
+template <> struct BigKernelArgs<GilKind::Resume> { using type = GilrBigArgs; };
+
+// V = the variant, a compile-time property, so that each kernel is the code it was before the others existed:
+//   Structure  also reduce the structure sums at an observation (gillespie_structure.hpp);
+//   Capture    anchor capture and cluster statistics (gillespie_capture.hpp).  Its slots lie behind ctl[] in LDS, its bind times
+//              in global memory; the event loop holds no register for either;
+//   Profile    ensemble density and field profiles (gillespie_profile.hpp).  Its slots lie behind ctl[] in LDS and are used at an
+//              observation only;
+//   Resume     a resumable launch (gillespie_resume.hpp): the start state is a checkpoint (pos0 / sigma0 as big_field_init_live
+//              reads them, n0 = n_cap: any slot may be alive; flags, origins, clock, event count and first row from a0.rs).  The
+//              end state is the global scratch itself (pos, flg, ref), which the driver reads back.
+template <GilKind V>
+__global__ __launch_bounds__(BT) void gil_big_kernel(const typename BigKernelArgs<V>::type a0) {
+    constexpr bool ST = V == GilKind::Structure, CP = V == GilKind::Capture, PF = V == GilKind::Profile, RS = V == GilKind::Resume;
     extern __shared__ double lds[];
     BigArgs a = a0;
     select_system(a, (size_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x));
@@ -648,214 +655,111 @@ int big_plan(const char *who, std::string &err, const gil_params *p, bool want_s
     // states: pos (int) + sigma + flags per slot and observation; scalars; exits; n_recorded, n_events, t_final, n_exits
     info.output_bytes = (want_states ? S * O * N * 6 : 0) + (want_scalars ? S * O * GIL_NSCALARS * 8 : 0) + S * N * 24 + S * 24;
     if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
-    if (S * info.work_bytes_per_system + info.output_bytes > MAX_BYTES)
+    if (S * info.work_bytes_per_system + info.output_bytes > GIL_PLAN_MAX_BYTES)
         return bad("the batch needs " + std::to_string(S * info.work_bytes_per_system) + " bytes of work memory and " +
-                   std::to_string(info.output_bytes) + " bytes of outputs, more than the " + std::to_string(MAX_BYTES) + " bytes a plan accepts");
+                   std::to_string(info.output_bytes) + " bytes of outputs, more than the " + std::to_string(GIL_PLAN_MAX_BYTES) + " bytes a plan accepts");
     if (out) *out = info;
     if (table) *table = std::move(tab);
     return GIL_OK;
 }
 
-// The one host driver of the large-system kernel: S = p->n_systems systems, one workgroup each.  The callers have checked
-// their required pointers and S.  pos0 / sigma0 / bound0 hold [S][n_cap] entries (a single system: its n0[0] particles).
-int big_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
-            const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
-            int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
-            int k_max = 0, int first_obs = 0, double *structure_obs = nullptr, const GilcCall *cap = nullptr, const GilpCall *prof = nullptr,
-            GilrCall *rs = nullptr) {
+// The large-system kernel of variant V: the one place that names the instantiation.  Raises its LDS limit and launches it; the
+// timed window holds this launch alone.
+template <GilKind V>
+int big_launch(OneShot &job, int S, size_t lds, const typename BigKernelArgs<V>::type &a) {
+    const auto kernel = &gil_big_kernel<V>;
+    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(kernel), lds)) return rc;
+    job.ev.start();
+    hipLaunchKernelGGL(kernel, dim3((unsigned)S), dim3(BT), lds, nullptr, a);
+    job.ev.stop();
+    return 0;
+}
+
+}  // namespace
+
+// The one host driver of the large-system kernel (hidden: the entry points of gillespie_hip.hip call it too): S = p->n_systems
+// systems, one workgroup each.  The callers have checked their required pointers and S.  pos0 / sigma0 / bound0 hold [S][n_cap]
+// entries (a single system: its n0[0] particles).
+int gil_large_run(const char *who, std::string &err, const gil_params *p, const GilIo &io, const GilExtras &ex) {
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilm_plan_info info{};
     std::vector<double> table;
-    if (int rc = big_plan(who, err, p, pos_obs || sigma_obs || flags_obs, scalars_obs != nullptr, &info, &table)) return rc;
+    if (int rc = big_plan(who, err, p, io.states(), io.scalars_obs != nullptr, &info, &table)) return rc;
     const int S = p->n_systems, L = p->L, N = p->n_cap;
-    const size_t row = 4 + 2 * (size_t)k_max;                 // of structure sums (gils_run)
-    if (structure_obs) {
+    const GilcCall *cap = ex.cap; const GilpCall *prof = ex.prof; GilrCall *rs = ex.rs;
+    if (ex.structure_obs) {                                   // rows of structure sums (gils_run)
         info.lds_bytes += (int32_t)(gils_lds_doubles(BT) * sizeof(double));
-        info.output_bytes += (int64_t)S * p->n_obs * (int64_t)row * 8;
-        if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
+        info.output_bytes += (int64_t)S * p->n_obs * (4 + 2 * (int64_t)ex.k_max) * 8;
     }
-    const size_t crow = cap ? (size_t)(GILC_FIXED + cap->n_groups + cap->c_bins) : 0;   // of capture counts (gilc_run)
-    if (cap) {
+    if (cap) {                                                // of capture counts (gilc_run)
         info.lds_bytes += (int32_t)(gilc_lds_slots(BT, cap->n_groups, cap->c_bins, cap->h_bins) * 8);
-        info.output_bytes += (int64_t)S * (p->n_obs * (int64_t)crow * 8 + 2 * (int64_t)cap->h_bins * 8 + 32);
-        if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
+        info.output_bytes += (int64_t)S * (p->n_obs * (int64_t)(GILC_FIXED + cap->n_groups + cap->c_bins) * 8 + 2 * (int64_t)cap->h_bins * 8 + 32);
     }
     if (prof) {                                               // of ensemble profiles (gilp_run)
         info.lds_bytes += (int32_t)gilp_lds_bytes(prof->n_bins, prof->want_field != 0);
-        info.output_bytes = gilp_output_bytes(p, prof->n_groups, prof->n_bins, pos_obs || sigma_obs || flags_obs, prof->profile_obs != nullptr);
-        if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
+        info.output_bytes = gilp_output_bytes(p, prof->n_groups, prof->n_bins, io.states(), prof->profile_obs != nullptr);
     }
+    if (info.lds_bytes > 160 * 1024) return bad("LDS budget exceeded");
     // a resumable launch (rs: its start state, checked by gilr_prepare, which comes back as the end state) reads no n0 / pos0 /
     // sigma0 / bound0: every slot's site, and its spin or 0 where it is not alive
+    GilIo in = io;
     std::vector<int32_t> n0_all;
     std::vector<int8_t> spin_all;
     if (rs) {
         n0_all.assign((size_t)S, N);
         spin_all.resize(rs->flg.size());
         for (size_t q = 0; q < spin_all.size(); ++q) spin_all[q] = (rs->flg[q] & GILR_ALIVE) ? ((rs->flg[q] & GILR_PLUS) ? 1 : -1) : 0;
-        n0 = n0_all.data(); pos0 = rs->pos.data(); sigma0 = spin_all.data(); bound0 = nullptr;
-    }
-    for (int s = 0; s < S && !rs; ++s) {
-        if (n0[s] < 0 || n0[s] > N) return bad("bad n_cap / n0 / n_obs / max_events");
-        if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * N, sigma0 + (size_t)s * N)) return bad(why);
-    }
+        in.n0 = n0_all.data(); in.pos0 = rs->pos.data(); in.sigma0 = spin_all.data(); in.bound0 = nullptr;
+    } else { const std::string why = gil_check_start(p, io, "bad n_cap / n0 / n_obs / max_events"); if (!why.empty()) return bad(why); }
     if (const char *why = gil_check_flip_table(p)) return bad(why);
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: the scratch arrays start from zero
     if (int rc = job.select_device(p->device)) return rc;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
-    const int64_t work_bytes = (int64_t)S * info.work_bytes_per_system + (structure_obs ? (int64_t)L * 16 : 0) +
+    const int64_t work_bytes = (int64_t)S * info.work_bytes_per_system + (ex.structure_obs ? (int64_t)L * 16 : 0) +
                                (cap ? (int64_t)S * N * 8 + (cap->n_groups > 0 ? (int64_t)L * 4 : 0) : 0) + (prof ? (int64_t)S * 4 : 0);
-    if ((uint64_t)(work_bytes + info.output_bytes) > (uint64_t)free_b)
-        return bad("the batch needs " + std::to_string(work_bytes) + " bytes of work memory and " +
-                   std::to_string(info.output_bytes) + " bytes of outputs, the device has " + std::to_string(free_b) + " bytes free");
+    if (int rc = gil_refuse_device_bytes(job, work_bytes, info.output_bytes)) return rc;
     GilpBigArgs a{};
     a.p = *p; a.tlen = info.table_len; a.nblk = info.n_blocks; a.cb = (a.nblk + BT - 1) / BT;
     a.tab_in_lds = info.table_in_lds;
     a.m = gil_model(p);
-    const size_t SN = (size_t)S * N, SL = (size_t)S * L, SO = (size_t)S * p->n_obs, NIN = S == 1 && !rs ? (size_t)n0[0] : SN;
-    UP(table, table.data(), table.size()); UP(times, p->times_obs, (size_t)p->n_obs);
-    UP(betas, p->beta, (size_t)S); UP(n0, n0, (size_t)S);
-    UP(pos0, pos0, NIN); UP(sigma0, sigma0, NIN);
-    if (bound0) UP(bound0, bound0, NIN);
-    if (p->anchor_mask) UP(anchor, p->anchor_mask, (size_t)L);
-    if (scalars_obs && p->front_lo) UP(front_lo, p->front_lo, (size_t)L);
-    if (scalars_obs && p->block_table) UP(block_table, p->block_table, (size_t)(p->K + 1) * (p->K + 1));
-    if (uniforms) UP(uniforms, uniforms, (size_t)S * p->max_events * 4);
-    if (int rc = gil_upload_flip_table(job, p, a.m)) return rc;
+    const size_t SN = (size_t)S * N, SL = (size_t)S * L;
+    if (int rc = gil_stage_common(job, a, p, in, table, S == 1 && !rs ? (size_t)in.n0[0] : SN, io.scalars_obs != nullptr, p->block_table,
+                                  (size_t)(p->K + 1) * (p->K + 1))) return rc;
     WORK(pos, SN); WORK(occ, SL); WORK(occp, SL); WORK(slot, SL * p->K); WORK(work, SN); WORK(ref, SN);
     WORK(flg, SN); WORK(rate, SN); WORK(bsum, (size_t)S * a.nblk); WORK(W, SL); WORK(S, SL);
-    OUT(pos_obs, pos_obs, SO * N); OUT(sigma_obs, sigma_obs, SO * N); OUT(flags_obs, flags_obs, SO * N);
-    OUT(scalars, scalars_obs, SO * GIL_NSCALARS);
-    OUT(n_recorded, n_recorded, (size_t)S); OUT(n_events, n_events, (size_t)S); OUT(t_final, t_final, (size_t)S);
-    OUT(exits, exits, SN * 3); OUT(n_exits, n_exits, (size_t)S);
     const size_t lds = (size_t)info.lds_bytes;
-    GilsArgs &sa = a.st;
-    GilrArgs ra{};
-    if (structure_obs) {
-        double *phase = nullptr;
-        if (int rc = job.alloc(&sa.rows, SO * row, "structure_obs")) return rc;
-        if (int rc = job.alloc(&phase, (size_t)2 * L, "phase")) return rc;
-        sa.phase = phase; sa.k_max = k_max; sa.first_obs = first_obs;
-        if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<true>), lds)) return rc;
-        hipLaunchKernelGGL(gils_phase_table, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, nullptr, phase, L);
-    } else if (cap) {
-        GilcArgs &ca = a.cp;
-        ca.n_groups = cap->n_groups; ca.c_bins = cap->c_bins; ca.h_bins = cap->h_bins; ca.first_obs = cap->first_obs; ca.h_dt = cap->h_dt;
-        if (cap->group_of_site) UP(cp.group, cap->group_of_site, (size_t)L);
-        WORK(cp.rows, SO * crow); WORK(cp.life_hist, (size_t)S * 2 * cap->h_bins); WORK(cp.life_sums, (size_t)S * 4); WORK(cp.tbind, SN);
-        if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false, true>), lds)) return rc;
-    } else if (prof) {
-        GilpArgs &pa = a.pf;
-        const size_t GO = (size_t)prof->n_groups * p->n_obs;
-        pa.n_bins = prof->n_bins; pa.width = (L + prof->n_bins - 1) / prof->n_bins; pa.n_used = (L + pa.width - 1) / pa.width;
-        pa.first_obs = prof->first_obs; pa.want_field = prof->want_field;
-        if (prof->group_of_system) UP(pf.group, prof->group_of_system, (size_t)S); else WORK(pf.group, (size_t)S);   // zero-filled: group 0
-        WORK(pf.sums, GO * GILP_COLS * prof->n_bins); WORK(pf.members, GO);
-        if (prof->profile_obs) WORK(pf.rows, SO * 3 * prof->n_bins);
-        if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false, false, true>), lds)) return rc;
-    } else if (rs) {
-        ra.fresh = rs->fresh;
-        if (int rc = job.upload(&ra.ref, rs->ref.data(), SN, "checkpoint ref")) return rc;
-        if (int rc = job.upload(&ra.flg, rs->flg.data(), SN, "checkpoint flags")) return rc;
-        if (int rc = job.upload(&ra.k_start, rs->k_start.data(), (size_t)S, "checkpoint next_obs")) return rc;
-        if (int rc = job.upload(&ra.t, rs->t.data(), (size_t)S, "checkpoint t")) return rc;
-        if (int rc = job.upload(&ra.n_ev, reinterpret_cast<const long long *>(rs->n_ev.data()), (size_t)S, "checkpoint n_events")) return rc;
-        if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false, false, false, true>), lds)) return rc;
-    } else if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&gil_big_kernel<false>), lds)) return rc;
-    if (int rc = job.create_events()) return rc;
-    if (rs) hipLaunchKernelGGL(big_field_init_live, dim3((unsigned)((L + 255) / 256), (unsigned)S), dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
-    else hipLaunchKernelGGL(big_field_init, dim3((unsigned)((L + 255) / 256), (unsigned)S), dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
-    job.ev.start();
-    if (structure_obs) hipLaunchKernelGGL(gil_big_kernel<true>, dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const GilsBigArgs &>(a));
-    else if (cap) hipLaunchKernelGGL((gil_big_kernel<false, true>), dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const GilcBigArgs &>(a));
-    else if (prof) hipLaunchKernelGGL((gil_big_kernel<false, false, true>), dim3((unsigned)S), dim3(BT), lds, nullptr, a);
-    else if (rs) {
-        GilrBigArgs b{};
-        static_cast<BigArgs &>(b) = static_cast<const BigArgs &>(a); b.rs = ra;
-        hipLaunchKernelGGL((gil_big_kernel<false, false, false, true>), dim3((unsigned)S), dim3(BT), lds, nullptr, b);
-    } else hipLaunchKernelGGL(gil_big_kernel<false>, dim3((unsigned)S), dim3(BT), lds, nullptr, static_cast<const BigArgs &>(a));
-    job.ev.stop();
-    if (int rc = job.finish(hipGetLastError(), "gil_big_kernel", kernel_ms)) return rc;
-    DOWN(pos_obs, pos_obs, SO * N * 4); DOWN(sigma_obs, sigma_obs, SO * N); DOWN(flags_obs, flags_obs, SO * N);
-    DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8);
-    DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8); DOWN(t_final, t_final, (size_t)S * 8);
-    DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
-    if (structure_obs) if (int rc = job.download(structure_obs, sa.rows, SO * row * 8, "structure_obs")) return rc;
-    if (rs) {
-        if (int rc = job.download(rs->pos.data(), a.pos, SN * 4, "checkpoint pos")) return rc;
-        if (int rc = job.download(rs->ref.data(), a.ref, SN * 4, "checkpoint ref")) return rc;
-        if (int rc = job.download(rs->flg.data(), a.flg, SN, "checkpoint flags")) return rc;
-    }
-    if (cap) {
-        if (int rc = job.download(cap->capture_obs, a.cp.rows, SO * crow * 8, "capture_obs")) return rc;
-        if (int rc = job.download(cap->life_hist, a.cp.life_hist, (size_t)S * 2 * cap->h_bins * 8, "life_hist")) return rc;
-        if (int rc = job.download(cap->life_sums, a.cp.life_sums, (size_t)S * 4 * 8, "life_sums")) return rc;
-    }
-    if (prof) {
-        const size_t GO = (size_t)prof->n_groups * p->n_obs;
-        if (int rc = job.download(prof->ensemble_sums, a.pf.sums, GO * GILP_COLS * prof->n_bins * 8, "ensemble_sums")) return rc;
-        if (int rc = job.download(prof->members, a.pf.members, GO * 4, "members")) return rc;
-        if (int rc = job.download(prof->profile_obs, a.pf.rows, SO * 3 * prof->n_bins * 4, "profile_obs")) return rc;
-    }
-    return GIL_OK;
+    GilrBigArgs b{};                                            // the resumable launch's arguments: a's own and the checkpoint
+    int rc = ex.structure_obs ? gil_stage_structure(job, a, p, ex.k_max, ex.first_obs, true, false)
+             : cap            ? gil_stage_capture(job, a, p, *cap, true)
+             : prof           ? gil_stage_profile(job, a, p, *prof)
+             : rs             ? gil_stage_checkpoint(job, b.rs, p, *rs, false) : 0;
+    if (rc) return rc;
+    if ((rc = job.create_events())) return rc;
+    static_cast<BigArgs &>(b) = a;
+    const dim3 field_grid((unsigned)((L + 255) / 256), (unsigned)S);   // W, S of the start state: before the timed window
+    if (rs) hipLaunchKernelGGL(big_field_init_live, field_grid, dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
+    else hipLaunchKernelGGL(big_field_init, field_grid, dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
+    rc = ex.structure_obs ? big_launch<GilKind::Structure>(job, S, lds, a)
+         : cap            ? big_launch<GilKind::Capture>(job, S, lds, a)
+         : prof           ? big_launch<GilKind::Profile>(job, S, lds, a)
+         : rs             ? big_launch<GilKind::Resume>(job, S, lds, b) : big_launch<GilKind::Plain>(job, S, lds, a);
+    if (rc) return rc;
+    if ((rc = job.finish(hipGetLastError(), "gil_big_kernel", io.kernel_ms))) return rc;
+    if ((rc = gil_fetch_common(job, a, p, io))) return rc;
+    if (ex.structure_obs) rc = gil_fetch_structure(job, a, p, ex.structure_obs);
+    else if (cap) rc = gil_fetch_capture(job, a, p, *cap);
+    else if (prof) rc = gil_fetch_profile(job, a, p, *prof);
+    else if (rs) rc = gil_fetch_checkpoint(job, *rs, p, a.pos, a.ref, a.flg);
+    return rc ? rc : GIL_OK;
 }
 
-}  // namespace
-
-int gils_large_plan(const char *who, std::string &err, const gil_params *p, int32_t *lds_bytes, int64_t *work_bytes) {
+int gil_large_plan(const char *who, std::string &err, const gil_params *p, int32_t extra_lds, int32_t *lds_bytes, int64_t *work_bytes) {
     if (p->n_systems > GILM_MAX_SYSTEMS) { err = std::string(who) + ": n_systems must be in [1, GILM_MAX_SYSTEMS]"; return GIL_ERR_ARG; }
     gilm_plan_info info{};
     if (int rc = big_plan(who, err, p, false, false, &info, nullptr)) return rc;
-    *lds_bytes = info.lds_bytes + (int32_t)(gils_lds_doubles(BT) * sizeof(double));
+    *lds_bytes = info.lds_bytes + extra_lds;
     *work_bytes = (int64_t)p->n_systems * info.work_bytes_per_system;
     if (*lds_bytes > 160 * 1024) { err = std::string(who) + ": LDS budget exceeded"; return GIL_ERR_ARG; }
     return GIL_OK;
-}
-
-int gils_large_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
-                   const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs,
-                   int64_t *scalars_obs, int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits,
-                   double *kernel_ms, int k_max, int first_obs, double *structure_obs) {
-    return big_run(who, err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
-                   t_final, exits, n_exits, kernel_ms, k_max, first_obs, structure_obs);
-}
-
-int gilc_large_plan(const char *who, std::string &err, const gil_params *p, int32_t cap_lds, int32_t *lds_bytes, int64_t *work_bytes) {
-    if (p->n_systems > GILM_MAX_SYSTEMS) { err = std::string(who) + ": n_systems must be in [1, GILM_MAX_SYSTEMS]"; return GIL_ERR_ARG; }
-    gilm_plan_info info{};
-    if (int rc = big_plan(who, err, p, false, false, &info, nullptr)) return rc;
-    *lds_bytes = info.lds_bytes + cap_lds;
-    *work_bytes = (int64_t)p->n_systems * info.work_bytes_per_system;
-    if (*lds_bytes > 160 * 1024) { err = std::string(who) + ": LDS budget exceeded"; return GIL_ERR_ARG; }
-    return GIL_OK;
-}
-
-int gilc_large_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
-                   const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs,
-                   int64_t *scalars_obs, int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits,
-                   double *kernel_ms, const GilcCall *cap) {
-    return big_run(who, err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
-                   t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, cap);
-}
-
-int gilr_large_run(const char *who, std::string &err, const gil_params *p, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs,
-                   uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits,
-                   int32_t *n_exits, double *kernel_ms, GilrCall *rs) {
-    return big_run(who, err, p, nullptr, nullptr, nullptr, nullptr, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
-                   t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, nullptr, nullptr, rs);
-}
-
-int gilp_large_plan(const char *who, std::string &err, const gil_params *p, int32_t prof_lds, int32_t *lds_bytes, int64_t *work_bytes) {
-    return gilc_large_plan(who, err, p, prof_lds, lds_bytes, work_bytes);   // the same arithmetic: the kernel's own LDS plus the slots
-}
-
-int gilp_large_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
-                   const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs,
-                   int64_t *scalars_obs, int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits,
-                   double *kernel_ms, const GilpCall *prof) {
-    return big_run(who, err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events,
-                   t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, nullptr, prof);
 }
 
 extern "C" {
@@ -866,8 +770,8 @@ int gil_run_large(const gil_params *p, int32_t n0, const int32_t *pos0, const in
     auto bad = [&](const char *m) { g_big_err = std::string("gil_run_large: ") + m; return GIL_ERR_ARG; };
     if (!p || !pos0 || !sigma0 || !p->beta || !p->times_obs) return bad("null argument");
     if (p->n_systems != 1) return bad("one system per call");
-    return big_run("gil_run_large", g_big_err, p, &n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, nullptr,
-                   n_recorded, n_events, t_final, exits, n_exits, kernel_ms);
+    const GilIo io{&n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, nullptr, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    return gil_large_run("gil_run_large", g_big_err, p, io, GilExtras{});
 }
 
 const char *gil_large_last_error(void) { return g_big_err.c_str(); }
@@ -887,8 +791,8 @@ int gilm_run(const gil_params *p, const int32_t *n0, const int32_t *pos0, const 
     auto bad = [&](const char *m) { g_many_err = std::string("gilm_run: ") + m; return GIL_ERR_ARG; };
     if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs) return bad("null argument");
     if (p->n_systems < 1 || p->n_systems > GILM_MAX_SYSTEMS) return bad("n_systems must be in [1, GILM_MAX_SYSTEMS]");
-    return big_run("gilm_run", g_many_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
-                   n_recorded, n_events, t_final, exits, n_exits, kernel_ms);
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    return gil_large_run("gilm_run", g_many_err, p, io, GilExtras{});
 }
 
 }  // extern "C"

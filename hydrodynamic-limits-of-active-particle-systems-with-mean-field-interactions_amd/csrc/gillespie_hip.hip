@@ -13,6 +13,9 @@
 //      recomputation bit for bit)
 //   E  t += tau; states / scalar sums of the observation times that were crossed go to HBM (ref :517-536)
 // Randomness: Philox4x32-10 keyed by the seed, counter (event index, system) -- or numbers supplied by the caller.
+// Host side: every extern "C" run function fills a GilIo and a GilExtras (gillespie_common.hpp) and calls batch_run, mixed_run or,
+// for the large shape, gil_large_run of gillespie_big_hip.hip; the drivers stage and fetch through the helpers of
+// gillespie_common.hpp, and gil_launch<V> is the one place that names a kernel instantiation.
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -20,7 +23,6 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "gillespie.h"
@@ -31,7 +33,7 @@
 #include "gillespie_mixed_structure.h"
 #include "gillespie_resume.h"
 #include "aps_common.hpp"
-#include "gillespie_common.hpp"           // model, initial-state check, the driver of the one-shot entry points
+#include "gillespie_common.hpp"           // the call record, the variant tags, the staging path of the drivers
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiations only)
 #include "gillespie_capture.hpp"          // anchor capture and cluster statistics (capture instantiations only)
 #include "gillespie_profile.hpp"          // ensemble density and field profiles (profile instantiations only)
@@ -49,7 +51,7 @@ struct GilArgs {
     Model m;
     gil_params p;
     int tlen, chunk;
-    const double *beta, *table, *times, *uniforms;
+    const double *betas, *table, *times, *uniforms;
     const uint8_t *anchor, *block_table;
     const int32_t *front_lo, *n0, *pos0;
     const int8_t *sigma0;
@@ -78,6 +80,16 @@ struct GilxBatchArgs : GilArgs { GilxArgs mx; };            // arguments of the 
 struct GilxsBatchArgs : GilxBatchArgs { GilsArgs st; GilwArgs wn; };   // arguments of the mixed structure instantiations (gilxs_run's)
 struct GilrBatchArgs : GilArgs { GilrArgs rs; };            // arguments of the resumable instantiations (gilr_run's)
 
+// the argument struct of each variant of the batch kernel
+template <GilKind V> struct GilKernelArgs;
+template <> struct GilKernelArgs<GilKind::Plain> { using type = GilArgs; };
+template <> struct GilKernelArgs<GilKind::Structure> { using type = GilsBatchArgs; };
+template <> struct GilKernelArgs<GilKind::Capture> { using type = GilcBatchArgs; };
+template <> struct GilKernelArgs<GilKind::Profile> { using type = GilpBatchArgs; };
+template <> struct GilKernelArgs<GilKind::Mixed> { using type = GilxBatchArgs; };
+template <> struct GilKernelArgs<GilKind::MixedStructure> { using type = GilxsBatchArgs; };
+template <> struct GilKernelArgs<GilKind::Resume> { using type = GilrBatchArgs; };
+
 // the structure sums' slots: behind the loop's own LDS (which ends with the plus-occupancy bytes), at the next multiple of 8
 __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L) {
     const size_t end = (size_t)(reinterpret_cast<char *>(occp + ((L + 15) & ~15)) - reinterpret_cast<char *>(lds));
@@ -85,22 +97,21 @@ __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L)
 }
 
 // NT = threads per system: one wavefront (no real barriers, six systems per CU by LDS) for small systems, four for large ones.
-// ST = also reduce the structure sums at an observation (gillespie_structure.hpp): a compile-time property, so that the
-// kernels without it are the code they were before it existed.
-// CP = anchor capture and cluster statistics (gillespie_capture.hpp), likewise; not combined with ST.
-// PF = ensemble density and field profiles (gillespie_profile.hpp), likewise; not combined with ST or CP.
-// MX = a mixed batch (gillespie_mixed.hpp): the system of a workgroup comes from a launch order, and the weight table, the
-// blocking table, the slot count and the Philox key are the system's own; likewise; not combined with ST, CP or PF.  In such a
-// launch a.tlen is the longest table's length (the LDS layout is the launch's).  MX with ST: the structure sums of a mixed launch,
-// with the window reduction of gillespie_window.hpp; the rows themselves are optional there.
-// RS = a resumable launch (gillespie_resume.hpp): the start state is a checkpoint (slots may be dead, the clock, the event count
-// and the next observation are the checkpoint's) and the end state is written out; likewise; combined with none of the others.
-template <int NT, bool ST, bool CP = false, bool PF = false, bool MX = false, bool RS = false>
-__global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<RS, GilrBatchArgs, std::conditional_t<MX, std::conditional_t<ST, GilxsBatchArgs, GilxBatchArgs>, std::conditional_t<PF, GilpBatchArgs, std::conditional_t<CP, GilcBatchArgs, std::conditional_t<ST, GilsBatchArgs, GilArgs>>>>> a) {
-    static_assert(!(RS && (ST || CP || PF || MX)), "the resumable launches take none of the other sums");
-    static_assert(!(ST && CP), "the capture launches take no structure sums");
-    static_assert(!(PF && (ST || CP)), "the profile launches take no structure sums and no capture statistics");
-    static_assert(!(MX && (CP || PF)), "the mixed launches take no capture statistics and no profiles");
+// V = the variant, a compile-time property, so that each kernel is the code it was before the others existed:
+//   Structure       also reduce the structure sums at an observation (gillespie_structure.hpp);
+//   Capture         anchor capture and cluster statistics (gillespie_capture.hpp);
+//   Profile         ensemble density and field profiles (gillespie_profile.hpp);
+//   Mixed           a mixed batch (gillespie_mixed.hpp): the system of a workgroup comes from a launch order, and the weight table,
+//                   the blocking table, the slot count and the Philox key are the system's own.  In such a launch a.tlen is the
+//                   longest table's length (the LDS layout is the launch's);
+//   MixedStructure  the structure sums of a mixed launch, with the window reduction of gillespie_window.hpp; the rows themselves
+//                   are optional there;
+//   Resume          a resumable launch (gillespie_resume.hpp): the start state is a checkpoint (slots may be dead, the clock, the
+//                   event count and the next observation are the checkpoint's) and the end state is written out.
+template <int NT, GilKind V>
+__global__ __launch_bounds__(NT) void gil_kernel(const typename GilKernelArgs<V>::type a) {
+    constexpr bool ST = V == GilKind::Structure || V == GilKind::MixedStructure, CP = V == GilKind::Capture, PF = V == GilKind::Profile;
+    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedStructure, RS = V == GilKind::Resume;
     extern __shared__ double lds[];
     const Model &M = a.m;
     const GilxView vw = gilx_view<MX, NT>(a);                  // empty without MX
@@ -122,7 +133,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const std::conditional_t<RS, Gi
     uint8_t *flg = reinterpret_cast<uint8_t *>(ctl + 16);     // [ncap]
     uint8_t *occ = flg + ((ncap + 15) & ~15);                 // [L] particles per site
     uint8_t *occp = occ + ((L + 15) & ~15);                   // [L] plus particles per site (blocking table)
-    const double beta = a.beta[sys];
+    const double beta = a.betas[sys];
     const int n_init = RS ? ncap : a.n0[sys];                  // RS: any slot may be alive, the loops below ask its flags
     // ---- load the system
     for (int i = t; i <= GX_TLEN; i += NT) tab[i] = (MX ? vw.table : a.table)[i];
@@ -547,175 +558,129 @@ int64_t gils_output_bytes(const gil_params *p, int k_max, bool states, bool scal
     return S * ((states ? O * N * 6 : 0) + (scalars ? O * GIL_NSCALARS * 8 : 0) + N * 24 + 24 + O * (4 + 2 * (int64_t)k_max) * 8);
 }
 
-// The one host driver of the batch kernel.  structure_obs: gils_run's rows (k_max modes, from observation first_obs on),
-// nullptr for gil_run_batch; cap: gilc_run's call; prof: gilp_run's; rs: gilr_run's start state (checked by gilr_prepare; n0, pos0,
-// sigma0 and bound0 are not read then), which comes back as the end state.  The callers have checked their required pointers.
-int batch_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
-              const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
-              int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
-              int k_max, int first_obs, double *structure_obs, const GilcCall *cap = nullptr, const GilpCall *prof = nullptr,
-              GilrCall *rs = nullptr) {
+// The batch kernel of variant V with NT threads a system: the one place that names the instantiation.  Raises its LDS limit
+// and launches it; the timed window holds this launch alone.
+template <GilKind V, int NT>
+int gil_launch_nt(OneShot &job, int S, size_t lds, const typename GilKernelArgs<V>::type &a) {
+    const auto kernel = &gil_kernel<NT, V>;
+    if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(kernel), lds)) return rc;
+    job.ev.start();
+    hipLaunchKernelGGL(kernel, dim3((unsigned)S), dim3(NT), lds, nullptr, a);
+    job.ev.stop();
+    return 0;
+}
+
+template <GilKind V>
+int gil_launch(OneShot &job, int NT, int S, size_t lds, const typename GilKernelArgs<V>::type &a) {
+    return NT == 64 ? gil_launch_nt<V, 64>(job, S, lds, a) : gil_launch_nt<V, 256>(job, S, lds, a);
+}
+
+// The one host driver of the batch kernel for the launches of one variant.  A resumable launch (ex.rs) reads no start state from
+// io.  The callers have checked their required pointers.
+int batch_run(const char *who, std::string &err, const gil_params *p, const GilIo &io, const GilExtras &ex) {
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     if (p->L < 2 || p->L > GIL_MAX_L) return bad("L must be in [2, GIL_MAX_L]");
     if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
     if (p->n_systems < 1 || p->n_cap < 1 || p->n_cap > GIL_MAX_N || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
     const int S = p->n_systems, L = p->L, ncap = p->n_cap;
-    for (int s = 0; s < S && !rs; ++s) {
-        if (n0[s] < 0 || n0[s] > ncap) return bad("n0 outside [0, n_cap]");
-        if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * ncap, sigma0 + (size_t)s * ncap)) return bad(why);
-    }
+    const GilcCall *cap = ex.cap; const GilpCall *prof = ex.prof;
+    if (!ex.rs) { const std::string why = gil_check_start(p, io, "n0 outside [0, n_cap]"); if (!why.empty()) return bad(why); }
     if (const char *why = gil_check_flip_table(p)) return bad(why);
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: a run may record fewer observations than it has room for
     if (int rc = job.select_device(p->device)) return rc;
-    if (structure_obs || cap || prof) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
+    if (ex.structure_obs || cap || prof) {
         const int64_t work = prof ? (int64_t)S * 4 : cap ? (cap->n_groups > 0 ? (int64_t)L * 4 : 0) : (int64_t)L * 16,
-                      outb = prof ? gilp_output_bytes(p, prof->n_groups, prof->n_bins, pos_obs || sigma_obs || flags_obs, prof->profile_obs != nullptr)
-                             : cap ? gilc_output_bytes(p, *cap, pos_obs || sigma_obs || flags_obs)
-                                 : gils_output_bytes(p, k_max, pos_obs || sigma_obs || flags_obs, scalars_obs != nullptr);
-        if ((uint64_t)(work + outb) > (uint64_t)free_b)
-            return bad("the batch needs " + std::to_string(work) + " bytes of work memory and " + std::to_string(outb) +
-                       " bytes of outputs, the device has " + std::to_string(free_b) + " bytes free");
+                      outb = prof ? gilp_output_bytes(p, prof->n_groups, prof->n_bins, io.states(), prof->profile_obs != nullptr)
+                             : cap ? gilc_output_bytes(p, *cap, io.states())
+                                 : gils_output_bytes(p, ex.k_max, io.states(), io.scalars_obs != nullptr);
+        if (int rc = gil_refuse_device_bytes(job, work, outb)) return rc;
     }
 
     std::vector<double> table; int tlen = 0, q = 0;
     weight_table(p->sigma_grid, L, p->K, p->periodic != 0, table, tlen, q);
     GilpBatchArgs a{};
     int NT; size_t lds; bool phase_in_lds = false;
-    batch_shape(L, ncap, tlen, structure_obs != nullptr, NT, lds, &phase_in_lds, cap, prof ? gilp_lds_bytes(prof->n_bins, prof->want_field != 0) : 0);
+    batch_shape(L, ncap, tlen, ex.structure_obs != nullptr, NT, lds, &phase_in_lds, cap, prof ? gilp_lds_bytes(prof->n_bins, prof->want_field != 0) : 0);
     a.p = *p; a.tlen = tlen; a.chunk = (ncap + NT - 1) / NT;
     a.m = gil_model(p);
-    const size_t SN = (size_t)S * ncap, SO = (size_t)S * p->n_obs;
-    UP(beta, p->beta, (size_t)S); UP(table, table.data(), table.size()); UP(times, p->times_obs, (size_t)p->n_obs);
-    if (!rs) { UP(n0, n0, (size_t)S); UP(pos0, pos0, SN); UP(sigma0, sigma0, SN); }
-    if (!rs && bound0) UP(bound0, bound0, SN);
-    if (p->anchor_mask) UP(anchor, p->anchor_mask, (size_t)L);
-    if (p->front_lo) UP(front_lo, p->front_lo, (size_t)L);
-    if (p->block_table) UP(block_table, p->block_table, (size_t)(p->K + 1) * (p->K + 1));
-    if (int rc = gil_upload_flip_table(job, p, a.m)) return rc;
-    if (uniforms) UP(uniforms, uniforms, (size_t)S * p->max_events * 4);
-    OUT(pos_obs, pos_obs, SO * ncap); OUT(sigma_obs, sigma_obs, SO * ncap); OUT(flags_obs, flags_obs, SO * ncap);
-    OUT(scalars, scalars_obs, SO * GIL_NSCALARS);
-    OUT(n_recorded, n_recorded, (size_t)S); OUT(t_final, t_final, (size_t)S); OUT(exits, exits, SN * 3); OUT(n_exits, n_exits, (size_t)S);
-    OUT(n_events, n_events, (size_t)S);
+    if (int rc = gil_stage_common(job, a, p, io, table, (size_t)S * ncap, true, p->block_table, (size_t)(p->K + 1) * (p->K + 1))) return rc;
     if (lds > 160 * 1024) return bad("system does not fit the 160 KB of LDS");
-    const size_t row = 4 + 2 * (size_t)k_max;
-    GilsArgs &sa = a.st;
-    GilrArgs ra{};
-    if (structure_obs) {
-        double *phase = nullptr;
-        if (int rc = job.alloc(&sa.rows, SO * row, "structure_obs")) return rc;
-        if (int rc = job.alloc(&phase, (size_t)2 * L, "phase")) return rc;
-        sa.phase = phase; sa.k_max = k_max; sa.first_obs = first_obs; sa.phase_in_lds = phase_in_lds ? 1 : 0;
-        if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, true>) : reinterpret_cast<const void *>(&gil_kernel<256, true>), lds)) return rc;
-        hipLaunchKernelGGL(gils_phase_table, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, nullptr, phase, L);
-    } else if (cap) {
-        GilcArgs &ca = a.cp;
-        ca.n_groups = cap->n_groups; ca.c_bins = cap->c_bins; ca.h_bins = cap->h_bins; ca.first_obs = cap->first_obs; ca.h_dt = cap->h_dt;
-        if (cap->group_of_site) UP(cp.group, cap->group_of_site, (size_t)L);
-        WORK(cp.rows, SO * (size_t)(GILC_NFIXED + cap->n_groups + cap->c_bins));
-        WORK(cp.life_hist, (size_t)S * 2 * cap->h_bins); WORK(cp.life_sums, (size_t)S * 4);
-        if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, true>) : reinterpret_cast<const void *>(&gil_kernel<256, false, true>), lds)) return rc;
-    } else if (prof) {
-        GilpArgs &pa = a.pf;
-        const size_t GO = (size_t)prof->n_groups * p->n_obs;
-        pa.n_bins = prof->n_bins; pa.width = (L + prof->n_bins - 1) / prof->n_bins; pa.n_used = (L + pa.width - 1) / pa.width;
-        pa.first_obs = prof->first_obs; pa.want_field = prof->want_field;
-        if (prof->group_of_system) UP(pf.group, prof->group_of_system, (size_t)S); else WORK(pf.group, (size_t)S);   // zero-filled: group 0
-        WORK(pf.sums, GO * GILP_COLS * prof->n_bins); WORK(pf.members, GO);
-        if (prof->profile_obs) WORK(pf.rows, SO * 3 * prof->n_bins);
-        if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, false, true>) : reinterpret_cast<const void *>(&gil_kernel<256, false, false, true>), lds)) return rc;
-    } else if (rs) {
-        ra.fresh = rs->fresh;
-        if (int rc = job.upload(&ra.pos, rs->pos.data(), SN, "checkpoint pos")) return rc;
-        if (int rc = job.upload(&ra.ref, rs->ref.data(), SN, "checkpoint ref")) return rc;
-        if (int rc = job.upload(&ra.flg, rs->flg.data(), SN, "checkpoint flags")) return rc;
-        if (int rc = job.upload(&ra.k_start, rs->k_start.data(), (size_t)S, "checkpoint next_obs")) return rc;
-        if (int rc = job.upload(&ra.t, rs->t.data(), (size_t)S, "checkpoint t")) return rc;
-        if (int rc = job.upload(&ra.n_ev, reinterpret_cast<const long long *>(rs->n_ev.data()), (size_t)S, "checkpoint n_events")) return rc;
-        if (int rc = job.alloc(&ra.pos_out, SN, "checkpoint pos")) return rc;
-        if (int rc = job.alloc(&ra.ref_out, SN, "checkpoint ref")) return rc;
-        if (int rc = job.alloc(&ra.flg_out, SN, "checkpoint flags")) return rc;
-        if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, false, false, false, true>) : reinterpret_cast<const void *>(&gil_kernel<256, false, false, false, false, true>), lds)) return rc;
-    } else if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false>) : reinterpret_cast<const void *>(&gil_kernel<256, false>), lds)) return rc;
-    if (int rc = job.create_events()) return rc;
-    job.ev.start();
-    if (structure_obs) {
-        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, true>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilsBatchArgs &>(a));
-        else hipLaunchKernelGGL((gil_kernel<256, true>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilsBatchArgs &>(a));
-    } else if (cap) {
-        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilcBatchArgs &>(a));
-        else hipLaunchKernelGGL((gil_kernel<256, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilcBatchArgs &>(a));
-    } else if (prof) {
-        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
-        else hipLaunchKernelGGL((gil_kernel<256, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
-    } else if (rs) {
-        GilrBatchArgs b{};
-        static_cast<GilArgs &>(b) = static_cast<const GilArgs &>(a); b.rs = ra;
-        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, false, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, b);
-        else hipLaunchKernelGGL((gil_kernel<256, false, false, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, b);
-    } else if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilArgs &>(a));
-    else hipLaunchKernelGGL((gil_kernel<256, false>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilArgs &>(a));
-    job.ev.stop();
-    if (int rc = job.finish(hipGetLastError(), "gil_kernel", kernel_ms)) return rc;
-    DOWN(pos_obs, pos_obs, SO * ncap * 4); DOWN(sigma_obs, sigma_obs, SO * ncap); DOWN(flags_obs, flags_obs, SO * ncap);
-    DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8); DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8);
-    DOWN(t_final, t_final, (size_t)S * 8); DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
-    if (structure_obs) if (int rc = job.download(structure_obs, sa.rows, SO * row * 8, "structure_obs")) return rc;
-    if (rs) {
-        if (int rc = job.download(rs->pos.data(), ra.pos_out, SN * 4, "checkpoint pos")) return rc;
-        if (int rc = job.download(rs->ref.data(), ra.ref_out, SN * 4, "checkpoint ref")) return rc;
-        if (int rc = job.download(rs->flg.data(), ra.flg_out, SN, "checkpoint flags")) return rc;
-    }
-    if (cap) {
-        if (int rc = job.download(cap->capture_obs, a.cp.rows, SO * (size_t)(GILC_NFIXED + cap->n_groups + cap->c_bins) * 8, "capture_obs")) return rc;
-        if (int rc = job.download(cap->life_hist, a.cp.life_hist, (size_t)S * 2 * cap->h_bins * 8, "life_hist")) return rc;
-        if (int rc = job.download(cap->life_sums, a.cp.life_sums, (size_t)S * 4 * 8, "life_sums")) return rc;
-    }
-    if (prof) {
-        const size_t GO = (size_t)prof->n_groups * p->n_obs;
-        if (int rc = job.download(prof->ensemble_sums, a.pf.sums, GO * GILP_COLS * prof->n_bins * 8, "ensemble_sums")) return rc;
-        if (int rc = job.download(prof->members, a.pf.members, GO * 4, "members")) return rc;
-        if (int rc = job.download(prof->profile_obs, a.pf.rows, SO * 3 * prof->n_bins * 4, "profile_obs")) return rc;
-    }
-    return GIL_OK;
+    GilrBatchArgs b{};                                          // the resumable launch's arguments: a's own and the checkpoint
+    int rc = ex.structure_obs ? gil_stage_structure(job, a, p, ex.k_max, ex.first_obs, true, phase_in_lds)
+             : cap            ? gil_stage_capture(job, a, p, *cap, false)
+             : prof           ? gil_stage_profile(job, a, p, *prof)
+             : ex.rs          ? gil_stage_checkpoint(job, b.rs, p, *ex.rs, true) : 0;
+    if (rc) return rc;
+    if ((rc = job.create_events())) return rc;
+    static_cast<GilArgs &>(b) = a;
+    rc = ex.structure_obs ? gil_launch<GilKind::Structure>(job, NT, S, lds, a)
+         : cap            ? gil_launch<GilKind::Capture>(job, NT, S, lds, a)
+         : prof           ? gil_launch<GilKind::Profile>(job, NT, S, lds, a)
+         : ex.rs          ? gil_launch<GilKind::Resume>(job, NT, S, lds, b) : gil_launch<GilKind::Plain>(job, NT, S, lds, a);
+    if (rc) return rc;
+    if ((rc = job.finish(hipGetLastError(), "gil_kernel", io.kernel_ms))) return rc;
+    if ((rc = gil_fetch_common(job, a, p, io))) return rc;
+    if (ex.structure_obs) rc = gil_fetch_structure(job, a, p, ex.structure_obs);
+    else if (cap) rc = gil_fetch_capture(job, a, p, *cap);
+    else if (prof) rc = gil_fetch_profile(job, a, p, *prof);
+    else if (ex.rs) rc = gil_fetch_checkpoint(job, *ex.rs, p, b.rs.pos_out, b.rs.ref_out, b.rs.flg_out);
+    return rc ? rc : GIL_OK;
 }
 
 std::string g_gilr_err;
 
 // gilr_run and gilrm_run: the start state is checked and laid out here, the launch is the shape's own driver
-int gilr_drive(bool large, const char *who, const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
-               const uint8_t *bound0, const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
-               int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
-               int32_t obs_first, const gil_checkpoint *from, gil_checkpoint *to) {
+int gilr_drive(bool large, const char *who, const gil_params *p, const GilIo &io, int32_t obs_first, const gil_checkpoint *from,
+               gil_checkpoint *to) {
     auto bad = [&](const std::string &m) { g_gilr_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
-    if (!p || !p->beta || !p->times_obs || (!from && (!n0 || !pos0 || !sigma0))) return bad("null argument");
+    if (!p || !p->beta || !p->times_obs || (!from && (!io.n0 || !io.pos0 || !io.sigma0))) return bad("null argument");
     if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0 || p->L < 2 || p->K < 1) return bad("bad n_systems / n_cap / n_obs / max_events / L / K");
     if (large && p->n_systems > GILM_MAX_SYSTEMS) return bad("n_systems must be in [1, GILM_MAX_SYSTEMS]");
-    const size_t S = (size_t)p->n_systems, N = (size_t)p->n_cap;
-    for (size_t s = 0; s < S && !from; ++s) {
-        if (n0[s] < 0 || n0[s] > p->n_cap) return bad("n0 outside [0, n_cap]");
-        if (const char *why = gil_check_state(p, n0[s], pos0 + s * N, sigma0 + s * N)) return bad(why);
-    }
+    const size_t S = (size_t)p->n_systems;
+    if (!from) { const std::string why = gil_check_start(p, io, "n0 outside [0, n_cap]"); if (!why.empty()) return bad(why); }
     GilrCall call;
-    const std::string why = gilr_prepare(p, n0, pos0, sigma0, bound0, obs_first, from, to, call);
+    const std::string why = gilr_prepare(p, io.n0, io.pos0, io.sigma0, io.bound0, obs_first, from, to, call);
     if (!why.empty()) return bad(why);
     std::vector<int32_t> nrec(S, 0);                           // the checkpoint needs these three whether or not the caller wants them
     std::vector<int64_t> nev(S, 0);
     std::vector<double> tfin(S, 0.0);
-    const int rc = large ? gilr_large_run(who, g_gilr_err, p, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, nrec.data(), nev.data(),
-                                          tfin.data(), exits, n_exits, kernel_ms, &call)
-                         : batch_run(who, g_gilr_err, p, nullptr, nullptr, nullptr, nullptr, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
-                                     nrec.data(), nev.data(), tfin.data(), exits, n_exits, kernel_ms, 0, 0, nullptr, nullptr, nullptr, &call);
-    if (rc) return rc;
+    GilIo run = io;                                            // the launch's own record: no start state, the three outputs here
+    run.n0 = run.pos0 = nullptr; run.sigma0 = nullptr; run.bound0 = nullptr;
+    run.n_recorded = nrec.data(); run.n_events = nev.data(); run.t_final = tfin.data();
+    GilExtras ex; ex.rs = &call;
+    if (int rc = large ? gil_large_run(who, g_gilr_err, p, run, ex) : batch_run(who, g_gilr_err, p, run, ex)) return rc;
     gilr_finish(p, call, nrec.data(), nev.data(), tfin.data());
     for (size_t s = 0; s < S; ++s) {
-        if (n_recorded) n_recorded[s] = nrec[s];
-        if (n_events) n_events[s] = nev[s];
-        if (t_final) t_final[s] = tfin[s];
+        if (io.n_recorded) io.n_recorded[s] = nrec[s];
+        if (io.n_events) io.n_events[s] = nev[s];
+        if (io.t_final) io.t_final[s] = tfin[s];
     }
     return GIL_OK;
+}
+
+// What the plans with two shapes (gils, gilc, gilp) check alike: nullptr, or the text of the complaint
+const char *gil_check_plan_params(const gil_params *p) {
+    if (p->L < 2) return "L must be at least 2";
+    if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0) return "bad n_systems / n_cap / n_obs / max_events";
+    return nullptr;
+}
+
+// The shape such a plan chooses: the batch shape where a system with its extras (batch_shape's st, cap, prof_bytes) fits the
+// 160 KB of LDS, else the large shape with large_lds bytes of slots behind the kernel's own.  large_work: the large shape's
+// scratch, 0 in the batch shape.  0, or GIL_ERR_ARG with the text in `err`.
+struct GilShape { int32_t shape, threads, lds_bytes, phase_in_lds; int64_t large_work; };
+int gil_choose_shape(const char *who, std::string &err, const gil_params *p, bool st, const GilcCall *cap, size_t prof_bytes,
+                     int32_t large_lds, GilShape &sh) {
+    sh = GilShape{GILS_SHAPE_LARGE, 1024, 0, 0, 0};
+    if (p->L <= GIL_MAX_L && p->n_cap <= GIL_MAX_N) {
+        if (p->K < 1 || p->K > 32) { err = std::string(who) + ": site capacity K must be in [1, 32]"; return GIL_ERR_ARG; }
+        std::vector<double> table; int tlen = 0, q = 0, NT = 0; size_t lds = 0;
+        weight_table(p->sigma_grid, p->L, p->K, p->periodic != 0, table, tlen, q);
+        bool phase_in_lds = false;
+        batch_shape(p->L, p->n_cap, tlen, st, NT, lds, &phase_in_lds, cap, prof_bytes);
+        if (lds <= 160 * 1024) { sh = GilShape{GILS_SHAPE_BATCH, NT, (int32_t)lds, phase_in_lds ? 1 : 0, 0}; return GIL_OK; }
+    }
+    return gil_large_plan(who, err, p, large_lds, &sh.lds_bytes, &sh.large_work);
 }
 
 std::string g_gils_err;
@@ -723,34 +688,17 @@ std::string g_gils_err;
 // the checks gils_plan and gils_run share, and the shape: 0 with `info` filled, or GIL_ERR_ARG with the text in g_gils_err
 int gils_decide(const char *who, const gil_params *p, int k_max, int first_obs, bool states, bool scalars, gils_plan_info &info) {
     auto bad = [&](const std::string &m) { g_gils_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
-    if (p->L < 2) return bad("L must be at least 2");
-    if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
+    if (const char *why = gil_check_plan_params(p)) return bad(why);
     if (k_max < 1 || k_max > std::min(p->L, GILS_MAX_K)) return bad("k_max must be in [1, min(L, GILS_MAX_K)]");
     if (first_obs < 0 || first_obs > p->n_obs) return bad("first_obs must be in [0, n_obs]");
+    GilShape sh;
+    if (int rc = gil_choose_shape(who, g_gils_err, p, true, nullptr, 0, (int32_t)(gils_lds_doubles(1024) * sizeof(double)), sh)) return rc;
     info = gils_plan_info{};
     info.row_len = 4 + 2 * k_max;
     info.output_bytes = gils_output_bytes(p, k_max, states, scalars);
-    info.shape = GILS_SHAPE_LARGE;
-    if (p->L <= GIL_MAX_L && p->n_cap <= GIL_MAX_N) {
-        if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
-        std::vector<double> table; int tlen = 0, q = 0, NT = 0; size_t lds = 0;
-        weight_table(p->sigma_grid, p->L, p->K, p->periodic != 0, table, tlen, q);
-        bool phase_in_lds = false;
-        batch_shape(p->L, p->n_cap, tlen, true, NT, lds, &phase_in_lds);
-        if (lds <= 160 * 1024) {
-            info.shape = GILS_SHAPE_BATCH; info.threads = NT; info.lds_bytes = (int32_t)lds; info.phase_in_lds = phase_in_lds ? 1 : 0;
-            info.work_bytes = (int64_t)p->L * 16;
-        }
-    }
-    if (info.shape == GILS_SHAPE_LARGE) {
-        int32_t lds = 0; int64_t work = 0;
-        if (int rc = gils_large_plan(who, g_gils_err, p, &lds, &work)) return rc;
-        info.threads = 1024; info.lds_bytes = lds; info.work_bytes = work + (int64_t)p->L * 16;
-    }
-    if (info.work_bytes + info.output_bytes > (1ll << 38))
-        return bad("the batch needs " + std::to_string(info.work_bytes) + " bytes of work memory and " + std::to_string(info.output_bytes) +
-                   " bytes of outputs, more than the " + std::to_string(1ll << 38) + " bytes a plan accepts");
-    return GIL_OK;
+    info.shape = sh.shape; info.threads = sh.threads; info.lds_bytes = sh.lds_bytes; info.phase_in_lds = sh.phase_in_lds;
+    info.work_bytes = sh.large_work + (int64_t)p->L * 16;
+    return gil_refuse_plan_bytes(who, g_gils_err, info.work_bytes, info.output_bytes);
 }
 
 std::string g_gilc_err;
@@ -758,8 +706,7 @@ std::string g_gilc_err;
 // the checks gilc_plan and gilc_run share, and the shape: 0 with `info` filled, or GIL_ERR_ARG with the text in g_gilc_err
 int gilc_decide(const char *who, const gil_params *p, const GilcCall &c, bool states, gilc_plan_info &info) {
     auto bad = [&](const std::string &m) { g_gilc_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
-    if (p->L < 2) return bad("L must be at least 2");
-    if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
+    if (const char *why = gil_check_plan_params(p)) return bad(why);
     if (c.n_groups < 0 || c.n_groups > GILC_MAX_GROUPS) return bad("n_groups = " + std::to_string(c.n_groups) + " is outside [0, " + std::to_string(GILC_MAX_GROUPS) + "]");
     if (c.c_bins < 2 || c.c_bins > GILC_MAX_CBINS) return bad("c_bins = " + std::to_string(c.c_bins) + " is outside [2, " + std::to_string(GILC_MAX_CBINS) + "]");
     if (c.h_bins < 1 || c.h_bins > GILC_MAX_HBINS) return bad("h_bins = " + std::to_string(c.h_bins) + " is outside [1, " + std::to_string(GILC_MAX_HBINS) + "]");
@@ -771,27 +718,15 @@ int gilc_decide(const char *who, const gil_params *p, const GilcCall &c, bool st
             if (g < -1 || g >= c.n_groups) return bad("group id " + std::to_string(g) + " at site " + std::to_string(x) + " is outside [-1, n_groups = " + std::to_string(c.n_groups) + ")");
             if (g >= 0 && !(p->anchor_mask && p->anchor_mask[x])) return bad("site " + std::to_string(x) + " carries group " + std::to_string(g) + " but anchor_mask does not mark it");
         }
+    GilShape sh;
+    if (int rc = gil_choose_shape(who, g_gilc_err, p, false, &c, 0, (int32_t)(gilc_lds_slots(1024, c.n_groups, c.c_bins, c.h_bins) * 8), sh)) return rc;
     info = gilc_plan_info{};
     info.row_len = GILC_NFIXED + c.n_groups + c.c_bins;
     info.output_bytes = gilc_output_bytes(p, c, states);
-    info.shape = GILS_SHAPE_LARGE;
-    const int64_t group_bytes = c.n_groups > 0 ? (int64_t)p->L * 4 : 0;
-    if (p->L <= GIL_MAX_L && p->n_cap <= GIL_MAX_N) {
-        if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
-        std::vector<double> table; int tlen = 0, q = 0, NT = 0; size_t lds = 0;
-        weight_table(p->sigma_grid, p->L, p->K, p->periodic != 0, table, tlen, q);
-        batch_shape(p->L, p->n_cap, tlen, false, NT, lds, nullptr, &c);
-        if (lds <= 160 * 1024) { info.shape = GILS_SHAPE_BATCH; info.threads = NT; info.lds_bytes = (int32_t)lds; info.work_bytes = group_bytes; }
-    }
-    if (info.shape == GILS_SHAPE_LARGE) {
-        int32_t lds = 0; int64_t work = 0;
-        if (int rc = gilc_large_plan(who, g_gilc_err, p, (int32_t)(gilc_lds_slots(1024, c.n_groups, c.c_bins, c.h_bins) * 8), &lds, &work)) return rc;
-        info.threads = 1024; info.lds_bytes = lds; info.work_bytes = work + (int64_t)p->n_systems * p->n_cap * 8 + group_bytes;
-    }
-    if (info.work_bytes + info.output_bytes > (1ll << 38))
-        return bad("the batch needs " + std::to_string(info.work_bytes) + " bytes of work memory and " + std::to_string(info.output_bytes) +
-                   " bytes of outputs, more than the " + std::to_string(1ll << 38) + " bytes a plan accepts");
-    return GIL_OK;
+    info.shape = sh.shape; info.threads = sh.threads; info.lds_bytes = sh.lds_bytes;
+    info.work_bytes = (c.n_groups > 0 ? (int64_t)p->L * 4 : 0);   // the group table; large shape: the bind times too
+    if (sh.shape == GILS_SHAPE_LARGE) info.work_bytes += sh.large_work + (int64_t)p->n_systems * p->n_cap * 8;
+    return gil_refuse_plan_bytes(who, g_gilc_err, info.work_bytes, info.output_bytes);
 }
 
 std::string g_gilp_err;
@@ -799,8 +734,7 @@ std::string g_gilp_err;
 // the checks gilp_plan and gilp_run share, and the shape: 0 with `info` filled, or GIL_ERR_ARG with the text in g_gilp_err
 int gilp_decide(const char *who, const gil_params *p, const GilpCall &c, bool states, gilp_plan_info &info) {
     auto bad = [&](const std::string &m) { g_gilp_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
-    if (p->L < 2) return bad("L must be at least 2");
-    if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
+    if (const char *why = gil_check_plan_params(p)) return bad(why);
     const int max_bins = std::min(p->L, GILP_MAX_BINS);
     if (c.n_bins < 1 || c.n_bins > max_bins) return bad("n_bins = " + std::to_string(c.n_bins) + " is outside [1, min(L, GILP_MAX_BINS) = " + std::to_string(max_bins) + "]");
     if (c.n_groups < 1 || c.n_groups > GILP_MAX_GROUPS) return bad("n_groups = " + std::to_string(c.n_groups) + " is outside [1, " + std::to_string(GILP_MAX_GROUPS) + "]");
@@ -813,28 +747,16 @@ int gilp_decide(const char *who, const gil_params *p, const GilpCall &c, bool st
             const int g = c.group_of_system[s];
             if (g < 0 || g >= c.n_groups) return bad("group id " + std::to_string(g) + " of system " + std::to_string(s) + " is outside [0, n_groups = " + std::to_string(c.n_groups) + ")");
         }
+    const size_t prof_lds = gilp_lds_bytes(c.n_bins, c.want_field != 0);
+    GilShape sh;
+    if (int rc = gil_choose_shape(who, g_gilp_err, p, false, nullptr, prof_lds, (int32_t)prof_lds, sh)) return rc;
     info = gilp_plan_info{};
     info.bin_width = (p->L + c.n_bins - 1) / c.n_bins;
     info.n_bins_used = (p->L + info.bin_width - 1) / info.bin_width;
     info.output_bytes = gilp_output_bytes(p, c.n_groups, c.n_bins, states, c.profile_obs != nullptr);
-    info.shape = GILS_SHAPE_LARGE;
-    const size_t prof_lds = gilp_lds_bytes(c.n_bins, c.want_field != 0);
-    if (p->L <= GIL_MAX_L && p->n_cap <= GIL_MAX_N) {
-        if (p->K < 1 || p->K > 32) return bad("site capacity K must be in [1, 32]");
-        std::vector<double> table; int tlen = 0, q = 0, NT = 0; size_t lds = 0;
-        weight_table(p->sigma_grid, p->L, p->K, p->periodic != 0, table, tlen, q);
-        batch_shape(p->L, p->n_cap, tlen, false, NT, lds, nullptr, nullptr, prof_lds);
-        if (lds <= 160 * 1024) { info.shape = GILS_SHAPE_BATCH; info.threads = NT; info.lds_bytes = (int32_t)lds; info.work_bytes = (int64_t)p->n_systems * 4; }
-    }
-    if (info.shape == GILS_SHAPE_LARGE) {
-        int32_t lds = 0; int64_t work = 0;
-        if (int rc = gilp_large_plan(who, g_gilp_err, p, (int32_t)prof_lds, &lds, &work)) return rc;
-        info.threads = 1024; info.lds_bytes = lds; info.work_bytes = work + (int64_t)p->n_systems * 4;
-    }
-    if (info.work_bytes + info.output_bytes > (1ll << 38))
-        return bad("the batch needs " + std::to_string(info.work_bytes) + " bytes of work memory and " + std::to_string(info.output_bytes) +
-                   " bytes of outputs, more than the " + std::to_string(1ll << 38) + " bytes a plan accepts");
-    return GIL_OK;
+    info.shape = sh.shape; info.threads = sh.threads; info.lds_bytes = sh.lds_bytes;
+    info.work_bytes = sh.large_work + (int64_t)p->n_systems * 4;
+    return gil_refuse_plan_bytes(who, g_gilp_err, info.work_bytes, info.output_bytes);
 }
 
 std::string g_gilx_err;
@@ -898,9 +820,6 @@ int gilx_decide(const char *who, const gil_params *p, const gilx_variants *v, bo
 
 std::string g_gilxs_err;
 
-// what gilxs_run adds to gilx_run: the structure sums (rows optional) and their window reduction
-struct GilxsCall { int k_max, first_obs; double *structure_obs, *head_obs, *window; int32_t *n_window, *n_empty; };
-
 // the checks gilxs_plan and gilxs_run share, the tables and the shape: 0 with `info` and `tb` filled, or GIL_ERR_ARG with the
 // text in g_gilxs_err.  gilx_decide's refusals first, then gils_decide's.
 int gilxs_decide(const char *who, const gil_params *p, const gilx_variants *v, int k_max, int first_obs, bool states, bool rows,
@@ -923,91 +842,52 @@ int gilxs_decide(const char *who, const gil_params *p, const gilx_variants *v, i
     info.work_bytes = (int64_t)p->L * 16;
     const int64_t S = p->n_systems, O = p->n_obs;
     info.output_bytes = xi.output_bytes + S * (O * 32 + (int64_t)k_max * 24 + 8) + (rows ? S * O * info.row_len * 8 : 0);
-    if (info.work_bytes + info.output_bytes > (1ll << 38))
-        return bad("the batch needs " + std::to_string(info.work_bytes) + " bytes of work memory and " + std::to_string(info.output_bytes) +
-                   " bytes of outputs, more than the " + std::to_string(1ll << 38) + " bytes a plan accepts");
-    return GIL_OK;
+    return gil_refuse_plan_bytes(who, g_gilxs_err, info.work_bytes, info.output_bytes);
 }
 
-// gilx_run's driver: batch_run for a launch of the mixed instantiations; xs: gilxs_run's call, with the structure sums
-int mixed_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
-              const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
-              int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms, const GilxsCall *xs = nullptr) {
+// gilx_run's driver, and with ex.xs gilxs_run's: the variant tables, the launch order, the seeds and streams and the window
+// outputs are its own, the rest is the staging path batch_run takes
+int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, const GilExtras &ex) {
+    const GilxsCall *xs = ex.xs;
     const char *who = xs ? "gilxs_run" : "gilx_run";
     std::string &err = xs ? g_gilxs_err : g_gilx_err;
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilx_plan_info info; GilxTables tb;
     gilxs_plan_info sinfo{};
     if (xs) {
-        if (int rc = gilxs_decide(who, p, v, xs->k_max, xs->first_obs, pos_obs || sigma_obs || flags_obs, xs->structure_obs != nullptr, sinfo, tb)) return rc;
+        if (int rc = gilxs_decide(who, p, v, xs->k_max, xs->first_obs, io.states(), xs->structure_obs != nullptr, sinfo, tb)) return rc;
         info = gilx_plan_info{};
         info.threads = sinfo.threads; info.lds_bytes = sinfo.lds_bytes;
-    } else if (int rc = gilx_decide(who, p, v, pos_obs || sigma_obs || flags_obs, info, tb)) return rc;
-    const int S = p->n_systems, L = p->L, ncap = p->n_cap, V = v->n_variants, NT = info.threads;
-    for (int s = 0; s < S; ++s) {
-        if (n0[s] < 0 || n0[s] > ncap) return bad("n0 = " + std::to_string(n0[s]) + " of system " + std::to_string(s) + " is outside [0, n_cap = " + std::to_string(ncap) + "]");
-        if (const char *why = gil_check_state(p, n0[s], pos0 + (size_t)s * ncap, sigma0 + (size_t)s * ncap)) return bad(why);
-    }
+    } else if (int rc = gilx_decide(who, p, v, io.states(), info, tb)) return rc;
+    const int S = p->n_systems, V = v->n_variants, NT = info.threads;
+    { const std::string why = gil_check_start(p, io, nullptr); if (!why.empty()) return bad(why); }
     if (const char *why = gil_check_flip_table(p)) return bad(why);
     std::vector<int32_t> order((size_t)S), stream((size_t)S);
     std::vector<uint64_t> seed((size_t)S);
     for (int s = 0; s < S; ++s) { order[(size_t)s] = v->order ? v->order[s] : s; stream[(size_t)s] = v->stream ? v->stream[s] : s; seed[(size_t)s] = v->seed ? v->seed[s] : p->seed; }
-    if (!v->order) std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return n0[x] > n0[y]; });   // long systems first
+    if (!v->order) std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return io.n0[x] > io.n0[y]; });   // long systems first
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: slots beyond n0 and rows never reached stay zero
     if (int rc = job.select_device(p->device)) return rc;
-    if (xs) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return job.fail(GIL_ERR_HIP, std::string(who) + ": hipMemGetInfo failed");
-        if ((uint64_t)(sinfo.work_bytes + sinfo.output_bytes) > (uint64_t)free_b)
-            return bad("the batch needs " + std::to_string(sinfo.work_bytes) + " bytes of work memory and " + std::to_string(sinfo.output_bytes) +
-                       " bytes of outputs, the device has " + std::to_string(free_b) + " bytes free");
-    }
+    if (xs) if (int rc = gil_refuse_device_bytes(job, sinfo.work_bytes, sinfo.output_bytes)) return rc;
     GilxsBatchArgs a{};
     a.p = *p; a.p.sigma_grid = 0.0; a.p.block_table = nullptr;
-    a.tlen = tb.max_tlen; a.chunk = (ncap + NT - 1) / NT;        // the layout's table length; the kernel takes every system's own chunk
+    a.tlen = tb.max_tlen; a.chunk = (p->n_cap + NT - 1) / NT;    // the layout's table length; the kernel takes every system's own chunk
     a.m = gil_model(p);
-    const size_t lds = (size_t)info.lds_bytes, SN = (size_t)S * ncap, SO = (size_t)S * p->n_obs, KK = (size_t)(p->K + 1) * (p->K + 1);
-    UP(beta, p->beta, (size_t)S); UP(table, tb.table.data(), tb.table.size()); UP(times, p->times_obs, (size_t)p->n_obs);
-    UP(n0, n0, (size_t)S); UP(pos0, pos0, SN); UP(sigma0, sigma0, SN);
-    if (bound0) UP(bound0, bound0, SN);
-    if (p->anchor_mask) UP(anchor, p->anchor_mask, (size_t)L);
-    if (p->front_lo) UP(front_lo, p->front_lo, (size_t)L);
-    if (v->block_table) { UP(block_table, v->block_table, (size_t)V * KK); a.mx.has_block = 1; }
+    const size_t lds = (size_t)info.lds_bytes, SO = (size_t)S * p->n_obs, KK = (size_t)(p->K + 1) * (p->K + 1);
+    if (int rc = gil_stage_common(job, a, p, io, tb.table, (size_t)S * p->n_cap, true, v->block_table, (size_t)V * KK)) return rc;
+    a.mx.has_block = v->block_table ? 1 : 0;
     UP(mx.order, order.data(), (size_t)S); UP(mx.variant_of_system, v->variant_of_system, (size_t)S); UP(mx.variants, tb.var.data(), (size_t)V);
     UP(mx.seed, seed.data(), (size_t)S); UP(mx.stream, stream.data(), (size_t)S);
-    if (int rc = gil_upload_flip_table(job, p, a.m)) return rc;
-    if (uniforms) UP(uniforms, uniforms, (size_t)S * p->max_events * 4);
-    OUT(pos_obs, pos_obs, SO * ncap); OUT(sigma_obs, sigma_obs, SO * ncap); OUT(flags_obs, flags_obs, SO * ncap);
-    OUT(scalars, scalars_obs, SO * GIL_NSCALARS);
-    OUT(n_recorded, n_recorded, (size_t)S); OUT(t_final, t_final, (size_t)S); OUT(exits, exits, SN * 3); OUT(n_exits, n_exits, (size_t)S);
-    OUT(n_events, n_events, (size_t)S);
-    const size_t row = xs ? 4 + 2 * (size_t)xs->k_max : 0;
     if (xs) {
-        GilsArgs &sa = a.st;
-        double *phase = nullptr;
-        if (xs->structure_obs) if (int rc = job.alloc(&sa.rows, SO * row, "structure_obs")) return rc;
-        if (int rc = job.alloc(&phase, (size_t)2 * L, "phase")) return rc;
-        sa.phase = phase; sa.k_max = xs->k_max; sa.first_obs = xs->first_obs; sa.phase_in_lds = sinfo.phase_in_lds;
+        if (int rc = gil_stage_structure(job, a, p, xs->k_max, xs->first_obs, xs->structure_obs != nullptr, sinfo.phase_in_lds != 0)) return rc;
         WORK(wn.head, SO * 4); WORK(wn.window, (size_t)S * 3 * xs->k_max); WORK(wn.n_window, (size_t)S); WORK(wn.n_empty, (size_t)S);
-        if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, true, false, false, true>)
-                                                  : reinterpret_cast<const void *>(&gil_kernel<256, true, false, false, true>), lds)) return rc;
-        hipLaunchKernelGGL(gils_phase_table, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, nullptr, phase, L);
-    } else if (int rc = job.raise_lds_limit(NT == 64 ? reinterpret_cast<const void *>(&gil_kernel<64, false, false, false, true>)
-                                                     : reinterpret_cast<const void *>(&gil_kernel<256, false, false, false, true>), lds)) return rc;
+    }
     if (int rc = job.create_events()) return rc;
-    job.ev.start();
+    if (int rc = xs ? gil_launch<GilKind::MixedStructure>(job, NT, S, lds, a) : gil_launch<GilKind::Mixed>(job, NT, S, lds, a)) return rc;
+    if (int rc = job.finish(hipGetLastError(), "gil_kernel (mixed)", io.kernel_ms)) return rc;
+    if (int rc = gil_fetch_common(job, a, p, io)) return rc;
     if (xs) {
-        if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, true, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, a);
-        else hipLaunchKernelGGL((gil_kernel<256, true, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, a);
-    } else if (NT == 64) hipLaunchKernelGGL((gil_kernel<64, false, false, false, true>), dim3((unsigned)S), dim3(64), lds, nullptr, static_cast<const GilxBatchArgs &>(a));
-    else hipLaunchKernelGGL((gil_kernel<256, false, false, false, true>), dim3((unsigned)S), dim3(256), lds, nullptr, static_cast<const GilxBatchArgs &>(a));
-    job.ev.stop();
-    if (int rc = job.finish(hipGetLastError(), "gil_kernel (mixed)", kernel_ms)) return rc;
-    DOWN(pos_obs, pos_obs, SO * ncap * 4); DOWN(sigma_obs, sigma_obs, SO * ncap); DOWN(flags_obs, flags_obs, SO * ncap);
-    DOWN(scalars_obs, scalars, SO * GIL_NSCALARS * 8); DOWN(n_recorded, n_recorded, (size_t)S * 4); DOWN(n_events, n_events, (size_t)S * 8);
-    DOWN(t_final, t_final, (size_t)S * 8); DOWN(exits, exits, SN * 3 * 8); DOWN(n_exits, n_exits, (size_t)S * 4);
-    if (xs) {
-        if (xs->structure_obs) if (int rc = job.download(xs->structure_obs, a.st.rows, SO * row * 8, "structure_obs")) return rc;
+        if (int rc = gil_fetch_structure(job, a, p, xs->structure_obs)) return rc;
         if (int rc = job.download(xs->head_obs, a.wn.head, SO * 4 * 8, "head_obs")) return rc;
         if (int rc = job.download(xs->window, a.wn.window, (size_t)S * 3 * xs->k_max * 8, "window")) return rc;
         if (int rc = job.download(xs->n_window, a.wn.n_window, (size_t)S * 4, "n_window")) return rc;
@@ -1034,8 +914,8 @@ int gilx_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, con
              const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
              int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
     if (!p || !v || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !v->variant_of_system) { g_gilx_err = "gilx_run: null argument"; return GIL_ERR_ARG; }
-    return mixed_run(p, v, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final,
-                     exits, n_exits, kernel_ms);
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    return mixed_run(p, v, io, GilExtras{});
 }
 
 const char *gilxs_last_error(void) { return g_gilxs_err.c_str(); }
@@ -1057,9 +937,10 @@ int gilxs_run(const gil_params *p, const gilx_variants *v, int32_t k_max, int32_
     if (!p || !v || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !v->variant_of_system || !head_obs || !window || !n_window || !n_empty) {
         g_gilxs_err = "gilxs_run: null argument"; return GIL_ERR_ARG;
     }
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
     const GilxsCall xs{k_max, first_obs, structure_obs, head_obs, window, n_window, n_empty};
-    return mixed_run(p, v, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final,
-                     exits, n_exits, kernel_ms, &xs);
+    GilExtras ex; ex.xs = &xs;
+    return mixed_run(p, v, io, ex);
 }
 
 const char *gilp_last_error(void) { return g_gilp_err.c_str(); }
@@ -1081,14 +962,12 @@ int gilp_run(const gil_params *p, int32_t n_bins, int32_t first_obs, int32_t wan
              int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, int64_t *ensemble_sums, int32_t *members,
              int32_t *profile_obs, double *kernel_ms) {
     if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !ensemble_sums || !members) { g_gilp_err = "gilp_run: null argument"; return GIL_ERR_ARG; }
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
     const GilpCall c{group_of_system, n_groups, n_bins, first_obs, want_field, ensemble_sums, members, profile_obs};
     gilp_plan_info info;
-    if (int rc = gilp_decide("gilp_run", p, c, pos_obs || sigma_obs || flags_obs, info)) return rc;
-    if (info.shape == GILS_SHAPE_BATCH)
-        return batch_run("gilp_run", g_gilp_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
-                         n_recorded, n_events, t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, nullptr, &c);
-    return gilp_large_run("gilp_run", g_gilp_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
-                          n_recorded, n_events, t_final, exits, n_exits, kernel_ms, &c);
+    if (int rc = gilp_decide("gilp_run", p, c, io.states(), info)) return rc;
+    GilExtras ex; ex.prof = &c;
+    return info.shape == GILS_SHAPE_BATCH ? batch_run("gilp_run", g_gilp_err, p, io, ex) : gil_large_run("gilp_run", g_gilp_err, p, io, ex);
 }
 
 const char *gilc_last_error(void) { return g_gilc_err.c_str(); }
@@ -1108,14 +987,12 @@ int gilc_run(const gil_params *p, const int32_t *group_of_site, int32_t n_groups
              int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, int64_t *capture_obs, int64_t *life_hist,
              double *life_sums, double *kernel_ms) {
     if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !capture_obs || !life_hist || !life_sums) { g_gilc_err = "gilc_run: null argument"; return GIL_ERR_ARG; }
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
     const GilcCall c{group_of_site, n_groups, c_bins, h_bins, first_obs, h_dt, capture_obs, life_hist, life_sums};
     gilc_plan_info info;
-    if (int rc = gilc_decide("gilc_run", p, c, pos_obs || sigma_obs || flags_obs, info)) return rc;
-    if (info.shape == GILS_SHAPE_BATCH)
-        return batch_run("gilc_run", g_gilc_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
-                         n_recorded, n_events, t_final, exits, n_exits, kernel_ms, 0, 0, nullptr, &c);
-    return gilc_large_run("gilc_run", g_gilc_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
-                          n_recorded, n_events, t_final, exits, n_exits, kernel_ms, &c);
+    if (int rc = gilc_decide("gilc_run", p, c, io.states(), info)) return rc;
+    GilExtras ex; ex.cap = &c;
+    return info.shape == GILS_SHAPE_BATCH ? batch_run("gilc_run", g_gilc_err, p, io, ex) : gil_large_run("gilc_run", g_gilc_err, p, io, ex);
 }
 
 const char *gil_last_error(void) { return g_gil_err.c_str(); }
@@ -1124,8 +1001,8 @@ int gil_run_batch(const gil_params *p, const int32_t *n0, const int32_t *pos0, c
                   const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
                   int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
     if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs) { g_gil_err = "gil_run_batch: null argument"; return GIL_ERR_ARG; }
-    return batch_run("gil_run_batch", g_gil_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
-                     n_recorded, n_events, t_final, exits, n_exits, kernel_ms, 0, 0, nullptr);
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    return batch_run("gil_run_batch", g_gil_err, p, io, GilExtras{});
 }
 
 const char *gilr_last_error(void) { return g_gilr_err.c_str(); }
@@ -1134,16 +1011,16 @@ int gilr_run(const gil_params *p, const int32_t *n0, const int32_t *pos0, const 
              const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
              int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
              int32_t obs_first, const gil_checkpoint *from, gil_checkpoint *to) {
-    return gilr_drive(false, "gilr_run", p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded,
-                      n_events, t_final, exits, n_exits, kernel_ms, obs_first, from, to);
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    return gilr_drive(false, "gilr_run", p, io, obs_first, from, to);
 }
 
 int gilrm_run(const gil_params *p, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
               const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
               int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
               int32_t obs_first, const gil_checkpoint *from, gil_checkpoint *to) {
-    return gilr_drive(true, "gilrm_run", p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded,
-                      n_events, t_final, exits, n_exits, kernel_ms, obs_first, from, to);
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    return gilr_drive(true, "gilrm_run", p, io, obs_first, from, to);
 }
 
 const char *gils_last_error(void) { return g_gils_err.c_str(); }
@@ -1161,13 +1038,11 @@ int gils_run(const gil_params *p, int32_t k_max, int32_t first_obs,
              int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
              int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *structure_obs, double *kernel_ms) {
     if (!p || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !structure_obs) { g_gils_err = "gils_run: null argument"; return GIL_ERR_ARG; }
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
     gils_plan_info info;
-    if (int rc = gils_decide("gils_run", p, k_max, first_obs, pos_obs || sigma_obs || flags_obs, scalars_obs != nullptr, info)) return rc;
-    if (info.shape == GILS_SHAPE_BATCH)
-        return batch_run("gils_run", g_gils_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
-                         n_recorded, n_events, t_final, exits, n_exits, kernel_ms, k_max, first_obs, structure_obs);
-    return gils_large_run("gils_run", g_gils_err, p, n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs,
-                          n_recorded, n_events, t_final, exits, n_exits, kernel_ms, k_max, first_obs, structure_obs);
+    if (int rc = gils_decide("gils_run", p, k_max, first_obs, io.states(), scalars_obs != nullptr, info)) return rc;
+    GilExtras ex; ex.k_max = k_max; ex.first_obs = first_obs; ex.structure_obs = structure_obs;
+    return info.shape == GILS_SHAPE_BATCH ? batch_run("gils_run", g_gils_err, p, io, ex) : gil_large_run("gils_run", g_gils_err, p, io, ex);
 }
 
 }  // extern "C"

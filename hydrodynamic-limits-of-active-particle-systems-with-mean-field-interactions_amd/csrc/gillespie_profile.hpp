@@ -104,13 +104,3 @@ __device__ inline void gilp_record(const GilpArgs &c, void *slots, size_t sys, i
 }
 
 }  // namespace
-
-// gilp_run (gillespie_hip.hip) reaches the large-system kernel of gillespie_big_hip.hip through these two: inside the
-// library only.  prof_lds: the profile slots' bytes, added to the kernel's own.
-__attribute__((visibility("hidden"))) int gilp_large_plan(const char *who, std::string &err, const gil_params *p, int32_t prof_lds,
-                                                          int32_t *lds_bytes, int64_t *work_bytes);
-__attribute__((visibility("hidden"))) int gilp_large_run(const char *who, std::string &err, const gil_params *p, const int32_t *n0,
-                                                         const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0, const double *uniforms,
-                                                         int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
-                                                         int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits,
-                                                         int32_t *n_exits, double *kernel_ms, const GilpCall *prof);

@@ -98,10 +98,3 @@ inline void gilr_finish(const gil_params *p, GilrCall &c, int32_t *n_recorded, c
 }
 
 }  // namespace
-
-// gilrm_run (gillespie_hip.hip) reaches the large-system kernel of gillespie_big_hip.hip through this one: gilm_run's driver with
-// the resumable instantiation; `rs` is the checked start state and comes back as the end state.
-__attribute__((visibility("hidden"))) int gilr_large_run(const char *who, std::string &err, const gil_params *p, const double *uniforms,
-                                                         int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
-                                                         int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits,
-                                                         int32_t *n_exits, double *kernel_ms, GilrCall *rs);
