@@ -47,7 +47,7 @@ struct LoopArgs {
 #endif
 };
 
-struct TlLds { size_t seg, cells, cells2, props, occ, misc, plist, fw, fs, tab, total; };
+struct TlLds { size_t seg, cells, cells2, props, occ, misc, plist, hrnd, fw, fs, tab, total; };
 __host__ __device__ inline TlLds tl_lds_layout(int tlen, int RS, int own, int K, int wbytes, int seg, int nw) {
     TlLds l;
     const size_t TS = 64 * (size_t)RS, ncell = (TS + 2) * K;
@@ -59,7 +59,8 @@ __host__ __device__ inline TlLds tl_lds_layout(int tlen, int RS, int own, int K,
     l.occ = up(l.props + TS * K, 8);
     l.misc = up(l.occ + TS + 2, 8);
     l.plist = l.misc + 128;
-    l.fw = up(l.plist + TS * (size_t)K * 8, 16);
+    l.hrnd = up(l.plist + TS * (size_t)K * 8, 16);
+    l.fw = l.hrnd + (nw == 8 ? 6 * (size_t)K * 16 : 0);      // the halo particles' random numbers (eight waves)
     l.fs = l.fw + TS * wbytes;
     l.tab = up(l.fs + TS * wbytes, 16);
     l.total = l.tab + (size_t)ts_table_chunks(tlen, RS, own, wbytes) * 1024;
@@ -190,6 +191,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
     uint8_t *occL = reinterpret_cast<uint8_t *>(lds_c + lay.occ);            // [TS + 2]
     int *misc = reinterpret_cast<int *>(lds_c + lay.misc);                   // by iteration parity: 0/1 deposits of this tile, 2/3 particles of the owned sites, 4/5 of the halo sites
     uint2 *plist = reinterpret_cast<uint2 *>(lds_c + lay.plist);
+    uint4 *hrnd = reinterpret_cast<uint4 *>(lds_c + lay.hrnd);               // eight waves, [6 K]: the random numbers of the halo particles, entry i belongs to plist[n0 + i]
     W *fieldW = reinterpret_cast<W *>(lds_c + lay.fw), *fieldS = reinterpret_cast<W *>(lds_c + lay.fs);   // [TS] each: the frame's field, kept across the steps
     W *tab = reinterpret_cast<W *>(lds_c + lay.tab);
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), e = blockIdx.y;
@@ -321,7 +323,13 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
 #ifdef APS_LOOP_STAMPS
     unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t0 = __builtin_amdgcn_s_memtime();
     const unsigned long long st_begin = st_t0;
-#define TLSTAMP(k) { const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t1_ - st_t0; st_t0 = t1_; }
+    // APS_LOOP_STAMP_MASK: the stamps a build keeps (bit k: stamp k).  A stamp that is left out reads no clock and its time falls to the next
+    // one kept, so a few stamps give whole segments of the chain -- 0x298: 9 = barrier E .. barrier S, 7 = sweep .. barrier B, 3 = proposals ..
+    // barrier D, 4 = exclusion .. barrier E -- at a handful of counters, few enough for the eight-wave kernels to stay within their registers
+#ifndef APS_LOOP_STAMP_MASK
+#define APS_LOOP_STAMP_MASK 0xFFF
+#endif
+#define TLSTAMP(k) if constexpr (((APS_LOOP_STAMP_MASK) >> (k)) & 1) { const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t1_ - st_t0; st_t0 = t1_; }
 #else
 #define TLSTAMP(k)
 #endif
@@ -351,6 +359,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
         unsigned long long *rec_out = la.xrec + ((size_t)(it & 1) * a.E * a.ntile + rec_e + tile) * la.rec;
         int *dcount = misc + (it & 1), *pcount = misc + 2 + (it & 1);
         bool gave_up = false;
+        constexpr bool PUBLISH_FIRST = WIDE && K1;             // eight waves: the record's boundary cells and tail are stored as early as they are known
         // ------------------------------------------------------------ A  this thread's particle and its random numbers (while the records travel)
         const int n0 = *pcount;                                // the owned sites' particles (first iteration: the whole frame's)
         uint2 mine = make_uint2(0u, CELL_EMPTY);
@@ -543,6 +552,15 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
         __syncthreads();                                       // S: the lists are complete
         TLSTAMP(9)
         if (misc[TL_ABORT]) return;                            // uniform: some wait ran out (here or in another workgroup)
+        // Eight waves: the halo particles joined the list after the random numbers were drawn; theirs are drawn here, by the wave
+        // that appended them, and kept next to the list -- ahead of the sweep, where this wave's quad has the smaller half of the
+        // rows, not inside the proposals phase, which is as long as its slowest wave.  (Four waves: every wave sweeps all rows, the
+        // draw costs the same wherever it stands, and it stays in the proposals phase.)
+        if (WIDE && wave == NW - 1 && lane < misc[4 + (it & 1)]) {
+            uint32_t x[4];
+            philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), plist[n0 + lane].y & CELL_ID, (uint32_t)(a.ens_base + e), a.seed_lo, a.seed_hi, x);
+            hrnd[lane] = make_uint4(x[0], x[1], x[2], x[3]);
+        }
         // the lists, class by class, into the rows of this wave (RQ of them from row0 on), then into the frame's field
         auto sweep_lists = [&](auto rq_c, auto &ac) {
             constexpr int RQ = decltype(rq_c)::value;
@@ -620,14 +638,18 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
             if (t < n_part) {
                 if (t >= n0) {                                 // a halo particle that joined after the random numbers were drawn
                     mine = plist[t];
-                    philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), mine.y & CELL_ID, (uint32_t)(a.ens_base + e), a.seed_lo, a.seed_hi, rx);
+                    if constexpr (WIDE) {                      // (drawn behind barrier S)
+                        const uint4 h4 = hrnd[t - n0];
+                        rx[0] = h4.x; rx[1] = h4.y; rx[2] = h4.z; rx[3] = h4.w;
+                    } else philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), mine.y & CELL_ID, (uint32_t)(a.ens_base + e), a.seed_lo, a.seed_hi, rx);
                 }
                 propose_one(mine, rx);
             }
             for (int j = NT + t; j < n_part; j += NT) {        // more particles on the frame than threads
                 const uint2 pc = plist[j];
                 uint32_t x[4];
-                philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), pc.y & CELL_ID, (uint32_t)(a.ens_base + e), a.seed_lo, a.seed_hi, x);
+                if (WIDE && j >= n0) { const uint4 h4 = hrnd[j - n0]; x[0] = h4.x; x[1] = h4.y; x[2] = h4.z; x[3] = h4.w; }
+                else philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), pc.y & CELL_ID, (uint32_t)(a.ens_base + e), a.seed_lo, a.seed_hi, x);
                 propose_one(pc, x);
             }
         }
@@ -703,6 +725,14 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
                 // granted arrivals (capacity of this site: max(1, 1 - occupancy) = 1; a rival is the other neighbour with a smaller id)
                 if (from_l1 && !(from_r1 && (cp1 & CELL_ID) < (cm1 & CELL_ID))) { newc[r] = cm1; newn[r] += 1; }
                 if (from_r1 && !(from_l1 && (cm1 & CELL_ID) < (cp1 & CELL_ID))) { newc[r] = cp1; newn[r] += 1; }
+                // Eight waves: a boundary cell goes out as soon as its thread knows it, ahead of barrier E -- like the deposits above.  The
+                // record of this parity is free: its previous content was read in the neighbours' iteration it - 1, which ended before
+                // they wrote the records this tile's wait of iteration it has seen
+                if (PUBLISH_FIRST && !last) {
+                    const int io = xi - 2;
+                    if (io < 3) tl_store_granule(rec_out + la.drec + io, tag_out, newc[r]);
+                    if (io >= own_n - 3) tl_store_granule(rec_out + la.drec + 3 + (io - (own_n - 3)), tag_out, newc[r]);
+                }
                 continue;
             }
             uint32_t *outN = cellN + (xi + 1) * K;
@@ -747,18 +777,25 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
         //                                                                 next iteration's list and occupancy of the owned sites
         const int count = min(*dcount, a.dcap);
         int *pnext = misc + 2 + ((it + 1) & 1);
+        auto put_tail = [&]() {                                // the rest of the record's last page: empty slots (at least one)
+            const int idx = count + t;
+            if (t < NSLOT && idx < (count / NSLOT + 1) * NSLOT && idx < la.drec) tl_store_granule(rec_out + idx, tag_out, DEP_NULL);
+        };
+        // Eight waves: what every neighbour waits for goes out first -- the page's tail (the count is final since barrier E; the boundary
+        // cells went out in the exclusion phase); the list, the occupancy and the bookkeeping of the next iteration follow
+        if (PUBLISH_FIRST && !last) put_tail();
 #pragma unroll
         for (int r = 0; r < NOLD; ++r) {
             const int xi = r * NT + t;
             const bool mine_site = !(xi < 2 || xi >= 2 + own_n || xi >= TS);
-            const int io = xi - 2;
             for (int k = 0; k < K; ++k) {                      // (uniform trip count: the list's ballots)
                 uint32_t c = CELL_EMPTY;
                 if (mine_site) {
                     c = K1 ? newc[r] : cellN[(xi + 1) * K + k];
                     cellL[(xi + 1) * K + k] = c;
                     if (last) cell_o[(unsigned)frame_site(xi) * (unsigned)K + (unsigned)k] = c;
-                    else {
+                    else if (!PUBLISH_FIRST) {
+                        const int io = xi - 2;
                         if (io < 3) tl_store_granule(rec_out + la.drec + io * K + k, tag_out, c);
                         if (io >= own_n - 3) tl_store_granule(rec_out + la.drec + 3 * K + (io - (own_n - 3)) * K + k, tag_out, c);
                     }
@@ -773,10 +810,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
                 }
             }
         }
-        if (!last && t < NSLOT) {                              // the rest of the record's last page: empty slots (at least one)
-            const int idx = count + t;
-            if (idx < (count / NSLOT + 1) * NSLOT && idx < la.drec) tl_store_granule(rec_out + idx, tag_out, DEP_NULL);
-        }
+        if (!PUBLISH_FIRST && !last) put_tail();
         for (int i = t; i < (TS * K + 3) / 4; i += NT) reinterpret_cast<uint32_t *>(propL)[i] = 0u;
         if (t == 0) {
             misc[(it + 1) & 1] = 0;                            // the next iteration's deposit counter (this one's is still being read)
@@ -784,7 +818,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
             misc[8 + 2 * (it & 1)] = 0; misc[9 + 2 * (it & 1)] = 0;   // and its list lengths
             if (last) {
                 a.dcnt_out[(size_t)e * a.ntile + tile] = (uint32_t)count;
-                if (tile == 0 && e == 0) a.stepw[(a.par + la.nsteps) & 1] = la.step0 + (unsigned long long)la.nsteps;   // (nobody reads the step words in here)
+                if (tile == 0 && e == 0) a.stepw[(a.par + la.nsteps) & 1] =   // (nobody reads the step words in here)
+                        WIDE ? step + 1ull : la.step0 + (unsigned long long)la.nsteps;   // eight waves: from the running index, not a sum kept in VGPRs across the loop
             }
         }
         if (!last) {                                           // ask for the next iteration's records now: in flight across the barrier and the random numbers

@@ -1,5 +1,7 @@
 """Diagnostic: build the library with -DAPS_LOOP_STAMPS into /tmp and print where a workgroup of the resident loop
-(csrc/tile_loop.hpp) spends an iteration.  Usage (GPU box): python tools/stamps_loop.py [steps] [-DAPS_...]"""
+(csrc/tile_loop.hpp) spends an iteration.  Usage (GPU box): python tools/stamps_loop.py [steps] [-DAPS_...]
+-DAPS_LOOP_STAMP_MASK=0x298 keeps four stamps only (barrier E .. S, sweep .. B, proposals .. D, exclusion .. E): a stamped
+eight-wave kernel without scratch.  With APS_LIB (a build made beforehand) give the same -D so that the rows are named right."""
 import ctypes as C, importlib, os, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,18 +35,34 @@ NW = h.loop_waves() or 4                                     # waves per tile of
 allw = buf.reshape(-1, NW, 16).astype(float) / steps         # [tile][wave][16]
 idxt = np.flatnonzero(allw[:, 0, 6] > 0)
 allw = allw[idxt]
-NAMES = ((2, "barrier F + random numbers"), (0, "wait for the records"), (8, "intake (pooling)"), (9, "barrier S"), (10, "sweep"), (11, "ds_add into the field"),
-         (7, "barrier B"), (3, "proposals (D)"), (4, "exclusion (E)"), (5, "hand over + ask ahead"), (6, "total"))
+PHASES = ((2, "barrier F + random numbers"), (0, "wait for the records"), (8, "intake (pooling)"), (9, "barrier S"), (10, "sweep"), (11, "ds_add into the field"),
+          (7, "barrier B"), (3, "proposals (D)"), (4, "exclusion (E)"), (5, "hand over + ask ahead"))       # in the order of an iteration
+mask = 0xFFF
+for x in extra:
+    if x.startswith("-DAPS_LOOP_STAMP_MASK="):
+        mask = int(x.split("=", 1)[1], 0)
+# a stamp that the build leaves out gives its time to the next one kept (around the end of the iteration too)
+kept = [i for i, (k, _) in enumerate(PHASES) if (mask >> k) & 1]
+NAMES = []
+for n, i in enumerate(kept):
+    j, parts = kept[n - 1], []
+    while j != i:
+        j = (j + 1) % len(PHASES)
+        parts.append(PHASES[j][1])
+    NAMES.append((PHASES[i][0], " + ".join(parts) if mask != 0xFFF else PHASES[i][1]))
+NAMES.append((6, "total"))
 print("workgroups", len(allw), f"of {NW} waves; cycles per iteration (s_memtime), per wave: mean over tiles [wave 0 .. {NW - 1}]")
 for k, name in NAMES:
-    print(f"  {name:28s} " + "  ".join(f"{allw[:, wv, k].mean():9.1f}" for wv in range(NW)) + f"   | max over waves, mean over tiles {allw[:, :, k].max(axis=1).mean():9.1f}")
-st = np.zeros((len(allw), 8))
-st[:, :8] = allw[:, 0, :8]
-idx = idxt
-for k, name in ((1, "intake, barrier S, sweep (wave 0)"),):
-    print(f"  {name:24s} mean {st[:, k].mean():9.1f}   median {np.median(st[:, k]):9.1f}   min {st[:, k].min():9.1f}   max {st[:, k].max():9.1f}")
-worst = np.argsort(-st[:, 1])[:8]
-print("  longest intake .. sweep: tiles", idx[worst], st[worst, 1].round(0), " their waits", st[worst, 0].round(0))
-best = np.argsort(st[:, 0])[:8]
-print("  shortest waits: tiles", idx[best], st[best, 0].round(0), "their intake+sweep", st[best, 1].round(0))
+    label = f"  {name:28s} " if mask == 0xFFF else f"  {name}\n  {'':28s} "
+    print(label + "  ".join(f"{allw[:, wv, k].mean():9.1f}" for wv in range(NW)) + f"   | max over waves, mean over tiles {allw[:, :, k].max(axis=1).mean():9.1f}")
+if mask == 0xFFF:                                            # (per-tile waits and intake .. sweep need the stamps 0 and 8 .. 11 of their own)
+    st = np.zeros((len(allw), 8))
+    st[:, :8] = allw[:, 0, :8]
+    idx = idxt
+    for k, name in ((1, "intake, barrier S, sweep (wave 0)"),):
+        print(f"  {name:24s} mean {st[:, k].mean():9.1f}   median {np.median(st[:, k]):9.1f}   min {st[:, k].min():9.1f}   max {st[:, k].max():9.1f}")
+    worst = np.argsort(-st[:, 1])[:8]
+    print("  longest intake .. sweep: tiles", idx[worst], st[worst, 1].round(0), " their waits", st[worst, 0].round(0))
+    best = np.argsort(st[:, 0])[:8]
+    print("  shortest waits: tiles", idx[best], st[best, 0].round(0), "their intake+sweep", st[best, 1].round(0))
 h.close()
