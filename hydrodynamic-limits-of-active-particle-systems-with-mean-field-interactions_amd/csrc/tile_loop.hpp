@@ -30,6 +30,10 @@ __host__ __device__ constexpr int tl_ng(int nw) { return 8 / nw; }
 #ifndef TL_MIN_WAVES
 #define TL_MIN_WAVES 2                     /* waves per SIMD the register allocator must leave room for (tuning builds may ask for more) */
 #endif
+// Eight waves, one cell per site: s_sleep units (64 cycles each) between two polls of a record that is not there yet.  Config 2 keeps
+// 4 096 waves polling; re-reading as fast as the answers come back slows the very stores the polls wait for (a second, staggered poll
+// in flight costs 0.4 us per step), and 16 is where the step is shortest (1, 4, 8, 16, 32 measured: DESIGN 7)
+constexpr int TL_REPOLL_SLEEP = 16;
 constexpr int TL_ABORT = 31;               // misc word: this workgroup leaves (a wait ran out, here or elsewhere)
 
 struct LoopArgs {
@@ -371,7 +375,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
         TLSTAMP(2)
         // ------------------------------------------------------------ B  bounded waits: re-read until the granule carries this step's tag
         auto spin_check = [&](unsigned &spins, unsigned long long &t_w) -> bool {     // true: give up
-            __builtin_amdgcn_s_sleep(1);
+            __builtin_amdgcn_s_sleep(PUBLISH_FIRST ? TL_REPOLL_SLEEP : 1);
             if ((++spins & 63u) != 0u) return false;
             const bool other = __hip_atomic_load((tl_gu32 *)la.abort_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
             const unsigned long long now = __builtin_amdgcn_s_memrealtime();
