@@ -1126,14 +1126,18 @@ struct ScalarArgs {                          // blockIdx.y = ensemble index with
     long long *out;                          // [n][16]
     const int *lo_hi;                        // [n][2] site range of the range count, or null (lo, hi below)
     int Npad, L, K, x_wall, lo, hi;
+    int site_lo, site_hi;                    // the sites whose particles count: [0, L), or a site-sharded handle's own range
 };
 enum { SC_N = 0, SC_SPIN, SC_POS, SC_WALL, SC_MAXPOS, SC_RANGE, SC_ATTEMPT, SC_BLOCKED, SC_DISP, SC_DISP2, SC_NDISP, SC_COUNT };
 
-__global__ __launch_bounds__(256) void count_sites(const uint32_t *__restrict__ src, uint32_t *cnt_pm, int Npad, int L) {
+// (site_lo, site_hi: a site-sharded handle counts the particles on its own sites -- straight after an upload its records still
+// hold every particle, none marked away)
+__global__ __launch_bounds__(256) void count_sites(const uint32_t *__restrict__ src, uint32_t *cnt_pm, int Npad, int L, int site_lo, int site_hi) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Npad) return;
     const uint32_t w = src[(size_t)blockIdx.y * Npad + i];
     if (w & (DEAD_BIT | AWAY_BIT)) return;
+    if ((int)(w & POS_MASK) < site_lo || (int)(w & POS_MASK) >= site_hi) return;
     atomicAdd(&cnt_pm[(size_t)blockIdx.y * L + (w & POS_MASK)], (w & SPIN_BIT) ? 1u : 65536u);
 }
 
@@ -1154,6 +1158,7 @@ __global__ __launch_bounds__(256) void observe_scalars(const ScalarArgs a) {
         const uint32_t w = src[i];
         if (w & (DEAD_BIT | AWAY_BIT)) continue;
         const int p = (int)(w & POS_MASK);
+        if (p < a.site_lo || p >= a.site_hi) continue;
         const bool plus = (w & SPIN_BIT) != 0;
         v[SC_N] += 1; v[SC_SPIN] += plus ? 1 : -1; v[SC_POS] += p;
         v[SC_WALL] += p >= a.x_wall;
@@ -1390,12 +1395,13 @@ __global__ __launch_bounds__(256) void structure_sites(const uint32_t *__restric
 
 // Fourier sums of the site histogram, one workgroup per mode k: sum over live particles of exp(-2 pi i k pos / L)
 // (= fft(counts)[k], the reference's np.fft.fft(total) up to the 1 / (n dx) normalisation, ref :527-533)
-__global__ __launch_bounds__(256) void structure_dft(const uint32_t *__restrict__ src, int Npad, int L, double *out) {
+__global__ __launch_bounds__(256) void structure_dft(const uint32_t *__restrict__ src, int Npad, int L, double *out, int site_lo, int site_hi) {
     const int k = blockIdx.x;
     double re = 0.0, im = 0.0, n = 0.0;
     for (int i = threadIdx.x; i < Npad; i += blockDim.x) {
         const uint32_t w = src[i];
         if (w & (DEAD_BIT | AWAY_BIT)) continue;
+        if ((int)(w & POS_MASK) < site_lo || (int)(w & POS_MASK) >= site_hi) continue;
         const long long r = ((long long)k * (long long)(w & POS_MASK)) % (long long)L;   // exact argument reduction
         double sn, cs;
         sincospi(-2.0 * ((double)r / (double)L), &sn, &cs);
@@ -1421,6 +1427,28 @@ __global__ __launch_bounds__(256) void bin_counts(const uint32_t *__restrict__ s
     if (w & (DEAD_BIT | AWAY_BIT)) return;
     if ((int)(w & POS_MASK) < site_lo || (int)(w & POS_MASK) >= site_hi) return;       // a site-sharded handle counts the particles on its own sites
     atomicAdd(((w & SPIN_BIT) ? plus : minus) + (w & POS_MASK) / (uint32_t)bin_sites, 1ull);
+}
+
+// ---- observation on a site-sharded handle: what its own records do not hold
+// the cells of ONE site into cnt_pm (blockIdx.y = ensemble of the call): the right neighbour rank's first site, which decides
+// whether the plus particles on this rank's last site are blocked; count_sites left it 0 (its particles are another rank's)
+__global__ __launch_bounds__(64) void count_cell_site(const uint32_t *__restrict__ cell, uint32_t *cnt_pm, int L, int K, int site) {
+    if ((int)threadIdx.x >= K) return;
+    const uint32_t c = cell[((size_t)blockIdx.y * L + site) * K + threadIdx.x];
+    if (c != CELL_EMPTY) atomicAdd(&cnt_pm[(size_t)blockIdx.y * L + site], (c & CELL_PLUS) ? 1u : 65536u);
+}
+
+// m(x) on the sites [lo, hi) from the {W, S} the handle maintains there (exact sums: the bits field_sites derives from all
+// particles), 0 on every other site -- so that sums of m over the L sites add up over the ranks
+__global__ __launch_bounds__(256) void own_site_field(const double2 *__restrict__ ws, double *m_out, int L, int lo, int hi) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= L) return;
+    double mloc = 0.0;
+    if (x >= lo && x < hi) {
+        const double2 v = ws[x];                              // (W, S)
+        if (v.x > 0.0) { mloc = v.y / v.x; mloc = mloc > 1.0 ? 1.0 : (mloc < -1.0 ? -1.0 : mloc); }
+    }
+    m_out[x] = mloc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2780,6 +2808,25 @@ bool all_set(const aps_handle *h) {
     return true;
 }
 
+bool site_sharded(const aps_handle *h) { return is_tiles(h) && h->world > 1; }
+// the sites whose particles an observation of this handle covers
+int observed_lo(const aps_handle *h) { return site_sharded(h) ? h->own_lo : 0; }
+int observed_hi(const aps_handle *h) { return site_sharded(h) ? h->own_hi : h->p.L; }
+
+// m(x) of ensemble e into d_mfield (after sync_slots).  One handle: all L sites, from the particles.  A site-sharded handle
+// holds only its own particles, and m is not additive over ranks: it reports m on its OWN sites, from the {W, S} it
+// maintains there, and 0 elsewhere -- the ranks' fields, and their sums over the sites, then add up to the single handle's
+int observe_field(aps_handle *h, int e, const char *who) {
+    if (!site_sharded(h))
+        return launch_field(h, e, h->d_sp8 + (size_t)e * h->Npad, h->d_tinfo + (size_t)e * h->ntiles, (int)h->ntiles, h->d_mfield);
+    if (!h->model.field_mode)
+        return fail(h, APS_ERR_STATE, std::string(who) + ": the global mean field of a site-sharded handle needs all ranks' particles; not available");
+    const int L = h->p.L;
+    hipLaunchKernelGGL(own_site_field, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, h->stream, h->d_ws + (size_t)e * L, h->d_mfield, L, h->own_lo, h->own_hi);
+    HIP_TRY(h, hipGetLastError());
+    return APS_OK;
+}
+
 }  // namespace
 
 // ================================================================================== C ABI
@@ -3030,7 +3077,8 @@ int aps_get_state(aps_handle *h, int32_t e, int32_t *pos, int8_t *sigma, uint8_t
         if (pos) pos[i] = (int32_t)(w & POS_MASK);
         if (sigma) sigma[i] = (w & SPIN_BIT) ? 1 : -1;
         if (bound) bound[i] = (w & BOUND_BIT) ? 1 : 0;
-        if (alive) alive[i] = (w & DEAD_BIT) ? 0 : ((w & AWAY_BIT) ? 2 : 1);
+        const bool away = (w & AWAY_BIT) || (int)(w & POS_MASK) < observed_lo(h) || (int)(w & POS_MASK) >= observed_hi(h);   // (no mark yet after an upload)
+        if (alive) alive[i] = (w & DEAD_BIT) ? 0 : (away ? 2 : 1);
     }
     return APS_OK;
 }
@@ -3427,6 +3475,9 @@ int aps_mark_reference(aps_handle *h, int32_t e) {
     if (!h) return APS_ERR_ARG;
     if (e < 0 || e >= h->E) return fail(h, APS_ERR_ARG, "aps_mark_reference: bad ensemble");
     if (h->n_set[(size_t)e] < 0) return fail(h, APS_ERR_STATE, "aps_mark_reference: no state uploaded for this ensemble");
+    // a rank's records of the particles on other ranks' sites are stale, and particles change ranks: no rank could pair a
+    // particle with its own reference position
+    if (site_sharded(h)) return fail(h, APS_ERR_STATE, "aps_mark_reference: not available on a site-sharded handle (displacements need every particle's own reference; merge aps_get_state over the ranks)");
     { int rc_ = sync_slots(h); if (rc_) return rc_; }
     int rc;
     if (!h->d_ref && (rc = dev_alloc(h, &h->d_ref, (size_t)h->E * h->Npad))) return rc;
@@ -3441,10 +3492,19 @@ int aps_mark_reference(aps_handle *h, int32_t e) {
 
 namespace {
 // scalar sums of ensembles [e0, e0 + n): one counting launch, one summing launch, one download
-int observe_scalars_impl(aps_handle *h, int e0, int n, int32_t x_wall, const int32_t *lo_hi, int32_t lo, int32_t hi,
+int observe_scalars_impl(aps_handle *h, const char *who, int e0, int n, int32_t x_wall, const int32_t *lo_hi, int32_t lo, int32_t hi,
                          const uint8_t *block_table, int64_t *out11) {
     const int K = h->p.K, L = h->p.L;
     int rc;
+    // a site range: whether the plus particles on the last own site are blocked is decided by the right neighbour rank's first
+    // site.  Its cells are here after a state upload and after every halo exchange (halo_segments: the neighbour's first three
+    // sites, written into the buffer the commit makes current), but the steps between two exchanges of an interval > 1 leave
+    // them behind: the ghost range shrinks to the own tiles (launch_tile_step).  Then no count of this rank alone is right.
+    const bool need_halo_site = site_sharded(h) && h->own_hi < L;
+    if (need_halo_site && h->halo_age != 0)
+        return fail(h, APS_ERR_STATE, std::string(who) +
+                    ": site-sharded handle between two halo exchanges (aps_halo_info: age " + std::to_string(h->halo_age) +
+                    "): the neighbour rank's boundary site, which the blocked count reads, is not current; observe after a step whose exchange was due");
     if ((rc = sync_slots(h))) return rc;
     if (!h->d_cnt_pm && (rc = dev_alloc(h, &h->d_cnt_pm, (size_t)L * h->E))) return rc;
     if (!h->d_scal && ((rc = dev_alloc(h, &h->d_scal, (size_t)16 * h->E)) ||
@@ -3463,12 +3523,15 @@ int observe_scalars_impl(aps_handle *h, int e0, int n, int32_t x_wall, const int
     if (lo_hi) HIP_TRY(h, hipMemcpyAsync(h->d_lo_hi, lo_hi, (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->d_cnt_pm, 0, (size_t)L * n * 4, h->stream));
     const uint32_t *src = h->d_src + (size_t)e0 * h->Npad;
-    hipLaunchKernelGGL(count_sites, dim3((unsigned)(h->Npad / 256), (unsigned)n), dim3(256), 0, h->stream, src, h->d_cnt_pm, (int)h->Npad, L);
+    hipLaunchKernelGGL(count_sites, dim3((unsigned)(h->Npad / 256), (unsigned)n), dim3(256), 0, h->stream, src, h->d_cnt_pm, (int)h->Npad, L, observed_lo(h), observed_hi(h));
+    if (need_halo_site)
+        hipLaunchKernelGGL(count_cell_site, dim3(1u, (unsigned)n), dim3(64), 0, h->stream, h->d_cell[h->step & 1] + (size_t)e0 * L * K, h->d_cnt_pm, L, K, h->own_hi);
     ScalarArgs a{};
     a.src = src; a.block_table = h->d_block_table; a.cnt_pm = h->d_cnt_pm; a.out = h->d_scal;
     a.ref = h->d_ref ? h->d_ref + (size_t)e0 * h->Npad : nullptr; a.ref_ok = h->d_ref_ok;
     a.lo_hi = lo_hi ? h->d_lo_hi : nullptr;
     a.Npad = (int)h->Npad; a.L = L; a.K = K; a.x_wall = x_wall; a.lo = lo; a.hi = hi;
+    a.site_lo = observed_lo(h); a.site_hi = observed_hi(h);
     hipLaunchKernelGGL(observe_scalars, dim3((unsigned)std::min<int64_t>(h->Npad / 256, 512), (unsigned)n), dim3(256), 0, h->stream, a);
     HIP_TRY(h, hipGetLastError());
     std::vector<long long> res((size_t)16 * n);
@@ -3486,22 +3549,22 @@ int aps_observe_scalars(aps_handle *h, int32_t e, int32_t x_wall, int32_t range_
     if (!h) return APS_ERR_ARG;
     if (e < 0 || e >= h->E || !out11) return fail(h, APS_ERR_ARG, "aps_observe_scalars: bad argument");
     if (h->n_set[(size_t)e] < 0) return fail(h, APS_ERR_STATE, "aps_observe_scalars: no state uploaded for this ensemble");
-    return observe_scalars_impl(h, e, 1, x_wall, nullptr, range_lo, range_hi, block_table, out11);
+    return observe_scalars_impl(h, "aps_observe_scalars", e, 1, x_wall, nullptr, range_lo, range_hi, block_table, out11);
 }
 
 int aps_observe_scalars_all(aps_handle *h, int32_t x_wall, const int32_t *range_lo_hi, const uint8_t *block_table, int64_t *out11) {
     if (!h) return APS_ERR_ARG;
     if (!out11) return fail(h, APS_ERR_ARG, "aps_observe_scalars_all: bad argument");
     if (!all_set(h)) return fail(h, APS_ERR_STATE, "aps_observe_scalars_all: upload a state for every ensemble first");
-    return observe_scalars_impl(h, 0, h->E, x_wall, range_lo_hi, 0, -1, block_table, out11);
+    return observe_scalars_impl(h, "aps_observe_scalars_all", 0, h->E, x_wall, range_lo_hi, 0, -1, block_table, out11);
 }
 
 int aps_observe_structure(aps_handle *h, int32_t e, int32_t k_max, double *out) {
     if (!h) return APS_ERR_ARG;
     if (e < 0 || e >= h->E || !out || k_max < 1 || k_max > h->p.L) return fail(h, APS_ERR_ARG, "aps_observe_structure: bad argument");
     if (h->n_set[(size_t)e] < 0) return fail(h, APS_ERR_STATE, "aps_observe_structure: no state uploaded for this ensemble");
-    int rc = sync_slots(h);
-    if (rc) return rc;
+    int rc = site_sharded(h) ? ensure_lattice(h) : APS_OK;    // (the own-site field is read from the maintained {W, S})
+    if (rc || (rc = sync_slots(h))) return rc;
     const int L = h->p.L;
     const size_t nout = 4 + 2 * (size_t)k_max;
     if (!h->d_cnt_pm && (rc = dev_alloc(h, &h->d_cnt_pm, (size_t)L * h->E))) return rc;
@@ -3511,10 +3574,10 @@ int aps_observe_structure(aps_handle *h, int32_t e, int32_t k_max, double *out) 
     if (hipMemsetAsync(d_out, 0, nout * sizeof(double), h->stream) != hipSuccess ||
         hipMemsetAsync(h->d_cnt_pm, 0, (size_t)L * 4, h->stream) != hipSuccess) return fail(h, APS_ERR_HIP, "aps_observe_structure: memset failed");
     const uint32_t *src = h->d_src + (size_t)e * h->Npad;
-    hipLaunchKernelGGL(count_sites, dim3((unsigned)(h->Npad / 256), 1u), dim3(256), 0, h->stream, src, h->d_cnt_pm, (int)h->Npad, L);
-    if ((rc = launch_field(h, e, h->d_sp8 + (size_t)e * h->Npad, h->d_tinfo + (size_t)e * h->ntiles, (int)h->ntiles, h->d_mfield))) return rc;
+    hipLaunchKernelGGL(count_sites, dim3((unsigned)(h->Npad / 256), 1u), dim3(256), 0, h->stream, src, h->d_cnt_pm, (int)h->Npad, L, observed_lo(h), observed_hi(h));
+    if ((rc = observe_field(h, e, "aps_observe_structure"))) return rc;
     hipLaunchKernelGGL(structure_sites, dim3((unsigned)std::min(1024, (L + 255) / 256)), dim3(256), 0, h->stream, h->d_cnt_pm, h->d_mfield, L, d_out);
-    hipLaunchKernelGGL(structure_dft, dim3((unsigned)k_max), dim3(256), 0, h->stream, src, (int)h->Npad, L, d_out);
+    hipLaunchKernelGGL(structure_dft, dim3((unsigned)k_max), dim3(256), 0, h->stream, src, (int)h->Npad, L, d_out, observed_lo(h), observed_hi(h));
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
         hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, APS_ERR_HIP, "aps_observe_structure: kernel or copy failed");
     return APS_OK;
@@ -3532,7 +3595,7 @@ int aps_observe_bins(aps_handle *h, int32_t e, int32_t nbins, int64_t *plus, int
     HIP_TRY(h, tmp.alloc(&d, (size_t)2 * nbins));
     if (hipMemsetAsync(d, 0, (size_t)2 * nbins * 8, h->stream) != hipSuccess) return fail(h, APS_ERR_HIP, "aps_observe_bins: memset failed");
     hipLaunchKernelGGL(bin_counts, dim3((unsigned)(h->Npad / 256)), dim3(256), 0, h->stream, h->d_src + (size_t)e * h->Npad, (int)h->Npad, bin_sites, d, d + nbins,
-                       is_tiles(h) && h->world > 1 ? h->own_lo : 0, is_tiles(h) && h->world > 1 ? h->own_hi : h->p.L);
+                       observed_lo(h), observed_hi(h));
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(plus, d, (size_t)nbins * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
         hipMemcpyAsync(minus, d + nbins, (size_t)nbins * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
         hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, APS_ERR_HIP, "aps_observe_bins: kernel or copy failed");
@@ -3990,6 +4053,7 @@ int aps_observe(aps_handle *h, int32_t e, int64_t *counts_p, int64_t *counts_m, 
     if (!h) return APS_ERR_ARG;
     if (e < 0 || e >= h->E) return fail(h, APS_ERR_ARG, "aps_observe: bad ensemble");
     if (h->n_set[(size_t)e] < 0) return fail(h, APS_ERR_STATE, "aps_observe: no state uploaded for this ensemble");
+    if (m_field && site_sharded(h)) { int rc_ = ensure_lattice(h); if (rc_) return rc_; }   // (the own-site field is read from the maintained {W, S})
     { int rc_ = sync_slots(h); if (rc_) return rc_; }
     const int L = h->p.L;
     if (counts_p || counts_m) {
@@ -3999,13 +4063,14 @@ int aps_observe(aps_handle *h, int32_t e, int64_t *counts_p, int64_t *counts_m, 
         if (counts_p) std::fill(counts_p, counts_p + L, 0);
         if (counts_m) std::fill(counts_m, counts_m + L, 0);
         for (uint32_t w : src) {
-            if (w & DEAD_BIT) continue;
+            if (w & (DEAD_BIT | AWAY_BIT)) continue;           // (away: on another rank's sites, counted there)
+            if ((int)(w & POS_MASK) < observed_lo(h) || (int)(w & POS_MASK) >= observed_hi(h)) continue;   // (straight after an upload)
             if (w & SPIN_BIT) { if (counts_p) counts_p[w & POS_MASK]++; }
             else if (counts_m) counts_m[w & POS_MASK]++;
         }
     }
     if (m_field) {
-        int rc = launch_field(h, e, h->d_sp8 + (size_t)e * h->Npad, h->d_tinfo + (size_t)e * h->ntiles, (int)h->ntiles, h->d_mfield);
+        int rc = observe_field(h, e, "aps_observe");
         if (rc) return rc;
         HIP_TRY(h, hipMemcpyAsync(m_field, h->d_mfield, (size_t)L * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));

@@ -139,8 +139,22 @@ int aps_comm_init(aps_handle *h, const uint8_t *id128);
  * deposit lists within the table's reach (ncclSend / ncclRecv inside aps_step once aps_comm_init was called).  A caller
  * that moves the halo itself calls aps_propose (the kernel), transfers, then aps_commit; aps_halo_copy is that transfer
  * between two handles living on ONE device (tests, single-process multi-handle runs).  On such handles aps_get_state
- * reports alive = 2 for particles that currently sit on another rank's sites, the lattice arrays are valid on the own sites,
- * and the scalar observables / exit log cover the own particles: the caller adds them up over the ranks. */
+ * reports alive = 2 for particles that currently sit on another rank's sites (from the upload on: every rank is given the whole
+ * state and keeps what lies in its range) and the lattice arrays are valid on the own sites.
+ * Observation on such a handle covers the particles on its OWN sites; a number it returns is right once added over the ranks
+ * (max for the largest position), and what cannot be made so is refused with APS_ERR_STATE:
+ *   add up     aps_get_exits (merge by time, index); aps_observe counts; aps_observe_bins; aps_observe_scalars[_all] entries
+ *              0 .. 7; aps_observe_structure out[0], out[1] and the Fourier sums out[4 ..]
+ *   own sites  the m_field of aps_observe is m(x) on the own sites (from the maintained W, S: the single handle's bits) and 0 on
+ *              all others, so the ranks' fields add up to the whole field, and out[2], out[3] of aps_observe_structure, sums over
+ *              the sites, add up too; refused when sigma_grid <= 0 (the global mean needs all ranks' particles)
+ *   blocked    entry 7 of the scalars reads the RIGHT neighbour rank's first site for the plus particles on this rank's last site.
+ *              Those cells are current after aps_set_state and after a commit whose halo exchange was due (aps_halo_info:
+ *              age 0), i.e. always with halo_interval 1.  Between two exchanges of a longer interval a rank that has a right
+ *              neighbour (own range ending below L) refuses aps_observe_scalars / aps_observe_scalars_all altogether
+ *   refused    aps_mark_reference: a rank's records of particles elsewhere are stale and particles change ranks, so no rank
+ *              can pair a particle with its reference; entries 8 .. 10 of the scalars are therefore 0.  Displacements of a
+ *              sharded run are taken from aps_get_state merged over the ranks */
 int aps_owned_sites(aps_handle *h, int32_t *lo, int32_t *hi);
 int aps_halo_copy(aps_handle *dst, aps_handle *src_neighbour);
 /* The same halo through host memory, for any transport: aps_halo_pack copies this rank's first (side 0, for the left
@@ -192,7 +206,8 @@ int aps_observe(aps_handle *h, int32_t ensemble, int64_t *counts_p, int64_t *cou
  * PARTICLE_solver_BIOLOGY_EXCLUSION_sweep_beta.py:123-229, :316-319, :500-525), all exact integers over the live
  * particles of one ensemble: out11 = { n, sum sigma, sum pos, #(pos >= x_wall), max pos (-1 if none),
  * #(range_lo <= pos <= range_hi), #(plus particles on sites < L-1), of those: blocked by the right neighbour,
- * sum d, sum d^2, #d } with d = pos - reference pos of the same particle (aps_mark_reference; zeros if none marked).
+ * sum d, sum d^2, #d } with d = pos - reference pos of the same particle (aps_mark_reference; zeros if none marked), over the
+ * particles alive now and at the mark; on a torus d is NOT unwrapped (a particle that went round counts as L - 1 back).
  * block_table[(K+1)*(K+1)], indexed [plus count * (K+1) + minus count] of the right neighbour site, says whether
  * that occupancy blocks (NULL: any particle blocks). */
 int aps_mark_reference(aps_handle *h, int32_t ensemble);
