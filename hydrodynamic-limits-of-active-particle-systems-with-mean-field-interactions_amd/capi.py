@@ -48,16 +48,6 @@ class GilxsPlanInfo(C.Structure):
                 ("systems_per_cu", C.c_int32), ("row_len", C.c_int32), ("work_bytes", C.c_int64), ("output_bytes", C.c_int64)]
 
 
-def declare_mixed_structure(lib, params_ptr, variants_ptr):
-    """The prototypes of include/gillespie_mixed_structure.h on `lib`; the two pointer types are gillespie.py's (gil_params and
-    gilx_variants are declared there)."""
-    lib.gilxs_last_error.restype, lib.gilxs_last_error.argtypes = C.c_char_p, []
-    lib.gilxs_plan.restype = C.c_int
-    lib.gilxs_plan.argtypes = [params_ptr, variants_ptr, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GilxsPlanInfo)]
-    lib.gilxs_run.restype = C.c_int             # n0 .. n_exits as gilx_run (14), then rows, head, window, n_window, n_empty
-    lib.gilxs_run.argtypes = [params_ptr, variants_ptr, C.c_int32, C.c_int32] + [C.c_void_p] * 19 + [C.POINTER(C.c_double)]
-
-
 _lib = None
 
 

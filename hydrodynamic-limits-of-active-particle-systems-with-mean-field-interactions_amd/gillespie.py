@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import json
+import types
 
 import numpy as np
 
@@ -90,59 +91,177 @@ GILC_NFIXED = 9
 CAPTURE_COLUMNS = ("n", "n_bound", "binds", "unbinds", "exits", "occupied_sites", "n_clusters", "largest_cluster", "sum_size2")
 
 
-def _lib():
-    lib = capi.load()
-    if not getattr(lib, "_gil_ready", False):
-        lib.gil_last_error.restype, lib.gil_last_error.argtypes = C.c_char_p, []
-        lib.gil_run_batch.restype = C.c_int
-        lib.gil_run_batch.argtypes = [C.POINTER(GilParams)] + [C.c_void_p] * 14 + [C.POINTER(C.c_double)]
-        lib.gil_large_last_error.restype, lib.gil_large_last_error.argtypes = C.c_char_p, []
-        lib.gil_run_large.restype = C.c_int
-        lib.gil_run_large.argtypes = [C.POINTER(GilParams), C.c_int32] + [C.c_void_p] * 12 + [C.POINTER(C.c_double)]
-        lib.gilm_last_error.restype, lib.gilm_last_error.argtypes = C.c_char_p, []
-        lib.gilm_plan.restype = C.c_int
-        lib.gilm_plan.argtypes = [C.POINTER(GilParams), C.c_int32, C.c_int32, C.POINTER(GilmPlanInfo)]
-        lib.gilm_run.restype = C.c_int
-        lib.gilm_run.argtypes = [C.POINTER(GilParams)] + [C.c_void_p] * 14 + [C.POINTER(C.c_double)]
-        lib.gils_last_error.restype, lib.gils_last_error.argtypes = C.c_char_p, []
-        lib.gils_plan.restype = C.c_int
-        lib.gils_plan.argtypes = [C.POINTER(GilParams), C.c_int32, C.c_int32, C.c_int32, C.POINTER(GilsPlanInfo)]
-        lib.gils_run.restype = C.c_int
-        lib.gils_run.argtypes = [C.POINTER(GilParams), C.c_int32, C.c_int32] + [C.c_void_p] * 15 + [C.POINTER(C.c_double)]
-        if hasattr(lib, "gilc_run"):           # an older build named by APS_LIB (a timing yardstick) has no capture entry points
-            lib.gilc_last_error.restype, lib.gilc_last_error.argtypes = C.c_char_p, []
-            lib.gilc_plan.restype = C.c_int
-            lib.gilc_plan.argtypes = [C.POINTER(GilParams)] + [C.c_int32] * 5 + [C.POINTER(GilcPlanInfo)]
-            lib.gilc_run.restype = C.c_int
-            lib.gilc_run.argtypes = ([C.POINTER(GilParams), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32] +
-                                     [C.c_void_p] * 17 + [C.POINTER(C.c_double)])
-        if hasattr(lib, "gilp_run"):           # likewise: no profile entry points in a build from before them
-            lib.gilp_last_error.restype, lib.gilp_last_error.argtypes = C.c_char_p, []
-            lib.gilp_plan.restype = C.c_int
-            lib.gilp_plan.argtypes = [C.POINTER(GilParams)] + [C.c_int32] * 6 + [C.POINTER(GilpPlanInfo)]
-            lib.gilp_run.restype = C.c_int
-            lib.gilp_run.argtypes = ([C.POINTER(GilParams), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] +
-                                     [C.c_void_p] * 17 + [C.POINTER(C.c_double)])
-        if hasattr(lib, "gilx_run"):           # likewise: no mixed batches in a build from before them
-            lib.gilx_last_error.restype, lib.gilx_last_error.argtypes = C.c_char_p, []
-            lib.gilx_plan.restype = C.c_int
-            lib.gilx_plan.argtypes = [C.POINTER(GilParams), C.POINTER(GilxVariants), C.c_int32, C.POINTER(GilxPlanInfo)]
-            lib.gilx_run.restype = C.c_int
-            lib.gilx_run.argtypes = [C.POINTER(GilParams), C.POINTER(GilxVariants)] + [C.c_void_p] * 14 + [C.POINTER(C.c_double)]
-        if hasattr(lib, "gilr_run"):           # likewise: no resumable launches in a build from before them
-            lib.gilr_last_error.restype, lib.gilr_last_error.argtypes = C.c_char_p, []
-            for name in ("gilr_run", "gilrm_run"):
-                getattr(lib, name).restype = C.c_int
-                getattr(lib, name).argtypes = ([C.POINTER(GilParams)] + [C.c_void_p] * 14 + [C.POINTER(C.c_double), C.c_int32,
-                                                                                           C.POINTER(GilCheckpoint), C.POINTER(GilCheckpoint)])
-        if hasattr(lib, "gilxs_run"):          # likewise: no mixed structure launches in a build from before them
-            capi.declare_mixed_structure(lib, C.POINTER(GilParams), C.POINTER(GilxVariants))
-        lib._gil_ready = True
-    return lib
+_I32, _DBL, _PTR, _MS = C.c_int32, C.c_double, C.c_void_p, C.POINTER(C.c_double)
+_PAR, _VAR, _CKP = C.POINTER(GilParams), C.POINTER(GilxVariants), C.POINTER(GilCheckpoint)
+N_COMMON = 14       # n0, pos0, sigma0, bound0, uniforms; pos, sigma, flags, scalars, n_recorded, n_events, t_final, exits, n_exits
 
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# ---- the entry points.  One launch is  entry(gil_params *, front..., the 14 common pointers, behind..., double *kernel_ms, tail...);
+# a row of ENTRIES says what an entry point puts around the common part, and its stage function makes those arguments for a call
+# `c` (the numbers of _run_batch_entry: S, M, ncap, L, K, the checkpoint's arrays `ck_in`, the common output arrays `results`)
+# from the keywords it names, out of all the extra keywords of _run_batch_entry, and names the outputs it adds to the dictionary.
+# An array whose bare address goes into a structure is appended to c.keep: c outlives the call.
+
+def _stage_plain(c, **_):
+    return [], [], [], {}
+
+
+def _stage_resumable(c, *, obs_first, **_):
+    """obs_first, the checkpoint to start from (NULL: a fresh start) and the one to fill, behind kernel_ms"""
+    ck_out = {k: np.zeros((c.S, c.ncap)[:nd], dt) for k, dt, nd in CHECKPOINT_ARRAYS}
+    c_in = None if c.ck_in is None else GilCheckpoint(**{k: _p(v).value for k, v in c.ck_in.items()})     # c.ck_in holds the arrays
+    c_out = GilCheckpoint(**{k: _p(v).value for k, v in ck_out.items()})                                  # the dictionary returned does
+    # first_row reads the checkpoint to start from only, which the library does not write (const in gillespie_resume.h)
+    first_row = np.zeros(c.S, np.int32) if c.ck_in is None else np.clip(c.ck_in["next_obs"] - int(obs_first), 0, None).astype(np.int32)
+    if c.ck_in is not None:
+        first_row[c.ck_in["next_obs"] < int(obs_first)] = 0        # ended before this segment: n_recorded is 0 too
+    return [], [], [int(obs_first), None if c_in is None else C.byref(c_in), C.byref(c_out)], dict(
+        checkpoint=ck_out, first_row=first_row, obs_first=int(obs_first), n0=np.full(c.S, c.ncap, np.int32))   # any slot may be alive
+
+
+def _stage_structure(c, *, k_max, first_obs, **_):
+    rows = np.zeros((c.S, c.M, 4 + 2 * max(int(k_max), 0)))
+    return [int(k_max), int(first_obs)], [_p(rows)], [], dict(structure=rows)
+
+
+def _stage_capture(c, *, group_of_site, n_groups, c_bins, h_bins, h_dt, first_obs, **_):
+    groups = None if group_of_site is None else np.ascontiguousarray(group_of_site, dtype=np.int32)
+    if groups is not None and groups.shape != (c.L,):
+        raise ValueError("group_of_site must have one entry per site")
+    capture = np.zeros((c.S, c.M, GILC_NFIXED + max(int(n_groups), 0) + max(int(c_bins), 0)), np.int64)
+    life_hist, life_sums = np.zeros((c.S, 2, max(int(h_bins), 1)), np.int64), np.zeros((c.S, 2, 2))
+    return ([_p(groups), int(n_groups), int(c_bins), int(h_bins), float(h_dt), int(first_obs)], [_p(capture), _p(life_hist), _p(life_sums)],
+            [], dict(capture=capture, life_hist=life_hist, life_sums=life_sums))
+
+
+def _stage_profiles(c, *, n_bins, first_obs, want_field, group_of_system, n_groups, per_system, **_):
+    groups = None if group_of_system is None else np.ascontiguousarray(group_of_system, dtype=np.int32)
+    if groups is not None and groups.shape != (c.S,):
+        raise ValueError("group_of_system must have one entry per system")
+    G, B = max(int(n_groups), 1), max(int(n_bins), 1)                     # a number below 1 is the library's to refuse
+    sums, members = np.zeros((G, c.M, GILP_NCOLS, B), np.int64), np.zeros((G, c.M), np.int32)
+    prof = np.zeros((c.S, c.M, 3, B), np.int32) if per_system else None
+    return ([int(n_bins), int(first_obs), int(want_field), _p(groups), int(n_groups)], [_p(sums), _p(members), _p(prof)], [],
+            dict(ensemble_sums=sums, members=members, profile_obs=prof))
+
+
+def _profile_bins(c, *, n_bins, **_):
+    """What a finished gilp_run adds behind its outputs (the library has accepted n_bins by then)."""
+    width = -(-int(c.L) // int(n_bins))
+    return dict(bin_width=width, n_bins_used=-(-int(c.L) // width))
+
+
+def _stage_mixed(c, *, mixed, **_):
+    desc, keep = _mixed_descriptor(c.S, int(c.K), **mixed)
+    if desc.variant_of_system is None:
+        raise ValueError("variant_of_system must have one entry per system")
+    c.keep.append(keep)
+    return [C.byref(desc)], [], [], {}
+
+
+def _stage_mixed_structure(c, *, mixed, k_max, first_obs, want_rows, **_):
+    front = _stage_mixed(c, mixed=mixed)[0]
+    kk = max(int(k_max), 0)
+    rows = np.zeros((c.S, c.M, 4 + 2 * kk)) if want_rows else None
+    head, window = np.zeros((c.S, c.M, 4)), np.zeros((c.S, kk, 3))          # gilxs_run refuses k_max < 1
+    n_window, n_empty = np.zeros(c.S, np.int32), np.zeros(c.S, np.int32)
+    back = c.results + [rows, head, window, n_window, n_empty]
+    return (front + [int(k_max), int(first_obs)], [_p(rows), _p(head), _p(window), _p(n_window), _p(n_empty)], [],
+            dict(structure=rows, head=head, window=window, n_window=n_window, n_empty=n_empty,
+                 bytes_back=int(sum(x.nbytes for x in back if x is not None))))
+
+
+class _Entry:
+    """last_error; the C types in `front` of the common pointers, `behind` them and, after kernel_ms, in the `tail`; `stage`;
+    `header`: named by the error of a call that finds the entry point missing in the loaded library; `finish`: like `stage`, what a
+    call that returned 0 adds to the dictionary last."""
+
+    def __init__(self, last_error, stage=_stage_plain, front=(), behind=(), tail=(), header=None, finish=None):
+        self.last_error, self.stage, self.front, self.behind, self.tail = last_error, stage, list(front), list(behind), list(tail)
+        self.header, self.finish = header, finish
+
+
+_RESUMABLE = dict(stage=_stage_resumable, tail=[_I32, _CKP, _CKP], header="include/gillespie_resume.h")
+ENTRIES = {
+    "gil_run_batch": _Entry("gil_last_error"),                     # systems in LDS
+    "gilm_run": _Entry("gilm_last_error"),                         # large systems
+    "gilr_run": _Entry("gilr_last_error", **_RESUMABLE),           # one segment of a run, systems in LDS
+    "gilrm_run": _Entry("gilr_last_error", **_RESUMABLE),          # the same, large systems
+    "gils_run": _Entry("gils_last_error", _stage_structure, [_I32, _I32], [_PTR]),
+    "gilc_run": _Entry("gilc_last_error", _stage_capture, [_PTR, _I32, _I32, _I32, _DBL, _I32], [_PTR] * 3),
+    "gilp_run": _Entry("gilp_last_error", _stage_profiles, [_I32, _I32, _I32, _PTR, _I32], [_PTR] * 3, finish=_profile_bins),
+    "gilx_run": _Entry("gilx_last_error", _stage_mixed, [_VAR]),   # a variant per system
+    "gilxs_run": _Entry("gilxs_last_error", _stage_mixed_structure, [_VAR, _I32, _I32], [_PTR] * 5),
+}
+# the plans: name -> (last_error, the C types between gil_params and the info structure, the info structure)
+PLANS = {
+    "gilm_plan": ("gilm_last_error", [_I32, _I32], GilmPlanInfo),
+    "gils_plan": ("gils_last_error", [_I32, _I32, _I32], GilsPlanInfo),
+    "gilc_plan": ("gilc_last_error", [_I32] * 5, GilcPlanInfo),
+    "gilp_plan": ("gilp_last_error", [_I32] * 6, GilpPlanInfo),
+    "gilx_plan": ("gilx_last_error", [_VAR, _I32], GilxPlanInfo),
+    "gilxs_plan": ("gilxs_last_error", [_VAR, _I32, _I32, _I32, _I32], capi.GilxsPlanInfo),
+}
+# an older build named by APS_LIB (a timing yardstick) may lack any entry point but these
+EVERY_BUILD = ("gil_run_batch", "gil_run_large", "gilm_run", "gilm_plan", "gils_run", "gils_plan")
+
+
+def _lib():
+    lib = capi.load()
+    if not getattr(lib, "_gil_ready", False):
+        protos = {"gil_run_large": ("gil_large_last_error", [_PAR, _I32] + [_PTR] * 12 + [_MS])}
+        for name, e in ENTRIES.items():
+            protos[name] = (e.last_error, [_PAR] + e.front + [_PTR] * N_COMMON + e.behind + [_MS] + e.tail)
+        for name, (last_error, middle, info) in PLANS.items():
+            protos[name] = (last_error, [_PAR] + middle + [C.POINTER(info)])
+        for name, (last_error, argtypes) in protos.items():
+            if name not in EVERY_BUILD and not hasattr(lib, name):
+                continue
+            getattr(lib, name).restype, getattr(lib, name).argtypes = C.c_int, argtypes
+            getattr(lib, last_error).restype, getattr(lib, last_error).argtypes = C.c_char_p, []
+        lib._gil_ready = True
+    return lib
+
+
+def _params(*, L, K, periodic, n_systems, n_cap, n_obs, sigma_grid=0.0, minus_anchor=False, immobilize=False, suppress_flip=False,
+            crowding=False, device=0, x_wall=0, ref_obs=0, rate_diffusion=0.0, rate_active=0.0, k_on=0.0, k_off=0.0, k_exit=0.0, T=0.0,
+            seed=0, max_events=0, beta=None, times_obs=None, anchor_mask=None, front_lo=None, block_table=None, flip_table=None):
+    """struct gil_params for a launch or a plan (a plan reads the shape alone), and the arrays it points to (keep them alive for the
+    call).  `beta` and `times_obs` are float64 arrays already; the tables are converted here."""
+    mask = None if anchor_mask is None or not np.any(anchor_mask) else np.ascontiguousarray(anchor_mask, dtype=np.uint8)
+    flo = None if front_lo is None else np.ascontiguousarray(front_lo, dtype=np.int32)
+    btab = None if block_table is None else np.ascontiguousarray(block_table, dtype=np.uint8)
+    ftab = None if flip_table is None else np.ascontiguousarray(flip_table, dtype=np.float64)      # [2][n + 1] (aps_set_flip_table)
+    keep = [beta, times_obs, mask, flo, btab, ftab]
+    address = [None if a is None else _p(a).value for a in keep]
+    par = GilParams(flip_n=0 if ftab is None else ftab.shape[1] - 1, L=L, K=K, periodic=int(bool(periodic)), minus_anchor=int(bool(minus_anchor)),
+                    immobilize=int(bool(immobilize)), suppress_flip=int(bool(suppress_flip)), crowding=int(bool(crowding)), n_systems=n_systems,
+                    n_cap=n_cap, n_obs=n_obs, device=device, x_wall=int(x_wall), ref_obs=int(ref_obs), sigma_grid=float(sigma_grid),
+                    rate_diffusion=float(rate_diffusion), rate_active=float(rate_active), k_on=float(k_on), k_off=float(k_off),
+                    k_exit=float(k_exit), T=float(T), seed=int(seed) & (2 ** 64 - 1), max_events=int(max_events), beta=address[0],
+                    times_obs=address[1], anchor_mask=address[2], front_lo=address[3], block_table=address[4], flip_table=address[5])
+    return par, keep
+
+
+def _plan(name, shape, numbers, variants=None):
+    """The one body of the plan_* functions: `shape` = the keywords of _params, `numbers` = the integers behind gil_params,
+    `variants` = the keywords of _mixed_descriptor for the plans of a mixed launch."""
+    lib = _lib()
+    last_error, _, info_type = PLANS[name]
+    par, keep = _params(**shape)                               # both `keep` lists live until this function returns
+    front = []
+    if variants is not None:
+        desc, keep_variants = _mixed_descriptor(int(shape["n_systems"]), int(shape["K"]), **variants)
+        front = [C.byref(desc)]
+    info = info_type()
+    rc = getattr(lib, name)(C.byref(par), *front, *numbers, C.byref(info))
+    if rc != 0:
+        raise capi.ApsError(rc, getattr(lib, last_error)().decode())
+    return {k: int(getattr(info, k)) for k, _ in info_type._fields_ if k != "reserved"}
 
 
 def run_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
@@ -186,13 +305,8 @@ CHECKPOINT_ARRAYS = (("pos", np.int32, 2), ("flags", np.uint8, 2), ("ref", np.in
 
 def plan_many_large(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, want_states=True, want_scalars=True):
     """gilm_plan: what a batch of large systems would use (blocks, table, LDS, bytes), by host arithmetic; no device needed."""
-    lib = _lib()
-    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), sigma_grid=float(sigma_grid), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
-    info = GilmPlanInfo()
-    rc = lib.gilm_plan(C.byref(par), int(bool(want_states)), int(bool(want_scalars)), C.byref(info))
-    if rc != 0:
-        raise capi.ApsError(rc, lib.gilm_last_error().decode())
-    return {k: int(getattr(info, k)) for k, _ in GilmPlanInfo._fields_ if k != "reserved"}
+    return _plan("gilm_plan", dict(L=L, K=K, periodic=periodic, sigma_grid=sigma_grid, n_systems=n_systems, n_cap=n_cap, n_obs=n_obs),
+                 [int(bool(want_states)), int(bool(want_scalars))])
 
 
 def run_structure_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
@@ -212,13 +326,8 @@ def run_structure_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active
 def plan_structure(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, k_max, first_obs=0, want_states=True):
     """gils_plan: which kernel `run_structure_raw` would use (shape 0: systems in LDS, 1: large systems), its threads per system,
     LDS, work and output bytes, by host arithmetic; no device needed.  Refuses what the run would refuse on these numbers."""
-    lib = _lib()
-    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), sigma_grid=float(sigma_grid), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
-    info = GilsPlanInfo()
-    rc = lib.gils_plan(C.byref(par), int(k_max), int(first_obs), int(bool(want_states)), C.byref(info))
-    if rc != 0:
-        raise capi.ApsError(rc, lib.gils_last_error().decode())
-    return {k: int(getattr(info, k)) for k, _ in GilsPlanInfo._fields_ if k != "reserved"}
+    return _plan("gils_plan", dict(L=L, K=K, periodic=periodic, sigma_grid=sigma_grid, n_systems=n_systems, n_cap=n_cap, n_obs=n_obs),
+                 [int(k_max), int(first_obs), int(bool(want_states))])
 
 
 def run_capture_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
@@ -246,13 +355,8 @@ def plan_capture(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, n_group
     """gilc_plan: which kernel `run_capture_raw` would use (shape 0: systems in LDS, 1: large systems), its threads per system,
     LDS, row length, work and output bytes, by host arithmetic; no device needed.  Refuses what the run would refuse on these
     numbers."""
-    lib = _lib()
-    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), sigma_grid=float(sigma_grid), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
-    info = GilcPlanInfo()
-    rc = lib.gilc_plan(C.byref(par), int(n_groups), int(c_bins), int(h_bins), int(first_obs), int(bool(want_states)), C.byref(info))
-    if rc != 0:
-        raise capi.ApsError(rc, lib.gilc_last_error().decode())
-    return {k: int(getattr(info, k)) for k, _ in GilcPlanInfo._fields_}
+    return _plan("gilc_plan", dict(L=L, K=K, periodic=periodic, sigma_grid=sigma_grid, n_systems=n_systems, n_cap=n_cap, n_obs=n_obs),
+                 [int(n_groups), int(c_bins), int(h_bins), int(first_obs), int(bool(want_states))])
 
 
 def run_profiles_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
@@ -280,14 +384,8 @@ def plan_profiles(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, n_bins
     """gilp_plan: which kernel `run_profiles_raw` would use (shape 0: systems in LDS, 1: large systems), its threads per system,
     LDS, the bin width and the bins that hold sites, work and output bytes, by host arithmetic; no device needed.  Refuses what
     the run would refuse on these numbers."""
-    lib = _lib()
-    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), sigma_grid=float(sigma_grid), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
-    info = GilpPlanInfo()
-    rc = lib.gilp_plan(C.byref(par), int(n_bins), int(n_groups), int(first_obs), int(want_field), int(bool(want_states)),
-                       int(bool(per_system)), C.byref(info))
-    if rc != 0:
-        raise capi.ApsError(rc, lib.gilp_last_error().decode())
-    return {k: int(getattr(info, k)) for k, _ in GilpPlanInfo._fields_ if k != "reserved"}
+    return _plan("gilp_plan", dict(L=L, K=K, periodic=periodic, sigma_grid=sigma_grid, n_systems=n_systems, n_cap=n_cap, n_obs=n_obs),
+                 [int(n_bins), int(n_groups), int(first_obs), int(want_field), int(bool(want_states)), int(bool(per_system))])
 
 
 def _mixed_descriptor(S, K, sigma_grids, variant_of_system, block_tables=None, seeds=None, streams=None, order=None):
@@ -324,14 +422,8 @@ def plan_mixed(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs, variant_
     """gilx_plan: what a mixed launch (`run_mixed_raw`) would use -- threads per system, LDS of a workgroup (the longest table of
     the batch), that table's length, the doubles of all tables, systems per CU by LDS and the output bytes -- by host arithmetic;
     no device needed.  Refuses what the run would refuse on these numbers."""
-    lib = _lib()
-    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
-    desc, keep = _mixed_descriptor(int(n_systems), int(K), sigma_grids, variant_of_system, order=order)
-    info = GilxPlanInfo()
-    rc = lib.gilx_plan(C.byref(par), C.byref(desc), int(bool(want_states)), C.byref(info))
-    if rc != 0:
-        raise capi.ApsError(rc, lib.gilx_last_error().decode())
-    return {k: int(getattr(info, k)) for k, _ in GilxPlanInfo._fields_}
+    return _plan("gilx_plan", dict(L=L, K=K, periodic=periodic, n_systems=n_systems, n_cap=n_cap, n_obs=n_obs), [int(bool(want_states))],
+                 dict(sigma_grids=sigma_grids, variant_of_system=variant_of_system, order=order))
 
 
 def run_mixed_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
@@ -355,14 +447,9 @@ def plan_mixed_structure(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs
     a workgroup (with the sums' slots and, where it fits, the phase table), the longest table's length, systems per CU by LDS, the
     row length, work and output bytes -- by host arithmetic; no device needed.  Refuses what the run would refuse on these
     numbers.  Without rows and states the output bytes do not grow with n_obs * k_max."""
-    lib = _lib()
-    par = GilParams(L=L, K=K, periodic=int(bool(periodic)), n_systems=n_systems, n_cap=n_cap, n_obs=n_obs)
-    desc, keep = _mixed_descriptor(int(n_systems), int(K), sigma_grids, variant_of_system, order=order)
-    info = capi.GilxsPlanInfo()
-    rc = lib.gilxs_plan(C.byref(par), C.byref(desc), int(k_max), int(first_obs), int(bool(want_states)), int(bool(want_rows)), C.byref(info))
-    if rc != 0:
-        raise capi.ApsError(rc, lib.gilxs_last_error().decode())
-    return {k: int(getattr(info, k)) for k, _ in capi.GilxsPlanInfo._fields_}
+    return _plan("gilxs_plan", dict(L=L, K=K, periodic=periodic, n_systems=n_systems, n_cap=n_cap, n_obs=n_obs),
+                 [int(k_max), int(first_obs), int(bool(want_states)), int(bool(want_rows))],
+                 dict(sigma_grids=sigma_grids, variant_of_system=variant_of_system, order=order))
 
 
 def run_mixed_structure_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs, T,
@@ -391,18 +478,16 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
                      want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table, k_max=None, first_obs=0,
                      group_of_site=None, n_groups=0, c_bins=0, h_bins=0, h_dt=0.0, n_cap=None, n_bins=0, want_field=False,
                      group_of_system=None, per_system=False, mixed=None, want_rows=True, obs_first=0, checkpoint=None):
-    """The batch entry points take the same arguments: gil_run_batch (systems in LDS), gilm_run (large systems), gils_run
-    (either, with the structure sums: k_max, first_obs) and gilc_run (either, with the capture statistics: group_of_site,
-    n_groups, c_bins, h_bins, h_dt, first_obs); gilp_run (either, with the ensemble profiles: n_bins, first_obs, want_field,
-    group_of_system, n_groups, per_system); gilx_run (systems in LDS, a variant per system: `mixed`, the keywords of
-    _mixed_descriptor); gilr_run and gilrm_run (one segment of a run: obs_first, checkpoint)."""
-    lib = _lib()
-    if entry in ("gilr_run", "gilrm_run") and not hasattr(lib, entry):
-        raise capi.ApsError(-1, f"the loaded library has no {entry} (include/gillespie_resume.h)")
-    call = getattr(lib, entry)
-    last_error = getattr(lib, {"gil_run_batch": "gil_last_error", "gilm_run": "gilm_last_error", "gils_run": "gils_last_error",
-                               "gilc_run": "gilc_last_error", "gilp_run": "gilp_last_error", "gilx_run": "gilx_last_error", "gilxs_run": "gilxs_last_error",
-                               "gilr_run": "gilr_last_error", "gilrm_run": "gilr_last_error"}[entry])
+    """One launch of the entry point `entry` of ENTRIES.  The batch entry points take the same arguments: gil_run_batch (systems in
+    LDS), gilm_run (large systems), gils_run (either, with the structure sums: k_max, first_obs) and gilc_run (either, with the
+    capture statistics: group_of_site, n_groups, c_bins, h_bins, h_dt, first_obs); gilp_run (either, with the ensemble profiles:
+    n_bins, first_obs, want_field, group_of_system, n_groups, per_system); gilx_run (systems in LDS, a variant per system: `mixed`,
+    the keywords of _mixed_descriptor) and gilxs_run (the same with the structure sums: k_max, first_obs, want_rows); gilr_run and
+    gilrm_run (one segment of a run: obs_first, checkpoint)."""
+    lib, row = _lib(), ENTRIES[entry]
+    if row.header is not None and not hasattr(lib, entry):
+        raise capi.ApsError(-1, f"the loaded library has no {entry} ({row.header})")
+    call, last_error = getattr(lib, entry), getattr(lib, row.last_error)
     ck_in = None
     if checkpoint is not None:                                 # a resumed segment: the systems and their slots are the checkpoint's
         ck_in = {k: np.ascontiguousarray(checkpoint[k], dtype=dt) for k, dt, _ in CHECKPOINT_ARRAYS}
@@ -433,17 +518,11 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
         max_events = uniforms.shape[1]
     elif max_events is None:
         max_events = 2 ** 40
-    mask = None if anchor_mask is None or not np.any(anchor_mask) else np.ascontiguousarray(anchor_mask, dtype=np.uint8)
-    flo = None if front_lo is None else np.ascontiguousarray(front_lo, dtype=np.int32)
-    btab = None if block_table is None else np.ascontiguousarray(block_table, dtype=np.uint8)
-    ftab = None if flip_table is None else np.ascontiguousarray(flip_table, dtype=np.float64)      # [2][n + 1] (aps_set_flip_table)
-    par = GilParams(flip_n=0 if ftab is None else ftab.shape[1] - 1, flip_table=None if ftab is None else _p(ftab).value, L=L, K=K, periodic=int(bool(periodic)), minus_anchor=int(bool(minus_anchor)), immobilize=int(bool(immobilize)),
-                    suppress_flip=int(bool(suppress_flip)), crowding=int(bool(crowding)), n_systems=S, n_cap=ncap, n_obs=M,
-                    device=device, x_wall=int(x_wall), ref_obs=int(ref_obs), sigma_grid=float(sigma_grid),
-                    rate_diffusion=float(rate_diffusion), rate_active=float(rate_active), k_on=float(k_on), k_off=float(k_off),
-                    k_exit=float(k_exit), T=float(T), seed=int(seed) & (2 ** 64 - 1), max_events=int(max_events),
-                    beta=_p(betas).value, anchor_mask=None if mask is None else _p(mask).value, times_obs=_p(times).value,
-                    front_lo=None if flo is None else _p(flo).value, block_table=None if btab is None else _p(btab).value)
+    par, keep = _params(L=L, K=K, periodic=periodic, n_systems=S, n_cap=ncap, n_obs=M, sigma_grid=sigma_grid, minus_anchor=minus_anchor,
+                        immobilize=immobilize, suppress_flip=suppress_flip, crowding=crowding, device=device, x_wall=x_wall, ref_obs=ref_obs,
+                        rate_diffusion=rate_diffusion, rate_active=rate_active, k_on=k_on, k_off=k_off, k_exit=k_exit, T=T, seed=seed,
+                        max_events=max_events, beta=betas, times_obs=times, anchor_mask=anchor_mask, front_lo=front_lo, block_table=block_table,
+                        flip_table=flip_table)
     pos_obs = np.zeros((S, M, ncap), np.int32) if want_states else None
     sg_obs = np.zeros((S, M, ncap), np.int8) if want_states else None
     fl_obs = np.zeros((S, M, ncap), np.uint8) if want_states else None
@@ -451,72 +530,86 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     n_rec, n_ev, t_fin = np.zeros(S, np.int32), np.zeros(S, np.int64), np.zeros(S)
     exits, n_exit = np.zeros((S, ncap, 3)), np.zeros(S, np.int32)
     ms = C.c_double()
-    args = [_p(n0), _p(pos0), _p(sg0), _p(bd0), _p(uniforms), _p(pos_obs), _p(sg_obs), _p(fl_obs), _p(scal), _p(n_rec), _p(n_ev),
-            _p(t_fin), _p(exits), _p(n_exit)]
-    rows = capture = sums = head = ck_out = None
-    if entry in ("gilr_run", "gilrm_run"):
-        ck_out = {k: np.zeros((S, ncap)[:nd], dt) for k, dt, nd in CHECKPOINT_ARRAYS}
-        c_in = None if ck_in is None else GilCheckpoint(**{k: _p(v).value for k, v in ck_in.items()})
-        c_out = GilCheckpoint(**{k: _p(v).value for k, v in ck_out.items()})
-        rc = call(C.byref(par), *args, C.byref(ms), int(obs_first), None if c_in is None else C.byref(c_in), C.byref(c_out))
-    elif entry == "gils_run":
-        rows = np.zeros((S, M, 4 + 2 * max(int(k_max), 0)))
-        rc = call(C.byref(par), int(k_max), int(first_obs), *args, _p(rows), C.byref(ms))
-    elif entry == "gilc_run":
-        groups = None if group_of_site is None else np.ascontiguousarray(group_of_site, dtype=np.int32)
-        if groups is not None and groups.shape != (L,):
-            raise ValueError("group_of_site must have one entry per site")
-        capture = np.zeros((S, M, GILC_NFIXED + max(int(n_groups), 0) + max(int(c_bins), 0)), np.int64)
-        life_hist, life_sums = np.zeros((S, 2, max(int(h_bins), 1)), np.int64), np.zeros((S, 2, 2))
-        rc = call(C.byref(par), _p(groups), int(n_groups), int(c_bins), int(h_bins), float(h_dt), int(first_obs), *args,
-                  _p(capture), _p(life_hist), _p(life_sums), C.byref(ms))
-    elif entry == "gilp_run":
-        groups = None if group_of_system is None else np.ascontiguousarray(group_of_system, dtype=np.int32)
-        if groups is not None and groups.shape != (S,):
-            raise ValueError("group_of_system must have one entry per system")
-        G, B = max(int(n_groups), 1), max(int(n_bins), 1)
-        sums, members = np.zeros((G, M, GILP_NCOLS, B), np.int64), np.zeros((G, M), np.int32)
-        prof = np.zeros((S, M, 3, B), np.int32) if per_system else None
-        rc = call(C.byref(par), int(n_bins), int(first_obs), int(want_field), _p(groups), int(n_groups), *args, _p(sums), _p(members),
-                  _p(prof), C.byref(ms))
-    elif entry == "gilx_run":
-        desc, keep = _mixed_descriptor(S, int(K), **mixed)
-        if desc.variant_of_system is None:
-            raise ValueError("variant_of_system must have one entry per system")
-        rc = call(C.byref(par), C.byref(desc), *args, C.byref(ms))
-    elif entry == "gilxs_run":
-        desc, keep = _mixed_descriptor(S, int(K), **mixed)
-        if desc.variant_of_system is None:
-            raise ValueError("variant_of_system must have one entry per system")
-        kk = max(int(k_max), 0)
-        rows = np.zeros((S, M, 4 + 2 * kk)) if want_rows else None
-        head, window = np.zeros((S, M, 4)), np.zeros((S, kk, 3))          # gilxs_run refuses k_max < 1
-        n_window, n_empty = np.zeros(S, np.int32), np.zeros(S, np.int32)
-        rc = call(C.byref(par), C.byref(desc), int(k_max), int(first_obs), *args, _p(rows), _p(head), _p(window), _p(n_window), _p(n_empty),
-                  C.byref(ms))
-    else:
-        rc = call(C.byref(par), *args, C.byref(ms))
+    results = [pos_obs, sg_obs, fl_obs, scal, n_rec, n_ev, t_fin, exits, n_exit]
+    c = types.SimpleNamespace(S=S, M=M, ncap=ncap, L=L, K=K, ck_in=ck_in, results=results, keep=[keep])
+    own = dict(k_max=k_max, first_obs=first_obs, group_of_site=group_of_site, n_groups=n_groups, c_bins=c_bins, h_bins=h_bins, h_dt=h_dt,
+               n_bins=n_bins, want_field=want_field, group_of_system=group_of_system, per_system=per_system, mixed=mixed, want_rows=want_rows,
+               obs_first=obs_first)
+    front, behind, tail, extra = row.stage(c, **own)
+    rc = call(C.byref(par), *front, _p(n0), _p(pos0), _p(sg0), _p(bd0), _p(uniforms), *[_p(a) for a in results], *behind, C.byref(ms), *tail)
     if rc != 0:
         raise capi.ApsError(rc, last_error().decode())
     out = dict(pos=pos_obs, sigma=sg_obs, flags=fl_obs, scalars=scal, n_recorded=n_rec, n_events=n_ev, t_final=t_fin,
                exits=exits, n_exits=n_exit, n0=n0, kernel_ms=ms.value)
-    if ck_out is not None:
-        first_row = np.zeros(S, np.int32) if ck_in is None else np.clip(ck_in["next_obs"] - int(obs_first), 0, None).astype(np.int32)
-        if ck_in is not None:
-            first_row[ck_in["next_obs"] < int(obs_first)] = 0        # ended before this segment: n_recorded is 0 too
-        out.update(checkpoint=ck_out, first_row=first_row, obs_first=int(obs_first), n0=np.full(S, ncap, np.int32))   # any slot may be alive
-    if rows is not None:
-        out["structure"] = rows
-    if head is not None:
-        back = [pos_obs, sg_obs, fl_obs, scal, n_rec, n_ev, t_fin, exits, n_exit, rows, head, window, n_window, n_empty]
-        out.update(structure=rows, head=head, window=window, n_window=n_window, n_empty=n_empty,
-                   bytes_back=int(sum(x.nbytes for x in back if x is not None)))
-    if capture is not None:
-        out.update(capture=capture, life_hist=life_hist, life_sums=life_sums)
-    if sums is not None:
-        width = -(-int(L) // int(n_bins))
-        out.update(ensemble_sums=sums, members=members, profile_obs=prof, bin_width=width, n_bins_used=-(-int(L) // width))
+    out.update(extra)
+    if row.finish is not None:
+        out.update(row.finish(c, **own))
     return out
+
+
+def _large_shape(L, n):
+    """Beyond one workgroup's LDS: the large-system kernel, one workgroup per system in one launch (system s: key seed + s)."""
+    return L > GIL_MAX_L or n > GIL_MAX_N
+
+
+def _open_batch(who, systems, *, resume=None, no_exit=False, seed=True, **variants):
+    """Opens a batch: the systems may differ in beta, rng / initial condition and particle number only (`variants`: the options of
+    particle_system.require_same_shape), `no_exit` asks for k_exit = 0.  Then ALL initial states are drawn, in the order of the
+    list, and only then the Philox key (`seed=False`: the caller takes keys per group, mixed_keys).  A resumed run consumes no
+    generator.  Returns (first system, initial states, key)."""
+    from .particle_system import batch_seed, require_same_shape
+    first = require_same_shape(who, systems, **variants)
+    if no_exit and first.k_exit:
+        raise ValueError(f"{who} needs k_exit = 0")
+    if resume is not None:
+        return first, None, None
+    inits = [ps.init_particles() for ps in systems]
+    return first, inits, batch_seed(first) if seed else None
+
+
+def _model(first, systems, **more):
+    """The launch keywords every entry point shares, from the batch's first system (and beta from all of them); `more` adds to
+    them or replaces them."""
+    kw = dict(L=first.L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
+              rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], minus_anchor=first.minus_anchor,
+              immobilize=first.immobilize_when_anchored, suppress_flip=first.suppress_flip_when_bound,
+              crowding=first.crowding_suppresses_rates, k_on=first.k_on, k_off=first.k_off, k_exit=first.k_exit,
+              anchor_mask=first.is_anchor_site, device=first.device, flip_table=first.flip_table())
+    kw.update(more)
+    return kw
+
+
+def _statistics_keywords(who, first, times_obs, n_live, one_table=True):
+    """The keywords of a launch that takes the sums of observables.DeviceObservables over `times_obs`, and the blocking table of
+    every system (the threshold depends on the particle number).  `one_table`: the launch has one table for all, so they must agree."""
+    from . import observables
+    acc0 = observables.DeviceObservables(times_obs, first.L, first.dx, first.K)
+    tables = [acc0.block_table(n) for n in n_live]
+    kw = dict(want_states=False, x_wall=acc0.x_wall, ref_obs=acc0.start, front_lo=np.array([acc0.front_range(s)[0] for s in range(first.L)], np.int32))
+    if one_table:
+        if any(not np.array_equal(t, tables[0]) for t in tables[1:]):
+            raise ValueError(f"{who}: the systems' particle numbers give different blocking thresholds; run them in separate batches")
+        kw.update(k_exit=0.0, block_table=tables[0])
+    return kw, tables
+
+
+def _require_recorded(r, s, M):
+    if int(r["n_recorded"][s]) < M:
+        raise RuntimeError("a system passed T before its last observation time (choose T beyond the last observation)")
+
+
+def _reduce_structure_rows(rows, M, L, dx, start_fraction, kk, first_obs, return_series):
+    """observables.DeviceStructure over the rows [M][4 + 2 kk] of one system from `first_obs` on: (its result over the window, the
+    accumulator over all observations or None)."""
+    from . import observables
+    acc = observables.DeviceStructure(M, L, dx, start_fraction, kk)
+    series = observables.DeviceStructure(M, L, dx, 0.0, kk) if return_series else None
+    for k in range(first_obs, M):
+        row = rows[k]
+        acc.add(k, row[0], row[1], row[2], row[3], row[4:])
+        if series is not None:
+            series.add(k, row[0], row[1], row[2], row[3], row[4:])
+    return acc.result(), series
 
 
 def run_batched_exact(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False, uniforms=None, want_m_local=True,
@@ -538,31 +631,17 @@ def run_batched_exact(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var
     stopping time; the next event draws fresh numbers, so the switched process is exact).  A longer `T` extends a finished run.
     `obs_per_launch=n`: run the range as a chain of launches of at most n observations each and return what one launch returns.
     With none of the four keywords the run is one launch of the entry points that have no checkpoint."""
-    from .particle_system import ParticleSystem, _SHAPE_ATTRS
-    first = systems[0]
-    for ps in systems[1:]:
-        for k in _SHAPE_ATTRS:
-            if getattr(ps, k) != getattr(first, k):
-                raise ValueError(f"run_batched_exact: systems differ in {k}")
-    L, dx = first.L, first.dx
+    who = "run_batched_exact"
+    first, inits, seed = _open_batch(who, systems, resume=resume)
     if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
-        r, times_obs, ck = _segmented_launches("run_batched_exact", systems, T, obs_dt, resume=resume, obs_range=obs_range,
+        r, times_obs, ck = _segmented_launches(who, systems, T, obs_dt, inits, seed, resume=resume, obs_range=obs_range,
                                                obs_per_launch=obs_per_launch, uniforms=uniforms)
         outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
         first.kernel_ms = r["kernel_ms"]
         return (outs, ck) if return_checkpoint else outs
-    inits = [ps.init_particles() for ps in systems]
-    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
     times_obs = np.arange(0.0, T, obs_dt)
-    M = len(times_obs)
-    # beyond one workgroup's LDS: the large-system kernel, one workgroup per system in one launch (system s: key seed + s)
-    run = run_many_large_raw if (L > GIL_MAX_L or max(len(p) for p, _ in inits) > GIL_MAX_N) else run_raw
-    r = run(L=L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
-            rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs, T=T,
-            seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
-            suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
-            k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms, device=first.device,
-            flip_table=first.flip_table())
+    run = run_many_large_raw if _large_shape(first.L, max(len(p) for p, _ in inits)) else run_raw
+    r = run(**_model(first, systems, states=inits, times_obs=times_obs, T=T, seed=seed, uniforms=uniforms))
     outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
     first.kernel_ms = r["kernel_ms"]
     return outs
@@ -611,17 +690,10 @@ def run_batched_exact_statistics(systems, T=10.0, obs_dt=0.01, resume=None, obs_
     `resume`, `obs_range`, `return_checkpoint`, `obs_per_launch`: as in run_batched_exact.  The observables are those of the
     observations of `obs_range` (the windows of DeviceObservables lie within them); `obs_per_launch` chains the launches and
     evaluates the concatenated sums, which are the single launch's."""
-    from . import observables
-    from .particle_system import _SHAPE_ATTRS
-    first = systems[0]
-    for ps in systems[1:]:
-        for k in _SHAPE_ATTRS:
-            if getattr(ps, k) != getattr(first, k):
-                raise ValueError(f"run_batched_exact_statistics: systems differ in {k}")
-    if first.k_exit:
-        raise ValueError("run_batched_exact_statistics needs k_exit = 0")
+    who = "run_batched_exact_statistics"
+    first, inits, seed = _open_batch(who, systems, resume=resume, no_exit=True)
     if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
-        r, times_obs, ck = _segmented_launches("run_batched_exact_statistics", systems, T, obs_dt, resume=resume, obs_range=obs_range,
+        r, times_obs, ck = _segmented_launches(who, systems, T, obs_dt, inits, seed, resume=resume, obs_range=obs_range,
                                                obs_per_launch=obs_per_launch, statistics=True)
         if np.any(r["first_row"] > 0):
             raise ValueError("run_batched_exact_statistics: the checkpoint's systems stand at different observations; "
@@ -629,23 +701,11 @@ def run_batched_exact_statistics(systems, T=10.0, obs_dt=0.01, resume=None, obs_
         rows = _statistics_rows(systems, r, times_obs)
         first.kernel_ms = r["kernel_ms"]
         return (rows, ck) if return_checkpoint else rows
-    inits = [ps.init_particles() for ps in systems]
-    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
     times_obs = np.arange(0.0, T, obs_dt)
-    acc0 = observables.DeviceObservables(times_obs, first.L, first.dx, first.K)
-    tables = [acc0.block_table(len(p)) for p, _ in inits]      # the blocking threshold depends on the particle number
-    if any(not np.array_equal(t, tables[0]) for t in tables[1:]):
-        raise ValueError("run_batched_exact_statistics: the systems' particle numbers give different blocking thresholds; "
-                         "run them in separate batches")
-    front_lo = np.array([acc0.front_range(s)[0] for s in range(first.L)], np.int32)
-    # beyond one workgroup's LDS: the large-system kernel takes the same sums (gilm_run); no state array leaves the device either way
-    run = run_many_large_raw if (first.L > GIL_MAX_L or max(len(p) for p, _ in inits) > GIL_MAX_N) else run_raw
-    r = run(L=first.L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
-            rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs, T=T,
-            seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
-            suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
-            k_off=first.k_off, k_exit=0.0, anchor_mask=first.is_anchor_site, want_states=False, x_wall=acc0.x_wall,
-            ref_obs=acc0.start, front_lo=front_lo, block_table=tables[0], device=first.device, flip_table=first.flip_table())
+    kw, _ = _statistics_keywords(who, first, times_obs, [len(p) for p, _ in inits])
+    # the large-system kernel takes the same sums (gilm_run); no state array leaves the device either way
+    run = run_many_large_raw if _large_shape(first.L, max(len(p) for p, _ in inits)) else run_raw
+    r = run(**_model(first, systems, states=inits, times_obs=times_obs, T=T, seed=seed, **kw))
     rows = _statistics_rows(systems, r, times_obs)
     first.kernel_ms = r["kernel_ms"]
     return rows
@@ -657,8 +717,7 @@ def _statistics_rows(systems, r, times_obs):
     first = systems[0]
     rows = []
     for s, ps in enumerate(systems):
-        if int(r["n_recorded"][s]) < len(times_obs):
-            raise RuntimeError("a system passed T before its last observation time (choose T beyond the last observation)")
+        _require_recorded(r, s, len(times_obs))
         acc = observables.DeviceObservables(times_obs, first.L, first.dx, first.K)
         for k in range(len(times_obs)):
             sums = dict(zip(SCALARS, (int(v) for v in r["scalars"][s, k])))
@@ -756,28 +815,24 @@ def _merge_segments(parts, k0):
     return out
 
 
-def _segmented_launches(who, systems, T, obs_dt, *, resume, obs_range, obs_per_launch, uniforms=None, statistics=False):
-    """The observations `obs_range` of the run (T, obs_dt) of `systems`, from `resume` or from fresh initial conditions, in
-    launches of at most `obs_per_launch` observations (gilr_run / gilrm_run): (merged raw outputs, their observation times,
-    the Checkpoint at the end)."""
-    from . import observables
+def _segmented_launches(who, systems, T, obs_dt, inits, seed, *, resume, obs_range, obs_per_launch, uniforms=None, statistics=False):
+    """The observations `obs_range` of the run (T, obs_dt) of `systems`, from `resume` or from the fresh initial conditions `inits`
+    under the key `seed` (_open_batch), in launches of at most `obs_per_launch` observations (gilr_run / gilrm_run): (merged raw
+    outputs, their observation times, the Checkpoint at the end)."""
     first = systems[0]
     times_all = np.arange(0.0, T, obs_dt)
     M, S = len(times_all), len(systems)
     mask = np.zeros(first.L, np.uint8) if first.is_anchor_site is None else (np.asarray(first.is_anchor_site).reshape(-1) != 0).astype(np.uint8)
     if resume is None:
-        inits = [ps.init_particles() for ps in systems]
-        seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
-        large = first.L > GIL_MAX_L or max(len(p) for p, _ in inits) > GIL_MAX_N
+        large = _large_shape(first.L, max(len(p) for p, _ in inits))
         ck, k_lo, n_live = None, 0, [len(p) for p, _ in inits]
     else:
         if not isinstance(resume, Checkpoint):
             raise TypeError(f"{who}: resume must be a gillespie.Checkpoint")
         resume.require(L=first.L, K=first.K, periodic=bool(first.periodic), local_kernel_sigma=float(first.local_kernel_sigma),
-                       anchor_mask=mask, n_systems=S, obs_dt=float(obs_dt),
-                       streams="large" if (first.L > GIL_MAX_L or resume.n_cap > GIL_MAX_N) else "batch",
+                       anchor_mask=mask, n_systems=S, obs_dt=float(obs_dt), streams="large" if _large_shape(first.L, resume.n_cap) else "batch",
                        **({} if first.seed is None else {"seed": int(first.seed)}))
-        inits, seed, large, ck = None, resume.seed, resume.streams == "large", resume.arrays()
+        seed, large, ck = resume.seed, resume.streams == "large", resume.arrays()
         k_lo, n_live = int(resume.next_obs.min()), [int(((f & GILR_ALIVE) != 0).sum()) for f in resume.flags]
     k0, k1 = (k_lo, M) if obs_range is None else (int(obs_range[0]), int(obs_range[1]))
     if not 0 <= k0 < k1 <= M:
@@ -787,20 +842,11 @@ def _segmented_launches(who, systems, T, obs_dt, *, resume, obs_range, obs_per_l
     step = k1 - k0 if obs_per_launch is None else int(obs_per_launch)
     if step < 1:
         raise ValueError(f"{who}: obs_per_launch must be at least 1")
-    kw = dict(L=first.L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
-              rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], T=T, seed=seed, minus_anchor=first.minus_anchor,
-              immobilize=first.immobilize_when_anchored, suppress_flip=first.suppress_flip_when_bound,
-              crowding=first.crowding_suppresses_rates, k_on=first.k_on, k_off=first.k_off, k_exit=first.k_exit,
-              anchor_mask=first.is_anchor_site, uniforms=uniforms, device=first.device, flip_table=first.flip_table(), large=large)
+    kw = _model(first, systems, T=T, seed=seed, uniforms=uniforms, large=large)
     ref_abs = -1
     if statistics:                                             # the keywords of run_batched_exact_statistics' launch
-        acc0 = observables.DeviceObservables(times_all[k0:k1], first.L, first.dx, first.K)
-        tables = [acc0.block_table(n) for n in n_live]         # the blocking threshold depends on the particle number
-        if any(not np.array_equal(t, tables[0]) for t in tables[1:]):
-            raise ValueError(f"{who}: the systems' particle numbers give different blocking thresholds; run them in separate batches")
-        kw.update(k_exit=0.0, want_states=False, x_wall=acc0.x_wall, block_table=tables[0],
-                  front_lo=np.array([acc0.front_range(s)[0] for s in range(first.L)], np.int32))
-        ref_abs = k0 + acc0.start
+        kw.update(_statistics_keywords(who, first, times_all[k0:k1], n_live)[0])
+        ref_abs = k0 + kw.pop("ref_obs")
     parts = []
     for a in range(k0, k1, step):
         b = min(a + step, k1)
@@ -834,13 +880,14 @@ def mixed_keys(systems, groups=None):
     `run_raw` launch of the host loop would hold: the key is the seed of the group's FIRST system (its `seed`, or a number drawn
     from its rng -- call this after the initial states were drawn, as the per-group functions do) and the index is the place
     within the group.  None: one group."""
+    from .particle_system import batch_seed
     groups = [0] * len(systems) if groups is None else [int(g) for g in groups]
     if len(groups) != len(systems):
         raise ValueError("groups must have one entry per system")
     key, count, seeds, streams = {}, {}, [], []
     for ps, g in zip(systems, groups):
         if g not in key:
-            key[g] = ps.seed if ps.seed is not None else int(ps.rng.random() * 2.0 ** 53)
+            key[g] = batch_seed(ps)
             count[g] = 0
         seeds.append(int(key[g]))
         streams.append(count[g])
@@ -852,34 +899,19 @@ def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, or
     """The one launch behind run_batched_exact_mixed and run_batched_exact_statistics_mixed: checks, initial states, variants,
     keys, gilx_run.  `structure` = (k_max or None, start_fraction, want_rows, all_observations): the launch behind
     run_batched_exact_structure_mixed instead, gilxs_run without states.  Returns (raw outputs, times_obs)."""
-    from . import observables
-    from .particle_system import _SHAPE_ATTRS
-    first = systems[0]
-    for ps in systems[1:]:
-        for k in _SHAPE_ATTRS:
-            if k != "local_kernel_sigma" and getattr(ps, k) != getattr(first, k):
-                raise ValueError(f"{who}: systems differ in {k}")
-        if not np.array_equal(ps.is_anchor_site, first.is_anchor_site):
-            raise ValueError(f"{who}: systems differ in their anchor sites")
-        if (ps.flip_table() is None) != (first.flip_table() is None) or (ps.flip_table() is not None and not np.array_equal(ps.flip_table(), first.flip_table())):
-            raise ValueError(f"{who}: systems differ in flip_rate_fn")
-    if statistics and first.k_exit:
-        raise ValueError(f"{who} needs k_exit = 0")
-    inits = [ps.init_particles() for ps in systems]
+    first, inits, _ = _open_batch(who, systems, skip=("local_kernel_sigma",), anchors="their anchor sites", flip=True, no_exit=statistics, seed=False)
     n_cap = max(1, max(len(p) for p, _ in inits))
-    if first.L > GIL_MAX_L or n_cap > GIL_MAX_N:
+    if _large_shape(first.L, n_cap):
         raise ValueError(f"{who}: L = {first.L}, N = {n_cap} is a large shape (beyond L = {GIL_MAX_L}, N = {GIL_MAX_N}); "
                          "the large-system kernel takes no mixed batches")
     seeds, streams = mixed_keys(systems, groups)
     times_obs = np.arange(0.0, T, obs_dt)
-    kw = {}
-    tables = None
-    if statistics:
-        acc0 = observables.DeviceObservables(times_obs, first.L, first.dx, first.K)
-        tables = [acc0.block_table(len(p)) for p, _ in inits]  # the blocking threshold depends on the particle number
-        kw = dict(want_states=False, x_wall=acc0.x_wall, ref_obs=acc0.start,
-                  front_lo=np.array([acc0.front_range(s)[0] for s in range(first.L)], np.int32))
+    kw, tables = {}, None
+    if statistics:                                             # every system is counted with the table of its own particle number
+        kw, tables = _statistics_keywords(who, first, times_obs, [len(p) for p, _ in inits], one_table=False)
     sig, tabs, owner = mixed_variants([ps._sigma_grid for ps in systems], tables)
+    shape = dict(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems), n_cap=n_cap, n_obs=len(times_obs),
+                 variant_of_system=owner)
     run_fn = run_mixed_raw
     if structure is not None:
         k_max, start_fraction, want_rows, all_obs = structure
@@ -887,19 +919,15 @@ def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, or
         first_obs = 0 if all_obs else int(start_fraction * len(times_obs))
         kw = dict(want_states=False, k_max=kk, first_obs=first_obs, want_rows=want_rows)
         run_fn = run_mixed_structure_raw
-        plan = plan_mixed_structure(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems), n_cap=n_cap,
-                                    n_obs=len(times_obs), variant_of_system=owner, **kw)
+        plan = plan_mixed_structure(**shape, **kw)
     else:
-        plan = plan_mixed(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems), n_cap=n_cap,
-                          n_obs=len(times_obs), variant_of_system=owner, want_states=not statistics)
+        plan = plan_mixed(**shape, want_states=not statistics)
     if plan["lds_bytes"] > GILX_LDS_LIMIT:
         raise ValueError(f"{who}: the launch needs {plan['lds_bytes']} bytes of LDS per system, over the limit of {GILX_LDS_LIMIT} bytes")
-    r = run_fn(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, variant_of_system=owner, block_tables=tabs,
-               rate_diffusion=first.rate_diffusion, rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems],
-               states=inits, times_obs=times_obs, T=T, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
-               suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
-               k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms, device=first.device,
-               flip_table=first.flip_table(), seeds=seeds, streams=streams, order=order, **kw)
+    model = _model(first, systems, sigma_grids=sig, variant_of_system=owner, block_tables=tabs, states=inits, times_obs=times_obs, T=T,
+                   uniforms=uniforms, seeds=seeds, streams=streams, order=order, **kw)
+    del model["sigma_grid"]                                    # a mixed launch has a range per variant instead
+    r = run_fn(**model)
     r["plan"] = plan
     return r, times_obs
 
@@ -952,19 +980,11 @@ def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fracti
     first_obs = 0 if (rows_wanted and return_series) else int(start_fraction * M)
     out = []
     for s, ps in enumerate(systems):
-        if int(r["n_recorded"][s]) < M:
-            raise RuntimeError("a system passed T before its last observation time (choose T beyond the last observation)")
+        _require_recorded(r, s, M)
         win = observables.DeviceStructureWindow(r["head"][s], r["window"][s], r["n_window"][s], r["n_empty"][s], L, first.dx, start_fraction)
         series = None
         if rows_wanted:
-            acc = observables.DeviceStructure(M, L, first.dx, start_fraction, kk)
-            series = observables.DeviceStructure(M, L, first.dx, 0.0, kk) if return_series else None
-            for k in range(first_obs, M):
-                row = r["structure"][s, k]
-                acc.add(k, row[0], row[1], row[2], row[3], row[4:])
-                if series is not None:
-                    series.add(k, row[0], row[1], row[2], row[3], row[4:])
-            res = acc.result()
+            res, series = _reduce_structure_rows(r["structure"][s], M, L, first.dx, start_fraction, kk, first_obs, return_series)
         else:
             res = win.result()
         if return_series:
@@ -989,37 +1009,16 @@ def run_batched_exact_structure(systems, T=10.0, obs_dt=0.01, start_fraction=0.5
     sums at every observation and adds `times_obs`, `fft_amp_series` [M][k_max] and `var_series` [M] (what the reference's
     time_to_pattern, :195-202, reads).  Particles may leave (k_exit > 0): n is the live count of the observation."""
     _refuse_resume("run_batched_exact_structure", resume)
-    from . import observables
-    from .particle_system import _SHAPE_ATTRS
-    first = systems[0]
-    for ps in systems[1:]:
-        for k in _SHAPE_ATTRS:
-            if getattr(ps, k) != getattr(first, k):
-                raise ValueError(f"run_batched_exact_structure: systems differ in {k}")
-    inits = [ps.init_particles() for ps in systems]
-    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+    first, inits, seed = _open_batch("run_batched_exact_structure", systems)
     times_obs = np.arange(0.0, T, obs_dt)
     M, L = len(times_obs), first.L
     kk = L if k_max is None else min(int(k_max), L)
     first_obs = 0 if return_series else int(start_fraction * M)
-    r = run_structure_raw(L=L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
-                          rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs,
-                          T=T, seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
-                          suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
-                          k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, want_states=False,
-                          device=first.device, flip_table=first.flip_table(), k_max=kk, first_obs=first_obs)
+    r = run_structure_raw(**_model(first, systems, states=inits, times_obs=times_obs, T=T, seed=seed, want_states=False, k_max=kk, first_obs=first_obs))
     rows = []
     for s, ps in enumerate(systems):
-        if int(r["n_recorded"][s]) < M:
-            raise RuntimeError("a system passed T before its last observation time (choose T beyond the last observation)")
-        acc = observables.DeviceStructure(M, L, first.dx, start_fraction, kk)
-        series = observables.DeviceStructure(M, L, first.dx, 0.0, kk) if return_series else None
-        for k in range(first_obs, M):
-            row = r["structure"][s, k]
-            acc.add(k, row[0], row[1], row[2], row[3], row[4:])
-            if series is not None:
-                series.add(k, row[0], row[1], row[2], row[3], row[4:])
-        res = acc.result()
+        _require_recorded(r, s, M)
+        res, series = _reduce_structure_rows(r["structure"][s], M, L, first.dx, start_fraction, kk, first_obs, return_series)
         if series is not None:
             res.update(times_obs=times_obs.copy(), fft_amp_series=np.array(series.amp), var_series=np.array(series.var))
         rows.append(res)
@@ -1038,33 +1037,18 @@ def run_batched_exact_capture(systems, T=10.0, obs_dt=0.01, c_bins=16, h_bins=40
     to obs_dt and, after the first exit, attributed to shifted particle ids."""
     _refuse_resume("run_batched_exact_capture", resume)
     from . import observables
-    from .particle_system import _SHAPE_ATTRS
-    first = systems[0]
-    for ps in systems[1:]:
-        for k in _SHAPE_ATTRS:
-            if getattr(ps, k) != getattr(first, k):
-                raise ValueError(f"run_batched_exact_capture: systems differ in {k}")
-        if not np.array_equal(ps.is_anchor_site, first.is_anchor_site):
-            raise ValueError("run_batched_exact_capture: systems differ in their anchor sites")
-    inits = [ps.init_particles() for ps in systems]
-    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+    first, inits, seed = _open_batch("run_batched_exact_capture", systems, anchors="their anchor sites")
     times_obs = np.arange(0.0, T, obs_dt)
     M, L = len(times_obs), first.L
     groups = observables.anchor_groups(first)
     n_groups = len(first.anchor_idxs)
     h_dt = float(T) / int(h_bins) if h_dt is None else float(h_dt)
-    r = run_capture_raw(L=L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
-                        rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs,
-                        T=T, seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
-                        suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
-                        k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms,
-                        want_states=False, device=first.device, flip_table=first.flip_table(),
-                        group_of_site=groups if n_groups else None, n_groups=n_groups, c_bins=c_bins, h_bins=h_bins, h_dt=h_dt,
-                        first_obs=int(start_fraction * M))
+    r = run_capture_raw(**_model(first, systems, states=inits, times_obs=times_obs, T=T, seed=seed, uniforms=uniforms, want_states=False,
+                                 group_of_site=groups if n_groups else None, n_groups=n_groups, c_bins=c_bins, h_bins=h_bins, h_dt=h_dt,
+                                 first_obs=int(start_fraction * M)))
     rows = []
     for s, ps in enumerate(systems):
-        if int(r["n_recorded"][s]) < M:
-            raise RuntimeError("a system passed T before its last observation time (choose T beyond the last observation)")
+        _require_recorded(r, s, M)
         acc = observables.DeviceCapture(times_obs, L, n_groups, c_bins, h_dt)
         rows.append(acc.result(r["scalars"][s, :, 0], r["capture"][s], r["exits"][s, :int(r["n_exits"][s])], r["life_hist"][s],
                                r["life_sums"][s]))
@@ -1083,26 +1067,15 @@ def run_batched_exact_profiles(systems, T=10.0, obs_dt=0.01, n_bins=None, groups
     adds each member's own counts as `profile_obs` [members][observations][3][n_bins] (single-run heat maps at n_bins = L)."""
     _refuse_resume("run_batched_exact_profiles", resume)
     from . import observables
-    from .particle_system import _SHAPE_ATTRS
-    first = systems[0]
-    for ps in systems[1:]:
-        for k in _SHAPE_ATTRS:
-            if getattr(ps, k) != getattr(first, k):
-                raise ValueError(f"run_batched_exact_profiles: systems differ in {k}")
-    inits = [ps.init_particles() for ps in systems]
-    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+    first, inits, seed = _open_batch("run_batched_exact_profiles", systems)
     times_obs = np.arange(0.0, T, obs_dt)
     L = first.L
     n_bins = min(L, GILP_MAX_BINS) if n_bins is None else int(n_bins)
     owner = np.zeros(len(systems), np.int32) if groups is None else np.asarray(groups, dtype=np.int32)
     n_groups = int(owner.max()) + 1 if owner.size else 1
-    r = run_profiles_raw(L=L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, rate_diffusion=first.rate_diffusion,
-                         rate_active=first.rate_active, betas=[float(ps.beta) for ps in systems], states=inits, times_obs=times_obs,
-                         T=T, seed=seed, minus_anchor=first.minus_anchor, immobilize=first.immobilize_when_anchored,
-                         suppress_flip=first.suppress_flip_when_bound, crowding=first.crowding_suppresses_rates, k_on=first.k_on,
-                         k_off=first.k_off, k_exit=first.k_exit, anchor_mask=first.is_anchor_site, uniforms=uniforms,
-                         want_states=False, device=first.device, flip_table=first.flip_table(), n_bins=n_bins,
-                         first_obs=first_obs, want_field=want_field, group_of_system=owner, n_groups=n_groups, per_system=per_system)
+    r = run_profiles_raw(**_model(first, systems, states=inits, times_obs=times_obs, T=T, seed=seed, uniforms=uniforms, want_states=False,
+                                  n_bins=n_bins, first_obs=first_obs, want_field=want_field, group_of_system=owner, n_groups=n_groups,
+                                  per_system=per_system))
     out = []
     for g in range(n_groups):
         mine = np.flatnonzero(owner == g)
@@ -1135,16 +1108,11 @@ def run_large_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, be
     elif max_events is None:
         max_events = 2 ** 40
     betas = np.array([float(beta)])
-    mask = None if anchor_mask is None or not np.any(anchor_mask) else np.ascontiguousarray(anchor_mask, dtype=np.uint8)
-    ftab = None if flip_table is None else np.ascontiguousarray(flip_table, dtype=np.float64)
-    par = GilParams(flip_n=0 if ftab is None else ftab.shape[1] - 1, flip_table=None if ftab is None else _p(ftab).value,
-                    L=L, K=K, periodic=int(bool(periodic)), minus_anchor=int(bool(minus_anchor)), immobilize=int(bool(immobilize)),
-                    suppress_flip=int(bool(suppress_flip)), crowding=int(bool(crowding)), n_systems=1, n_cap=max(n0, 1), n_obs=M,
-                    device=device, x_wall=0, ref_obs=-1, sigma_grid=float(sigma_grid), rate_diffusion=float(rate_diffusion),
-                    rate_active=float(rate_active), k_on=float(k_on), k_off=float(k_off), k_exit=float(k_exit), T=float(T),
-                    seed=int(seed) & (2 ** 64 - 1), max_events=int(max_events), beta=_p(betas).value,
-                    anchor_mask=None if mask is None else _p(mask).value, times_obs=_p(times).value, front_lo=None, block_table=None)
     ncap = max(n0, 1)
+    par, keep = _params(L=L, K=K, periodic=periodic, n_systems=1, n_cap=ncap, n_obs=M, sigma_grid=sigma_grid, minus_anchor=minus_anchor,
+                        immobilize=immobilize, suppress_flip=suppress_flip, crowding=crowding, device=device, x_wall=0, ref_obs=-1,
+                        rate_diffusion=rate_diffusion, rate_active=rate_active, k_on=k_on, k_off=k_off, k_exit=k_exit, T=T, seed=seed,
+                        max_events=max_events, beta=betas, times_obs=times, anchor_mask=anchor_mask, flip_table=flip_table)
     pos_obs = np.zeros((M, ncap), np.int32) if want_states else None
     sg_obs = np.zeros((M, ncap), np.int8) if want_states else None
     fl_obs = np.zeros((M, ncap), np.uint8) if want_states else None

@@ -396,6 +396,29 @@ _SHAPE_ATTRS = ("L", "xlim", "K", "rate_diffusion", "rate_active", "k_on", "k_of
                 "crowding_suppresses_rates")
 
 
+def require_same_shape(who, systems, skip=(), anchors=None, flip=False):
+    """ValueError, in the name of `who`, at the first system that differs from systems[0] in an attribute of _SHAPE_ATTRS (those of
+    `skip` left out), then, if asked for, in the anchor sites (`anchors`: what `who` calls them) or in the flip table.  Returns
+    systems[0]."""
+    first = systems[0]
+    for ps in systems[1:]:
+        for k in _SHAPE_ATTRS:
+            if k not in skip and getattr(ps, k) != getattr(first, k):
+                raise ValueError(f"{who}: systems differ in {k}")
+        if anchors and not np.array_equal(ps.is_anchor_site, first.is_anchor_site):
+            raise ValueError(f"{who}: systems differ in {anchors}")
+        if flip and ((ps.flip_table() is None) != (first.flip_table() is None)
+                     or (ps.flip_table() is not None and not np.array_equal(ps.flip_table(), first.flip_table()))):
+            raise ValueError(f"{who}: systems differ in flip_rate_fn")
+    return first
+
+
+def batch_seed(first):
+    """The Philox key of a batch: its first system's `seed`, or a number drawn from that system's rng (call it after the initial
+    states were drawn).  The reference only requires choice / poisson / exponential / random of an rng object (ref :75-78)."""
+    return first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+
+
 def run_batched(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False):
     """`run()` of several ParticleSystem objects at once: they may differ in beta, rng / initial condition and
     particle number but share every other parameter, and are stepped together as independent ensembles of ONE
@@ -405,19 +428,10 @@ def run_batched(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False
     Ensemble e uses Philox counter word 3 = systems[0].ensemble + e under the common key `seed` of the first
     system (drawn from its rng after the initial conditions unless given), so a batched run equals separate
     runs with `ParticleSystem(..., seed=seed, ensemble=e)`."""
-    first = systems[0]
-    for ps in systems[1:]:
-        for k in _SHAPE_ATTRS:
-            if getattr(ps, k) != getattr(first, k):
-                raise ValueError(f"run_batched: systems differ in {k}")
-        if not np.array_equal(ps.is_anchor_site, first.is_anchor_site):
-            raise ValueError("run_batched: systems differ in anchor sites")
-        if (ps.flip_table() is None) != (first.flip_table() is None) or (ps.flip_table() is not None and not np.array_equal(ps.flip_table(), first.flip_table())):
-            raise ValueError("run_batched: systems differ in flip_rate_fn")
+    first = require_same_shape("run_batched", systems, anchors="anchor sites", flip=True)
     L, dx = first.L, first.dx
     inits = [ps.init_particles() for ps in systems]
-    # the reference only requires choice / poisson / exponential / random of an rng object (ref :75-78)
-    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+    seed = batch_seed(first)
     if first.dt is None:
         first.dt = min(ps.default_dt() for ps in systems)
     for ps in systems:
@@ -483,15 +497,11 @@ def run_batched_statistics(systems, T=10.0, obs_dt=0.01):
     (aps_observe_scalars).  Only valid while no particle exits (k_exit = 0, as in every reference sweep); returns a
     list of dicts like observables.run_observables."""
     from . import observables
-    first = systems[0]
-    for ps in systems[1:]:
-        for k in _SHAPE_ATTRS:
-            if getattr(ps, k) != getattr(first, k):
-                raise ValueError(f"run_batched_statistics: systems differ in {k}")
+    first = require_same_shape("run_batched_statistics", systems)
     if first.k_exit:
         raise ValueError("run_batched_statistics needs k_exit = 0 (use run_batched and observables.run_observables)")
     inits = [ps.init_particles() for ps in systems]
-    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+    seed = batch_seed(first)
     if first.dt is None:
         first.dt = min(ps.default_dt() for ps in systems)
     for ps in systems:
@@ -546,13 +556,9 @@ def run_batched_structure(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_ma
     the reference materialises three M x L arrays per run for them.  `k_max=None` means all L modes, as in the reference.
     Returns a list of dicts with the reference's eight keys (observables.DeviceStructure.result)."""
     from . import observables
-    first = systems[0]
-    for ps in systems[1:]:
-        for k in _SHAPE_ATTRS:
-            if getattr(ps, k) != getattr(first, k):
-                raise ValueError(f"run_batched_structure: systems differ in {k}")
+    first = require_same_shape("run_batched_structure", systems)
     inits = [ps.init_particles() for ps in systems]
-    seed = first.seed if first.seed is not None else int(first.rng.random() * 2.0 ** 53)
+    seed = batch_seed(first)
     if first.dt is None:
         first.dt = min(ps.default_dt() for ps in systems)
     for ps in systems:
