@@ -1,9 +1,10 @@
 // pde_common.hpp -- what the two execution shapes of the hydrodynamic-limit solver share: pde_hip.hip (one workgroup per
 // system, include/pde.h) and pde_wide_hip.hip (one system over many workgroups, include/pde_wide.h).
 //
-// Host side: argument checks, the Thomas factorisation of the constant diffusion matrix with its Sherman-Morrison vector,
-// the normalised kernel taps, the Fourier twiddles.  Device side: the Curie-Weiss rate, Philox4x32-10,
-// the workgroup sum and the workgroup scan of affine maps.  One copy, so both shapes solve with the same numbers.
+// Host side: the call record of the solves and its checks, the Thomas factorisation of the constant diffusion matrix with its
+// Sherman-Morrison vector, the normalised kernel taps, the Fourier twiddles, the staging both shapes share.  Device side: the
+// Curie-Weiss rate, Philox4x32-10, the workgroup sum and the workgroup scan of affine maps.  One copy, so both shapes solve
+// with the same numbers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "pde.h"
+#include "dev_mem.hpp"                    // OneShot and the UP / WORK / OUT / DOWN of the staging
 
 namespace pde_common {
 
@@ -20,20 +22,31 @@ constexpr int NT = 256;                 // threads per workgroup = chunks of the
 
 // ---------------------------------------------------------------------------------------------------------------- host
 
+// The call record: the seven inputs, twelve outputs (null: not wanted) and kernel time every solve of include/pde.h takes
+struct PdeIo {
+    const double *beta, *rho_p0, *rho_m0, *tracer_x0; const int8_t *tracer_s0; const double *rand_u, *rand_n;
+    double *rho_p, *rho_m, *m_series, *var_series, *v_eff_series, *D_eff_series, *snapshots, *m_snapshots, *fft_re, *fft_im, *tracer_x;
+    int8_t *tracer_s; double *kernel_ms;
+};
+
 // nullptr when the arguments of a solve are acceptable, else the text of the complaint
-inline const char *check_args(const pde_params *p, int32_t n_systems, const double *beta, const double *rho_p0, const double *rho_m0,
-                              const double *tracer_x0, const int8_t *tracer_s0, const double *rand_u, const double *rand_n,
-                              const double *fft_re, const double *fft_im) {
-    if (!p || !beta || !rho_p0 || !rho_m0 || n_systems < 1) return "null argument or n_systems < 1";
+inline const char *check_args(const pde_params *p, int32_t n_systems, const PdeIo &io) {
+    if (!p || !io.beta || !io.rho_p0 || !io.rho_m0 || n_systems < 1) return "null argument or n_systems < 1";
     if (p->L < 4 || p->L > PDE_MAX_L) return "L must be in [4, PDE_MAX_L]";
     if (p->nsteps < 0 || !(p->dt > 0.0) || !(p->xlim > 0.0)) return "nsteps >= 0, dt > 0, xlim > 0 required";
     if (p->snapshot_interval < 1) return "snapshot_interval must be >= 1";
     if (p->kernel_mode < 0 || p->kernel_mode > 2) return "kernel_mode must be 0, 1 or 2";
-    if (p->n_tracers < 0 || (p->n_tracers > 0 && (!tracer_x0 || !tracer_s0 || p->window < 1))) return "tracers need initial positions, states and window >= 1";
-    if ((rand_u == nullptr) != (rand_n == nullptr)) return "rand_u and rand_n come together";
-    if (p->n_fft_modes < 0 || p->n_fft_modes > p->L / 2 + 1 || ((fft_re == nullptr) != (fft_im == nullptr))) return "bad fft request";
+    if (p->n_tracers < 0 || (p->n_tracers > 0 && (!io.tracer_x0 || !io.tracer_s0 || p->window < 1))) return "tracers need initial positions, states and window >= 1";
+    if ((io.rand_u == nullptr) != (io.rand_n == nullptr)) return "rand_u and rand_n come together";
+    if (p->n_fft_modes < 0 || p->n_fft_modes > p->L / 2 + 1 || ((io.fft_re == nullptr) != (io.fft_im == nullptr))) return "bad fft request";
     return nullptr;
 }
+
+struct PdeExtents {        // systems, and systems times sites, recorded steps, tracers; snapshots per system
+    size_t S, SL, SN, ST; int n_snap;
+    PdeExtents(const pde_params *p, int32_t n)
+        : S((size_t)n), SL(S * p->L), SN(S * (p->nsteps + 1)), ST(S * p->n_tracers), n_snap(p->nsteps / p->snapshot_interval + 1) {}
+};
 
 struct Factor {            // (I - gamma dt Lap / dx^2) = L U, and the Sherman-Morrison data of the periodic corners
     std::vector<double> up, fw, finv, fz;     // upper diagonal, multipliers, 1/pivots, S-M vector z   [L]
@@ -91,6 +104,49 @@ inline int kernel_taps(const pde_params *p, double dx, std::vector<double> &ktab
 inline void twiddles(int L, std::vector<double> &twc, std::vector<double> &tws) {
     twc.resize(L); tws.resize(L);
     for (int j = 0; j < L; ++j) { const double ang = 6.283185307179586476925 * (double)j / (double)L; twc[j] = std::cos(ang); tws[j] = std::sin(ang); }
+}
+
+// The staging both shapes share, into the driver's argument struct `a` (PdeArgs, WArgs: the same member names), in two halves:
+// a shape allocates its own work memory between them.  First what the kernels read; `ktab` are the taps, reaching `ktaps` sites.
+template <class Args>
+int pde_stage_inputs(OneShot &job, Args &a, const pde_params *p, const PdeExtents &x, const PdeIo &io, int ktaps, const std::vector<double> &ktab) {
+    const size_t L = (size_t)p->L;
+    a.p = *p; a.dx = p->xlim / p->L; a.ktaps = ktaps; a.n_snap = x.n_snap;
+    Factor fac;
+    factorise(p, a.dx, fac);
+    a.sm_coef = fac.sm_coef; a.sm_denom = fac.sm_denom;
+    std::vector<double> twc, tws;
+    twiddles(p->L, twc, tws);
+    UP(beta, io.beta, x.S); UP(rho_p0, io.rho_p0, x.SL); UP(rho_m0, io.rho_m0, x.SL);
+    UP(fw, fac.fw.data(), L); UP(finv, fac.finv.data(), L); UP(fu, fac.up.data(), L); UP(fz, fac.fz.data(), L);
+    UP(ktab, ktab.data(), ktab.size()); UP(twc, twc.data(), L); UP(tws, tws.data(), L);
+    return 0;
+}
+
+// Then the tracer block and the series, snapshot and Fourier outputs the caller asked for (tracer_series: v_eff / D_eff among
+// them).  The final fields and tracers are each shape's own.
+template <class Args>
+int pde_stage_outputs(OneShot &job, Args &a, const pde_params *p, const PdeExtents &x, const PdeIo &io, bool tracer_series) {
+    const size_t L = (size_t)p->L, ntr = (size_t)p->n_tracers;
+    if (ntr) {
+        UP(tracer_x0, io.tracer_x0, x.ST); UP(tracer_s0, io.tracer_s0, x.ST);
+        if (io.rand_u) { UP(rand_u, io.rand_u, x.SN * ntr); UP(rand_n, io.rand_n, x.SN * ntr); }
+        WORK(hist, x.S * p->window * ntr); WORK(trx, x.ST); WORK(trs, x.ST);
+    }
+    OUT(m_series, io.m_series, x.SN); OUT(var_series, io.var_series, x.SN);
+    if (tracer_series) { OUT(v_eff, io.v_eff_series, x.SN); OUT(D_eff, io.D_eff_series, x.SN); }
+    OUT(snapshots, io.snapshots, x.S * x.n_snap * L); OUT(m_snapshots, io.m_snapshots, x.S * x.n_snap * L);
+    OUT(fft_re, io.fft_re, x.SN * p->n_fft_modes); OUT(fft_im, io.fft_im, x.SN * p->n_fft_modes);
+    return 0;
+}
+
+template <class Args>                                          // the outputs of pde_stage_outputs, back to the caller
+int pde_fetch_outputs(OneShot &job, const Args &a, const pde_params *p, const PdeExtents &x, const PdeIo &io, bool tracer_series) {
+    DOWN(io.m_series, m_series, x.SN * 8); DOWN(io.var_series, var_series, x.SN * 8);
+    if (tracer_series) { DOWN(io.v_eff_series, v_eff, x.SN * 8); DOWN(io.D_eff_series, D_eff, x.SN * 8); }
+    DOWN(io.snapshots, snapshots, x.S * x.n_snap * p->L * 8); DOWN(io.m_snapshots, m_snapshots, x.S * x.n_snap * p->L * 8);
+    DOWN(io.fft_re, fft_re, x.SN * p->n_fft_modes * 8); DOWN(io.fft_im, fft_im, x.SN * p->n_fft_modes * 8);
+    return 0;
 }
 
 // -------------------------------------------------------------------------------------------------------------- device

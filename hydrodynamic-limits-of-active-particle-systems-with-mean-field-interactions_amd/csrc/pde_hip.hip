@@ -345,59 +345,34 @@ int make_sweep_plan(const pde_params *p, int32_t n_systems, const double *kernel
 }
 
 // ---- host: the driver of both entry points.  sweep == nullptr: pde_solve_batch, one table of taps from p->kernel_sigma.
-int solve_impl(const char *who, std::string &err, const SweepPlan *sweep, const pde_params *p, int32_t n_systems, const double *beta,
-               const double *rho_p0, const double *rho_m0,
-               const double *tracer_x0, const int8_t *tracer_s0, const double *rand_u, const double *rand_n,
-               double *rho_p, double *rho_m, double *m_series, double *var_series, double *v_eff_series,
-               double *D_eff_series, double *snapshots, double *m_snapshots, double *fft_re, double *fft_im,
-               double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
+int solve_impl(const char *who, std::string &err, const SweepPlan *sweep, const pde_params *p, int32_t n_systems, const PdeIo &io) {
     OneShot job{who, err, false, PDE_ERR_NODEVICE, PDE_ERR_ARG, PDE_ERR_HIP};   // no zero-fill: the kernel writes every output in full
     if (int rc = job.select_device(p->device)) return rc;
 
-    const int L = p->L, ntr = p->n_tracers, ns = p->nsteps + 1;
-    const double dx = p->xlim / L;
-    // ---- constant matrix: Thomas factorisation (and the Sherman-Morrison vector for periodic corners); kernel taps (ref :84-93)
-    Factor fac;
-    factorise(p, dx, fac);
-    const std::vector<double> &up = fac.up, &fw = fac.fw, &finv = fac.finv, &fz = fac.fz;
-    const double sm_coef = fac.sm_coef, sm_denom = fac.sm_denom;
-    std::vector<double> ktab;
-    const int ktaps = sweep ? sweep->info.ktaps_max : kernel_taps(p, dx, ktab);
-    if (sweep) ktab = sweep->ktab;
-    std::vector<double> twc, tws;
-    twiddles(L, twc, tws);
-
+    const int L = p->L;
+    const PdeExtents x(p, n_systems);
+    std::vector<double> plain;                                 // kernel taps (ref :84-93) of the one width; a sweep brings its systems' tables
+    const int ktaps = sweep ? sweep->info.ktaps_max : kernel_taps(p, p->xlim / L, plain);
     PdeArgs a{};
-    a.p = *p; a.dx = dx; a.sm_coef = sm_coef; a.sm_denom = sm_denom; a.ktaps = ktaps;
-    a.chunk = (L + NT - 1) / NT; a.n_snap = p->nsteps / p->snapshot_interval + 1;
-    const size_t SL = (size_t)n_systems * L, SN = (size_t)n_systems * ns, ST = (size_t)n_systems * ntr;
-    UP(beta, beta, (size_t)n_systems); UP(rho_p0, rho_p0, SL); UP(rho_m0, rho_m0, SL);
-    UP(fw, fw.data(), (size_t)L); UP(finv, finv.data(), (size_t)L); UP(fu, up.data(), (size_t)L); UP(fz, fz.data(), (size_t)L);
-    UP(ktab, ktab.data(), ktab.size()); UP(twc, twc.data(), (size_t)L); UP(tws, tws.data(), (size_t)L);
+    a.chunk = (L + NT - 1) / NT;
+    if (int rc = pde_stage_inputs(job, a, p, x, io, ktaps, sweep ? sweep->ktab : plain)) return rc;
     if (sweep) {
-        UP(sys_mode, sweep->mode.data(), (size_t)n_systems); UP(sys_ktaps, sweep->ktaps.data(), (size_t)n_systems);
-        UP(sys_log2, sweep->log2.data(), (size_t)n_systems); UP(sys_ktab, sweep->ktab_off.data(), (size_t)n_systems);
+        UP(sys_mode, sweep->mode.data(), x.S); UP(sys_ktaps, sweep->ktaps.data(), x.S);
+        UP(sys_log2, sweep->log2.data(), x.S); UP(sys_ktab, sweep->ktab_off.data(), x.S);
         if (sweep->info.conv_log2_max) {
             std::vector<double2> ctw;
             pdek::build_twiddles(sweep->info.conv_log2_max, ctw);
             UP(ctw, ctw.data(), ctw.size());
         }
     }
-    if (ntr) {
-        UP(tracer_x0, tracer_x0, ST); UP(tracer_s0, tracer_s0, ST);
-        if (rand_u) { UP(rand_u, rand_u, SN * ntr); UP(rand_n, rand_n, SN * ntr); }
-        WORK(hist, (size_t)n_systems * p->window * ntr); WORK(trx, ST); WORK(trs, ST);
-    }
-    OUT(rho_p, rho_p, SL); OUT(rho_m, rho_m, SL); OUT(m_series, m_series, SN); OUT(var_series, var_series, SN);
-    OUT(v_eff, v_eff_series, SN); OUT(D_eff, D_eff_series, SN);
-    OUT(snapshots, snapshots, (size_t)n_systems * a.n_snap * L); OUT(m_snapshots, m_snapshots, (size_t)n_systems * a.n_snap * L);
-    OUT(fft_re, fft_re, SN * p->n_fft_modes); OUT(fft_im, fft_im, SN * p->n_fft_modes);
-    OUT(tracer_x, tracer_x, ST); OUT(tracer_s, tracer_s, ST);
+    const bool tracer_series = true;                           // wherever the caller gave the pointer; without tracers nothing writes them: unspecified values
+    if (int rc = pde_stage_outputs(job, a, p, x, io, tracer_series)) return rc;
+    OUT(rho_p, io.rho_p, x.SL); OUT(rho_m, io.rho_m, x.SL); OUT(tracer_x, io.tracer_x, x.ST); OUT(tracer_s, io.tracer_s, x.ST);
     size_t lds = base_lds_bytes(L, ktaps);
     if (sweep) lds = (size_t)sweep->info.lds_bytes;             // the plan has refused what does not fit
     else if (lds > 160 * 1024) {                               // beyond LDS: the fields live in global memory, the scans' scratch in LDS
         a.work_stride = (long long)((5 * (size_t)L + ((ktaps + 2) & ~1) + 3) & ~(size_t)3);
-        WORK(work, (size_t)n_systems * (size_t)a.work_stride);
+        WORK(work, x.S * (size_t)a.work_stride);
         lds = (size_t)((NT + 3) & ~3) * sizeof(double) + (size_t)2 * NT * sizeof(double4);
     }
     void (*kernel)(const PdeArgs) = !sweep ? pde_kernel<BATCH> : sweep->info.conv_log2_max ? pde_kernel<SWEEP_SPECTRAL> : pde_kernel<SWEEP_DIRECT>;
@@ -406,12 +381,10 @@ int solve_impl(const char *who, std::string &err, const SweepPlan *sweep, const 
     job.ev.start();
     hipLaunchKernelGGL(kernel, dim3((unsigned)n_systems), dim3(NT), lds, nullptr, a);
     job.ev.stop();
-    if (int rc = job.finish(hipGetLastError(), "pde_kernel", kernel_ms)) return rc;
-    DOWN(rho_p, rho_p, SL * 8); DOWN(rho_m, rho_m, SL * 8); DOWN(m_series, m_series, SN * 8); DOWN(var_series, var_series, SN * 8);
-    DOWN(v_eff_series, v_eff, SN * 8); DOWN(D_eff_series, D_eff, SN * 8);
-    DOWN(snapshots, snapshots, (size_t)n_systems * a.n_snap * L * 8); DOWN(m_snapshots, m_snapshots, (size_t)n_systems * a.n_snap * L * 8);
-    DOWN(fft_re, fft_re, SN * p->n_fft_modes * 8); DOWN(fft_im, fft_im, SN * p->n_fft_modes * 8);
-    DOWN(tracer_x, tracer_x, ST * 8); DOWN(tracer_s, tracer_s, ST);
+    if (int rc = job.finish(hipGetLastError(), "pde_kernel", io.kernel_ms)) return rc;
+    DOWN(io.rho_p, rho_p, x.SL * 8); DOWN(io.rho_m, rho_m, x.SL * 8);
+    if (int rc = pde_fetch_outputs(job, a, p, x, io, tracer_series)) return rc;
+    DOWN(io.tracer_x, tracer_x, x.ST * 8); DOWN(io.tracer_s, tracer_s, x.ST);
     return PDE_OK;
 }
 
@@ -426,11 +399,12 @@ int pde_solve_batch(const pde_params *p, int32_t n_systems, const double *beta, 
                     double *rho_p, double *rho_m, double *m_series, double *var_series, double *v_eff_series,
                     double *D_eff_series, double *snapshots, double *m_snapshots, double *fft_re, double *fft_im,
                     double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
+    const PdeIo io{beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m, m_series, var_series, v_eff_series,
+                   D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms};
     auto bad = [&](const char *m) { g_err = std::string("pde_solve_batch: ") + m; return PDE_ERR_ARG; };
-    if (const char *why = check_args(p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, fft_re, fft_im)) return bad(why);
+    if (const char *why = check_args(p, n_systems, io)) return bad(why);
     if (p->convolution != 0) return bad("convolution must be 0 here: the spectral convolution belongs to the wide shape (pdew_solve, include/pde_wide.h)");
-    return solve_impl("pde_solve_batch", g_err, nullptr, p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m,
-                      m_series, var_series, v_eff_series, D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms);
+    return solve_impl("pde_solve_batch", g_err, nullptr, p, n_systems, io);
 }
 
 const char *pdek_last_error(void) { return g_err_k.c_str(); }
@@ -455,13 +429,14 @@ int pdek_solve(const pde_params *p, int32_t n_systems, const double *beta, const
                double *rho_p, double *rho_m, double *m_series, double *var_series, double *v_eff_series,
                double *D_eff_series, double *snapshots, double *m_snapshots, double *fft_re, double *fft_im,
                double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
+    const PdeIo io{beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m, m_series, var_series, v_eff_series,
+                   D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms};
     auto bad = [&](const std::string &m) { g_err_k = "pdek_solve: " + m; return PDE_ERR_ARG; };
-    if (const char *why = check_args(p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, fft_re, fft_im)) return bad(why);
+    if (const char *why = check_args(p, n_systems, io)) return bad(why);
     SweepPlan pl;
     std::string why;
     if (make_sweep_plan(p, n_systems, kernel_sigma, pl, why)) return bad(why);
-    return solve_impl("pdek_solve", g_err_k, &pl, p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m,
-                      m_series, var_series, v_eff_series, D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms);
+    return solve_impl("pdek_solve", g_err_k, &pl, p, n_systems, io);
 }
 
 }  // extern "C"

@@ -546,33 +546,27 @@ int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const
                double *rho_p, double *rho_m, double *m_series, double *var_series, double *v_eff_series,
                double *D_eff_series, double *snapshots, double *m_snapshots, double *fft_re, double *fft_im,
                double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
+    const PdeIo io{beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m, m_series, var_series, v_eff_series,
+                   D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms};
     auto bad = [&](const char *m) { g_err = std::string("pdew_solve: ") + m; return PDE_ERR_ARG; };
-    if (const char *why = check_args(p, n_systems, beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, fft_re, fft_im)) return bad(why);
-    const int L = p->L, ntr = p->n_tracers, ns = p->nsteps + 1;
-    const double dx = p->xlim / L;
+    if (const char *why = check_args(p, n_systems, io)) return bad(why);
+    const int L = p->L, ntr = p->n_tracers;
     std::vector<double> ktab;
-    const int ktaps = kernel_taps(p, dx, ktab);
+    const int ktaps = kernel_taps(p, p->xlim / L, ktab);
     Plan pl;
     if (const char *why = make_plan(p, n_systems, workgroups, ktaps, pl)) return bad(why);
     OneShot job{"pdew_solve", g_err, false, PDE_ERR_NODEVICE, PDE_ERR_ARG, PDE_ERR_HIP};   // no zero-fill: the kernels write every buffer before it is read
     if (int rc = job.select_device(p->device)) return rc;
 
-    Factor fac;                                                // the factorisation pde_solve_batch uses
-    factorise(p, dx, fac);
-    std::vector<double> twc, tws;
-    twiddles(L, twc, tws);
-
-    WArgs a{};
-    a.p = *p; a.dx = dx; a.sm_coef = fac.sm_coef; a.sm_denom = fac.sm_denom; a.ktaps = ktaps;
-    a.G = pl.G; a.q = pl.q; a.r = pl.r; a.n_snap = p->nsteps / p->snapshot_interval + 1;
+    const PdeExtents x(p, n_systems);
+    const size_t S = x.S, SL = x.SL;
     const int G = pl.G;
-    const size_t S = (size_t)n_systems, SL = S * L, SN = S * ns, ST = S * ntr;
-    UP(beta, beta, S); UP(rho_p0, rho_p0, SL); UP(rho_m0, rho_m0, SL);
-    UP(fw, fac.fw.data(), (size_t)L); UP(finv, fac.finv.data(), (size_t)L); UP(fu, fac.up.data(), (size_t)L); UP(fz, fac.fz.data(), (size_t)L);
-    UP(ktab, ktab.data(), ktab.size()); UP(twc, twc.data(), (size_t)L); UP(tws, tws.data(), (size_t)L);
+    WArgs a{};
+    a.G = pl.G; a.q = pl.q; a.r = pl.r;
+    if (int rc = pde_stage_inputs(job, a, p, x, io, ktaps, ktab)) return rc;   // the factorisation, taps and twiddles pde_solve_batch uses
     WORK(rp, SL); WORK(rm, SL); WORK(xp, SL); WORK(xm, SL); WORK(mf, SL);
     WORK(part, S * NSLOT * G); WORK(fmap, S * G * 3); WORK(bmap, S * G * 3); WORK(corner, S * 4);
-    if (fft_re) WORK(fpart, S * 2 * (size_t)p->n_fft_modes * G);
+    if (io.fft_re) WORK(fpart, S * 2 * (size_t)p->n_fft_modes * G);
     a.spectral = pl.spectral;
     double2 *taps_dev = nullptr;
     double *spec_dev = nullptr;
@@ -588,15 +582,8 @@ int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const
         if (int rc = job.alloc(&spec_dev, M, "spec")) return rc;
         a.sp.spec = spec_dev; a.sp.rp = a.rp; a.sp.rm = a.rm; a.sp.mf = a.mf;
     }
-    if (ntr) {
-        UP(tracer_x0, tracer_x0, ST); UP(tracer_s0, tracer_s0, ST);
-        if (rand_u) { UP(rand_u, rand_u, SN * ntr); UP(rand_n, rand_n, SN * ntr); }
-        WORK(hist, S * p->window * ntr); WORK(trx, ST); WORK(trs, ST);
-    }
-    OUT(m_series, m_series, SN); OUT(var_series, var_series, SN);
-    if (ntr) { OUT(v_eff, v_eff_series, SN); OUT(D_eff, D_eff_series, SN); }
-    OUT(snapshots, snapshots, S * a.n_snap * L); OUT(m_snapshots, m_snapshots, S * a.n_snap * L);
-    OUT(fft_re, fft_re, SN * p->n_fft_modes); OUT(fft_im, fft_im, SN * p->n_fft_modes);
+    const bool tracer_series = ntr > 0;                        // v_eff / D_eff only with tracers: no kernel here writes them otherwise
+    if (int rc = pde_stage_outputs(job, a, p, x, io, tracer_series)) return rc;
     const size_t mag_lds = pl.spectral ? 0 : pl.lds;            // (spectral: pl.lds is the transforms' static LDS)
     if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(&pdew_mag), mag_lds)) return rc;
     if (int rc = job.create_events()) return rc;
@@ -626,11 +613,10 @@ int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const
         err = hipGetLastError();
     }
     job.ev.stop();
-    if (int rc = job.finish(err, "pdew_solve", kernel_ms)) return rc;
-    DOWN(rho_p, rp, SL * 8); DOWN(rho_m, rm, SL * 8); DOWN(m_series, m_series, SN * 8); DOWN(var_series, var_series, SN * 8);
-    if (ntr) { DOWN(v_eff_series, v_eff, SN * 8); DOWN(D_eff_series, D_eff, SN * 8); DOWN(tracer_x, trx, ST * 8); DOWN(tracer_s, trs, ST); }
-    DOWN(snapshots, snapshots, S * a.n_snap * L * 8); DOWN(m_snapshots, m_snapshots, S * a.n_snap * L * 8);
-    DOWN(fft_re, fft_re, SN * p->n_fft_modes * 8); DOWN(fft_im, fft_im, SN * p->n_fft_modes * 8);
+    if (int rc = job.finish(err, "pdew_solve", io.kernel_ms)) return rc;
+    DOWN(io.rho_p, rp, SL * 8); DOWN(io.rho_m, rm, SL * 8);         // the fields end in their work buffers
+    if (int rc = pde_fetch_outputs(job, a, p, x, io, tracer_series)) return rc;
+    if (ntr) { DOWN(io.tracer_x, trx, x.ST * 8); DOWN(io.tracer_s, trs, x.ST); }   // and the tracers in theirs
     return PDE_OK;
 }
 

@@ -25,6 +25,7 @@ There is no CPU fallback: without libaps_hip.so or without a GPU `solve()` raise
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -58,27 +59,41 @@ class PdekPlanInfo(C.Structure):
 PDEK_MIN_LOG2, PDEK_MAX_LOG2 = 8, 11     # include/pde_sweep.h
 PDE_MAX_L = 1 << 22          # fields in LDS up to L ~ 3000 (PDE_LDS_L of include/pde.h), in global memory beyond
 
+# the launch keywords that describe the equation and the grid: what `_model` picks and `_params` reads
+MODEL = ("L", "xlim", "dt", "nsteps", "gamma", "lam", "bc", "active_model", "gaussian_kernel", "kernel_sigma",
+         "snapshot_interval", "device")
+# the pointers every solve takes (include/pde.h): seven inputs, twelve outputs, in the ABI's order; kernel_ms follows them
+SERIES = ("m_series", "var_series", "v_eff_series", "D_eff_series")
+COMMON = ("beta", "rho_p0", "rho_m0", "tracer_x0", "tracer_s0", "rand_u", "rand_n", "rho_p", "rho_m") + SERIES + (
+    "snapshots", "m_snapshots", "fft_re", "fft_im", "tracer_x", "tracer_s")
+_PAR, _PTR, _I32, _MS = C.POINTER(PdeParams), C.c_void_p, C.c_int32, C.POINTER(C.c_double)
+
+
+# The three solves: the entry's *_last_error, the C types of what it takes of its own next to the common pointers, and its call
+# (`own`: that argument's value, workgroups or kernel_sigma[], which stands behind beta; `ptrs`: the common pointers, kernel_ms).
+_Solve = collections.namedtuple("_Solve", "last_error own call")
+SOLVES = {
+    "pde_solve_batch": _Solve("pde_last_error", [], lambda lib, par, S, own, ptrs: lib.pde_solve_batch(par, S, *ptrs)),
+    "pdew_solve": _Solve("pdew_last_error", [_I32], lambda lib, par, S, own, ptrs: lib.pdew_solve(par, S, own, *ptrs)),
+    "pdek_solve": _Solve("pdek_last_error", [_PTR],
+                         lambda lib, par, S, own, ptrs: lib.pdek_solve(par, S, ptrs[0], _p(own), *ptrs[1:])),
+}
+# the plans: name -> (last_error, the C types behind pde_params)
+PLANS = {
+    "pdew_plan": ("pdew_last_error", [_I32, _I32, C.POINTER(PdewPlanInfo)]),
+    "pdek_plan": ("pdek_last_error", [_I32, _PTR, C.POINTER(PdekPlanInfo)] + [_PTR] * 3),
+}
+
 
 def _lib():
     lib = capi.load()
     if not getattr(lib, "_pde_ready", False):
-        vp = C.c_void_p
-        lib.pde_last_error.restype, lib.pde_last_error.argtypes = C.c_char_p, []
-        lib.pde_solve_batch.restype = C.c_int
-        lib.pde_solve_batch.argtypes = [C.POINTER(PdeParams), C.c_int32] + [vp] * 19 + [C.POINTER(C.c_double)]
-        lib.pdew_last_error.restype, lib.pdew_last_error.argtypes = C.c_char_p, []
-        lib.pdew_solve.restype = C.c_int
-        lib.pdew_solve.argtypes = [C.POINTER(PdeParams), C.c_int32, C.c_int32] + [vp] * 19 + [C.POINTER(C.c_double)]
-        lib.pdew_plan.restype = C.c_int
-        lib.pdew_plan.argtypes = [C.POINTER(PdeParams), C.c_int32, C.c_int32, C.POINTER(PdewPlanInfo)]
-        lib.pdes_last_error.restype, lib.pdes_last_error.argtypes = C.c_char_p, []
-        lib.pdes_plan.restype = C.c_int
-        lib.pdes_plan.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 3
-        lib.pdek_last_error.restype, lib.pdek_last_error.argtypes = C.c_char_p, []
-        lib.pdek_plan.restype = C.c_int
-        lib.pdek_plan.argtypes = [C.POINTER(PdeParams), C.c_int32, vp, C.POINTER(PdekPlanInfo)] + [vp] * 3
-        lib.pdek_solve.restype = C.c_int
-        lib.pdek_solve.argtypes = [C.POINTER(PdeParams), C.c_int32] + [vp] * 20 + [C.POINTER(C.c_double)]
+        protos = {name: (e.last_error, [_PAR, _I32] + e.own + [_PTR] * len(COMMON) + [_MS]) for name, e in SOLVES.items()}
+        protos.update({name: (last_error, [_PAR] + behind) for name, (last_error, behind) in PLANS.items()})
+        protos["pdes_plan"] = ("pdes_last_error", [_I32] * 3 + [C.POINTER(_I32)] * 3)
+        for name, (last_error, argtypes) in protos.items():
+            getattr(lib, name).restype, getattr(lib, name).argtypes = C.c_int, argtypes
+            getattr(lib, last_error).restype, getattr(lib, last_error).argtypes = C.c_char_p, []
         lib._pde_ready = True
     return lib
 
@@ -130,8 +145,19 @@ def _check_fft_modes(fft_modes, L):
     return int(fft_modes)
 
 
+def _check_bc(bc):
+    if bc not in ("periodic", "neumann"):
+        raise ValueError("bc must be 'periodic' or 'neumann'")
+
+
+def _model(kw):
+    """The model record: the keywords of MODEL out of `kw`, a raw function's locals() or a solver's attributes."""
+    return {k: kw[k] for k in MODEL}
+
+
 def _params(*, L, xlim, dt, nsteps, gamma, lam, bc, active_model, gaussian_kernel, kernel_sigma, snapshot_interval, n_tracers,
             n_fft_modes, seed, device, convolution=0):
+    """struct pde_params from the model record and what a call adds to it."""
     if not gaussian_kernel:
         mode = 0
     elif kernel_sigma > 100000:                                    # ref :161
@@ -143,6 +169,17 @@ def _params(*, L, xlim, dt, nsteps, gamma, lam, bc, active_model, gaussian_kerne
                      kernel_mode=mode, snapshot_interval=snapshot_interval, n_tracers=n_tracers, window=max(window, 1),
                      n_fft_modes=n_fft_modes, device=device, convolution=convolution, xlim=xlim, dt=dt, gamma=gamma, lam=lam,
                      kernel_sigma=kernel_sigma, seed=int(seed) & (2 ** 64 - 1))
+
+
+def _plan(lib, name, info, kw, conv, front, behind=()):
+    """The plan `name` for the keywords `kw` of plan() / sweep_plan(): pde_params without a seed, the call (`front` of and
+    `behind` the info structure), the structure's fields as a dict."""
+    par = _params(**_model(kw), n_tracers=kw["n_tracers"], n_fft_modes=_check_fft_modes(kw["fft_modes"], kw["L"]) or 0, seed=0,
+                  convolution=conv)
+    rc = getattr(lib, name)(C.byref(par), *front, C.byref(info), *behind)
+    if rc != 0:
+        raise capi.ApsError(rc, getattr(lib, PLANS[name][0])().decode())
+    return dict({field: getattr(info, field) for field, _ in info._fields_}, convolution="spectral" if conv else "direct")
 
 
 def plan(*, L, workgroups="auto", n_systems=1, xlim=1.0, dt=5e-4, T=None, nsteps=None, gamma=2.33e-4, lam=0.6, bc="periodic",
@@ -159,21 +196,53 @@ def plan(*, L, workgroups="auto", n_systems=1, xlim=1.0, dt=5e-4, T=None, nsteps
         raise ValueError("plan() describes the wide shape: workgroups must be 'auto' or an integer >= 1")
     if nsteps is None:
         nsteps = int(T / dt) if T is not None else 0
-    par = _params(L=L, xlim=xlim, dt=dt, nsteps=nsteps, gamma=gamma, lam=lam, bc=bc, active_model=active_model,
-                  gaussian_kernel=gaussian_kernel, kernel_sigma=kernel_sigma, snapshot_interval=snapshot_interval,
-                  n_tracers=n_tracers, n_fft_modes=_check_fft_modes(fft_modes, L) or 0, seed=0, device=device, convolution=conv)
     info = PdewPlanInfo()
-    rc = lib.pdew_plan(C.byref(par), n_systems, wg, C.byref(info))
-    if rc != 0:
-        raise capi.ApsError(rc, lib.pdew_last_error().decode())
-    out = {name: getattr(info, name) for name, _ in PdewPlanInfo._fields_}
-    out["convolution"] = "spectral" if conv else "direct"
+    out = _plan(lib, "pdew_plan", info, locals(), conv, (n_systems, wg))
     out["conv_blocks"] = out["conv_block_sites"] = 0
     if info.conv_log2:
         sp = spectral_plan(L, info.ktaps, int(os.environ.get("PDE_SPECTRAL_MAX_LOG2") or 21))
         assert sp["log2_m"] == info.conv_log2
         out["conv_blocks"], out["conv_block_sites"] = sp["blocks"], sp["block_sites"]
     out["slab_lengths"] = [info.slab_len] * info.n_long_slabs + [info.slab_len_min] * (info.workgroups - info.n_long_slabs)
+    return out
+
+
+def _launch(lib, name, own, model, *, betas, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, n_fft_modes, seed,
+            want_snapshots, convolution):
+    """One launch of SOLVES[name], `own` its own argument: broadcasts the start fields, tracers and random numbers over the
+    systems and pins them as the ABI's types, allocates the outputs, calls, raises the entry's error, returns the result dict."""
+    L, nsteps, every = model["L"], model["nsteps"], model["snapshot_interval"]
+    betas = np.ascontiguousarray(np.atleast_1d(betas), dtype=np.float64)
+    S = len(betas)
+
+    def pin(a, *shape, dtype=np.float64):
+        return np.ascontiguousarray(np.broadcast_to(a, shape), dtype=dtype)
+
+    arg = dict(beta=betas, rho_p0=pin(rho_p0, S, L), rho_m0=pin(rho_m0, S, L))       # what the C call takes, by COMMON's names
+    ntr = 0 if tracer_x0 is None else np.shape(tracer_x0)[-1]
+    if ntr:
+        arg.update(tracer_x0=pin(tracer_x0, S, ntr), tracer_s0=pin(tracer_s0, S, ntr, dtype=np.int8))
+    if rand_u is not None:
+        arg.update(rand_u=pin(rand_u, S, nsteps + 1, ntr), rand_n=pin(rand_n, S, nsteps + 1, ntr))
+    par = _params(**model, n_tracers=ntr, n_fft_modes=n_fft_modes, seed=seed, convolution=convolution)
+    _check_bc(model["bc"])           # where solve_batch_raw has always refused a bad bc (solve_sweep_raw does before it comes here)
+    n_snap = nsteps // every + 1
+    out = dict(rho_p=np.zeros((S, L)), rho_m=np.zeros((S, L)), m_series=np.zeros((S, nsteps + 1)),
+               var_series=np.zeros((S, nsteps + 1)), v_eff_series=np.full((S, nsteps + 1), np.nan),
+               D_eff_series=np.full((S, nsteps + 1), np.nan),
+               snapshots=np.zeros((S, n_snap, L)) if want_snapshots else None,
+               m_snapshots=np.zeros((S, n_snap, L)) if want_snapshots else None,
+               fft_re=np.zeros((S, nsteps + 1, n_fft_modes)) if n_fft_modes else None,
+               fft_im=np.zeros((S, nsteps + 1, n_fft_modes)) if n_fft_modes else None,
+               tracers_unwrapped=np.zeros((S, ntr)) if ntr else None, tracer_state=np.zeros((S, ntr), np.int8) if ntr else None)
+    arg.update(out, tracer_x=out["tracers_unwrapped"], tracer_s=out["tracer_state"])
+    if not ntr:
+        arg.update(v_eff_series=None, D_eff_series=None)           # without tracers the caller's two series stay NaN
+    ms = C.c_double()
+    rc = SOLVES[name].call(lib, C.byref(par), S, own, [_p(arg.get(k)) for k in COMMON] + [C.byref(ms)])
+    if rc != 0:
+        raise capi.ApsError(rc, getattr(lib, SOLVES[name].last_error)().decode())
+    out.update(times=np.arange(n_snap) * every * model["dt"], kernel_ms=ms.value)
     return out
 
 
@@ -190,51 +259,9 @@ def solve_batch_raw(*, L, xlim, dt, nsteps, gamma, lam, betas, bc, active_model,
     wg = _check_workgroups(workgroups)
     conv = _check_convolution(convolution, wg)
     fm = _check_fft_modes(fft_modes, L)
-    if fm is not None:
-        n_fft_modes = fm
-    betas = np.ascontiguousarray(np.atleast_1d(betas), dtype=np.float64)
-    S = len(betas)
-    rho_p0 = np.ascontiguousarray(np.broadcast_to(rho_p0, (S, L)), dtype=np.float64)
-    rho_m0 = np.ascontiguousarray(np.broadcast_to(rho_m0, (S, L)), dtype=np.float64)
-    ntr = 0 if tracer_x0 is None else np.shape(tracer_x0)[-1]
-    if ntr:
-        tracer_x0 = np.ascontiguousarray(np.broadcast_to(tracer_x0, (S, ntr)), dtype=np.float64)
-        tracer_s0 = np.ascontiguousarray(np.broadcast_to(tracer_s0, (S, ntr)), dtype=np.int8)
-    if rand_u is not None:
-        rand_u = np.ascontiguousarray(np.broadcast_to(rand_u, (S, nsteps + 1, ntr)), dtype=np.float64)
-        rand_n = np.ascontiguousarray(np.broadcast_to(rand_n, (S, nsteps + 1, ntr)), dtype=np.float64)
-    par = _params(L=L, xlim=xlim, dt=dt, nsteps=nsteps, gamma=gamma, lam=lam, bc=bc, active_model=active_model,
-                  gaussian_kernel=gaussian_kernel, kernel_sigma=kernel_sigma, snapshot_interval=snapshot_interval,
-                  n_tracers=ntr, n_fft_modes=n_fft_modes, seed=seed, device=device, convolution=conv)
-    if bc not in ("periodic", "neumann"):
-        raise ValueError("bc must be 'periodic' or 'neumann'")
-    n_snap = nsteps // snapshot_interval + 1
-    out = dict(rho_p=np.zeros((S, L)), rho_m=np.zeros((S, L)), m_series=np.zeros((S, nsteps + 1)),
-               var_series=np.zeros((S, nsteps + 1)), v_eff_series=np.full((S, nsteps + 1), np.nan),
-               D_eff_series=np.full((S, nsteps + 1), np.nan))
-    snaps = np.zeros((S, n_snap, L)) if want_snapshots else None
-    msnaps = np.zeros((S, n_snap, L)) if want_snapshots else None
-    fre = np.zeros((S, nsteps + 1, n_fft_modes)) if n_fft_modes else None
-    fim = np.zeros((S, nsteps + 1, n_fft_modes)) if n_fft_modes else None
-    tx = np.zeros((S, ntr)) if ntr else None
-    ts = np.zeros((S, ntr), np.int8) if ntr else None
-    ms = C.c_double()
-    bufs = (_p(betas), _p(rho_p0), _p(rho_m0), _p(tracer_x0) if ntr else None,
-            _p(tracer_s0) if ntr else None, _p(rand_u), _p(rand_n), _p(out["rho_p"]), _p(out["rho_m"]),
-            _p(out["m_series"]), _p(out["var_series"]), _p(out["v_eff_series"]) if ntr else None,
-            _p(out["D_eff_series"]) if ntr else None, _p(snaps), _p(msnaps), _p(fre), _p(fim), _p(tx), _p(ts),
-            C.byref(ms))
-    if wg is None:
-        rc = lib.pde_solve_batch(C.byref(par), S, *bufs)
-        if rc != 0:
-            raise capi.ApsError(rc, lib.pde_last_error().decode())
-    else:
-        rc = lib.pdew_solve(C.byref(par), S, wg, *bufs)
-        if rc != 0:
-            raise capi.ApsError(rc, lib.pdew_last_error().decode())
-    out.update(snapshots=snaps, m_snapshots=msnaps, fft_re=fre, fft_im=fim, tracers_unwrapped=tx, tracer_state=ts,
-               times=np.arange(n_snap) * snapshot_interval * dt, kernel_ms=ms.value)
-    return out
+    return _launch(lib, "pde_solve_batch" if wg is None else "pdew_solve", wg, _model(locals()), betas=betas, rho_p0=rho_p0,
+                   rho_m0=rho_m0, tracer_x0=tracer_x0, tracer_s0=tracer_s0, rand_u=rand_u, rand_n=rand_n,
+                   n_fft_modes=n_fft_modes if fm is None else fm, seed=seed, want_snapshots=want_snapshots, convolution=conv)
 
 
 def _sweep_axes(betas, kernel_sigmas):
@@ -263,20 +290,11 @@ def sweep_plan(*, L, kernel_sigmas, convolution=None, xlim=1.0, dt=5e-4, T=None,
     ks = np.ascontiguousarray(np.atleast_1d(np.asarray(kernel_sigmas, dtype=np.float64)))
     if ks.ndim != 1:
         raise ValueError("kernel_sigmas must be a scalar or one-dimensional")
-    S = len(ks)
-    par = _params(L=L, xlim=xlim, dt=dt, nsteps=nsteps, gamma=gamma, lam=lam, bc=bc, active_model=active_model,
-                  gaussian_kernel=gaussian_kernel, kernel_sigma=0.0, snapshot_interval=snapshot_interval, n_tracers=n_tracers,
-                  n_fft_modes=_check_fft_modes(fft_modes, L) or 0, seed=0, device=device, convolution=conv)
-    info = PdekPlanInfo()
-    mode, kt, lg = (np.zeros(S, np.int32) for _ in range(3))
-    rc = lib.pdek_plan(C.byref(par), S, _p(ks), C.byref(info), _p(mode), _p(kt), _p(lg))
-    if rc != 0:
-        raise capi.ApsError(rc, lib.pdek_last_error().decode())
-    out = dict(kernel_mode=mode.tolist(), ktaps=kt.tolist(), conv_log2=lg.tolist())
-    out.update({name: getattr(info, name) for name, _ in PdekPlanInfo._fields_})
-    out["fields_in_lds"] = bool(info.fields_in_lds)
-    out["convolution"] = "spectral" if conv else "direct"
-    return out
+    mode, kt, lg = (np.zeros(len(ks), np.int32) for _ in range(3))
+    info = _plan(lib, "pdek_plan", PdekPlanInfo(), dict(locals(), kernel_sigma=0.0), conv, (len(ks), _p(ks)),
+                 (_p(mode), _p(kt), _p(lg)))
+    info["fields_in_lds"] = bool(info["fields_in_lds"])
+    return dict(kernel_mode=mode.tolist(), ktaps=kt.tolist(), conv_log2=lg.tolist(), **info)
 
 
 def solve_sweep_raw(*, L, xlim, dt, nsteps, gamma, lam, betas, kernel_sigmas, bc, active_model, gaussian_kernel,
@@ -289,45 +307,11 @@ def solve_sweep_raw(*, L, xlim, dt, nsteps, gamma, lam, betas, kernel_sigmas, bc
     lib = _lib()
     conv = _check_convolution(convolution)
     fm = _check_fft_modes(fft_modes, L)
-    if fm is not None:
-        n_fft_modes = fm
     betas, ks = _sweep_axes(betas, kernel_sigmas)
-    S = len(betas)
-    if bc not in ("periodic", "neumann"):
-        raise ValueError("bc must be 'periodic' or 'neumann'")
-    rho_p0 = np.ascontiguousarray(np.broadcast_to(rho_p0, (S, L)), dtype=np.float64)
-    rho_m0 = np.ascontiguousarray(np.broadcast_to(rho_m0, (S, L)), dtype=np.float64)
-    ntr = 0 if tracer_x0 is None else np.shape(tracer_x0)[-1]
-    if ntr:
-        tracer_x0 = np.ascontiguousarray(np.broadcast_to(tracer_x0, (S, ntr)), dtype=np.float64)
-        tracer_s0 = np.ascontiguousarray(np.broadcast_to(tracer_s0, (S, ntr)), dtype=np.int8)
-    if rand_u is not None:
-        rand_u = np.ascontiguousarray(np.broadcast_to(rand_u, (S, nsteps + 1, ntr)), dtype=np.float64)
-        rand_n = np.ascontiguousarray(np.broadcast_to(rand_n, (S, nsteps + 1, ntr)), dtype=np.float64)
-    par = _params(L=L, xlim=xlim, dt=dt, nsteps=nsteps, gamma=gamma, lam=lam, bc=bc, active_model=active_model,
-                  gaussian_kernel=gaussian_kernel, kernel_sigma=0.0, snapshot_interval=snapshot_interval,
-                  n_tracers=ntr, n_fft_modes=n_fft_modes, seed=seed, device=device, convolution=conv)
-    n_snap = nsteps // snapshot_interval + 1
-    out = dict(rho_p=np.zeros((S, L)), rho_m=np.zeros((S, L)), m_series=np.zeros((S, nsteps + 1)),
-               var_series=np.zeros((S, nsteps + 1)), v_eff_series=np.full((S, nsteps + 1), np.nan),
-               D_eff_series=np.full((S, nsteps + 1), np.nan))
-    snaps = np.zeros((S, n_snap, L)) if want_snapshots else None
-    msnaps = np.zeros((S, n_snap, L)) if want_snapshots else None
-    fre = np.zeros((S, nsteps + 1, n_fft_modes)) if n_fft_modes else None
-    fim = np.zeros((S, nsteps + 1, n_fft_modes)) if n_fft_modes else None
-    tx = np.zeros((S, ntr)) if ntr else None
-    ts = np.zeros((S, ntr), np.int8) if ntr else None
-    ms = C.c_double()
-    rc = lib.pdek_solve(C.byref(par), S, _p(betas), _p(ks), _p(rho_p0), _p(rho_m0), _p(tracer_x0) if ntr else None,
-                        _p(tracer_s0) if ntr else None, _p(rand_u), _p(rand_n), _p(out["rho_p"]), _p(out["rho_m"]),
-                        _p(out["m_series"]), _p(out["var_series"]), _p(out["v_eff_series"]) if ntr else None,
-                        _p(out["D_eff_series"]) if ntr else None, _p(snaps), _p(msnaps), _p(fre), _p(fim), _p(tx), _p(ts),
-                        C.byref(ms))
-    if rc != 0:
-        raise capi.ApsError(rc, lib.pdek_last_error().decode())
-    out.update(snapshots=snaps, m_snapshots=msnaps, fft_re=fre, fft_im=fim, tracers_unwrapped=tx, tracer_state=ts,
-               times=np.arange(n_snap) * snapshot_interval * dt, kernel_ms=ms.value)
-    return out
+    _check_bc(bc)
+    return _launch(lib, "pdek_solve", ks, _model(dict(locals(), kernel_sigma=0.0)), betas=betas, rho_p0=rho_p0, rho_m0=rho_m0,
+                   tracer_x0=tracer_x0, tracer_s0=tracer_s0, rand_u=rand_u, rand_n=rand_n,
+                   n_fft_modes=n_fft_modes if fm is None else fm, seed=seed, want_snapshots=want_snapshots, convolution=conv)
 
 
 class IMEXPDE:
@@ -381,27 +365,44 @@ class IMEXPDE:
         self.tracer_state = np.random.choice([-1, 1], size=n_tracers)
         self._out = None
 
-    def _run(self, betas, rho_p0, rho_m0, tx0, ts0, rand_u=None, rand_n=None, want_snapshots=True):
-        seed = self.seed if self.seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
-        return solve_batch_raw(L=self.L, xlim=self.xlim, dt=self.dt, nsteps=self.nsteps, gamma=self.gamma, lam=self.lam,
-                               betas=betas, bc=self.bc, active_model=self.active_model,
-                               gaussian_kernel=self.gaussian_kernel, kernel_sigma=self.kernel_sigma,
-                               snapshot_interval=self.snapshot_interval, rho_p0=rho_p0, rho_m0=rho_m0, tracer_x0=tx0,
-                               tracer_s0=ts0, rand_u=rand_u, rand_n=rand_n,
-                               n_fft_modes=self.L // 2 + 1 if self.record_fft else 0, seed=seed, device=self.device,
-                               want_snapshots=want_snapshots, workgroups=self.workgroups, fft_modes=self.fft_modes,
-                               convolution=self.convolution)
+    def _model(self, sweep=False):
+        """The model record of this solver (MODEL above), as the raw solves and plan() take it; a sweep has a width per system
+        in place of kernel_sigma."""
+        model = _model(vars(self))
+        if sweep:
+            del model["kernel_sigma"]
+        return model
+
+    def _modes(self, fft_modes=None):
+        """The Fourier modes of a call: given with it, else the constructor's fft_modes, else all of them under record_fft."""
+        for n in (fft_modes, self.fft_modes):
+            if n is not None:
+                return n
+        return self.L // 2 + 1 if self.record_fft else 0
+
+    def _start(self):
+        """This solver's state as the start of a launch."""
+        return dict(rho_p0=self.rho_p, rho_m0=self.rho_m, tracer_x0=self.tracers_unwrapped if self.n_tracers else None,
+                    tracer_s0=self.tracer_state if self.n_tracers else None)
+
+    def _seed(self):
+        """The seed of a call: the solver's, else drawn from NumPy's global generator."""
+        return self.seed if self.seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
+
+    def _run(self, betas, rand_u=None, rand_n=None, want_snapshots=True, workgroups=None, fft_modes=None, convolution=None):
+        """solve_batch_raw from this solver's state; workgroups / fft_modes / convolution override the constructor's."""
+        return solve_batch_raw(**self._model(), **self._start(), seed=self._seed(), betas=betas, rand_u=rand_u, rand_n=rand_n,
+                               want_snapshots=want_snapshots, fft_modes=self._modes(fft_modes),
+                               workgroups=workgroups if workgroups is not None else self.workgroups,
+                               convolution=convolution if convolution is not None else self.convolution)
 
     def solve(self, rand_u=None, rand_n=None):                     # ref :236-290, on the GPU
-        r = self._run([self.beta], self.rho_p, self.rho_m, self.tracers_unwrapped if self.n_tracers else None,
-                      self.tracer_state if self.n_tracers else None, rand_u, rand_n)
-        self._adopt(r, 0)
+        self._adopt(self._run([self.beta], rand_u, rand_n), 0)
         return self
 
     def _adopt(self, r, s):
-        self.rho_p, self.rho_m = r["rho_p"][s], r["rho_m"][s]
-        self.m_series, self.var_series = r["m_series"][s], r["var_series"][s]
-        self.v_eff_series, self.D_eff_series = r["v_eff_series"][s], r["D_eff_series"][s]
+        for name in ("rho_p", "rho_m") + SERIES:
+            setattr(self, name, r[name][s])
         self.snapshots = list(r["snapshots"][s]) if r["snapshots"] is not None else []
         self.m_snapshots = list(r["m_snapshots"][s]) if r["m_snapshots"] is not None else []
         self.times = list(r["times"])
@@ -419,46 +420,28 @@ class IMEXPDE:
     def plan(self, n_systems=1, convolution=None):
         """What the wide shape would use for this solver (see `plan`); with workgroups=None, what "auto" would.
         convolution given here overrides the constructor's."""
-        return plan(L=self.L, workgroups=self.workgroups if self.workgroups is not None else "auto", n_systems=n_systems,
-                    xlim=self.xlim, dt=self.dt, nsteps=self.nsteps, gamma=self.gamma, lam=self.lam, bc=self.bc,
-                    active_model=self.active_model, gaussian_kernel=self.gaussian_kernel, kernel_sigma=self.kernel_sigma,
-                    snapshot_interval=self.snapshot_interval, n_tracers=getattr(self, "n_tracers", 0),
-                    fft_modes=self.fft_modes if self.fft_modes is not None else (self.L // 2 + 1 if self.record_fft else 0),
-                    device=self.device, convolution=convolution if convolution is not None else self.convolution)
+        return plan(**self._model(), workgroups=self.workgroups if self.workgroups is not None else "auto", n_systems=n_systems,
+                    n_tracers=getattr(self, "n_tracers", 0), fft_modes=self._modes(),
+                    convolution=convolution if convolution is not None else self.convolution)
 
     def solve_batch(self, betas, want_snapshots=False, workgroups=None, fft_modes=None, convolution=None):
         """The same initial condition evolved for every beta of `betas` in ONE launch (one workgroup per beta, or
         `workgroups` slabs per beta on the wide shape; independent tracer noise per system).  workgroups / fft_modes /
         convolution given here override the constructor's.  Returns the raw dict of arrays with a leading system axis."""
-        if workgroups is not None or fft_modes is not None or convolution is not None:
-            _check_workgroups(workgroups)
-            _check_fft_modes(fft_modes, self.L)
-            keep = self.workgroups, self.fft_modes, self.convolution
-            _check_convolution(convolution, workgroups if workgroups is not None else keep[0])
-            self.workgroups = workgroups if workgroups is not None else keep[0]
-            self.fft_modes = fft_modes if fft_modes is not None else keep[1]
-            self.convolution = convolution if convolution is not None else keep[2]
-            try:
-                return self.solve_batch(betas, want_snapshots=want_snapshots)
-            finally:
-                self.workgroups, self.fft_modes, self.convolution = keep
-        return self._run(betas, self.rho_p, self.rho_m, self.tracers_unwrapped if self.n_tracers else None,
-                         self.tracer_state if self.n_tracers else None, want_snapshots=want_snapshots)
+        _check_workgroups(workgroups)                              # what is given here is checked before the seed is drawn
+        _check_fft_modes(fft_modes, self.L)
+        _check_convolution(convolution, workgroups if workgroups is not None else self.workgroups)
+        return self._run(betas, want_snapshots=want_snapshots, workgroups=workgroups, fft_modes=fft_modes,
+                         convolution=convolution)
 
     def solve_sweep(self, betas=None, kernel_sigmas=None, convolution=None, want_snapshots=False):
         """This instance's initial condition evolved for every (beta, kernel_sigma) pair in ONE launch on the one-workgroup
         shape (`solve_sweep_raw`): betas and kernel_sigmas are broadcast against each other, each defaults to the instance's
         own value.  convolution: None / "direct" or "spectral" (the transform in LDS).  Returns the raw dict of arrays."""
-        seed = self.seed if self.seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
-        fm = self.fft_modes if self.fft_modes is not None else (self.L // 2 + 1 if self.record_fft else 0)
-        return solve_sweep_raw(L=self.L, xlim=self.xlim, dt=self.dt, nsteps=self.nsteps, gamma=self.gamma, lam=self.lam,
+        return solve_sweep_raw(seed=self._seed(), **self._model(sweep=True), **self._start(),
                                betas=self.beta if betas is None else betas,
                                kernel_sigmas=self.kernel_sigma if kernel_sigmas is None else kernel_sigmas,
-                               bc=self.bc, active_model=self.active_model, gaussian_kernel=self.gaussian_kernel,
-                               snapshot_interval=self.snapshot_interval, rho_p0=self.rho_p, rho_m0=self.rho_m,
-                               tracer_x0=self.tracers_unwrapped if self.n_tracers else None,
-                               tracer_s0=self.tracer_state if self.n_tracers else None, n_fft_modes=fm, seed=seed,
-                               device=self.device, want_snapshots=want_snapshots, convolution=convolution)
+                               n_fft_modes=self._modes(), want_snapshots=want_snapshots, convolution=convolution)
 
     def get_output(self):                                          # ref :293-306
         return dict(rho_p=self.rho_p, rho_m=self.rho_m, m_series=self.m_series, var_series=self.var_series,
@@ -493,12 +476,9 @@ def sweep_over_betas(beta_values, n_runs=3, t_min=20.0, t_max=40.0, seeds=None, 
             s.initialize(**init_kwargs)
             proto = proto or s
             betas.append(float(beta)); rp.append(s.rho_p); rm.append(s.rho_m); tx.append(s.tracers_unwrapped); ts.append(s.tracer_state)
-    r = solve_batch_raw(L=proto.L, xlim=proto.xlim, dt=proto.dt, nsteps=proto.nsteps, gamma=proto.gamma, lam=proto.lam, betas=betas,
-                        bc=proto.bc, active_model=proto.active_model, gaussian_kernel=proto.gaussian_kernel,
-                        kernel_sigma=proto.kernel_sigma, snapshot_interval=proto.snapshot_interval, rho_p0=np.array(rp),
-                        rho_m0=np.array(rm), tracer_x0=np.array(tx), tracer_s0=np.array(ts), seed=proto.seed or 0,
-                        device=proto.device, want_snapshots=False, workgroups=workgroups, fft_modes=fft_modes,
-                        convolution=convolution)
+    r = solve_batch_raw(**proto._model(), betas=betas, rho_p0=np.array(rp), rho_m0=np.array(rm), tracer_x0=np.array(tx),
+                        tracer_s0=np.array(ts), seed=proto.seed or 0, want_snapshots=False, workgroups=workgroups,
+                        fft_modes=fft_modes, convolution=convolution)
     t = np.linspace(0, proto.T, proto.nsteps + 1)
     mask = (t >= t_min) & (t <= t_max)
     v = np.abs(np.nanmean(r["v_eff_series"][:, mask], axis=1)).reshape(len(beta_values), n_runs)
@@ -532,15 +512,13 @@ def sweep_over_kernel_sigmas(kernel_sigma_values, n_runs=5, base_seed=100, init_
                 proto = s
             sig.append(float(sigma)); rp.append(s.rho_p); rm.append(s.rho_m); tx.append(s.tracers_unwrapped); ts.append(s.tracer_state)
     ntr = proto.n_tracers
-    r = solve_sweep_raw(L=proto.L, xlim=proto.xlim, dt=proto.dt, nsteps=proto.nsteps, gamma=proto.gamma, lam=proto.lam,
-                        betas=proto.beta, kernel_sigmas=sig, bc=proto.bc, active_model=proto.active_model,
-                        gaussian_kernel=proto.gaussian_kernel, snapshot_interval=proto.snapshot_interval, rho_p0=np.array(rp),
-                        rho_m0=np.array(rm), tracer_x0=np.array(tx) if ntr else None, tracer_s0=np.array(ts) if ntr else None,
-                        seed=proto.seed or 0, device=proto.device, want_snapshots=False, convolution=convolution)
+    r = solve_sweep_raw(**proto._model(sweep=True), betas=proto.beta, kernel_sigmas=sig, rho_p0=np.array(rp), rho_m0=np.array(rm),
+                        tracer_x0=np.array(tx) if ntr else None, tracer_s0=np.array(ts) if ntr else None, seed=proto.seed or 0,
+                        want_snapshots=False, convolution=convolution)
     out = {}
     for k, sigma in enumerate(kernel_sigma_values):
         rows = slice(k * n_runs, (k + 1) * n_runs)
-        out[sigma] = dict(m_series=np.abs(r["m_series"][rows]), v_eff_series=np.abs(r["v_eff_series"][rows]),
-                          D_eff_series=r["D_eff_series"][rows], var_series=r["var_series"][rows])
+        m, var, v, D = (r[name][rows] for name in SERIES)
+        out[sigma] = dict(m_series=np.abs(m), v_eff_series=np.abs(v), D_eff_series=D, var_series=var)
     out["kernel_ms"] = r["kernel_ms"]
     return out

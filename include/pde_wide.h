@@ -46,7 +46,8 @@ const char *pdew_last_error(void);
 int pdew_plan(const pde_params *p, int32_t n_systems, int32_t workgroups, pdew_plan_info *out);
 
 /* pde_solve_batch on the wide shape.  The buffer arguments are those of pde_solve_batch, in the same order, with the same
- * meaning.  workgroups = G per system (0: the library chooses); 1 <= G <= PDEW_MAX_WORKGROUPS, floor(L / G) >= PDEW_MIN_SLAB,
+ * meaning, with one difference: with n_tracers == 0, v_eff_series and D_eff_series are left as the caller passed them
+ * (pde_solve_batch and pdek_solve overwrite them with unspecified values).  workgroups = G per system (0: the library chooses); 1 <= G <= PDEW_MAX_WORKGROUPS, floor(L / G) >= PDEW_MIN_SLAB,
  * G * n_systems <= PDEW_MAX_GRID, n_systems <= 65535.
  * p->convolution (used with kernel_mode 1 only): 0 = direct circular convolution, 1 = spectral (include/pde_spectral.h); a shape
  * the spectral path cannot take fails with PDE_ERR_ARG and a text that says why -- there is no fall-back to the direct sum. */
