@@ -1191,6 +1191,11 @@ __global__ __launch_bounds__(256) void observe_scalars(const ScalarArgs a) {
 #include "tile_step.hpp"
 #include "tile_dense.hpp"
 #include "tile_loop.hpp"
+#ifdef APS_LOOP_STAMPS
+constexpr int64_t STAMP_WORDS = TL_STAMP_WORDS + TL_TRACE_WORDS;   // words of the stamps buffer: the loop's diagnostic build keeps the trace of its waits there too
+#else
+constexpr int64_t STAMP_WORDS = 8 * 4096;
+#endif
 #include "ntt_conv.hpp"
 
 // fp32 mode: the field as the tile kernel keeps it (int32, units of 2^-q) <-> the binary64 view of the other kernels; exact both ways
@@ -2933,7 +2938,7 @@ int aps_create(const aps_params *p, aps_handle **out) {
     if ((rc = dev_alloc(h, &h->d_src, EN)) || (rc = dev_alloc(h, &h->d_orig, EN)) || (rc = dev_alloc(h, &h->d_prop_own, EN)) ||
         (rc = dev_alloc(h, &h->d_sp8, EN)) ||
         (rc = dev_alloc(h, &h->d_tinfo, (size_t)h->E * h->ntiles)) ||
-        (rc = dev_alloc(h, &h->d_stamps, (size_t)8 * 4096)) ||
+        (rc = dev_alloc(h, &h->d_stamps, (size_t)STAMP_WORDS)) ||
         (rc = dev_alloc(h, &h->d_plan, (size_t)h->E * h->ntiles * PLAN_CAP)) || (rc = dev_alloc(h, &h->d_plan_n, (size_t)h->E * h->ntiles)) ||
         (rc = dev_alloc(h, &h->d_accW, EN * MAX_SPLIT)) || (rc = dev_alloc(h, &h->d_accS, EN * MAX_SPLIT)) ||
         (rc = dev_alloc(h, &h->d_occ, EN * MAX_SPLIT)) || (rc = dev_alloc(h, &h->d_pcnt, 2 * EL)) ||
@@ -3965,10 +3970,11 @@ int aps_bind_exchange_buffer(aps_handle *h, void *dev_ptr, int64_t nbytes) {
 }
 
 // diagnostic builds only (-DAPS_STAMPS): per-workgroup phase cycle totals of the last pair_propose launch
+// (-DAPS_LOOP_STAMPS: of the resident loop's last call, followed by the trace of its waits)
 int aps_debug_stamps(aps_handle *h, unsigned long long *out, int64_t nwords) {
     if (!h || !out) return APS_ERR_ARG;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(out, h->d_stamps, (size_t)std::min<int64_t>(nwords, 8 * 4096) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(out, h->d_stamps, (size_t)std::min<int64_t>(nwords, STAMP_WORDS) * 8, hipMemcpyDeviceToHost));
     return APS_OK;
 }
 

@@ -34,6 +34,11 @@ __host__ __device__ constexpr int tl_ng(int nw) { return 8 / nw; }
 // 4 096 waves polling; re-reading as fast as the answers come back slows the very stores the polls wait for (a second, staggered poll
 // in flight costs 0.4 us per step), and 16 is where the step is shortest (1, 4, 8, 16, 32 measured: DESIGN 7)
 constexpr int TL_REPOLL_SLEEP = 16;
+#ifndef TL_REPOLL_SLEEP_NARROW
+#define TL_REPOLL_SLEEP_NARROW 1           /* the same for the four-wave instances (tuning builds may ask for more: 16 measured at config 2) */
+#endif
+// diagnostic builds (APS_LOOP_STAMPS): the stamps buffer holds the phase totals ([tile][wave][16]) and behind them the trace of the wait
+constexpr int TL_STAMP_WORDS = 8 * 4096, TL_TRACE_TILES = 64, TL_TRACE_STRIDE = 8, TL_TRACE_ITERS = 256, TL_TRACE_WORDS = TL_TRACE_TILES * 8 * TL_TRACE_ITERS;
 constexpr int TL_ABORT = 31;               // misc word: this workgroup leaves (a wait ran out, here or elsewhere)
 
 struct LoopArgs {
@@ -156,6 +161,23 @@ __device__ __forceinline__ void tl_one_direct(const uint32_t entry, const int x0
         if (aw != 0) tl_lds_add(&fieldW[r * 64 + lane], aw);
         if (as != 0) tl_lds_add(&fieldS[r * 64 + lane], as);
     }
+}
+
+// The model record, read behind barrier B in every iteration, where the proposals' chain starts with it.  Through a plain pointer the compiler
+// cannot know that no store of the kernel touches the record and reads it with vector loads, in two dependent rounds (the first words are
+// made uniform before the rest is asked for).  The record is written by the host before the launch and by nobody during it, which is what the
+// constant address space says: there a uniform address is read with scalar loads, all in flight at once, into SGPRs.  Four waves: as before.
+template <bool SCALAR> __device__ __forceinline__ Model tl_load_model(const Model *p) {
+    if constexpr (SCALAR) {
+        typedef __attribute__((address_space(4))) const uint32_t tl_cu32;
+        constexpr int NWORD = (int)(sizeof(Model) / sizeof(uint32_t));
+        static_assert(sizeof(Model) % sizeof(uint32_t) == 0, "Model is read word by word");
+        union { Model m; uint32_t w[NWORD]; } u;
+        const tl_cu32 *src = (const tl_cu32 *)p;
+#pragma unroll
+        for (int i = 0; i < NWORD; ++i) u.w[i] = src[i];
+        return u.m;
+    } else return *p;
 }
 
 // Eight waves: the thread number as a value the compiler cannot follow from one iteration to the next.  Everything a lane derives from
@@ -334,8 +356,16 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
 #define APS_LOOP_STAMP_MASK 0xFFF
 #endif
 #define TLSTAMP(k) if constexpr (((APS_LOOP_STAMP_MASK) >> (k)) & 1) { const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t1_ - st_t0; st_t0 = t1_; }
+    // Bit 12: the trace of the records' wait, one word per wave and iteration of the call's first TL_TRACE_ITERS iterations, for every
+    // TL_TRACE_STRIDE-th tile, behind the phase totals in the stamps buffer ([slot][wave][iteration]): bit 0 the look asked ahead found
+    // everything, bits 1-15 the polls issued after it until the wait ended, bits 16-31 the round trip of the first of them (issue to data
+    // in registers), bits 32-63 the cycles from this wave's exit of barrier E to the end of its wait.
+#define TLTRACE(...) if constexpr (((APS_LOOP_STAMP_MASK) >> 12) & 1) { __VA_ARGS__ }
+    uint32_t lt_e = 0, lt_rt = 0, lt_polls = 0;
+    auto lt_clock = []() -> uint32_t { return (uint32_t)__builtin_amdgcn_s_memtime(); };
 #else
 #define TLSTAMP(k)
+#define TLTRACE(...)
 #endif
     // what this wave asked for at the end of the previous iteration (in flight across barrier F and the random numbers):
     // page 0 of its buckets of the first TL_NG groups, and (last wave) the neighbours' boundary cells
@@ -375,7 +405,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
         TLSTAMP(2)
         // ------------------------------------------------------------ B  bounded waits: re-read until the granule carries this step's tag
         auto spin_check = [&](unsigned &spins, unsigned long long &t_w) -> bool {     // true: give up
-            __builtin_amdgcn_s_sleep(PUBLISH_FIRST ? TL_REPOLL_SLEEP : 1);
+            __builtin_amdgcn_s_sleep(PUBLISH_FIRST ? TL_REPOLL_SLEEP : TL_REPOLL_SLEEP_NARROW);
             if ((++spins & 63u) != 0u) return false;
             const bool other = __hip_atomic_load((tl_gu32 *)la.abort_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
             const unsigned long long now = __builtin_amdgcn_s_memrealtime();
@@ -399,8 +429,13 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
         };
         if (!first) {                                          // everything asked for ahead: one round trip when the neighbours are done
             unsigned long long t_w = 0;
+            TLTRACE(                                           // a round of the loop below issues loads unless it is the first and nothing is missing
+                bool stale = h_act && (uint32_t)(xh >> 32) != tag_in;
+                for (int g = 0; g < TL_NG; ++g) { bool ok; bucket_of(g, sub, ok); stale |= ok && (uint32_t)(xg[g] >> 32) != tag_in; }
+                lt_polls = __ballot(stale) ? 0u : ~0u; lt_rt = 0;)
             for (unsigned spins = 0;;) {
                 bool bad = false;
+                TLTRACE(if (lt_polls == 0) { lt_rt = 0u - lt_clock(); asm volatile("" ::: "memory"); })
 #pragma unroll
                 for (int g = 0; g < TL_NG; ++g) {
                     bool ok;
@@ -414,9 +449,16 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
                     xh = tl_load_granule(rec_in + (size_t)h_nb * la.rec + la.drec + (h_side ? 0 : 3 * K) + h_i);
                     bad |= (uint32_t)(xh >> 32) != tag_in;
                 }
+                TLTRACE(if (lt_polls == 0) { asm volatile("" :: "s"(__ballot(bad)) : "memory"); lt_rt += lt_clock(); }   // (the ballot needs the data)
+                        ++lt_polls;)
                 if (!__ballot(bad)) break;
                 if (spin_check(spins, t_w)) break;
             }
+            TLTRACE(
+                const uint32_t off = lt_clock() - lt_e;
+                if (lane == 0 && tile % TL_TRACE_STRIDE == 0 && tile / TL_TRACE_STRIDE < TL_TRACE_TILES && it < TL_TRACE_ITERS && e == 0)
+                    a.rare->stamps[TL_STAMP_WORDS + ((size_t)(tile / TL_TRACE_STRIDE) * NW + wave) * TL_TRACE_ITERS + it] =
+                        (lt_polls ? 0ull : 1ull) | ((unsigned long long)min(lt_polls, 0x7FFFu) << 1) | ((unsigned long long)min(lt_rt, 0xFFFFu) << 16) | ((unsigned long long)off << 32);)
             // the neighbours' boundary cells: frame positions -1, 0, 1 and own_n + 2 .. own_n + 4 -- occupancy, and the
             // particles of the four halo sites join the list
             if (wave == NW - 1 && !gave_up) {
@@ -630,7 +672,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
         TLSTAMP(7)
         // ------------------------------------------------------------ 2  proposals, a lane per particle
         {
-            const Model M = *a.model;                          // uniform address: scalar loads, only now
+            const Model M = tl_load_model<WIDE>(a.model);      // uniform address, only now (eight waves: scalar loads)
             const int n_part = n0 + misc[4 + (it & 1)];
             auto propose_one = [&](const uint2 pc, const uint32_t (&x)[4]) {
                 const int pos = (int)(pc.x & 0xFFFFu), k = (int)(pc.x >> 16);
@@ -777,6 +819,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : TL_MIN_WAVES) void tile_loop
         }
         __syncthreads();                                       // E: nobody reads this step's cells, proposals, occupancy and list any more
         TLSTAMP(4)
+        TLTRACE(lt_e = lt_clock();)
         // ------------------------------------------------------------ 5  hand over: new cells, this tile's record (or the plain arrays),
         //                                                                 next iteration's list and occupancy of the owned sites
         const int count = min(*dcount, a.dcap);
