@@ -1,5 +1,5 @@
-// gillespie_big_hip.hip -- gil_run_large of include/gillespie.h, gilm_run of include/gillespie_many.h and the large shape of
-// gils_run, gilc_run, gilp_run and gilrm_run: the reference's
+// gillespie_big_hip.hip -- gil_run_large of include/gillespie.h, gilm_run of include/gillespie_many.h, gilxm_run of
+// include/gillespie_mixed_many.h and the large shape of gils_run, gilc_run, gilp_run and gilrm_run: the reference's
 // exact event loop (PARTICLE_solver_CLASS.py:511-538) for systems far too large for a workgroup's LDS (the BASELINE size:
 // N = 1e5 particles on L = 2e5 sites, where the reference manages 0.8 events/s because it recomputes the whole
 // field and all N rates before every event).  One kernel and one host driver serve both entry points: a batch is a grid
@@ -29,12 +29,14 @@
 
 #include "gillespie.h"
 #include "gillespie_many.h"
+#include "gillespie_mixed_many.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiation only)
 #include "gillespie_capture.hpp"          // anchor capture and cluster statistics (capture instantiation only)
 #include "gillespie_profile.hpp"          // ensemble density and field profiles (profile instantiation only)
 #include "gillespie_resume.hpp"           // start and end state of a launch (resumable instantiation only)
+#include "gillespie_mixed.hpp"            // a variant per system: table, blocking table, Philox key (mixed instantiation only)
 
 namespace {
 
@@ -42,7 +44,7 @@ constexpr int BT = 1024, BW = BT / 64;      // threads, waves of the workgroup
 constexpr int PB = 256;                     // particles per rate block
 constexpr int MAX_NB = 4096;                // rate blocks (N <= 2^20)
 constexpr int TAB_LDS_MAX = 10000;          // table entries kept in LDS
-std::string g_big_err, g_many_err;
+std::string g_big_err, g_many_err, g_gilxm_err;
 enum { F_PLUS = 1, F_BOUND = 2, F_ALIVE = 4 };
 enum { GS_N = 0, GS_SPIN, GS_POS, GS_WALL, GS_MAXPOS, GS_FRONT, GS_ATTEMPT, GS_BLOCKED, GS_DISP, GS_DISP2, GS_NDISP, GS_EVENTS };
 
@@ -89,12 +91,8 @@ __device__ inline void select_system(BigArgs &a, size_t sys) {
     if (a.n_exits) a.n_exits += sys;
 }
 
-// W, S from scratch on all sites (one-time): a thread per site over all particles; the system in grid.y
-__global__ __launch_bounds__(256) void big_field_init(const BigArgs a0) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= a0.m.L) return;
-    BigArgs a = a0;
-    select_system(a, (size_t)blockIdx.y);
+// W, S of site x from scratch: over all particles of the start state of the system `a` is narrowed to
+__device__ inline void field_init_site(const BigArgs &a, int x) {
     double w = 0.0, s = 0.0;
     if (a.m.field_mode)
         for (int j = 0; j < a.n_init; ++j) {
@@ -102,6 +100,15 @@ __global__ __launch_bounds__(256) void big_field_init(const BigArgs a0) {
             w += g; s += a.sigma0[j] > 0 ? g : -g;
         }
     a.W[x] = w; a.S[x] = s;
+}
+
+// W, S from scratch on all sites (one-time): a thread per site over all particles; the system in grid.y
+__global__ __launch_bounds__(256) void big_field_init(const BigArgs a0) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= a0.m.L) return;
+    BigArgs a = a0;
+    select_system(a, (size_t)blockIdx.y);
+    field_init_site(a, x);
 }
 
 // The same from a checkpoint (resumable launch): pos0 holds every slot's site, sigma0 its spin or 0 for a slot that is not alive
@@ -222,14 +229,27 @@ struct GilsBigArgs : BigArgs { GilsArgs st; };              // arguments of the 
 struct GilcBigArgs : GilsBigArgs { GilcArgs cp; };          // arguments of the capture instantiation
 struct GilpBigArgs : GilcBigArgs { GilpArgs pf; };          // arguments of the profile instantiation (the driver's one struct)
 struct GilrBigArgs : BigArgs { GilrArgs rs; };              // arguments of the resumable instantiation
+struct GilxBigArgs : BigArgs { GilxArgs mx; int tab_region; };   // arguments of the mixed instantiation; tab_region: doubles of LDS
+                                                                 //   for the table, the longest of the launch that is kept there
 
-// the argument struct of each variant of the large-system kernel (it takes no mixed batches)
+// The same for a mixed launch: table, length and field mode are the system's own
+__global__ __launch_bounds__(256) void big_field_init_mixed(const GilxBigArgs a0) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= a0.m.L) return;
+    BigArgs a = a0;
+    select_system(a, (size_t)blockIdx.y);
+    gilxm_select(a, a0.mx, (int)blockIdx.y, TAB_LDS_MAX);
+    field_init_site(a, x);
+}
+
+// the argument struct of each variant of the large-system kernel
 template <GilKind V> struct BigKernelArgs;
 template <> struct BigKernelArgs<GilKind::Plain> { using type = BigArgs; };
 template <> struct BigKernelArgs<GilKind::Structure> { using type = GilsBigArgs; };
 template <> struct BigKernelArgs<GilKind::Capture> { using type = GilcBigArgs; };
 template <> struct BigKernelArgs<GilKind::Profile> { using type = GilpBigArgs; };
 template <> struct BigKernelArgs<GilKind::Resume> { using type = GilrBigArgs; };
+template <> struct BigKernelArgs<GilKind::Mixed> { using type = GilxBigArgs; };
 
 // V = the variant, a compile-time property, so that each kernel is the code it was before the others existed:
 //   Structure  also reduce the structure sums at an observation (gillespie_structure.hpp);
@@ -240,16 +260,27 @@ template <> struct BigKernelArgs<GilKind::Resume> { using type = GilrBigArgs; };
 //   Resume     a resumable launch (gillespie_resume.hpp): the start state is a checkpoint (pos0 / sigma0 as big_field_init_live
 //              reads them, n0 = n_cap: any slot may be alive; flags, origins, clock, event count and first row from a0.rs).  The
 //              end state is the global scratch itself (pos, flg, ref), which the driver reads back.
+//   Mixed      a mixed batch (gillespie_mixed.hpp, include/gillespie_mixed_many.h): the workgroup takes system order[blockIdx.x],
+//              and the weight table, its length, whether it lies in LDS, the field mode, the blocking table and the Philox key and
+//              stream are that system's own, all uniform over the workgroup.  Outputs are indexed by the system.
 template <GilKind V>
 __global__ __launch_bounds__(BT) void gil_big_kernel(const typename BigKernelArgs<V>::type a0) {
     constexpr bool ST = V == GilKind::Structure, CP = V == GilKind::Capture, PF = V == GilKind::Profile, RS = V == GilKind::Resume;
+    constexpr bool MX = V == GilKind::Mixed;
     extern __shared__ double lds[];
     BigArgs a = a0;
-    select_system(a, (size_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x));
+    uint32_t stream = 0u;                                      // Philox counter word 2: the system's own with MX
+    if constexpr (MX) {
+        const int sys = __builtin_amdgcn_readfirstlane(a0.mx.order[blockIdx.x]);
+        select_system(a, (size_t)sys);
+        stream = gilxm_select(a, a0.mx, sys, TAB_LDS_MAX);
+    } else select_system(a, (size_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x));
     const Model &M = a.m;
     const int L = M.L, K = M.K, t = threadIdx.x, lane = t & 63, wave = t >> 6, nobs = a.p.n_obs, N = a.p.n_cap;
     double *tabl = lds;                                        // [tlen + 1] when it fits
-    double *xw = tabl + (a.tab_in_lds ? ((a.tlen + 2) & ~1) : 0);   // [32] cross-wave scratch
+    int tab_region = a.tab_in_lds ? ((a.tlen + 2) & ~1) : 0;   // with MX the launch's: the longest table kept in LDS
+    if constexpr (MX) tab_region = a0.tab_region;
+    double *xw = tabl + tab_region;                            // [32] cross-wave scratch
     double *draws = xw + 32;                                   // [BT][4]
     double *dsel = draws + 4 * BT;                             // [4] cumulative rate before the chosen block etc.
     long long *acc = reinterpret_cast<long long *>(dsel + 4);  // [GIL_NSCALARS] the scalar sums of an observation
@@ -450,8 +481,8 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const typename BigKernelArg
                 u0 = in ? src[0] : 0.0; u1 = in ? src[1] : 0.0; u2 = in ? src[2] : 0.0; u3 = in ? src[3] : 0.0;
             } else {
                 uint32_t x[4], y[4];
-                philox4x32_10((uint32_t)evn, (uint32_t)(evn >> 32), 0u, 0x47494C31u, M.seed_lo, M.seed_hi, x);
-                philox4x32_10((uint32_t)evn, (uint32_t)(evn >> 32), 0u, 0x47494C32u, M.seed_lo, M.seed_hi, y);
+                philox4x32_10((uint32_t)evn, (uint32_t)(evn >> 32), stream, 0x47494C31u, M.seed_lo, M.seed_hi, x);
+                philox4x32_10((uint32_t)evn, (uint32_t)(evn >> 32), stream, 0x47494C32u, M.seed_lo, M.seed_hi, y);
                 u0 = ((double)(x[0] >> 5) * 67108864.0 + (double)(x[1] >> 6)) * 0x1.0p-53;
                 u1 = ((double)(x[2] >> 5) * 67108864.0 + (double)(x[3] >> 6)) * 0x1.0p-53;
                 u2 = ((double)(y[0] >> 5) * 67108864.0 + (double)(y[1] >> 6)) * 0x1.0p-53;
@@ -663,6 +694,41 @@ int big_plan(const char *who, std::string &err, const gil_params *p, bool want_s
     return GIL_OK;
 }
 
+// The checks gilxm_plan and gilxm_run share, the variant tables and the plan of a mixed launch of large systems, by host
+// arithmetic alone: 0 with `info` and `tb` filled, or GIL_ERR_ARG with the text in `err`.  The limits are big_plan's, here with
+// the offending number; the variant checks and the tables are gilx_decide's (gillespie_mixed.hpp).
+int gilxm_decide(const char *who, std::string &err, const gil_params *p, const gilx_variants *v, bool want_states, bool want_scalars,
+                 gilxm_plan_info &info, GilxTables &tb) {
+    auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    auto num = [](int64_t x) { return std::to_string(x); };
+    if (p->L < 2 || p->L > (1 << 25)) return bad("L = " + num(p->L) + " is outside [2, 2^25 = " + num(1 << 25) + "]");
+    if (p->K < 1 || p->K > 32) return bad("site capacity K = " + num(p->K) + " is outside [1, 32]");
+    if ((int64_t)p->L * p->K > (1ll << 27)) return bad("L * K = " + num((int64_t)p->L * p->K) + " exceeds 2^27 = " + num(1ll << 27) + " (site map)");
+    if (p->n_systems < 1 || p->n_systems > GILM_MAX_SYSTEMS) return bad("n_systems = " + num(p->n_systems) + " is outside [1, GILM_MAX_SYSTEMS = " + num(GILM_MAX_SYSTEMS) + "]");
+    if (p->n_cap < 1 || p->n_cap > MAX_NB * PB) return bad("n_cap = " + num(p->n_cap) + " is outside [1, 2^20 = " + num(MAX_NB * PB) + "]");
+    if (p->n_obs < 1) return bad("n_obs = " + num(p->n_obs) + " must be at least 1");
+    if (p->max_events < 0) return bad("max_events = " + num(p->max_events) + " must not be negative");
+    { const std::string why = gilx_check_variants(p, v); if (!why.empty()) return bad(why); }
+    gilx_build_tables(p, v, tb);
+    const int64_t S = p->n_systems, L = p->L, N = p->n_cap, O = p->n_obs, nblk = (N + PB - 1) / PB;
+    info = gilxm_plan_info{};
+    info.n_systems = p->n_systems; info.n_blocks = (int32_t)nblk; info.max_tlen = tb.max_tlen; info.max_tlen_lds = -1;
+    for (const GilxVariant &gv : tb.var) {
+        if (gv.tlen + 1 <= TAB_LDS_MAX) info.max_tlen_lds = std::max(info.max_tlen_lds, gv.tlen);
+        else info.n_global += 1;
+    }
+    const int64_t region = info.max_tlen_lds >= 0 ? ((info.max_tlen_lds + 2) & ~1) : 0;
+    const int64_t lds = (region + 32 + 4 * BT + 4 + GIL_NSCALARS) * 8 + (2 * nblk + 32) * 4;     // big_plan's, for that table
+    info.lds_bytes = (int32_t)lds;
+    info.table_doubles = (int64_t)tb.table.size();
+    info.work_bytes_per_system = N * (4 + 4 + 4 + 1 + 8) + L * (4 + 4 + 8 + 8) + L * p->K * 4 + nblk * 8;
+    info.output_bytes = S * ((want_states ? O * N * 6 : 0) + (want_scalars ? O * GIL_NSCALARS * 8 : 0) + N * 24 + 24);
+    if (lds > 160 * 1024)
+        return bad("the launch needs " + num(lds) + " bytes of LDS per system (n_cap = " + num(N) + ", longest table kept in LDS " +
+                   num(info.max_tlen_lds) + "), more than the " + num(160 * 1024) + " bytes (160 KB) of a workgroup");
+    return gil_refuse_plan_bytes(who, err, S * info.work_bytes_per_system, info.output_bytes);
+}
+
 // The large-system kernel of variant V: the one place that names the instantiation.  Raises its LDS limit and launches it; the
 // timed window holds this launch alone.
 template <GilKind V>
@@ -684,7 +750,14 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilm_plan_info info{};
     std::vector<double> table;
-    if (int rc = big_plan(who, err, p, io.states(), io.scalars_obs != nullptr, &info, &table)) return rc;
+    const gilx_variants *mx = ex.mx;                          // a mixed launch (gilxm_run): a variant per system, no other extra
+    gilxm_plan_info xinfo{}; GilxTables tb;
+    if (mx) {
+        if (int rc = gilxm_decide(who, err, p, mx, io.states(), io.scalars_obs != nullptr, xinfo, tb)) return rc;
+        info.n_systems = xinfo.n_systems; info.n_blocks = xinfo.n_blocks; info.table_len = xinfo.max_tlen; info.lds_bytes = xinfo.lds_bytes;
+        info.work_bytes_per_system = xinfo.work_bytes_per_system; info.output_bytes = xinfo.output_bytes;
+        table = std::move(tb.table);
+    } else if (int rc = big_plan(who, err, p, io.states(), io.scalars_obs != nullptr, &info, &table)) return rc;
     const int S = p->n_systems, L = p->L, N = p->n_cap;
     const GilcCall *cap = ex.cap; const GilpCall *prof = ex.prof; GilrCall *rs = ex.rs;
     if (ex.structure_obs) {                                   // rows of structure sums (gils_run)
@@ -710,8 +783,20 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
         spin_all.resize(rs->flg.size());
         for (size_t q = 0; q < spin_all.size(); ++q) spin_all[q] = (rs->flg[q] & GILR_ALIVE) ? ((rs->flg[q] & GILR_PLUS) ? 1 : -1) : 0;
         in.n0 = n0_all.data(); in.pos0 = rs->pos.data(); in.sigma0 = spin_all.data(); in.bound0 = nullptr;
-    } else { const std::string why = gil_check_start(p, io, "bad n_cap / n0 / n_obs / max_events"); if (!why.empty()) return bad(why); }
+    } else { const std::string why = gil_check_start(p, io, mx ? nullptr : "bad n_cap / n0 / n_obs / max_events"); if (!why.empty()) return bad(why); }
     if (const char *why = gil_check_flip_table(p)) return bad(why);
+    // a mixed launch: the system of every workgroup (default: falling n0, ties by index -- the long systems start first when more
+    // are queued than fit), and every system's Philox key (default: p->seed + s in 64 bits, gilm_run's) and stream (default: 0)
+    std::vector<int32_t> order, stream;
+    std::vector<uint64_t> seed;
+    if (mx) {
+        order.resize((size_t)S); stream.resize((size_t)S); seed.resize((size_t)S);
+        for (int s = 0; s < S; ++s) {
+            order[(size_t)s] = mx->order ? mx->order[s] : s; stream[(size_t)s] = mx->stream ? mx->stream[s] : 0;
+            seed[(size_t)s] = mx->seed ? mx->seed[s] : p->seed + (uint64_t)s;
+        }
+        if (!mx->order) std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return io.n0[x] > io.n0[y]; });
+    }
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: the scratch arrays start from zero
     if (int rc = job.select_device(p->device)) return rc;
     const int64_t work_bytes = (int64_t)S * info.work_bytes_per_system + (ex.structure_obs ? (int64_t)L * 16 : 0) +
@@ -721,9 +806,10 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
     a.p = *p; a.tlen = info.table_len; a.nblk = info.n_blocks; a.cb = (a.nblk + BT - 1) / BT;
     a.tab_in_lds = info.table_in_lds;
     a.m = gil_model(p);
-    const size_t SN = (size_t)S * N, SL = (size_t)S * L;
-    if (int rc = gil_stage_common(job, a, p, in, table, S == 1 && !rs ? (size_t)in.n0[0] : SN, io.scalars_obs != nullptr, p->block_table,
-                                  (size_t)(p->K + 1) * (p->K + 1))) return rc;
+    if (mx) { a.p.sigma_grid = 0.0; a.p.block_table = nullptr; }   // ignored: the kernel takes every system's own
+    const size_t SN = (size_t)S * N, SL = (size_t)S * L, KK = (size_t)(p->K + 1) * (p->K + 1);
+    if (int rc = gil_stage_common(job, a, p, in, table, S == 1 && !rs ? (size_t)in.n0[0] : SN, io.scalars_obs != nullptr,
+                                  mx ? mx->block_table : p->block_table, mx ? (size_t)mx->n_variants * KK : KK)) return rc;
     WORK(pos, SN); WORK(occ, SL); WORK(occp, SL); WORK(slot, SL * p->K); WORK(work, SN); WORK(ref, SN);
     WORK(flg, SN); WORK(rate, SN); WORK(bsum, (size_t)S * a.nblk); WORK(W, SL); WORK(S, SL);
     const size_t lds = (size_t)info.lds_bytes;
@@ -735,12 +821,25 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
     if (rc) return rc;
     if ((rc = job.create_events())) return rc;
     static_cast<BigArgs &>(b) = a;
+    GilxBigArgs c{};                                            // the mixed launch's arguments: a's own and the variants
+    static_cast<BigArgs &>(c) = a;
+    if (mx) {
+        c.tab_region = xinfo.max_tlen_lds >= 0 ? ((xinfo.max_tlen_lds + 2) & ~1) : 0;
+        c.mx.has_block = mx->block_table ? 1 : 0;
+        if ((rc = job.upload(&c.mx.order, order.data(), (size_t)S, "order"))) return rc;
+        if ((rc = job.upload(&c.mx.variant_of_system, mx->variant_of_system, (size_t)S, "variant_of_system"))) return rc;
+        if ((rc = job.upload(&c.mx.variants, tb.var.data(), tb.var.size(), "variants"))) return rc;
+        if ((rc = job.upload(&c.mx.seed, seed.data(), (size_t)S, "seed"))) return rc;
+        if ((rc = job.upload(&c.mx.stream, stream.data(), (size_t)S, "stream"))) return rc;
+    }
     const dim3 field_grid((unsigned)((L + 255) / 256), (unsigned)S);   // W, S of the start state: before the timed window
     if (rs) hipLaunchKernelGGL(big_field_init_live, field_grid, dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
+    else if (mx) hipLaunchKernelGGL(big_field_init_mixed, field_grid, dim3(256), 0, nullptr, c);
     else hipLaunchKernelGGL(big_field_init, field_grid, dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
     rc = ex.structure_obs ? big_launch<GilKind::Structure>(job, S, lds, a)
          : cap            ? big_launch<GilKind::Capture>(job, S, lds, a)
          : prof           ? big_launch<GilKind::Profile>(job, S, lds, a)
+         : mx             ? big_launch<GilKind::Mixed>(job, S, lds, c)
          : rs             ? big_launch<GilKind::Resume>(job, S, lds, b) : big_launch<GilKind::Plain>(job, S, lds, a);
     if (rc) return rc;
     if ((rc = job.finish(hipGetLastError(), "gil_big_kernel", io.kernel_ms))) return rc;
@@ -777,6 +876,26 @@ int gil_run_large(const gil_params *p, int32_t n0, const int32_t *pos0, const in
 const char *gil_large_last_error(void) { return g_big_err.c_str(); }
 
 const char *gilm_last_error(void) { return g_many_err.c_str(); }
+
+const char *gilxm_last_error(void) { return g_gilxm_err.c_str(); }
+
+int gilxm_plan(const gil_params *p, const gilx_variants *v, int32_t want_states, gilxm_plan_info *out) {
+    if (!p || !v || !out) { g_gilxm_err = "gilxm_plan: null argument"; return GIL_ERR_ARG; }
+    gilxm_plan_info info; GilxTables tb;
+    if (int rc = gilxm_decide("gilxm_plan", g_gilxm_err, p, v, want_states != 0, true, info, tb)) return rc;
+    *out = info;
+    return GIL_OK;
+}
+
+int gilxm_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
+              const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+              int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms) {
+    if (!p || !v || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !v->variant_of_system) { g_gilxm_err = "gilxm_run: null argument"; return GIL_ERR_ARG; }
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    GilExtras ex;
+    ex.mx = v;
+    return gil_large_run("gilxm_run", g_gilxm_err, p, io, ex);
+}
 
 int gilm_plan(const gil_params *p, int32_t want_states, int32_t want_scalars, gilm_plan_info *out) {
     auto bad = [&](const char *m) { g_many_err = std::string("gilm_plan: ") + m; return GIL_ERR_ARG; };

@@ -19,6 +19,8 @@
 #include "gillespie_profile.hpp"          // GilpCall, GilpArgs
 #include "gillespie_resume.hpp"           // GilrCall, GilrArgs
 
+struct gilx_variants;                      // include/gillespie_mixed.h
+
 // what gilxs_run adds to gilx_run: the structure sums (rows optional) and their window reduction
 struct GilxsCall { int k_max, first_obs; double *structure_obs, *head_obs, *window; int32_t *n_window, *n_empty; };
 
@@ -32,10 +34,12 @@ struct GilIo {
 };
 
 // What one entry point adds, at most one of: gils_run's rows (k_max modes, from observation first_obs on), gilc_run's call,
-// gilp_run's, the start state of gilr_run / gilrm_run (checked by gilr_prepare; it comes back as the end state), gilxs_run's call.
+// gilp_run's, the start state of gilr_run / gilrm_run (checked by gilr_prepare; it comes back as the end state), gilxs_run's call,
+// gilxm_run's variants (the large shape's mixed launch).
 struct GilExtras {
     int k_max = 0, first_obs = 0; double *structure_obs = nullptr;
     const GilcCall *cap = nullptr; const GilpCall *prof = nullptr; GilrCall *rs = nullptr; const GilxsCall *xs = nullptr;
+    const gilx_variants *mx = nullptr;
 };
 
 // One enumerator per kernel variant that exists; a kernel family maps each of its own to an argument struct (GilKernelArgs in

@@ -761,9 +761,6 @@ int gilp_decide(const char *who, const gil_params *p, const GilpCall &c, bool st
 
 std::string g_gilx_err;
 
-// the V weight tables of a mixed batch, back to back, each as weight_table gives it for that sigma_grid alone
-struct GilxTables { std::vector<double> table; std::vector<GilxVariant> var; int max_tlen = 0; };
-
 // the checks gilx_plan and gilx_run share, the tables and the shape: 0 with `info` and `tb` filled, or GIL_ERR_ARG with the
 // text in g_gilx_err
 int gilx_decide(const char *who, const gil_params *p, const gilx_variants *v, bool states, gilx_plan_info &info, GilxTables &tb,
@@ -776,35 +773,9 @@ int gilx_decide(const char *who, const gil_params *p, const gilx_variants *v, bo
     if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0) return bad("bad n_systems / n_cap / n_obs / max_events");
     if (p->n_cap > GIL_MAX_N)
         return bad("n_cap = " + std::to_string(p->n_cap) + " is beyond GIL_MAX_N = " + std::to_string(GIL_MAX_N) + ": the large-system shape takes no mixed batches");
-    const int V = v->n_variants, S = p->n_systems;
-    if (V < 1 || V > GILX_MAX_VARIANTS) return bad("n_variants = " + std::to_string(V) + " is outside [1, " + std::to_string(GILX_MAX_VARIANTS) + "]");
-    if (!v->sigma_grid) return bad("null sigma_grid");
-    for (int i = 0; i < V; ++i)
-        if (!std::isfinite(v->sigma_grid[i]) || v->sigma_grid[i] < 0.0)
-            return bad("sigma_grid = " + std::to_string(v->sigma_grid[i]) + " of variant " + std::to_string(i) + " must be finite and not negative");
-    if (v->variant_of_system)
-        for (int s = 0; s < S; ++s) {
-            const int i = v->variant_of_system[s];
-            if (i < 0 || i >= V) return bad("variant index " + std::to_string(i) + " of system " + std::to_string(s) + " is outside [0, n_variants = " + std::to_string(V) + ")");
-        }
-    if (v->order) {
-        std::vector<uint8_t> seen((size_t)S, 0);
-        for (int b = 0; b < S; ++b) {
-            const int s = v->order[b];
-            if (s < 0 || s >= S) return bad("order is not a permutation: order[" + std::to_string(b) + "] = " + std::to_string(s) + " is outside [0, n_systems = " + std::to_string(S) + ")");
-            if (seen[(size_t)s]++) return bad("order is not a permutation: system " + std::to_string(s) + " appears twice (second time at " + std::to_string(b) + ")");
-        }
-    }
-    tb = GilxTables{};
-    tb.var.resize((size_t)V);
-    std::vector<double> one;
-    for (int i = 0; i < V; ++i) {
-        int tlen = 0, q = 0;
-        weight_table(v->sigma_grid[i], p->L, p->K, p->periodic != 0, one, tlen, q);
-        tb.var[(size_t)i] = GilxVariant{(int32_t)tb.table.size(), tlen, v->sigma_grid[i] > 0.0 ? 1 : 0, 0};
-        tb.table.insert(tb.table.end(), one.begin(), one.end());   // tlen taps and the closing zero
-        tb.max_tlen = std::max(tb.max_tlen, tlen);
-    }
+    { const std::string why = gilx_check_variants(p, v); if (!why.empty()) return bad(why); }
+    gilx_build_tables(p, v, tb);                                // gillespie_mixed.hpp: shared with the large shape's gilxm_decide
+    const int S = p->n_systems;
     int NT = 0; size_t lds = 0;
     batch_shape(p->L, p->n_cap, tb.max_tlen, false, NT, lds);
     if (lds > 160 * 1024)

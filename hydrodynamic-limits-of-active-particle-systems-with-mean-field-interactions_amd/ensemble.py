@@ -5,7 +5,8 @@ The two outer sweeps of the other drivers are here too: `sweep_over_sigmas` (int
 ..._sweep_beta_2.py:1030-1075) and `sweep_over_densities` (particle number x beta, ..._double_sweep.py:851-861) --
 one batched handle per sigma / per particle number (the weight table and the state capacity differ), all (beta, run)
 pairs inside it; under the exact dynamics `one_launch=True` puts the whole sweep into ONE mixed launch of the event loop
-(include/gillespie_mixed.h: a weight table and a blocking table per system).  `sweep_betas_for_structures` / `sweep_beta_structure_ensemble` are the pattern study's drivers
+(include/gillespie_mixed.h: a weight table and a blocking table per system; with `allow_large=True` also at L > 4096 or
+N > 2048, include/gillespie_mixed_many.h).  `sweep_betas_for_structures` / `sweep_beta_structure_ensemble` are the pattern study's drivers
 (PARTICLE_solver_BIOLOGY_local_structure.py:105-193), all (beta, run) pairs in one launch, the per-run observables from sums
 taken on the GPU; `sweep_sigmas_for_structures` is that study over the interaction range, all (sigma, beta, run) systems in one mixed
 launch with the window reduction on the device (include/gillespie_mixed_structure.h).  `capture_study` is the anchor-capture study (PARTICLE_solver_CLASS.py:766-976) as an ensemble in one launch.
@@ -85,12 +86,12 @@ def _beta_statistics(rows, owner, beta_values):
     return out
 
 
-def _sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_kwargs, rng_seeds, on_device, dynamics):
+def _sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_kwargs, rng_seeds, on_device, dynamics, allow_large=False):
     """One sweep_over_betas per case = (ps_kwargs, init_kwargs), all cases in ONE mixed launch of the exact event loop
     (gillespie.run_batched_exact_statistics_mixed / run_batched_exact_mixed).  The systems are built in the order of the host
     loop, and every case is a group of the launch: its systems draw what the case's own launch draws.  Returns the list of the
     per-case sweep dictionaries.  ValueError where no mixed launch exists: the fixed-dt stepper, a large shape (L > 4096 or
-    N > 2048), a launch over the 160 KB of LDS."""
+    N > 2048) without `allow_large`, a launch over the 160 KB of LDS."""
     from . import gillespie
     run_kwargs = dict(run_kwargs or {})
     for ps_kwargs, _ in cases:
@@ -111,9 +112,9 @@ def _sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_kwargs, 
                 owner.append(bi)
     if on_device:
         slim = {k: v for k, v in run_kwargs.items() if k in ("T", "obs_dt")}
-        rows = gillespie.run_batched_exact_statistics_mixed(systems, groups=group, **slim)
+        rows = gillespie.run_batched_exact_statistics_mixed(systems, groups=group, allow_large=allow_large, **slim)
     else:
-        outs = gillespie.run_batched_exact_mixed(systems, want_m_local=False, groups=group, **run_kwargs)
+        outs = gillespie.run_batched_exact_mixed(systems, want_m_local=False, groups=group, allow_large=allow_large, **run_kwargs)
         rows = [observables.run_observables(out, ps.L, ps.dx) for ps, out in zip(systems, outs)]
     per = len(beta_values) * n_runs_per_beta
     return [_beta_statistics(rows[ci * per:(ci + 1) * per], owner[ci * per:(ci + 1) * per], beta_values) for ci in range(len(cases))]
@@ -130,18 +131,22 @@ def sweep_beta_ensemble(beta, n_runs=10, ps_kwargs=None, init_kwargs=None, run_k
 
 
 def sweep_over_sigmas(sigma_values, beta_values, n_runs_per_beta=5, ps_kwargs=None, init_kwargs=None, run_kwargs=None,
-                      rng_seeds=None, on_device=False, dynamics=None, one_launch=False):
+                      rng_seeds=None, on_device=False, dynamics=None, one_launch=False, allow_large=False):
     """The sigma sweep of PARTICLE_solver_BIOLOGY_EXCLUSION_sweep_beta_2.py:1030-1075: for every interaction range
     `local_kernel_sigma` a whole beta sweep (one GPU handle per sigma: the weight table changes; sigma = 0 selects the global
     mean field, sigma wider than the box the folded table).  Returns {sigma: {"beta", "v_mean", "v_se", "D_mean", "D_se",
     "ps_kwargs"}} like the reference (which also writes one .npz per sigma; saving is left to the caller).
     `one_launch=True` (exact dynamics only): all (sigma, beta, run) systems in one mixed launch, with the draws and hence the
-    numbers of the loop over sigma; ValueError for the fixed-dt stepper, a large shape or a launch over the LDS limit."""
+    numbers of the loop over sigma; ValueError for the fixed-dt stepper, a large shape or a launch over the LDS limit.
+    `allow_large=True` (with one_launch): a large shape (L > 4096 or N > 2048) is one mixed launch of the large-system kernel
+    (include/gillespie_mixed_many.h) instead of a ValueError.  Its numbers equal the host loop's where every case of the sweep is
+    itself a large shape, which is always so when L > 4096; cases below the limit in a sweep that straddles it run on the large
+    kernel with its keys and equal gillespie.run_many_large_raw for them, not the batch kernel."""
     results = {}
     kws = [dict(ps_kwargs or {}, local_kernel_sigma=float(sigma)) for sigma in sigma_values]
     if one_launch:
         sweeps = _sweeps_in_one_launch("sweep_over_sigmas", [(kw, dict(init_kwargs or {})) for kw in kws], beta_values, n_runs_per_beta,
-                                       run_kwargs, rng_seeds, on_device, dynamics)
+                                       run_kwargs, rng_seeds, on_device, dynamics, allow_large)
     for si, (sigma, kw) in enumerate(zip(sigma_values, kws)):
         r = sweeps[si] if one_launch else sweep_over_betas(beta_values, n_runs_per_beta, kw, init_kwargs, run_kwargs, rng_seeds,
                                                            on_device=on_device, dynamics=dynamics)
@@ -151,7 +156,7 @@ def sweep_over_sigmas(sigma_values, beta_values, n_runs_per_beta=5, ps_kwargs=No
 
 
 def sweep_over_densities(n_part_values, beta_values, n_runs_per_beta=4, ps_kwargs=None, init_kwargs=None, run_kwargs=None,
-                         rng_seeds=None, on_device=False, dynamics=None, one_launch=False):
+                         rng_seeds=None, on_device=False, dynamics=None, one_launch=False, allow_large=False):
     """The density x beta double sweep of PARTICLE_solver_BIOLOGY_EXCLUSION_double_sweep.py:851-861
     (`list_N_part = np.linspace(50, 950, 19)`: N arrives as a float there and is used as an integer): one batched beta sweep
     per particle number.  Returns a list of the per-N sweep dictionaries (keys of `sweep_over_betas`) with "N_part" added;
@@ -159,7 +164,10 @@ def sweep_over_densities(n_part_values, beta_values, n_runs_per_beta=4, ps_kwarg
     numbers and stays with the caller.
     `one_launch=True` (exact dynamics only): all (N, beta, run) systems in one mixed launch, each counted with the blocking
     table of its own particle number, with the draws and hence the numbers of the loop over N; ValueError for the fixed-dt
-    stepper, a large shape or a launch over the LDS limit."""
+    stepper, a large shape or a launch over the LDS limit.
+    `allow_large=True` (with one_launch): as in sweep_over_sigmas.  Here a sweep straddles the limit when L <= 4096 and only some
+    particle numbers exceed 2048: the launch is then the large kernel's for all of them, and the particle numbers below the limit
+    equal gillespie.run_many_large_raw, not the host loop's batch kernel."""
     out = []
     for n_part in n_part_values:
         if float(n_part) != int(n_part):
@@ -167,7 +175,7 @@ def sweep_over_densities(n_part_values, beta_values, n_runs_per_beta=4, ps_kwarg
     iks = [dict(init_kwargs or {}, N=int(n_part)) for n_part in n_part_values]
     if one_launch:
         sweeps = _sweeps_in_one_launch("sweep_over_densities", [(dict(ps_kwargs or {}), ik) for ik in iks], beta_values, n_runs_per_beta,
-                                       run_kwargs, rng_seeds, on_device, dynamics)
+                                       run_kwargs, rng_seeds, on_device, dynamics, allow_large)
     for ni, (n_part, ik) in enumerate(zip(n_part_values, iks)):
         r = sweeps[ni] if one_launch else sweep_over_betas(beta_values, n_runs_per_beta, ps_kwargs, ik, run_kwargs, rng_seeds,
                                                            on_device=on_device, dynamics=dynamics)

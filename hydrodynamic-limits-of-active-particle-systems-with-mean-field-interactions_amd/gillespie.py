@@ -7,7 +7,8 @@ include/gillespie_structure.h); the anchor-capture study's cluster, lifetime and
 (`run_batched_exact_capture`, include/gillespie_capture.h); the ensemble density and field profiles of many runs
 (`run_batched_exact_profiles`, include/gillespie_profile.h) are summed over the runs on the device.  Systems that differ in
 the interaction range or in the blocking threshold of their particle number share ONE launch as a mixed batch
-(`run_batched_exact_mixed`, `run_batched_exact_statistics_mixed`, include/gillespie_mixed.h); the structure observables of such a batch come from sums the
+(`run_batched_exact_mixed`, `run_batched_exact_statistics_mixed`, include/gillespie_mixed.h; with `allow_large=True` also systems
+beyond one workgroup's LDS, include/gillespie_mixed_many.h); the structure observables of such a batch come from sums the
 mixed launch takes and reduces over the window on the device (`run_batched_exact_structure_mixed`,
 include/gillespie_mixed_structure.h).
 
@@ -74,6 +75,13 @@ class GilxPlanInfo(C.Structure):
     """struct gilx_plan_info of include/gillespie_mixed.h, field for field."""
     _fields_ = [("threads", C.c_int32), ("lds_bytes", C.c_int32), ("max_tlen", C.c_int32), ("systems_per_cu", C.c_int32),
                 ("table_doubles", C.c_int64), ("output_bytes", C.c_int64)]
+
+
+class GilxmPlanInfo(C.Structure):
+    """struct gilxm_plan_info of include/gillespie_mixed_many.h, field for field."""
+    _fields_ = [("n_systems", C.c_int32), ("n_blocks", C.c_int32), ("max_tlen", C.c_int32), ("max_tlen_lds", C.c_int32),
+                ("n_global", C.c_int32), ("lds_bytes", C.c_int32), ("table_doubles", C.c_int64), ("work_bytes_per_system", C.c_int64),
+                ("output_bytes", C.c_int64)]
 
 
 class GilCheckpoint(C.Structure):
@@ -196,6 +204,7 @@ ENTRIES = {
     "gilp_run": _Entry("gilp_last_error", _stage_profiles, [_I32, _I32, _I32, _PTR, _I32], [_PTR] * 3, finish=_profile_bins),
     "gilx_run": _Entry("gilx_last_error", _stage_mixed, [_VAR]),   # a variant per system
     "gilxs_run": _Entry("gilxs_last_error", _stage_mixed_structure, [_VAR, _I32, _I32], [_PTR] * 5),
+    "gilxm_run": _Entry("gilxm_last_error", _stage_mixed, [_VAR], header="include/gillespie_mixed_many.h"),   # the same, large systems
 }
 # the plans: name -> (last_error, the C types between gil_params and the info structure, the info structure)
 PLANS = {
@@ -205,6 +214,7 @@ PLANS = {
     "gilp_plan": ("gilp_last_error", [_I32] * 6, GilpPlanInfo),
     "gilx_plan": ("gilx_last_error", [_VAR, _I32], GilxPlanInfo),
     "gilxs_plan": ("gilxs_last_error", [_VAR, _I32, _I32, _I32, _I32], capi.GilxsPlanInfo),
+    "gilxm_plan": ("gilxm_last_error", [_VAR, _I32], GilxmPlanInfo),
 }
 # an older build named by APS_LIB (a timing yardstick) may lack any entry point but these
 EVERY_BUILD = ("gil_run_batch", "gil_run_large", "gilm_run", "gilm_plan", "gils_run", "gils_plan")
@@ -441,6 +451,28 @@ def run_mixed_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffus
     return _run_batch_entry("gilx_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
 
 
+def plan_mixed_many(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs, variant_of_system=None, order=None, want_states=True):
+    """gilxm_plan: what a mixed launch of large systems (`run_mixed_many_raw`) would use -- rate blocks, the longest table, the
+    longest one kept in LDS (-1: none), the variants read from global memory, LDS of a workgroup, the doubles of all tables, work
+    bytes per system and output bytes -- by host arithmetic; no device needed.  Refuses what the run would refuse on these numbers."""
+    return _plan("gilxm_plan", dict(L=L, K=K, periodic=periodic, n_systems=n_systems, n_cap=n_cap, n_obs=n_obs), [int(bool(want_states))],
+                 dict(sigma_grids=sigma_grids, variant_of_system=variant_of_system, order=order))
+
+
+def run_mixed_many_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
+                       minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
+                       anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
+                       block_tables=None, device=0, flip_table=None, seeds=None, streams=None, order=None, n_cap=None):
+    """`run_mixed_raw` for systems beyond one workgroup's LDS (gilxm_run of include/gillespie_mixed_many.h): the large-system
+    kernel of `run_many_large_raw`, one workgroup per system, with a variant per system.  Same keywords, same dictionary.  The
+    defaults of the keys are the large shape's: `seeds=None` is `seed` + s, `streams=None` is 0, so one variant with the defaults
+    is `run_many_large_raw`.  Any L >= 2 is accepted; system s is, bit for bit, the `run_many_large_raw` system with its
+    variant's range and blocking table under key `seeds[s]` (include/gillespie_mixed_many.h states the condition on n_cap)."""
+    kw = dict(locals())
+    mixed = {k: kw.pop(k) for k in ("sigma_grids", "variant_of_system", "block_tables", "seeds", "streams", "order")}
+    return _run_batch_entry("gilxm_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
+
+
 def plan_mixed_structure(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs, k_max, first_obs=0, variant_of_system=None,
                          order=None, want_states=True, want_rows=True):
     """gilxs_plan: what a mixed launch with the structure sums (`run_mixed_structure_raw`) would use -- threads per system, LDS of
@@ -482,7 +514,7 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     LDS), gilm_run (large systems), gils_run (either, with the structure sums: k_max, first_obs) and gilc_run (either, with the
     capture statistics: group_of_site, n_groups, c_bins, h_bins, h_dt, first_obs); gilp_run (either, with the ensemble profiles:
     n_bins, first_obs, want_field, group_of_system, n_groups, per_system); gilx_run (systems in LDS, a variant per system: `mixed`,
-    the keywords of _mixed_descriptor) and gilxs_run (the same with the structure sums: k_max, first_obs, want_rows); gilr_run and
+    the keywords of _mixed_descriptor), gilxm_run (the same, large systems) and gilxs_run (the same with the structure sums: k_max, first_obs, want_rows); gilr_run and
     gilrm_run (one segment of a run: obs_first, checkpoint)."""
     lib, row = _lib(), ENTRIES[entry]
     if row.header is not None and not hasattr(lib, entry):
@@ -875,11 +907,12 @@ def mixed_variants(sigma_grids, block_tables=None):
     return np.array(sig), (None if block_tables is None else np.stack(tabs)), np.array(owner, np.int32)
 
 
-def mixed_keys(systems, groups=None):
+def mixed_keys(systems, groups=None, large=False):
     """Philox key and system index of every system of a mixed batch.  `groups[s]` is the group of system s, a group being what one
     `run_raw` launch of the host loop would hold: the key is the seed of the group's FIRST system (its `seed`, or a number drawn
     from its rng -- call this after the initial states were drawn, as the per-group functions do) and the index is the place
-    within the group.  None: one group."""
+    within the group.  None: one group.  `large=True`: the keys of the large shape, where a group is one `run_many_large_raw`
+    launch -- the key is the group's key plus the place within the group (mod 2^64) and the stream is 0."""
     from .particle_system import batch_seed
     groups = [0] * len(systems) if groups is None else [int(g) for g in groups]
     if len(groups) != len(systems):
@@ -889,22 +922,24 @@ def mixed_keys(systems, groups=None):
         if g not in key:
             key[g] = batch_seed(ps)
             count[g] = 0
-        seeds.append(int(key[g]))
-        streams.append(count[g])
+        seeds.append((int(key[g]) + count[g]) % 2 ** 64 if large else int(key[g]))
+        streams.append(0 if large else count[g])
         count[g] += 1
     return seeds, streams
 
 
-def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, order=None, structure=None):
+def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, order=None, structure=None, allow_large=False):
     """The one launch behind run_batched_exact_mixed and run_batched_exact_statistics_mixed: checks, initial states, variants,
-    keys, gilx_run.  `structure` = (k_max or None, start_fraction, want_rows, all_observations): the launch behind
-    run_batched_exact_structure_mixed instead, gilxs_run without states.  Returns (raw outputs, times_obs)."""
+    keys, gilx_run -- or, for a large shape with `allow_large`, gilxm_run with the large shape's keys.  `structure` = (k_max or
+    None, start_fraction, want_rows, all_observations): the launch behind run_batched_exact_structure_mixed instead, gilxs_run
+    without states (no large shape).  Returns (raw outputs, times_obs)."""
     first, inits, _ = _open_batch(who, systems, skip=("local_kernel_sigma",), anchors="their anchor sites", flip=True, no_exit=statistics, seed=False)
     n_cap = max(1, max(len(p) for p, _ in inits))
-    if _large_shape(first.L, n_cap):
+    large = _large_shape(first.L, n_cap)
+    if large and not (allow_large and structure is None):
         raise ValueError(f"{who}: L = {first.L}, N = {n_cap} is a large shape (beyond L = {GIL_MAX_L}, N = {GIL_MAX_N}); "
                          "the large-system kernel takes no mixed batches")
-    seeds, streams = mixed_keys(systems, groups)
+    seeds, streams = mixed_keys(systems, groups, large=large)
     times_obs = np.arange(0.0, T, obs_dt)
     kw, tables = {}, None
     if statistics:                                             # every system is counted with the table of its own particle number
@@ -912,7 +947,7 @@ def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, or
     sig, tabs, owner = mixed_variants([ps._sigma_grid for ps in systems], tables)
     shape = dict(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems), n_cap=n_cap, n_obs=len(times_obs),
                  variant_of_system=owner)
-    run_fn = run_mixed_raw
+    run_fn = run_mixed_many_raw if large else run_mixed_raw
     if structure is not None:
         k_max, start_fraction, want_rows, all_obs = structure
         kk = first.L if k_max is None else min(int(k_max), first.L)
@@ -921,7 +956,7 @@ def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, or
         run_fn = run_mixed_structure_raw
         plan = plan_mixed_structure(**shape, **kw)
     else:
-        plan = plan_mixed(**shape, want_states=not statistics)
+        plan = (plan_mixed_many if large else plan_mixed)(**shape, want_states=not statistics)
     if plan["lds_bytes"] > GILX_LDS_LIMIT:
         raise ValueError(f"{who}: the launch needs {plan['lds_bytes']} bytes of LDS per system, over the limit of {GILX_LDS_LIMIT} bytes")
     model = _model(first, systems, sigma_grids=sig, variant_of_system=owner, block_tables=tabs, states=inits, times_obs=times_obs, T=T,
@@ -933,24 +968,30 @@ def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, or
 
 
 def run_batched_exact_mixed(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False, uniforms=None, want_m_local=True,
-                            groups=None, order=None, resume=None):
+                            groups=None, order=None, resume=None, allow_large=False):
     """`run_batched_exact` for systems that may ALSO differ in `local_kernel_sigma`: one mixed launch (include/gillespie_mixed.h).
     Every other attribute the batched functions compare, the anchor sites and the flip table must agree.  `groups[s]`: the group
     of system s; its systems draw what `run_batched_exact` on the group alone draws (`mixed_keys`).  Returns the list of the
-    reference's result dictionaries, one per system."""
+    reference's result dictionaries, one per system.
+    `allow_large=True`: a batch that is a large shape (L > 4096, or more than 2048 particles in any system) is one mixed launch
+    of the large-system kernel (include/gillespie_mixed_many.h) instead of a ValueError, with the large shape's keys
+    (`mixed_keys(..., large=True)`).  Its numbers equal `run_batched_exact` on each group alone where every group is itself a
+    large shape, which is always so when L > 4096.  A group below the limit in a batch that straddles it runs on the large kernel
+    with large keys: it then equals `run_many_large_raw` for it, not the batch kernel.  A batch that is no large shape is
+    launched as without the keyword."""
     _refuse_resume("run_batched_exact_mixed", resume)
-    r, times_obs = _mixed_launch("run_batched_exact_mixed", systems, T, obs_dt, groups, False, uniforms, order)
+    r, times_obs = _mixed_launch("run_batched_exact_mixed", systems, T, obs_dt, groups, False, uniforms, order, allow_large=allow_large)
     outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
     systems[0].kernel_ms = r["kernel_ms"]
     return outs
 
 
-def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None, order=None, resume=None):
+def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None, order=None, resume=None, allow_large=False):
     """`run_batched_exact_statistics` for systems that may also differ in `local_kernel_sigma` and whose particle numbers may give
     different blocking thresholds: every system is counted with the blocking table of its own particle number, in one mixed
-    launch.  `groups` as in run_batched_exact_mixed.  Returns the DeviceObservables rows, one per system."""
+    launch.  `groups`, `allow_large` as in run_batched_exact_mixed.  Returns the DeviceObservables rows, one per system."""
     _refuse_resume("run_batched_exact_statistics_mixed", resume)
-    r, times_obs = _mixed_launch("run_batched_exact_statistics_mixed", systems, T, obs_dt, groups, True, None, order)
+    r, times_obs = _mixed_launch("run_batched_exact_statistics_mixed", systems, T, obs_dt, groups, True, None, order, allow_large=allow_large)
     rows = _statistics_rows(systems, r, times_obs)
     systems[0].kernel_ms = r["kernel_ms"]
     return rows

@@ -23,7 +23,8 @@
  *
  * Outputs are indexed by the SYSTEM, never by the workgroup, with the strides of gil_run_batch (n_cap per system).  A system's
  * loops run over its own n0[s] slots; the slots at and beyond n0[s] are zero in pos_obs, sigma_obs and flags_obs.
- * The large-system shape (gilm_run) takes no mixed batches.
+ * The large-system shape (gilm_run) takes no mixed batches through these functions; its own mixed launch is gilxm_run of
+ * include/gillespie_mixed_many.h.
  * All functions return 0 on success and a negative code on failure; gilx_last_error() gives the text.
  */
 #ifndef GILLESPIE_MIXED_H
