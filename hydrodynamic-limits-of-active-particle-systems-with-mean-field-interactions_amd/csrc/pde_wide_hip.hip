@@ -495,7 +495,7 @@ const char *make_plan(const pde_params *p, int32_t n_systems, int32_t workgroups
                 if (nsub > 0) pl.lds = std::max(pl.lds, conv_lds_doubles(conv_shape(nsub, ktaps)) * sizeof(double));
     const long long S = n_systems, L = p->L, ntr = p->n_tracers;
     pl.work_bytes = 8 * (5 * S * L + S * NSLOT * G + S * 2 * p->n_fft_modes * G + 2 * S * G * 3 + 4 * S + S * p->window * ntr + S * ntr) + S * ntr;
-    pl.spectral = p->kernel_mode == 1 && p->convolution == 1;
+    pl.spectral = p->kernel_mode == 1 && p->convolution == 1 && ktaps > 0;   // a kernel of one tap is its direct sum: nothing to transform
     pl.conv_m = pl.conv_B = pl.conv_S = 0;
     if (pl.spectral) {                                         // no fall-back: a shape the transforms cannot take is refused
         if (const char *why = pdes_plan_blocks(L, ktaps, spectral_cap(), pl.conv_B, pl.conv_m, pl.conv_S)) return why;

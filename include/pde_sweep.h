@@ -10,8 +10,9 @@
  * be NULL); otherwise global mean (mode 2) when kernel_sigma[s] > 100000, else the periodic Gaussian kernel (mode 1) with its
  * own normalised taps, cut at 1e-17 of the centre tap, the antipodal tap of an even ring halved.
  *
- * Transform (p->convolution == 1, every mode-1 system): the window z[(i - kt) mod L], i < L + 2 kt, z = s + i tot, zero up to
- * M = 2^m, m = max(PDEK_MIN_LOG2, ceil(log2(L + 2 kt))); forward, product with the taps' real spectrum, inverse; outputs
+ * Transform (p->convolution == 1, every mode-1 system whose kernel reaches beyond its own site, kt >= 1): the window
+ * z[(i - kt) mod L], i < L + 2 kt, z = s + i tot, zero up to M = 2^m, m = max(PDEK_MIN_LOG2, ceil(log2(L + 2 kt))); forward,
+ * product with the taps' real spectrum, inverse; outputs
  * kt .. kt + L - 1 are kept.  Upper limit: PDEK_MAX_LOG2 and PDEK_LDS_LIMIT.  The launch's LDS is, in bytes,
  *     8 * ((5 L + ((ktaps_max + 2) & ~1) + 259) & ~3) + 16384        fields, taps, sums, the scans' scratch (as pde_solve_batch)
  *   + 33 * M_max                                                      buffer of M words padded by one in sixteen, M / 2 twiddles, M spectrum values
@@ -49,14 +50,17 @@ const char *pdek_last_error(void);
 
 /* What pdek_solve would use: a pure host function, no device is touched.  kernel_sigma[n_systems] (may be NULL when
  * p->kernel_mode == 0); info and the three arrays [n_systems] may each be NULL.  conv_log2[s] is 0 where no transform runs
- * (p->convolution == 0, or the system's mode is not 1).  A kernel_sigma that is not finite or not > 0 where a Gaussian kernel
+ * (p->convolution == 0, the system's mode is not 1, or its kernel is one tap: ktaps[s] == 0, where the direct sum is one exact
+ * product and a transform's round-off, divided by den + 1e-12 on an empty site, would only lose accuracy).  A kernel_sigma
+ * that is not finite or not > 0 where a Gaussian kernel
  * is asked for is refused. */
 int pdek_plan(const pde_params *p, int32_t n_systems, const double *kernel_sigma,
               pdek_plan_info *info, int32_t *kernel_mode, int32_t *ktaps, int32_t *conv_log2);
 
 /* pde_solve_batch with a kernel width per system: kernel_sigma[n_systems] replaces p->kernel_sigma; the 19 buffers and
  * kernel_ms are those of pde_solve_batch, in the same order, with the same meaning.  p->convolution: 0 = the direct circular
- * sum over the system's own taps (the arithmetic of pde_solve_batch), 1 = the transform for every mode-1 system.  Uses exactly
+ * sum over the system's own taps (the arithmetic of pde_solve_batch), 1 = the transform for every mode-1 system with
+ * ktaps >= 1.  Uses exactly
  * the plan of pdek_plan.  A system's result depends on its own parameters and (device-side tracer noise) on its index, not
  * on its companions in the launch. */
 int pdek_solve(const pde_params *p, int32_t n_systems, const double *beta, const double *kernel_sigma,

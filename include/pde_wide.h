@@ -49,7 +49,8 @@ int pdew_plan(const pde_params *p, int32_t n_systems, int32_t workgroups, pdew_p
  * meaning, with one difference: with n_tracers == 0, v_eff_series and D_eff_series are left as the caller passed them
  * (pde_solve_batch and pdek_solve overwrite them with unspecified values).  workgroups = G per system (0: the library chooses); 1 <= G <= PDEW_MAX_WORKGROUPS, floor(L / G) >= PDEW_MIN_SLAB,
  * G * n_systems <= PDEW_MAX_GRID, n_systems <= 65535.
- * p->convolution (used with kernel_mode 1 only): 0 = direct circular convolution, 1 = spectral (include/pde_spectral.h); a shape
+ * p->convolution (used with kernel_mode 1 only): 0 = direct circular convolution, 1 = spectral (include/pde_spectral.h; a kernel of one
+ * tap, ktaps == 0, is summed directly and conv_log2 is 0: its one product is exact, a transform's round-off is not); a shape
  * the spectral path cannot take fails with PDE_ERR_ARG and a text that says why -- there is no fall-back to the direct sum. */
 int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const double *beta, const double *rho_p0,
                const double *rho_m0, const double *tracer_x0, const int8_t *tracer_s0, const double *rand_u, const double *rand_n,

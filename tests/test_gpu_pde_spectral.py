@@ -6,7 +6,9 @@ Same oracle, same random numbers and the same bars as tests/test_gpu_pde_wide.py
     fft modes ......................................... 1e-12 absolute
     tracer spin states ................................ equal
     tracer positions, v_eff / D_eff series ............ 1e-9
-Blocks on small grids are forced with PDE_SPECTRAL_MAX_LOG2 (the cap of the transform's log2 length)."""
+Blocks on small grids are forced with PDE_SPECTRAL_MAX_LOG2 (the cap of the transform's log2 length).
+The yardstick is the binary64 oracle, itself a product of transforms; tests/test_gpu_pde_random.py measures both against the
+extended-precision reference of tests/pde_reference.py over random parameters and says where no transform can hold the bar."""
 import importlib
 import os
 import sys

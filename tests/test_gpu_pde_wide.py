@@ -8,7 +8,9 @@ other summation orders, the device's exp):
     fft modes ......................................... 1e-12 absolute
     tracer spin states ................................ equal
     tracer positions, v_eff / D_eff series ............ 1e-9
-and against the one-workgroup kernel itself where no fixed bar against the oracle can be set (L = 131 072)."""
+and against the one-workgroup kernel itself where no fixed bar against the oracle can be set (L = 131 072).
+The yardstick is the binary64 oracle at one point of the parameter space; tests/test_gpu_pde_random.py holds the same bars on 1,
+2 and 7 slabs over random parameters against the extended-precision reference of tests/pde_reference.py."""
 import importlib
 import time
 
