@@ -1,5 +1,5 @@
 // gillespie_big_hip.hip -- gil_run_large of include/gillespie.h, gilm_run of include/gillespie_many.h, gilxm_run of
-// include/gillespie_mixed_many.h and the large shape of gils_run, gilc_run, gilp_run and gilrm_run: the reference's
+// include/gillespie_mixed_many.h and the large shape of gils_run, gilc_run, gilp_run, gilrm_run and gilxmr_run: the reference's
 // exact event loop (PARTICLE_solver_CLASS.py:511-538) for systems far too large for a workgroup's LDS (the BASELINE size:
 // N = 1e5 particles on L = 2e5 sites, where the reference manages 0.8 events/s because it recomputes the whole
 // field and all N rates before every event).  One kernel and one host driver serve both entry points: a batch is a grid
@@ -112,11 +112,7 @@ __global__ __launch_bounds__(256) void big_field_init(const BigArgs a0) {
 }
 
 // The same from a checkpoint (resumable launch): pos0 holds every slot's site, sigma0 its spin or 0 for a slot that is not alive
-__global__ __launch_bounds__(256) void big_field_init_live(const BigArgs a0) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= a0.m.L) return;
-    BigArgs a = a0;
-    select_system(a, (size_t)blockIdx.y);
+__device__ inline void field_init_site_live(const BigArgs &a, int x) {
     double w = 0.0, s = 0.0;
     if (a.m.field_mode)
         for (int j = 0; j < a.p.n_cap; ++j) {
@@ -126,6 +122,14 @@ __global__ __launch_bounds__(256) void big_field_init_live(const BigArgs a0) {
             w += g; s += sg > 0 ? g : -g;
         }
     a.W[x] = w; a.S[x] = s;
+}
+
+__global__ __launch_bounds__(256) void big_field_init_live(const BigArgs a0) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= a0.m.L) return;
+    BigArgs a = a0;
+    select_system(a, (size_t)blockIdx.y);
+    field_init_site_live(a, x);
 }
 
 __device__ inline double big_rate(const BigArgs &a, const double *tab, int i, long long gs, long long gn) {
@@ -242,6 +246,18 @@ __global__ __launch_bounds__(256) void big_field_init_mixed(const GilxBigArgs a0
     field_init_site(a, x);
 }
 
+struct GilxrBigArgs : GilxBigArgs { GilrArgs rs; };         // arguments of the resumable mixed instantiation
+
+// From a checkpoint in a mixed launch: big_field_init_live with the system's own table, length and field mode
+__global__ __launch_bounds__(256) void big_field_init_live_mixed(const GilxBigArgs a0) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= a0.m.L) return;
+    BigArgs a = a0;
+    select_system(a, (size_t)blockIdx.y);
+    gilxm_select(a, a0.mx, (int)blockIdx.y, TAB_LDS_MAX);
+    field_init_site_live(a, x);
+}
+
 // the argument struct of each variant of the large-system kernel
 template <GilKind V> struct BigKernelArgs;
 template <> struct BigKernelArgs<GilKind::Plain> { using type = BigArgs; };
@@ -250,6 +266,7 @@ template <> struct BigKernelArgs<GilKind::Capture> { using type = GilcBigArgs; }
 template <> struct BigKernelArgs<GilKind::Profile> { using type = GilpBigArgs; };
 template <> struct BigKernelArgs<GilKind::Resume> { using type = GilrBigArgs; };
 template <> struct BigKernelArgs<GilKind::Mixed> { using type = GilxBigArgs; };
+template <> struct BigKernelArgs<GilKind::MixedResume> { using type = GilxrBigArgs; };
 
 // V = the variant, a compile-time property, so that each kernel is the code it was before the others existed:
 //   Structure  also reduce the structure sums at an observation (gillespie_structure.hpp);
@@ -263,17 +280,25 @@ template <> struct BigKernelArgs<GilKind::Mixed> { using type = GilxBigArgs; };
 //   Mixed      a mixed batch (gillespie_mixed.hpp, include/gillespie_mixed_many.h): the workgroup takes system order[blockIdx.x],
 //              and the weight table, its length, whether it lies in LDS, the field mode, the blocking table and the Philox key and
 //              stream are that system's own, all uniform over the workgroup.  Outputs are indexed by the system.
+//   MixedResume  a resumable mixed launch (include/gillespie_mixed_resume.h): Mixed with the start and end of Resume.  The
+//              checkpoint's rows are the system's (RS_ROW), not the workgroup's; gilxm_select is applied before anything is read.
+//              The rate sums are grouped by blocks of the launch's n_cap, so the slot count does not enter here.
 template <GilKind V>
 __global__ __launch_bounds__(BT) void gil_big_kernel(const typename BigKernelArgs<V>::type a0) {
-    constexpr bool ST = V == GilKind::Structure, CP = V == GilKind::Capture, PF = V == GilKind::Profile, RS = V == GilKind::Resume;
-    constexpr bool MX = V == GilKind::Mixed;
+    constexpr bool ST = V == GilKind::Structure, CP = V == GilKind::Capture, PF = V == GilKind::Profile;
+    constexpr bool RS = V == GilKind::Resume || V == GilKind::MixedResume;
+    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedResume;
     extern __shared__ double lds[];
     BigArgs a = a0;
     uint32_t stream = 0u;                                      // Philox counter word 2: the system's own with MX
+    [[maybe_unused]] int mx_sys = 0;                           // MX: the system this workgroup took
+// RS: the system's row of the checkpoint -- with MX not the workgroup's (MX is a constant: one arm is compiled)
+#define RS_ROW (MX ? (size_t)mx_sys : (size_t)blockIdx.x)
     if constexpr (MX) {
         const int sys = __builtin_amdgcn_readfirstlane(a0.mx.order[blockIdx.x]);
         select_system(a, (size_t)sys);
         stream = gilxm_select(a, a0.mx, sys, TAB_LDS_MAX);
+        mx_sys = sys;
     } else select_system(a, (size_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x));
     const Model &M = a.m;
     const int L = M.L, K = M.K, t = threadIdx.x, lane = t & 63, wave = t >> 6, nobs = a.p.n_obs, N = a.p.n_cap;
@@ -299,7 +324,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const typename BigKernelArg
     for (int i = t; i < N; i += BT) {
         bool live; int p, r0 = -1; uint8_t f;
         if constexpr (RS) {                                    // the checkpoint's slots: departed ones stay dead, origins are kept
-            p = a.pos0[i]; f = a0.rs.flg[(size_t)blockIdx.x * N + i]; r0 = a0.rs.ref[(size_t)blockIdx.x * N + i]; live = (f & F_ALIVE) != 0;
+            p = a.pos0[i]; f = a0.rs.flg[RS_ROW * N + i]; r0 = a0.rs.ref[RS_ROW * N + i]; live = (f & F_ALIVE) != 0;
         } else {
             live = i < a.n_init;
             p = live ? a.pos0[i] : 0;
@@ -337,7 +362,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const typename BigKernelArg
     long long n_ev = 0, ev_base = 0;
     int k_obs = 0, n_exit = 0;
     if constexpr (RS) {
-        tnow = a0.rs.t[blockIdx.x]; n_ev = a0.rs.n_ev[blockIdx.x]; k_obs = a0.rs.k_start[blockIdx.x];
+        tnow = a0.rs.t[RS_ROW]; n_ev = a0.rs.n_ev[RS_ROW]; k_obs = a0.rs.k_start[RS_ROW];
         ev_base = n_ev - BT;                                   // no draws held: the first iteration draws
     }
 
@@ -663,6 +688,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const typename BigKernelArg
         if (a.n_exits) a.n_exits[0] = n_exit;
     }
 }
+#undef RS_ROW
 
 
 // What a batch of p->n_systems large systems needs, by host arithmetic alone (gilm_plan); the weight table comes back
@@ -750,7 +776,7 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilm_plan_info info{};
     std::vector<double> table;
-    const gilx_variants *mx = ex.mx;                          // a mixed launch (gilxm_run): a variant per system, no other extra
+    const gilx_variants *mx = ex.mx;                          // a mixed launch (gilxm_run; with ex.rs gilxmr_run): a variant per system
     gilxm_plan_info xinfo{}; GilxTables tb;
     if (mx) {
         if (int rc = gilxm_decide(who, err, p, mx, io.states(), io.scalars_obs != nullptr, xinfo, tb)) return rc;
@@ -795,7 +821,8 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
             order[(size_t)s] = mx->order ? mx->order[s] : s; stream[(size_t)s] = mx->stream ? mx->stream[s] : 0;
             seed[(size_t)s] = mx->seed ? mx->seed[s] : p->seed + (uint64_t)s;
         }
-        if (!mx->order) std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return io.n0[x] > io.n0[y]; });
+        const int32_t *slots = rs ? rs->n_slots.data() : io.n0;   // a resumable mixed launch: the checkpoint's slot counts
+        if (!mx->order) std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return slots[x] > slots[y]; });
     }
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: the scratch arrays start from zero
     if (int rc = job.select_device(p->device)) return rc;
@@ -821,8 +848,9 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
     if (rc) return rc;
     if ((rc = job.create_events())) return rc;
     static_cast<BigArgs &>(b) = a;
-    GilxBigArgs c{};                                            // the mixed launch's arguments: a's own and the variants
-    static_cast<BigArgs &>(c) = a;
+    GilxrBigArgs c{};                                           // the mixed launch's arguments: a's own and the variants (and, resumable,
+    static_cast<BigArgs &>(c) = a;                              //   the checkpoint: GilxBigArgs is its base)
+    c.rs = b.rs;
     if (mx) {
         c.tab_region = xinfo.max_tlen_lds >= 0 ? ((xinfo.max_tlen_lds + 2) & ~1) : 0;
         c.mx.has_block = mx->block_table ? 1 : 0;
@@ -833,12 +861,14 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
         if ((rc = job.upload(&c.mx.stream, stream.data(), (size_t)S, "stream"))) return rc;
     }
     const dim3 field_grid((unsigned)((L + 255) / 256), (unsigned)S);   // W, S of the start state: before the timed window
-    if (rs) hipLaunchKernelGGL(big_field_init_live, field_grid, dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
-    else if (mx) hipLaunchKernelGGL(big_field_init_mixed, field_grid, dim3(256), 0, nullptr, c);
+    if (rs && mx) hipLaunchKernelGGL(big_field_init_live_mixed, field_grid, dim3(256), 0, nullptr, static_cast<const GilxBigArgs &>(c));
+    else if (rs) hipLaunchKernelGGL(big_field_init_live, field_grid, dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
+    else if (mx) hipLaunchKernelGGL(big_field_init_mixed, field_grid, dim3(256), 0, nullptr, static_cast<const GilxBigArgs &>(c));
     else hipLaunchKernelGGL(big_field_init, field_grid, dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
     rc = ex.structure_obs ? big_launch<GilKind::Structure>(job, S, lds, a)
          : cap            ? big_launch<GilKind::Capture>(job, S, lds, a)
          : prof           ? big_launch<GilKind::Profile>(job, S, lds, a)
+         : mx && rs       ? big_launch<GilKind::MixedResume>(job, S, lds, c)
          : mx             ? big_launch<GilKind::Mixed>(job, S, lds, c)
          : rs             ? big_launch<GilKind::Resume>(job, S, lds, b) : big_launch<GilKind::Plain>(job, S, lds, a);
     if (rc) return rc;

@@ -35,7 +35,8 @@ struct GilIo {
 
 // What one entry point adds, at most one of: gils_run's rows (k_max modes, from observation first_obs on), gilc_run's call,
 // gilp_run's, the start state of gilr_run / gilrm_run (checked by gilr_prepare; it comes back as the end state), gilxs_run's call,
-// gilxm_run's variants (the large shape's mixed launch).
+// gilxm_run's variants (the large shape's mixed launch).  The resumable mixed launches (include/gillespie_mixed_resume.h) have
+// `rs` (checked by gilxr_prepare) next to `xs` or `mx`.
 struct GilExtras {
     int k_max = 0, first_obs = 0; double *structure_obs = nullptr;
     const GilcCall *cap = nullptr; const GilpCall *prof = nullptr; GilrCall *rs = nullptr; const GilxsCall *xs = nullptr;
@@ -44,7 +45,7 @@ struct GilExtras {
 
 // One enumerator per kernel variant that exists; a kernel family maps each of its own to an argument struct (GilKernelArgs in
 // gillespie_hip.hip, BigKernelArgs in gillespie_big_hip.hip), so a combination nobody wrote cannot be instantiated.
-enum class GilKind { Plain, Structure, Capture, Profile, Mixed, MixedStructure, Resume };
+enum class GilKind { Plain, Structure, Capture, Profile, Mixed, MixedStructure, Resume, MixedResume, MixedStructureResume };
 
 namespace {
 

@@ -14,7 +14,7 @@
 //   E  t += tau; states / scalar sums of the observation times that were crossed go to HBM (ref :517-536)
 // Randomness: Philox4x32-10 keyed by the seed, counter (event index, system) -- or numbers supplied by the caller.
 // Host side: every extern "C" run function fills a GilIo and a GilExtras (gillespie_common.hpp) and calls batch_run, mixed_run or,
-// for the large shape, gil_large_run of gillespie_big_hip.hip; the drivers stage and fetch through the helpers of
+// for the large shape, gil_large_run of gillespie_big_hip.hip (the resumable ones through gilr_drive / gilxr_drive); the drivers stage and fetch through the helpers of
 // gillespie_common.hpp, and gil_launch<V> is the one place that names a kernel instantiation.
 
 #include <hip/hip_runtime.h>
@@ -32,6 +32,7 @@
 #include "gillespie_mixed.h"
 #include "gillespie_mixed_structure.h"
 #include "gillespie_resume.h"
+#include "gillespie_mixed_resume.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"           // the call record, the variant tags, the staging path of the drivers
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiations only)
@@ -79,6 +80,8 @@ struct GilpBatchArgs : GilcBatchArgs { GilpArgs pf; };      // arguments of the 
 struct GilxBatchArgs : GilArgs { GilxArgs mx; };            // arguments of the mixed instantiations (gilx_run's driver)
 struct GilxsBatchArgs : GilxBatchArgs { GilsArgs st; GilwArgs wn; };   // arguments of the mixed structure instantiations (gilxs_run's)
 struct GilrBatchArgs : GilArgs { GilrArgs rs; };            // arguments of the resumable instantiations (gilr_run's)
+struct GilxrBatchArgs : GilxBatchArgs { GilrArgs rs; };     // arguments of the resumable mixed instantiations (gilxr_run's)
+struct GilxsrBatchArgs : GilxsBatchArgs { GilrArgs rs; };   // arguments of the resumable mixed structure instantiations (gilxsr_run's)
 
 // the argument struct of each variant of the batch kernel
 template <GilKind V> struct GilKernelArgs;
@@ -89,6 +92,8 @@ template <> struct GilKernelArgs<GilKind::Profile> { using type = GilpBatchArgs;
 template <> struct GilKernelArgs<GilKind::Mixed> { using type = GilxBatchArgs; };
 template <> struct GilKernelArgs<GilKind::MixedStructure> { using type = GilxsBatchArgs; };
 template <> struct GilKernelArgs<GilKind::Resume> { using type = GilrBatchArgs; };
+template <> struct GilKernelArgs<GilKind::MixedResume> { using type = GilxrBatchArgs; };
+template <> struct GilKernelArgs<GilKind::MixedStructureResume> { using type = GilxsrBatchArgs; };
 
 // the structure sums' slots: behind the loop's own LDS (which ends with the plus-occupancy bytes), at the next multiple of 8
 __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L) {
@@ -108,10 +113,17 @@ __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L)
 //                   are optional there;
 //   Resume          a resumable launch (gillespie_resume.hpp): the start state is a checkpoint (slots may be dead, the clock, the
 //                   event count and the next observation are the checkpoint's) and the end state is written out.
+//   MixedResume, MixedStructureResume  a resumable mixed launch (include/gillespie_mixed_resume.h): Mixed / MixedStructure with the
+//                   start and end of Resume.  a.n0 holds the checkpoint's slot counts, so the system's loops and its chunk are
+//                   those of the run's start, and the loops ask the flags; the end state beyond these slots is written as
+//                   empty.  With the structure sums, st.first_obs counts within the launch's slice (the host subtracts the
+//                   slice's first index), and the window's accumulators and counts start from the checkpoint's.
 template <int NT, GilKind V>
 __global__ __launch_bounds__(NT) void gil_kernel(const typename GilKernelArgs<V>::type a) {
-    constexpr bool ST = V == GilKind::Structure || V == GilKind::MixedStructure, CP = V == GilKind::Capture, PF = V == GilKind::Profile;
-    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedStructure, RS = V == GilKind::Resume;
+    constexpr bool XR = V == GilKind::MixedResume || V == GilKind::MixedStructureResume;   // MX and RS together
+    constexpr bool ST = V == GilKind::Structure || V == GilKind::MixedStructure || V == GilKind::MixedStructureResume;
+    constexpr bool CP = V == GilKind::Capture, PF = V == GilKind::Profile;
+    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedStructure || XR, RS = V == GilKind::Resume || XR;
     extern __shared__ double lds[];
     const Model &M = a.m;
     const GilxView vw = gilx_view<MX, NT>(a);                  // empty without MX
@@ -134,7 +146,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const typename GilKernelArgs<V>
     uint8_t *occ = flg + ((ncap + 15) & ~15);                 // [L] particles per site
     uint8_t *occp = occ + ((L + 15) & ~15);                   // [L] plus particles per site (blocking table)
     const double beta = a.betas[sys];
-    const int n_init = RS ? ncap : a.n0[sys];                  // RS: any slot may be alive, the loops below ask its flags
+    const int n_init = XR ? vw.nslots : (RS ? ncap : a.n0[sys]);   // RS: any slot may be alive, the loops below ask its flags
     // ---- load the system
     for (int i = t; i <= GX_TLEN; i += NT) tab[i] = (MX ? vw.table : a.table)[i];
     for (int x = t; x < L; x += NT) { occ[x] = 0; occp[x] = 0; }
@@ -187,6 +199,7 @@ __global__ __launch_bounds__(NT) void gil_kernel(const typename GilKernelArgs<V>
     // MX with ST only: observations the window took, and empty ones it met.  The other instantiations never read them, so
     // they cost no register there (their assembly is the parent's)
     [[maybe_unused]] int n_win = 0, n_emp = 0;
+    if constexpr (XR && ST) { n_win = a.wn.n_window[sys]; n_emp = a.wn.n_empty[sys]; }   // the checkpoint's (zero on a fresh start)
     const int c0 = t * GX_CHUNK, c1 = min(GX_SLOTS, c0 + GX_CHUNK);
 
     auto record = [&](int k) {                                 // observation k: state and scalar sums (ref :517-536)
@@ -511,6 +524,12 @@ __global__ __launch_bounds__(NT) void gil_kernel(const typename GilKernelArgs<V>
     if constexpr (RS) {                                        // the end state: a resumed launch continues this trajectory
         __syncthreads();
         for (int i = t; i < ncap; i += NT) {
+            if constexpr (XR) {                                // LDS holds the system's own slots only: the others are empty
+                const bool own = i < vw.nslots;
+                a.rs.pos_out[(size_t)sys * ncap + i] = own ? pos[i] : 0; a.rs.flg_out[(size_t)sys * ncap + i] = own ? flg[i] : (uint8_t)0;
+                a.rs.ref_out[(size_t)sys * ncap + i] = own ? ref[i] : -1;
+                continue;
+            }
             a.rs.pos_out[(size_t)sys * ncap + i] = pos[i]; a.rs.flg_out[(size_t)sys * ncap + i] = flg[i]; a.rs.ref_out[(size_t)sys * ncap + i] = ref[i];
         }
     }
@@ -789,15 +808,15 @@ int gilx_decide(const char *who, const gil_params *p, const gilx_variants *v, bo
     return GIL_OK;
 }
 
-std::string g_gilxs_err;
+std::string g_gilxs_err, g_gilxr_err;
 
 // the checks gilxs_plan and gilxs_run share, the tables and the shape: 0 with `info` and `tb` filled, or GIL_ERR_ARG with the
 // text in g_gilxs_err.  gilx_decide's refusals first, then gils_decide's.
-int gilxs_decide(const char *who, const gil_params *p, const gilx_variants *v, int k_max, int first_obs, bool states, bool rows,
-                 gilxs_plan_info &info, GilxTables &tb) {
-    auto bad = [&](const std::string &m) { g_gilxs_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+int gilxs_decide(const char *who, std::string &err, const gil_params *p, const gilx_variants *v, int k_max, int first_obs, bool states,
+                 bool rows, gilxs_plan_info &info, GilxTables &tb) {
+    auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilx_plan_info xi;
-    if (int rc = gilx_decide(who, p, v, states, xi, tb, g_gilxs_err)) return rc;
+    if (int rc = gilx_decide(who, p, v, states, xi, tb, err)) return rc;
     const int max_k = std::min(p->L, GILS_MAX_K);
     if (k_max < 1 || k_max > max_k) return bad("k_max = " + std::to_string(k_max) + " is outside [1, min(L, GILS_MAX_K) = " + std::to_string(max_k) + "]");
     if (first_obs < 0 || first_obs > p->n_obs) return bad("first_obs = " + std::to_string(first_obs) + " is outside [0, n_obs = " + std::to_string(p->n_obs) + "]");
@@ -813,34 +832,38 @@ int gilxs_decide(const char *who, const gil_params *p, const gilx_variants *v, i
     info.work_bytes = (int64_t)p->L * 16;
     const int64_t S = p->n_systems, O = p->n_obs;
     info.output_bytes = xi.output_bytes + S * (O * 32 + (int64_t)k_max * 24 + 8) + (rows ? S * O * info.row_len * 8 : 0);
-    return gil_refuse_plan_bytes(who, g_gilxs_err, info.work_bytes, info.output_bytes);
+    return gil_refuse_plan_bytes(who, err, info.work_bytes, info.output_bytes);
 }
 
 // gilx_run's driver, and with ex.xs gilxs_run's: the variant tables, the launch order, the seeds and streams and the window
-// outputs are its own, the rest is the staging path batch_run takes
+// outputs are its own, the rest is the staging path batch_run takes.  With ex.rs (gilxr_run, gilxsr_run) the launch is a segment:
+// the start state, the slot counts and the window sums so far are the checkpoint's (gilxr_prepare has checked them), no start
+// state is read from io, and xs->first_obs counts within the slice.
 int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, const GilExtras &ex) {
     const GilxsCall *xs = ex.xs;
-    const char *who = xs ? "gilxs_run" : "gilx_run";
-    std::string &err = xs ? g_gilxs_err : g_gilx_err;
+    GilrCall *rs = ex.rs;
+    const char *who = rs ? (xs ? "gilxsr_run" : "gilxr_run") : xs ? "gilxs_run" : "gilx_run";
+    std::string &err = rs ? g_gilxr_err : xs ? g_gilxs_err : g_gilx_err;
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilx_plan_info info; GilxTables tb;
     gilxs_plan_info sinfo{};
     if (xs) {
-        if (int rc = gilxs_decide(who, p, v, xs->k_max, xs->first_obs, io.states(), xs->structure_obs != nullptr, sinfo, tb)) return rc;
+        if (int rc = gilxs_decide(who, err, p, v, xs->k_max, xs->first_obs, io.states(), xs->structure_obs != nullptr, sinfo, tb)) return rc;
         info = gilx_plan_info{};
         info.threads = sinfo.threads; info.lds_bytes = sinfo.lds_bytes;
-    } else if (int rc = gilx_decide(who, p, v, io.states(), info, tb)) return rc;
+    } else if (int rc = gilx_decide(who, p, v, io.states(), info, tb, err)) return rc;
     const int S = p->n_systems, V = v->n_variants, NT = info.threads;
-    { const std::string why = gil_check_start(p, io, nullptr); if (!why.empty()) return bad(why); }
+    if (!rs) { const std::string why = gil_check_start(p, io, nullptr); if (!why.empty()) return bad(why); }
     if (const char *why = gil_check_flip_table(p)) return bad(why);
+    const int32_t *slots = rs ? rs->n_slots.data() : io.n0;    // every system's slot count
     std::vector<int32_t> order((size_t)S), stream((size_t)S);
     std::vector<uint64_t> seed((size_t)S);
     for (int s = 0; s < S; ++s) { order[(size_t)s] = v->order ? v->order[s] : s; stream[(size_t)s] = v->stream ? v->stream[s] : s; seed[(size_t)s] = v->seed ? v->seed[s] : p->seed; }
-    if (!v->order) std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return io.n0[x] > io.n0[y]; });   // long systems first
+    if (!v->order) std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return slots[x] > slots[y]; });   // long systems first
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: slots beyond n0 and rows never reached stay zero
     if (int rc = job.select_device(p->device)) return rc;
     if (xs) if (int rc = gil_refuse_device_bytes(job, sinfo.work_bytes, sinfo.output_bytes)) return rc;
-    GilxsBatchArgs a{};
+    GilxsrBatchArgs a{};                                        // the driver's one struct: every mixed launch's arguments are a base of it
     a.p = *p; a.p.sigma_grid = 0.0; a.p.block_table = nullptr;
     a.tlen = tb.max_tlen; a.chunk = (p->n_cap + NT - 1) / NT;    // the layout's table length; the kernel takes every system's own chunk
     a.m = gil_model(p);
@@ -849,14 +872,25 @@ int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, cons
     a.mx.has_block = v->block_table ? 1 : 0;
     UP(mx.order, order.data(), (size_t)S); UP(mx.variant_of_system, v->variant_of_system, (size_t)S); UP(mx.variants, tb.var.data(), (size_t)V);
     UP(mx.seed, seed.data(), (size_t)S); UP(mx.stream, stream.data(), (size_t)S);
+    if (rs) {                                                  // io has no start state: the slot counts take n0's place
+        UP(n0, slots, (size_t)S);
+        if (int rc = gil_stage_checkpoint(job, a.rs, p, *rs, true)) return rc;
+    }
+    const bool carried = rs && xs && rs->xfrom;                // the window sums so far, instead of zeros
     if (xs) {
         if (int rc = gil_stage_structure(job, a, p, xs->k_max, xs->first_obs, xs->structure_obs != nullptr, sinfo.phase_in_lds != 0)) return rc;
-        WORK(wn.head, SO * 4); WORK(wn.window, (size_t)S * 3 * xs->k_max); WORK(wn.n_window, (size_t)S); WORK(wn.n_empty, (size_t)S);
+        WORK(wn.head, SO * 4);
+        if (carried) { UP(wn.window, rs->xfrom->window, (size_t)S * 3 * xs->k_max); UP(wn.n_window, rs->xfrom->n_window, (size_t)S); UP(wn.n_empty, rs->xfrom->n_empty, (size_t)S); }
+        else { WORK(wn.window, (size_t)S * 3 * xs->k_max); WORK(wn.n_window, (size_t)S); WORK(wn.n_empty, (size_t)S); }
     }
     if (int rc = job.create_events()) return rc;
-    if (int rc = xs ? gil_launch<GilKind::MixedStructure>(job, NT, S, lds, a) : gil_launch<GilKind::Mixed>(job, NT, S, lds, a)) return rc;
+    GilxrBatchArgs b{};                                         // gilxr_run's arguments: the mixed launch's own and the checkpoint
+    static_cast<GilxBatchArgs &>(b) = a; b.rs = a.rs;
+    if (int rc = rs ? (xs ? gil_launch<GilKind::MixedStructureResume>(job, NT, S, lds, a) : gil_launch<GilKind::MixedResume>(job, NT, S, lds, b))
+                    : (xs ? gil_launch<GilKind::MixedStructure>(job, NT, S, lds, a) : gil_launch<GilKind::Mixed>(job, NT, S, lds, a))) return rc;
     if (int rc = job.finish(hipGetLastError(), "gil_kernel (mixed)", io.kernel_ms)) return rc;
     if (int rc = gil_fetch_common(job, a, p, io)) return rc;
+    if (rs) if (int rc = gil_fetch_checkpoint(job, *rs, p, a.rs.pos_out, a.rs.ref_out, a.rs.flg_out)) return rc;
     if (xs) {
         if (int rc = gil_fetch_structure(job, a, p, xs->structure_obs)) return rc;
         if (int rc = job.download(xs->head_obs, a.wn.head, SO * 4 * 8, "head_obs")) return rc;
@@ -867,9 +901,76 @@ int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, cons
     return GIL_OK;
 }
 
+// gilxr_run, gilxmr_run (large) and gilxsr_run (xs: k_max, the ABSOLUTE first_obs, structure_obs, head_obs; its window outputs are
+// filled in here): the start state is checked and laid out here (gilxr_prepare), the launch is the shape's own mixed driver
+int gilxr_drive(bool large, const char *who, const gil_params *p, const gilx_variants *v, const GilIo &io, const GilxsCall *xs,
+                int32_t obs_first, const gilx_checkpoint *from, gilx_checkpoint *to) {
+    auto bad = [&](const std::string &m) { g_gilxr_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    if (!p || !v || !p->beta || !p->times_obs || !v->variant_of_system || (!from && (!io.n0 || !io.pos0 || !io.sigma0)) || (xs && !xs->head_obs))
+        return bad("null argument");
+    if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0 || p->L < 2 || p->K < 1) return bad("bad n_systems / n_cap / n_obs / max_events / L / K");
+    const size_t S = (size_t)p->n_systems;
+    if (xs && xs->first_obs < 0) return bad("first_obs = " + std::to_string(xs->first_obs) + " must not be negative: it is an index on the run's observation grid");
+    if (!from) { const std::string why = gil_check_start(p, io, nullptr); if (!why.empty()) return bad(why); }
+    GilrCall call;
+    const std::string why = gilxr_prepare(p, xs ? xs->k_max : 0, io.n0, io.pos0, io.sigma0, io.bound0, obs_first, from, to, call);
+    if (!why.empty()) return bad(why);
+    std::vector<int32_t> nrec(S, 0);                           // the checkpoint needs these three whether or not the caller wants them
+    std::vector<int64_t> nev(S, 0);
+    std::vector<double> tfin(S, 0.0);
+    GilIo run = io;                                            // the launch's own record: no start state, the three outputs here
+    run.n0 = run.pos0 = nullptr; run.sigma0 = nullptr; run.bound0 = nullptr;
+    run.n_recorded = nrec.data(); run.n_events = nev.data(); run.t_final = tfin.data();
+    GilExtras ex; ex.rs = &call;
+    GilxsCall slice{};                                         // the window starts at row first_obs - obs_first of this slice, within [0, n_obs]
+    if (xs) {
+        slice = *xs;
+        slice.first_obs = (int)std::min<int64_t>(std::max<int64_t>((int64_t)xs->first_obs - obs_first, 0), p->n_obs);
+        slice.window = to ? to->window : nullptr; slice.n_window = to ? to->n_window : nullptr; slice.n_empty = to ? to->n_empty : nullptr;
+        ex.xs = &slice;
+    }
+    if (large) ex.mx = v;
+    if (int rc = large ? gil_large_run(who, g_gilxr_err, p, run, ex) : mixed_run(p, v, run, ex)) return rc;
+    gilxr_finish(p, call, nrec.data(), nev.data(), tfin.data());
+    for (size_t s = 0; s < S; ++s) {
+        if (io.n_recorded) io.n_recorded[s] = nrec[s];
+        if (io.n_events) io.n_events[s] = nev[s];
+        if (io.t_final) io.t_final[s] = tfin[s];
+    }
+    return GIL_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+const char *gilxr_last_error(void) { return g_gilxr_err.c_str(); }
+
+int gilxr_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
+              const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+              int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
+              int32_t obs_first, const gilx_checkpoint *from, gilx_checkpoint *to) {
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    return gilxr_drive(false, "gilxr_run", p, v, io, nullptr, obs_first, from, to);
+}
+
+int gilxmr_run(const gil_params *p, const gilx_variants *v, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0,
+               const double *uniforms, int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs,
+               int32_t *n_recorded, int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *kernel_ms,
+               int32_t obs_first, const gilx_checkpoint *from, gilx_checkpoint *to) {
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    return gilxr_drive(true, "gilxmr_run", p, v, io, nullptr, obs_first, from, to);
+}
+
+int gilxsr_run(const gil_params *p, const gilx_variants *v, int32_t k_max, int32_t first_obs,
+               const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0, const double *uniforms,
+               int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
+               int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, double *structure_obs, double *head_obs,
+               double *kernel_ms, int32_t obs_first, const gilx_checkpoint *from, gilx_checkpoint *to) {
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    const GilxsCall xs{k_max, first_obs, structure_obs, head_obs, nullptr, nullptr, nullptr};
+    return gilxr_drive(false, "gilxsr_run", p, v, io, &xs, obs_first, from, to);
+}
 
 const char *gilx_last_error(void) { return g_gilx_err.c_str(); }
 
@@ -895,7 +996,7 @@ int gilxs_plan(const gil_params *p, const gilx_variants *v, int32_t k_max, int32
                gilxs_plan_info *out) {
     if (!p || !v || !out) { g_gilxs_err = "gilxs_plan: null argument"; return GIL_ERR_ARG; }
     gilxs_plan_info info; GilxTables tb;
-    if (int rc = gilxs_decide("gilxs_plan", p, v, k_max, first_obs, want_states != 0, want_rows != 0, info, tb)) return rc;
+    if (int rc = gilxs_decide("gilxs_plan", g_gilxs_err, p, v, k_max, first_obs, want_states != 0, want_rows != 0, info, tb)) return rc;
     *out = info;
     return GIL_OK;
 }

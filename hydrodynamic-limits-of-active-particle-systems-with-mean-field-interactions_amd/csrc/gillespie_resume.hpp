@@ -1,4 +1,5 @@
-// gillespie_resume.hpp -- what the resumable instantiations of the two exact-loop kernels share (include/gillespie_resume.h):
+// gillespie_resume.hpp -- what the resumable instantiations of the two exact-loop kernels share (include/gillespie_resume.h, and
+// for mixed batches include/gillespie_mixed_resume.h):
 // the start state a launch reads instead of n0 / pos0 / sigma0 / bound0, where it leaves its end state, and the host side
 // that checks a checkpoint, makes one of a fresh initial state, and fills the caller's from the launch's outputs.
 #pragma once
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "gillespie_resume.h"
+#include "gillespie_mixed_resume.h"
 
 // Host side: the start state of a launch, checked, and what to do with its end.
 struct GilrCall {
@@ -19,6 +21,12 @@ struct GilrCall {
     std::vector<int64_t> n_ev;
     int32_t fresh = 0, obs_first = 0;
     gil_checkpoint *to = nullptr;
+    // a mixed launch (include/gillespie_mixed_resume.h, gilxr_prepare) also has every system's slot count and, with the
+    // structure sums (k_max > 0), the window accumulators it starts from (null: zero) and where they go at the end
+    std::vector<int32_t> n_slots;
+    int32_t k_max = 0;
+    const gilx_checkpoint *xfrom = nullptr;
+    gilx_checkpoint *xto = nullptr;
 };
 
 namespace {
@@ -95,6 +103,44 @@ inline void gilr_finish(const gil_params *p, GilrCall &c, int32_t *n_recorded, c
         c.to->t[s] = t_final[s]; c.to->n_events[s] = n_events[s];
         c.to->next_obs[s] = c.skipped[s] ? c.next_obs[s] : c.obs_first + n_recorded[s];
     }
+}
+
+// The same for a mixed launch: gilr_prepare on the checkpoint's base, then what gilx_checkpoint adds -- the slot counts (from
+// n0 on a fresh start) and, where k_max > 0 (a structure launch), the window sums.
+inline std::string gilxr_prepare(const gil_params *p, int32_t k_max, const int32_t *n0, const int32_t *pos0, const int8_t *sigma0,
+                                 const uint8_t *bound0, int32_t obs_first, const gilx_checkpoint *from, gilx_checkpoint *to, GilrCall &c) {
+    const size_t S = (size_t)p->n_systems, N = (size_t)p->n_cap;
+    if (to && !to->n_slots) return "null n_slots in the checkpoint `to`";
+    if (to && k_max > 0 && !(to->window && to->n_window && to->n_empty)) return "null window, n_window or n_empty in the checkpoint `to` with k_max > 0";
+    if (from && !from->n_slots) return "null n_slots in the checkpoint `from`";
+    if (from && k_max > 0 && !(from->window && from->n_window && from->n_empty)) return "checkpoint: null window, n_window or n_empty with k_max > 0";
+    const std::string why = gilr_prepare(p, n0, pos0, sigma0, bound0, obs_first, from ? &from->base : nullptr, to ? &to->base : nullptr, c);
+    if (!why.empty()) return why;
+    c.k_max = k_max; c.xfrom = from; c.xto = to;
+    c.n_slots.assign(S, 0);
+    if (!from) { for (size_t s = 0; s < S; ++s) c.n_slots[s] = n0[s]; return ""; }
+    for (size_t s = 0; s < S; ++s) {
+        const int32_t ns = from->n_slots[s];
+        if (ns < 0 || (size_t)ns > N)
+            return "checkpoint: n_slots = " + std::to_string(ns) + " of system " + std::to_string(s) + " is outside [0, n_cap = " + std::to_string(N) + "]";
+        for (size_t i = (size_t)ns; i < N; ++i)
+            if (from->base.flags[s * N + i])
+                return "checkpoint: slot " + std::to_string(i) + " of system " + std::to_string(s) + " has flags " + std::to_string((int)from->base.flags[s * N + i]) +
+                       " but lies at or beyond n_slots = " + std::to_string(ns);
+        c.n_slots[s] = ns;
+    }
+    if (k_max > 0)
+        for (size_t s = 0; s < S; ++s) {
+            if (from->n_window[s] < 0) return "checkpoint: negative n_window = " + std::to_string(from->n_window[s]) + " of system " + std::to_string(s);
+            if (from->n_empty[s] < 0) return "checkpoint: negative n_empty = " + std::to_string(from->n_empty[s]) + " of system " + std::to_string(s);
+        }
+    return "";
+}
+
+// After a mixed launch: gilr_finish, and the slot counts.  The window sums were downloaded into `to` by the driver.
+inline void gilxr_finish(const gil_params *p, GilrCall &c, int32_t *n_recorded, const int64_t *n_events, const double *t_final) {
+    gilr_finish(p, c, n_recorded, n_events, t_final);
+    if (c.xto) for (size_t s = 0; s < (size_t)p->n_systems; ++s) c.xto->n_slots[s] = c.n_slots[s];
 }
 
 }  // namespace

@@ -86,14 +86,33 @@ def _beta_statistics(rows, owner, beta_values):
     return out
 
 
-def _sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_kwargs, rng_seeds, on_device, dynamics, allow_large=False):
+def _chain_keywords(who, one_launch, stepper, obs_per_launch, resume, return_checkpoint):
+    """The keywords a sweep passes on to its mixed launch for a run in segments (gillespie.MixedCheckpoint), or ValueError where
+    there is no such launch: `stepper` (the fixed-dt dynamics), or a sweep that is not one launch."""
+    given = [k for k, v in (("obs_per_launch", obs_per_launch), ("resume", resume), ("return_checkpoint", return_checkpoint or None)) if v is not None]
+    if not given:
+        return {}
+    if stepper:
+        raise ValueError(f"{given[0]} needs the exact dynamics; the fixed-dt stepper has no checkpointed launch")
+    if not one_launch:
+        raise ValueError(f"{who}: {given[0]} needs one_launch=True; the loop of one launch per case has no common checkpoint")
+    return dict(obs_per_launch=obs_per_launch, resume=resume, return_checkpoint=bool(return_checkpoint))
+
+
+def _is_stepper(ps_kwargs, dynamics):
+    ps_kwargs = ps_kwargs or {}
+    return dynamics == "sync" or (dynamics is None and (ps_kwargs.get("dt") is not None or ps_kwargs.get("mode") == "sync"))
+
+
+def _sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_kwargs, rng_seeds, on_device, dynamics, allow_large=False, chain=None):
     """One sweep_over_betas per case = (ps_kwargs, init_kwargs), all cases in ONE mixed launch of the exact event loop
     (gillespie.run_batched_exact_statistics_mixed / run_batched_exact_mixed).  The systems are built in the order of the host
     loop, and every case is a group of the launch: its systems draw what the case's own launch draws.  Returns the list of the
     per-case sweep dictionaries.  ValueError where no mixed launch exists: the fixed-dt stepper, a large shape (L > 4096 or
-    N > 2048) without `allow_large`, a launch over the 160 KB of LDS."""
+    N > 2048) without `allow_large`, a launch over the 160 KB of LDS.  `chain` (_chain_keywords): the launch in segments; with
+    its return_checkpoint the result is (the list, the MixedCheckpoint)."""
     from . import gillespie
-    run_kwargs = dict(run_kwargs or {})
+    run_kwargs, chain = dict(run_kwargs or {}), dict(chain or {})
     for ps_kwargs, _ in cases:
         d = dynamics
         if d is None:
@@ -112,12 +131,17 @@ def _sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_kwargs, 
                 owner.append(bi)
     if on_device:
         slim = {k: v for k, v in run_kwargs.items() if k in ("T", "obs_dt")}
-        rows = gillespie.run_batched_exact_statistics_mixed(systems, groups=group, allow_large=allow_large, **slim)
+        rows = gillespie.run_batched_exact_statistics_mixed(systems, groups=group, allow_large=allow_large, **slim, **chain)
     else:
-        outs = gillespie.run_batched_exact_mixed(systems, want_m_local=False, groups=group, allow_large=allow_large, **run_kwargs)
-        rows = [observables.run_observables(out, ps.L, ps.dx) for ps, out in zip(systems, outs)]
+        rows = gillespie.run_batched_exact_mixed(systems, want_m_local=False, groups=group, allow_large=allow_large, **run_kwargs, **chain)
+    ck = None
+    if chain.get("return_checkpoint"):
+        rows, ck = rows
+    if not on_device:
+        rows = [observables.run_observables(out, ps.L, ps.dx) for ps, out in zip(systems, rows)]
     per = len(beta_values) * n_runs_per_beta
-    return [_beta_statistics(rows[ci * per:(ci + 1) * per], owner[ci * per:(ci + 1) * per], beta_values) for ci in range(len(cases))]
+    sweeps = [_beta_statistics(rows[ci * per:(ci + 1) * per], owner[ci * per:(ci + 1) * per], beta_values) for ci in range(len(cases))]
+    return (sweeps, ck) if chain.get("return_checkpoint") else sweeps
 
 
 def sweep_beta_ensemble(beta, n_runs=10, ps_kwargs=None, init_kwargs=None, run_kwargs=None, rng_seeds=None):
@@ -131,7 +155,8 @@ def sweep_beta_ensemble(beta, n_runs=10, ps_kwargs=None, init_kwargs=None, run_k
 
 
 def sweep_over_sigmas(sigma_values, beta_values, n_runs_per_beta=5, ps_kwargs=None, init_kwargs=None, run_kwargs=None,
-                      rng_seeds=None, on_device=False, dynamics=None, one_launch=False, allow_large=False):
+                      rng_seeds=None, on_device=False, dynamics=None, one_launch=False, allow_large=False, obs_per_launch=None,
+                      resume=None, return_checkpoint=False):
     """The sigma sweep of PARTICLE_solver_BIOLOGY_EXCLUSION_sweep_beta_2.py:1030-1075: for every interaction range
     `local_kernel_sigma` a whole beta sweep (one GPU handle per sigma: the weight table changes; sigma = 0 selects the global
     mean field, sigma wider than the box the folded table).  Returns {sigma: {"beta", "v_mean", "v_se", "D_mean", "D_se",
@@ -141,22 +166,30 @@ def sweep_over_sigmas(sigma_values, beta_values, n_runs_per_beta=5, ps_kwargs=No
     `allow_large=True` (with one_launch): a large shape (L > 4096 or N > 2048) is one mixed launch of the large-system kernel
     (include/gillespie_mixed_many.h) instead of a ValueError.  Its numbers equal the host loop's where every case of the sweep is
     itself a large shape, which is always so when L > 4096; cases below the limit in a sweep that straddles it run on the large
-    kernel with its keys and equal gillespie.run_many_large_raw for them, not the batch kernel."""
+    kernel with its keys and equal gillespie.run_many_large_raw for them, not the batch kernel.
+    `obs_per_launch=n`, `resume=MixedCheckpoint`, `return_checkpoint=True` (with one_launch, exact dynamics): the one launch as a
+    chain of launches of at most n observations, started from a checkpoint of the same sweep, and returning (results, checkpoint)
+    (gillespie.run_batched_exact_mixed); the numbers are the one launch's, bit for bit.  ValueError without one_launch or under
+    the fixed-dt stepper."""
     results = {}
     kws = [dict(ps_kwargs or {}, local_kernel_sigma=float(sigma)) for sigma in sigma_values]
+    chain = _chain_keywords("sweep_over_sigmas", one_launch, _is_stepper(ps_kwargs, dynamics), obs_per_launch, resume, return_checkpoint)
     if one_launch:
         sweeps = _sweeps_in_one_launch("sweep_over_sigmas", [(kw, dict(init_kwargs or {})) for kw in kws], beta_values, n_runs_per_beta,
-                                       run_kwargs, rng_seeds, on_device, dynamics, allow_large)
+                                       run_kwargs, rng_seeds, on_device, dynamics, allow_large, chain)
+        if return_checkpoint:
+            sweeps, ck = sweeps
     for si, (sigma, kw) in enumerate(zip(sigma_values, kws)):
         r = sweeps[si] if one_launch else sweep_over_betas(beta_values, n_runs_per_beta, kw, init_kwargs, run_kwargs, rng_seeds,
                                                            on_device=on_device, dynamics=dynamics)
         results[sigma] = {"beta": np.asarray(beta_values, dtype=float), "v_mean": r["means"], "v_se": r["ses"], "D_mean": r["D_means"],
                           "D_se": r["D_ses"], "m_mean": r["m_means"], "block_mean": r["block_means"], "ps_kwargs": kw}
-    return results
+    return (results, ck) if return_checkpoint else results
 
 
 def sweep_over_densities(n_part_values, beta_values, n_runs_per_beta=4, ps_kwargs=None, init_kwargs=None, run_kwargs=None,
-                         rng_seeds=None, on_device=False, dynamics=None, one_launch=False, allow_large=False):
+                         rng_seeds=None, on_device=False, dynamics=None, one_launch=False, allow_large=False, obs_per_launch=None,
+                         resume=None, return_checkpoint=False):
     """The density x beta double sweep of PARTICLE_solver_BIOLOGY_EXCLUSION_double_sweep.py:851-861
     (`list_N_part = np.linspace(50, 950, 19)`: N arrives as a float there and is used as an integer): one batched beta sweep
     per particle number.  Returns a list of the per-N sweep dictionaries (keys of `sweep_over_betas`) with "N_part" added;
@@ -167,21 +200,25 @@ def sweep_over_densities(n_part_values, beta_values, n_runs_per_beta=4, ps_kwarg
     stepper, a large shape or a launch over the LDS limit.
     `allow_large=True` (with one_launch): as in sweep_over_sigmas.  Here a sweep straddles the limit when L <= 4096 and only some
     particle numbers exceed 2048: the launch is then the large kernel's for all of them, and the particle numbers below the limit
-    equal gillespie.run_many_large_raw, not the host loop's batch kernel."""
+    equal gillespie.run_many_large_raw, not the host loop's batch kernel.
+    `obs_per_launch`, `resume`, `return_checkpoint`: as in sweep_over_sigmas."""
     out = []
     for n_part in n_part_values:
         if float(n_part) != int(n_part):
             raise ValueError("particle numbers must be integral")
     iks = [dict(init_kwargs or {}, N=int(n_part)) for n_part in n_part_values]
+    chain = _chain_keywords("sweep_over_densities", one_launch, _is_stepper(ps_kwargs, dynamics), obs_per_launch, resume, return_checkpoint)
     if one_launch:
         sweeps = _sweeps_in_one_launch("sweep_over_densities", [(dict(ps_kwargs or {}), ik) for ik in iks], beta_values, n_runs_per_beta,
-                                       run_kwargs, rng_seeds, on_device, dynamics, allow_large)
+                                       run_kwargs, rng_seeds, on_device, dynamics, allow_large, chain)
+        if return_checkpoint:
+            sweeps, ck = sweeps
     for ni, (n_part, ik) in enumerate(zip(n_part_values, iks)):
         r = sweeps[ni] if one_launch else sweep_over_betas(beta_values, n_runs_per_beta, ps_kwargs, ik, run_kwargs, rng_seeds,
                                                            on_device=on_device, dynamics=dynamics)
         r["N_part"] = int(n_part)
         out.append(r)
-    return out
+    return (out, ck) if return_checkpoint else out
 
 
 def structure_ensemble_statistics(rows):
@@ -234,7 +271,8 @@ def sweep_betas_for_structures(beta_values, n_runs_per_beta, ps_kwargs, init_kwa
 
 
 def sweep_sigmas_for_structures(sigma_values, beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwargs, start_fraction=0.5,
-                                k_max=None, rng_seeds=None, one_launch=True, return_series=False):
+                                k_max=None, rng_seeds=None, one_launch=True, return_series=False, obs_per_launch=None, resume=None,
+                                return_checkpoint=False):
     """The pattern study over the interaction range: for every `local_kernel_sigma` of `sigma_values` the structure sweep of
     sweep_betas_for_structures -- the particle counterpart of pde.sweep_over_kernel_sigmas and of the reference's
     IMEX_PDE_solver_run_sweep_magn*.py.  Returns {sigma: {beta: structure_ensemble_statistics(...)}}.
@@ -247,10 +285,13 @@ def sweep_sigmas_for_structures(sigma_values, beta_values, n_runs_per_beta, ps_k
     means over the runs of |m|(t) and var(total)(t): the arrays the PDE width sweep records per width.
     Exact dynamics only: ValueError for the fixed-dt stepper (`dt` or `mode="sync"` in ps_kwargs) and, with one_launch, for a
     large shape (L > 4096 or N > 2048), neither of which has a mixed launch -- raised here before any system is built where the
-    numbers are known (L, and N of init="fixed"), and by the launch's own check once a Poisson initial state is drawn; `run_kwargs` may hold T, obs_dt, record_fft, record_var."""
+    numbers are known (L, and N of init="fixed"), and by the launch's own check once a Poisson initial state is drawn; `run_kwargs` may hold T, obs_dt, record_fft, record_var.
+    `obs_per_launch`, `resume`, `return_checkpoint` (with one_launch): as in sweep_over_sigmas; the window sums travel in the
+    MixedCheckpoint (gillespie.run_batched_exact_structure_mixed), and (results[, series], checkpoint) is returned."""
     from . import gillespie
     who = "sweep_sigmas_for_structures"
     ps_kwargs, init_kwargs, run_kwargs = dict(ps_kwargs or {}), dict(init_kwargs or {}), dict(run_kwargs or {})
+    chain = _chain_keywords(who, one_launch, _is_stepper(ps_kwargs, None), obs_per_launch, resume, return_checkpoint)
     if ps_kwargs.get("dt") is not None or ps_kwargs.get("mode") == "sync":
         raise ValueError(f"{who} needs the exact dynamics; the fixed-dt stepper has no mixed launch")
     unknown = set(run_kwargs) - {"T", "obs_dt", "record_fft", "record_var"}
@@ -273,7 +314,9 @@ def sweep_sigmas_for_structures(sigma_values, beta_values, n_runs_per_beta, ps_k
     per = len(beta_values) * n_runs_per_beta
     if one_launch:
         rows = gillespie.run_batched_exact_structure_mixed(systems, start_fraction=start_fraction, k_max=k_max, groups=group,
-                                                           reduce="device", return_series=return_series, **slim)
+                                                           reduce="device", return_series=return_series, **slim, **chain)
+        if return_checkpoint:
+            rows, ck = rows
     else:
         rows = []
         for si in range(len(sigma_values)):
@@ -295,7 +338,10 @@ def sweep_sigmas_for_structures(sigma_values, beta_values, n_runs_per_beta, ps_k
             by_beta = [[{k: v for k, v in row.items() if k not in ("times_obs", "m_series", "var_series", "fft_amp_series")} for row in sel]
                        for sel in by_beta]
         results[sigma] = {beta: structure_ensemble_statistics(sel) for beta, sel in zip(beta_values, by_beta)}
-    return (results, series) if return_series else results
+    out = (results, series) if return_series else (results,)
+    if return_checkpoint:
+        out += (ck,)
+    return out if len(out) > 1 else out[0]
 
 
 def sweep_beta_structure_ensemble(beta, n_runs, ps_kwargs, init_kwargs, run_kwargs, start_fraction=0.5, k_max=None, rng_seeds=None,

@@ -10,7 +10,8 @@ the interaction range or in the blocking threshold of their particle number shar
 (`run_batched_exact_mixed`, `run_batched_exact_statistics_mixed`, include/gillespie_mixed.h; with `allow_large=True` also systems
 beyond one workgroup's LDS, include/gillespie_mixed_many.h); the structure observables of such a batch come from sums the
 mixed launch takes and reduces over the window on the device (`run_batched_exact_structure_mixed`,
-include/gillespie_mixed_structure.h).
+include/gillespie_mixed_structure.h).  A run may be cut into segments and resumed bit for bit (`Checkpoint`,
+include/gillespie_resume.h), a mixed batch too (`MixedCheckpoint`, include/gillespie_mixed_resume.h).
 
 Differences to the reference: randomness is Philox4x32-10 keyed by `seed` (the reference consumes a NumPy Generator), so
 trajectories agree in distribution, not draw for draw; `m_local_list[k]` is the field of the observed state (the
@@ -90,6 +91,11 @@ class GilCheckpoint(C.Structure):
                 ("next_obs", C.c_void_p)]
 
 
+class GilxCheckpoint(C.Structure):
+    """struct gilx_checkpoint of include/gillespie_mixed_resume.h, field for field."""
+    _fields_ = [("base", GilCheckpoint), ("n_slots", C.c_void_p), ("window", C.c_void_p), ("n_window", C.c_void_p), ("n_empty", C.c_void_p)]
+
+
 GILR_PLUS, GILR_BOUND, GILR_ALIVE = 1, 2, 4     # bits of a checkpoint's flags
 GILX_MAX_VARIANTS = 4096
 GILX_LDS_LIMIT = 160 * 1024     # bytes of LDS a workgroup can have: what a mixed launch must fit
@@ -100,7 +106,7 @@ CAPTURE_COLUMNS = ("n", "n_bound", "binds", "unbinds", "exits", "occupied_sites"
 
 
 _I32, _DBL, _PTR, _MS = C.c_int32, C.c_double, C.c_void_p, C.POINTER(C.c_double)
-_PAR, _VAR, _CKP = C.POINTER(GilParams), C.POINTER(GilxVariants), C.POINTER(GilCheckpoint)
+_PAR, _VAR, _CKP, _XCKP = C.POINTER(GilParams), C.POINTER(GilxVariants), C.POINTER(GilCheckpoint), C.POINTER(GilxCheckpoint)
 N_COMMON = 14       # n0, pos0, sigma0, bound0, uniforms; pos, sigma, flags, scalars, n_recorded, n_events, t_final, exits, n_exits
 
 
@@ -183,6 +189,59 @@ def _stage_mixed_structure(c, *, mixed, k_max, first_obs, want_rows, **_):
                  bytes_back=int(sum(x.nbytes for x in back if x is not None))))
 
 
+def _mixed_checkpoints(c, obs_first, kk):
+    """The gilx_checkpoint to start from (None: a fresh start) and the one to fill, with the dictionary of the latter's arrays
+    and the first row of every system; kk > 0: with the window sums of kk modes.  c.ck_more holds what the caller's checkpoint
+    has beyond the six arrays of c.ck_in."""
+    ck_out = {k: np.zeros((c.S, c.ncap)[:nd], dt) for k, dt, nd in CHECKPOINT_ARRAYS}
+    ck_out["n_slots"] = np.zeros(c.S, np.int32)
+    if kk > 0:
+        ck_out.update(window=np.zeros((c.S, kk, 3)), n_window=np.zeros(c.S, np.int32), n_empty=np.zeros(c.S, np.int32))
+
+    def struct(arrays):
+        more = {k: _p(arrays[k]).value for k in ("n_slots", "window", "n_window", "n_empty") if arrays.get(k) is not None}
+        return GilxCheckpoint(base=GilCheckpoint(**{k: _p(arrays[k]).value for k, _, _ in CHECKPOINT_ARRAYS}), **more)
+
+    c_in, first_row = None, np.zeros(c.S, np.int32)
+    if c.ck_in is not None:
+        more = {}
+        for k, dt, shape in (("n_slots", np.int32, (c.S,)), ("window", np.float64, (c.S, kk, 3)), ("n_window", np.int32, (c.S,)), ("n_empty", np.int32, (c.S,))):
+            if c.ck_more.get(k) is None or (kk == 0 and k != "n_slots"):
+                continue                                       # a missing array is the library's to refuse
+            more[k] = np.ascontiguousarray(c.ck_more[k], dtype=dt)
+            if more[k].shape != shape:
+                raise ValueError(f"checkpoint: {k} must have the shape {shape}")
+        arrays = dict(c.ck_in, **more)
+        c.keep.append(arrays)
+        c_in = struct(arrays)
+        first_row = np.clip(c.ck_in["next_obs"] - int(obs_first), 0, None).astype(np.int32)
+        first_row[c.ck_in["next_obs"] < int(obs_first)] = 0        # ended before this segment: n_recorded is 0 too
+    c_out = struct(ck_out)
+    c.keep.append((c_in, c_out))
+    return [int(obs_first), None if c_in is None else C.byref(c_in), C.byref(c_out)], ck_out, first_row
+
+
+def _stage_mixed_resumable(c, *, mixed, obs_first, **_):
+    """the variants in front; obs_first, the checkpoint to start from and the one to fill behind kernel_ms"""
+    front = _stage_mixed(c, mixed=mixed)[0]
+    tail, ck_out, first_row = _mixed_checkpoints(c, obs_first, 0)
+    return front, [], tail, dict(checkpoint=ck_out, first_row=first_row, obs_first=int(obs_first), n0=ck_out["n_slots"])
+
+
+def _stage_mixed_structure_resumable(c, *, mixed, k_max, first_obs, want_rows, obs_first, **_):
+    """_stage_mixed_structure where the window sums travel in the checkpoints: rows and head behind the common outputs"""
+    front = _stage_mixed(c, mixed=mixed)[0]
+    kk = max(int(k_max), 0)
+    rows = np.zeros((c.S, c.M, 4 + 2 * kk)) if want_rows else None
+    head = np.zeros((c.S, c.M, 4))
+    tail, ck_out, first_row = _mixed_checkpoints(c, obs_first, kk)
+    back = c.results + [rows, head] + [ck_out.get(k) for k in ("window", "n_window", "n_empty")]
+    return (front + [int(k_max), int(first_obs)], [_p(rows), _p(head)], tail,
+            dict(structure=rows, head=head, window=ck_out.get("window"), n_window=ck_out.get("n_window"), n_empty=ck_out.get("n_empty"),
+                 checkpoint=ck_out, first_row=first_row, obs_first=int(obs_first), n0=ck_out["n_slots"],
+                 bytes_back=int(sum(x.nbytes for x in back if x is not None))))
+
+
 class _Entry:
     """last_error; the C types in `front` of the common pointers, `behind` them and, after kernel_ms, in the `tail`; `stage`;
     `header`: named by the error of a call that finds the entry point missing in the loaded library; `finish`: like `stage`, what a
@@ -205,6 +264,11 @@ ENTRIES = {
     "gilx_run": _Entry("gilx_last_error", _stage_mixed, [_VAR]),   # a variant per system
     "gilxs_run": _Entry("gilxs_last_error", _stage_mixed_structure, [_VAR, _I32, _I32], [_PTR] * 5),
     "gilxm_run": _Entry("gilxm_last_error", _stage_mixed, [_VAR], header="include/gillespie_mixed_many.h"),   # the same, large systems
+    # one segment of a mixed run: systems in LDS, large systems, systems in LDS with the structure sums
+    "gilxr_run": _Entry("gilxr_last_error", _stage_mixed_resumable, [_VAR], tail=[_I32, _XCKP, _XCKP], header="include/gillespie_mixed_resume.h"),
+    "gilxmr_run": _Entry("gilxr_last_error", _stage_mixed_resumable, [_VAR], tail=[_I32, _XCKP, _XCKP], header="include/gillespie_mixed_resume.h"),
+    "gilxsr_run": _Entry("gilxr_last_error", _stage_mixed_structure_resumable, [_VAR, _I32, _I32], [_PTR] * 2, [_I32, _XCKP, _XCKP],
+                         header="include/gillespie_mixed_resume.h"),
 }
 # the plans: name -> (last_error, the C types between gil_params and the info structure, the info structure)
 PLANS = {
@@ -505,6 +569,37 @@ def run_mixed_structure_raw(*, L, K, periodic, sigma_grids, variant_of_system, r
     return _run_batch_entry("gilxs_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
 
 
+def run_mixed_resumable_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
+                            minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
+                            anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
+                            block_tables=None, device=0, flip_table=None, seeds=None, streams=None, order=None, n_cap=None, large=False,
+                            obs_first=0, checkpoint=None):
+    """`run_mixed_raw` (large=True: `run_mixed_many_raw`) as one SEGMENT of a run (gilxr_run / gilxmr_run of
+    include/gillespie_mixed_resume.h), the counterpart of `run_resumable_raw`: `times_obs` holds the absolute times of the
+    observations obs_first, obs_first + 1, ... of the run's grid; `checkpoint` is the dictionary a previous segment returned under
+    "checkpoint" (the six arrays of `run_resumable_raw` and `n_slots`, every system's slot count of the run's start), or None for
+    a fresh start from `states`.  The keys (`seeds`, `streams`) and the variants are the resuming launch's: pass the same for the
+    same trajectory.  The result also has "checkpoint", "first_row", and "n0" = the slot counts."""
+    kw = dict(locals())
+    mixed = {k: kw.pop(k) for k in ("sigma_grids", "variant_of_system", "block_tables", "seeds", "streams", "order")}
+    return _run_batch_entry("gilxmr_run" if kw.pop("large") else "gilxr_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
+
+
+def run_mixed_structure_resumable_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs,
+                                      T, seed=0, minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0,
+                                      k_exit=0.0, anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1,
+                                      front_lo=None, block_tables=None, device=0, flip_table=None, seeds=None, streams=None, order=None,
+                                      n_cap=None, k_max=None, first_obs=0, want_rows=True, obs_first=0, checkpoint=None):
+    """`run_mixed_structure_raw` as one SEGMENT of a run (gilxsr_run of include/gillespie_mixed_resume.h).  `first_obs` is an
+    ABSOLUTE index on the run's grid, `k_max` the run's in every segment.  `checkpoint` also holds `window`, `n_window` and
+    `n_empty`, which the segment continues; the dictionary's `window`, `n_window`, `n_empty` are those of the checkpoint it
+    leaves (the sums over all segments so far), `head` and `structure` cover this segment's rows."""
+    k_max = min(int(L), 4096) if k_max is None else int(k_max)
+    kw = dict(locals())
+    mixed = {k: kw.pop(k) for k in ("sigma_grids", "variant_of_system", "block_tables", "seeds", "streams", "order")}
+    return _run_batch_entry("gilxsr_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
+
+
 def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed,
                      minus_anchor, immobilize, suppress_flip, crowding, k_on, k_off, k_exit, anchor_mask, uniforms, max_events,
                      want_states, x_wall, ref_obs, front_lo, block_table, device, flip_table, k_max=None, first_obs=0,
@@ -515,7 +610,8 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     capture statistics: group_of_site, n_groups, c_bins, h_bins, h_dt, first_obs); gilp_run (either, with the ensemble profiles:
     n_bins, first_obs, want_field, group_of_system, n_groups, per_system); gilx_run (systems in LDS, a variant per system: `mixed`,
     the keywords of _mixed_descriptor), gilxm_run (the same, large systems) and gilxs_run (the same with the structure sums: k_max, first_obs, want_rows); gilr_run and
-    gilrm_run (one segment of a run: obs_first, checkpoint)."""
+    gilrm_run (one segment of a run: obs_first, checkpoint); gilxr_run, gilxmr_run and gilxsr_run (one segment of a mixed run:
+    `mixed`, obs_first, and a checkpoint that also has n_slots and, for gilxsr_run, the window sums)."""
     lib, row = _lib(), ENTRIES[entry]
     if row.header is not None and not hasattr(lib, entry):
         raise capi.ApsError(-1, f"the loaded library has no {entry} ({row.header})")
@@ -563,7 +659,7 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     exits, n_exit = np.zeros((S, ncap, 3)), np.zeros(S, np.int32)
     ms = C.c_double()
     results = [pos_obs, sg_obs, fl_obs, scal, n_rec, n_ev, t_fin, exits, n_exit]
-    c = types.SimpleNamespace(S=S, M=M, ncap=ncap, L=L, K=K, ck_in=ck_in, results=results, keep=[keep])
+    c = types.SimpleNamespace(S=S, M=M, ncap=ncap, L=L, K=K, ck_in=ck_in, ck_more=checkpoint, results=results, keep=[keep])
     own = dict(k_max=k_max, first_obs=first_obs, group_of_site=group_of_site, n_groups=n_groups, c_bins=c_bins, h_bins=h_bins, h_dt=h_dt,
                n_bins=n_bins, want_field=want_field, group_of_system=group_of_system, per_system=per_system, mixed=mixed, want_rows=want_rows,
                obs_first=obs_first)
@@ -759,10 +855,11 @@ def _statistics_rows(systems, r, times_obs):
     return rows
 
 
-def _refuse_resume(who, resume):
+def _refuse_resume(who, resume, mixed=False):
     """The structure, capture, profile and mixed launches carry sums of their own across a run (window sums, bind times, group
-    rows), which a Checkpoint does not hold: they cannot start from one."""
-    if resume is not None:
+    rows) or values per system (slot counts, keys), which a Checkpoint does not hold: they cannot start from one.  `mixed`: the
+    mixed launches resume from a MixedCheckpoint, which is not refused here."""
+    if resume is not None and not (mixed and isinstance(resume, MixedCheckpoint)):
         raise ValueError(f"{who} cannot resume from a checkpoint: its launch carries sums across the run that a Checkpoint does not hold "
                          "(include/gillespie_resume.h); run_batched_exact and run_batched_exact_statistics can")
 
@@ -967,8 +1064,195 @@ def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, or
     return r, times_obs
 
 
+_MIXED_FINGERPRINT = ("L", "K", "periodic", "anchor_mask", "n_systems", "n_cap", "obs_dt", "large", "sigma_grids", "seeds", "streams", "n_slots")
+_MIXED_WINDOW = (("window", np.float64), ("n_window", np.int32), ("n_empty", np.int32))
+_MIXED_PER_SYSTEM = (("n_slots", np.int32), ("seeds", np.uint64), ("streams", np.int32), ("sigma_grids", np.float64))
+
+
+class MixedCheckpoint:
+    """The state of a MIXED batch between two launches of the exact event loop (struct gilx_checkpoint of
+    include/gillespie_mixed_resume.h): the six arrays of `Checkpoint` and, per system, the slot count of the run's start
+    (`n_slots`: a mixed system groups its rate sums by it, dead slots included), the Philox key and stream (`seeds`, `streams`)
+    and the interaction range on the grid (`sigma_grids`).  A run that counts statistics also keeps the systems' blocking tables
+    (`block_tables` [systems][K + 1][K + 1]); a structure run keeps `k_max`, `first_obs` (on the run's grid) and the window sums
+    so far (`window` [systems][k_max][3], `n_window`, `n_empty`).  `large`: the large-system kernel (its keys' convention).
+
+    The fingerprint is what must not change between segments: L, K, periodic, the anchor mask, the numbers of systems and slots,
+    obs_dt, `large`, and per system sigma_grids, seeds, streams and n_slots; a structure run adds k_max and first_obs.  Resuming
+    against another value raises ValueError naming the field.  Beta, the rate constants and flip_rate_fn are deliberately NOT
+    part of it, as in `Checkpoint`: other values on resume are the exact process with the parameter switched at the
+    checkpoint's time."""
+
+    def __init__(self, *, pos, flags, ref, t, n_events, next_obs, n_slots, seeds, streams, sigma_grids, L, K, periodic, anchor_mask, obs_dt,
+                 large=False, block_tables=None, k_max=None, first_obs=None, window=None, n_window=None, n_empty=None):
+        given = locals()
+        for k, dt, nd in CHECKPOINT_ARRAYS:
+            setattr(self, k, np.ascontiguousarray(given[k], dtype=dt))
+        if self.pos.ndim != 2 or any(getattr(self, k).shape != self.pos.shape[:nd] for k, _, nd in CHECKPOINT_ARRAYS):
+            raise ValueError("MixedCheckpoint: pos, flags, ref must be [systems][slots], t, n_events, next_obs [systems]")
+        S = self.pos.shape[0]
+        for k, dt in _MIXED_PER_SYSTEM:
+            a = [int(x) & (2 ** 64 - 1) for x in given[k]] if k == "seeds" else given[k]
+            setattr(self, k, np.ascontiguousarray(a, dtype=dt))
+            if getattr(self, k).shape != (S,):
+                raise ValueError(f"MixedCheckpoint: {k} must have one entry per system")
+        self.L, self.K, self.periodic, self.obs_dt, self.large = int(L), int(K), bool(periodic), float(obs_dt), bool(large)
+        self.anchor_mask = np.zeros(self.L, np.uint8) if anchor_mask is None else (np.asarray(anchor_mask).reshape(-1) != 0).astype(np.uint8)
+        self.block_tables = None if block_tables is None else np.ascontiguousarray(block_tables, dtype=np.uint8)
+        if self.block_tables is not None and self.block_tables.shape != (S, self.K + 1, self.K + 1):
+            raise ValueError("MixedCheckpoint: block_tables must be [systems][K + 1][K + 1]")
+        self.k_max = None if k_max is None else int(k_max)
+        self.first_obs = None if first_obs is None else int(first_obs)
+        if self.k_max is None:
+            self.window = self.n_window = self.n_empty = None
+        else:
+            if first_obs is None or window is None or n_window is None or n_empty is None:
+                raise ValueError("MixedCheckpoint: a structure run needs first_obs, window, n_window and n_empty")
+            for (k, dt), shape in zip(_MIXED_WINDOW, ((S, self.k_max, 3), (S,), (S,))):
+                setattr(self, k, np.ascontiguousarray(given[k], dtype=dt))
+                if getattr(self, k).shape != shape:
+                    raise ValueError(f"MixedCheckpoint: {k} must have the shape {shape}")
+
+    n_systems = property(lambda self: self.pos.shape[0])
+    n_cap = property(lambda self: self.pos.shape[1])
+    structure = property(lambda self: self.k_max is not None)
+
+    def arrays(self):
+        """The dictionary of arrays `run_mixed_resumable_raw(checkpoint=...)` takes (a structure run: with the window sums, as
+        `run_mixed_structure_resumable_raw` takes it)."""
+        out = {k: getattr(self, k) for k, _, _ in CHECKPOINT_ARRAYS}
+        out["n_slots"] = self.n_slots
+        if self.structure:
+            out.update({k: getattr(self, k) for k, _ in _MIXED_WINDOW})
+        return out
+
+    def fingerprint(self):
+        return {k: getattr(self, k) for k in _MIXED_FINGERPRINT + (("k_max", "first_obs") if self.structure else ())}
+
+    def require(self, **expected):
+        """ValueError naming the first fingerprint field whose value differs from `expected[field]`."""
+        mine = self.fingerprint()
+        for k in _MIXED_FINGERPRINT + ("k_max", "first_obs"):
+            if k not in expected:
+                continue
+            if k not in mine:
+                raise ValueError(f"MixedCheckpoint: the resuming run differs from the checkpoint in {k}: the checkpoint is of a run without structure sums")
+            want = expected[k]
+            if k == "anchor_mask":
+                same = np.array_equal(mine[k], np.asarray(want).reshape(-1) != 0)
+            elif k == "seeds":
+                same = np.array_equal(mine[k], np.array([int(x) & (2 ** 64 - 1) for x in want], dtype=np.uint64))
+            elif isinstance(mine[k], np.ndarray):
+                same = np.array_equal(mine[k], np.asarray(want, dtype=mine[k].dtype))
+            else:
+                same = mine[k] == want
+            if not same:
+                shown = "" if isinstance(mine[k], np.ndarray) and mine[k].size > 16 else f": the checkpoint has {mine[k]!r}, the resuming run {want!r}"
+                raise ValueError(f"MixedCheckpoint: the resuming run differs from the checkpoint in {k}{shown}")
+
+    def save(self, path):
+        """One .npz: the arrays, the anchor mask and the scalar fields (no pickles)."""
+        meta = dict(L=self.L, K=self.K, periodic=self.periodic, obs_dt=self.obs_dt, large=self.large, k_max=self.k_max, first_obs=self.first_obs)
+        more = {k: getattr(self, k) for k, _ in _MIXED_PER_SYSTEM if k != "n_slots"}
+        if self.block_tables is not None:
+            more["block_tables"] = self.block_tables
+        with open(path, "wb") as fh:
+            np.savez(fh, anchor_mask=self.anchor_mask, meta=np.array(json.dumps(meta)), **self.arrays(), **more)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(**{k: z[k] for k in z.files if k != "meta"}, **json.loads(str(z["meta"])))
+
+
+def _mixed_segments(who, systems, T, obs_dt, groups, statistics, uniforms=None, order=None, structure=None, allow_large=False, *,
+                    resume, obs_range, obs_per_launch):
+    """_mixed_launch as a chain of segments (gilxr_run / gilxmr_run / gilxsr_run of include/gillespie_mixed_resume.h): the
+    observations `obs_range` of the run (T, obs_dt), from the MixedCheckpoint `resume` or from fresh initial states, in launches of
+    at most `obs_per_launch` observations.  Returns (merged raw outputs, their observation times, the MixedCheckpoint at the end).
+    A structure run's window is [first_obs, M) on the WHOLE grid of M observations; the merged `head` and `structure` cover the
+    range, `window`, `n_window`, `n_empty` are the last checkpoint's."""
+    first, inits, _ = _open_batch(who, systems, resume=resume, skip=("local_kernel_sigma",), anchors="their anchor sites", flip=True,
+                                  no_exit=statistics, seed=False)
+    times_all = np.arange(0.0, T, obs_dt)
+    M, S = len(times_all), len(systems)
+    mask = np.zeros(first.L, np.uint8) if first.is_anchor_site is None else (np.asarray(first.is_anchor_site).reshape(-1) != 0).astype(np.uint8)
+    sig_sys = np.array([float(ps._sigma_grid) for ps in systems])
+    kk = first_obs = None
+    if structure is not None:
+        k_max, start_fraction, want_rows, all_obs = structure
+        kk = first.L if k_max is None else min(int(k_max), first.L)
+        first_obs = 0 if all_obs else int(start_fraction * M)
+    if resume is None:
+        n_cap = max(1, max(len(p) for p, _ in inits))
+        large = _large_shape(first.L, n_cap)
+    else:
+        more = {} if structure is None else dict(k_max=kk, first_obs=first_obs)
+        resume.require(L=first.L, K=first.K, periodic=bool(first.periodic), anchor_mask=mask, n_systems=S, obs_dt=float(obs_dt), sigma_grids=sig_sys, **more)
+        if structure is None and resume.structure:
+            raise ValueError(f"{who}: the checkpoint is of a structure run (it carries window sums); resume it with run_batched_exact_structure_mixed")
+        n_cap, large = resume.n_cap, resume.large
+    if large and not (allow_large and structure is None):
+        raise ValueError(f"{who}: L = {first.L}, N = {n_cap} is a large shape (beyond L = {GIL_MAX_L}, N = {GIL_MAX_N}); "
+                         "the large-system kernel takes no mixed batches")
+    if resume is None:
+        seeds, streams = mixed_keys(systems, groups, large=large)
+        ck, k_lo, n_live = None, 0, [len(p) for p, _ in inits]
+    else:
+        if all(ps.seed is not None for ps in systems):         # the keys this batch would take: no generator is consumed
+            seeds, streams = mixed_keys(systems, groups, large=large)
+            resume.require(seeds=seeds, streams=streams)
+        seeds, streams = [int(x) for x in resume.seeds], resume.streams
+        ck, k_lo, n_live = resume.arrays(), int(resume.next_obs.min()), [int(n) for n in resume.n_slots]
+    k0, k1 = (k_lo, M) if obs_range is None else (int(obs_range[0]), int(obs_range[1]))
+    if not 0 <= k0 < k1 <= M:
+        raise ValueError(f"{who}: obs_range must be a non-empty range within the {M} observations of the run (got [{k0}, {k1}))")
+    if resume is None and k0 != 0:
+        raise ValueError(f"{who}: a run without `resume` starts at observation 0")
+    step = k1 - k0 if obs_per_launch is None else int(obs_per_launch)
+    if step < 1:
+        raise ValueError(f"{who}: obs_per_launch must be at least 1")
+    kw, tables, ref_abs = {}, None, -1
+    if statistics:                                             # every system is counted with the table of its own particle number
+        kw, tables = _statistics_keywords(who, first, times_all[k0:k1], n_live, one_table=False)
+        if resume is not None and resume.block_tables is not None:
+            tables = list(resume.block_tables)
+        ref_abs = k0 + kw.pop("ref_obs")
+    sig, tabs, owner = mixed_variants(sig_sys, tables)
+    shape = dict(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=S, n_cap=n_cap, n_obs=min(step, k1 - k0), variant_of_system=owner)
+    if structure is not None:
+        kw = dict(want_states=False, k_max=kk, first_obs=first_obs, want_rows=want_rows)
+        run_fn = run_mixed_structure_resumable_raw
+        plan = plan_mixed_structure(**shape, **dict(kw, first_obs=min(first_obs, shape["n_obs"])))
+    else:
+        kw["large"] = large
+        run_fn = run_mixed_resumable_raw
+        plan = (plan_mixed_many if large else plan_mixed)(**shape, want_states=not statistics)
+    if plan["lds_bytes"] > GILX_LDS_LIMIT:
+        raise ValueError(f"{who}: the launch needs {plan['lds_bytes']} bytes of LDS per system, over the limit of {GILX_LDS_LIMIT} bytes")
+    model = _model(first, systems, sigma_grids=sig, variant_of_system=owner, block_tables=tabs, T=T, uniforms=uniforms, seeds=seeds, streams=streams,
+                   order=order, n_cap=n_cap, **kw)
+    del model["sigma_grid"]                                    # a mixed launch has a range per variant instead
+    parts = []
+    for a in range(k0, k1, step):
+        b = min(a + step, k1)
+        r = run_fn(states=inits, times_obs=times_all[a:b], obs_first=a, checkpoint=ck, ref_obs=ref_abs - a if a <= ref_abs < b else -1, **model)
+        ck = r["checkpoint"]
+        parts.append(r)
+    r = _merge_segments(parts, k0)
+    r.update(plan=plan, obs_range=(k0, k1))
+    if structure is not None:
+        r.update(head=np.concatenate([q["head"] for q in parts], axis=1), window=ck["window"], n_window=ck["n_window"], n_empty=ck["n_empty"],
+                 structure=np.concatenate([q["structure"] for q in parts], axis=1) if want_rows else None,
+                 bytes_back=int(sum(q["bytes_back"] for q in parts)), first_obs=first_obs)
+    return r, times_all[k0:k1], MixedCheckpoint(L=first.L, K=first.K, periodic=first.periodic, anchor_mask=mask, obs_dt=obs_dt, large=large,
+                                                seeds=seeds, streams=streams, sigma_grids=sig_sys, k_max=kk, first_obs=first_obs,
+                                                block_tables=None if tables is None else np.stack(tables), **ck)
+
+
 def run_batched_exact_mixed(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False, uniforms=None, want_m_local=True,
-                            groups=None, order=None, resume=None, allow_large=False):
+                            groups=None, order=None, resume=None, allow_large=False, obs_range=None, return_checkpoint=False,
+                            obs_per_launch=None):
     """`run_batched_exact` for systems that may ALSO differ in `local_kernel_sigma`: one mixed launch (include/gillespie_mixed.h).
     Every other attribute the batched functions compare, the anchor sites and the flip table must agree.  `groups[s]`: the group
     of system s; its systems draw what `run_batched_exact` on the group alone draws (`mixed_keys`).  Returns the list of the
@@ -978,19 +1262,42 @@ def run_batched_exact_mixed(systems, T=10.0, obs_dt=0.01, record_fft=False, reco
     (`mixed_keys(..., large=True)`).  Its numbers equal `run_batched_exact` on each group alone where every group is itself a
     large shape, which is always so when L > 4096.  A group below the limit in a batch that straddles it runs on the large kernel
     with large keys: it then equals `run_many_large_raw` for it, not the batch kernel.  A batch that is no large shape is
-    launched as without the keyword."""
-    _refuse_resume("run_batched_exact_mixed", resume)
+    launched as without the keyword.
+    `resume` (a MixedCheckpoint; a plain Checkpoint does not hold what a mixed launch needs and is refused), `obs_range`,
+    `return_checkpoint`, `obs_per_launch`: as in run_batched_exact, through the resumable mixed launches
+    (include/gillespie_mixed_resume.h); the segments together are, bit for bit, the one launch.  The keys and slot counts are the
+    checkpoint's.  With none of the four the run is the one launch it always was."""
+    who = "run_batched_exact_mixed"
+    _refuse_resume(who, resume, mixed=True)
+    if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
+        r, times_obs, ck = _mixed_segments(who, systems, T, obs_dt, groups, False, uniforms, order, allow_large=allow_large, resume=resume,
+                                           obs_range=obs_range, obs_per_launch=obs_per_launch)
+        outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
+        systems[0].kernel_ms = r["kernel_ms"]
+        return (outs, ck) if return_checkpoint else outs
     r, times_obs = _mixed_launch("run_batched_exact_mixed", systems, T, obs_dt, groups, False, uniforms, order, allow_large=allow_large)
     outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
     systems[0].kernel_ms = r["kernel_ms"]
     return outs
 
 
-def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None, order=None, resume=None, allow_large=False):
+def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None, order=None, resume=None, allow_large=False,
+                                       obs_range=None, return_checkpoint=False, obs_per_launch=None):
     """`run_batched_exact_statistics` for systems that may also differ in `local_kernel_sigma` and whose particle numbers may give
     different blocking thresholds: every system is counted with the blocking table of its own particle number, in one mixed
-    launch.  `groups`, `allow_large` as in run_batched_exact_mixed.  Returns the DeviceObservables rows, one per system."""
-    _refuse_resume("run_batched_exact_statistics_mixed", resume)
+    launch.  `groups`, `allow_large` as in run_batched_exact_mixed.  Returns the DeviceObservables rows, one per system.
+    `resume` (a MixedCheckpoint), `obs_range`, `return_checkpoint`, `obs_per_launch`: as in run_batched_exact_statistics; the
+    blocking tables are the checkpoint's."""
+    who = "run_batched_exact_statistics_mixed"
+    _refuse_resume(who, resume, mixed=True)
+    if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
+        r, times_obs, ck = _mixed_segments(who, systems, T, obs_dt, groups, True, None, order, allow_large=allow_large, resume=resume,
+                                           obs_range=obs_range, obs_per_launch=obs_per_launch)
+        if np.any(r["first_row"] > 0):
+            raise ValueError(f"{who}: the checkpoint's systems stand at different observations; the sums need a common first observation")
+        rows = _statistics_rows(systems, r, times_obs)
+        systems[0].kernel_ms = r["kernel_ms"]
+        return (rows, ck) if return_checkpoint else rows
     r, times_obs = _mixed_launch("run_batched_exact_statistics_mixed", systems, T, obs_dt, groups, True, None, order, allow_large=allow_large)
     rows = _statistics_rows(systems, r, times_obs)
     systems[0].kernel_ms = r["kernel_ms"]
@@ -998,7 +1305,8 @@ def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None
 
 
 def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_max=None, groups=None, order=None,
-                                      reduce="device", return_series=False, resume=None):
+                                      reduce="device", return_series=False, resume=None, obs_range=None, return_checkpoint=False,
+                                      obs_per_launch=None):
     """`run_batched_exact_structure` for systems that may ALSO differ in `local_kernel_sigma` (and, like there, in beta, state and
     particle number): one mixed launch that takes the structure sums (include/gillespie_mixed_structure.h).  The other attributes,
     the anchor sites and the flip table must agree, as in run_batched_exact_mixed; `groups`, `order` as there (`mixed_keys`).
@@ -1007,15 +1315,40 @@ def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fracti
     (observables.DeviceStructureWindow): no row, nothing of size observations x modes, leaves the GPU.  `reduce="rows"`: the launch
     returns the full rows and observables.DeviceStructure reduces them on the host (the cross-check route).
     `return_series=True` adds `times_obs`, `var_series` [M] (from the head rows), `m_series` [M] = sum sigma / n (from the scalar
-    sums) and, with reduce="rows" (the sums are then taken at every observation), `fft_amp_series` [M][k_max]."""
-    _refuse_resume("run_batched_exact_structure_mixed", resume)
+    sums) and, with reduce="rows" (the sums are then taken at every observation), `fft_amp_series` [M][k_max].
+    `resume` (a MixedCheckpoint of a structure run), `obs_range`, `return_checkpoint`, `obs_per_launch`: as in run_batched_exact.
+    The window is [int(start_fraction * M), M) on the WHOLE grid, and its sums travel in the checkpoint
+    (include/gillespie_mixed_resume.h), so a chain of calls or launches returns what the one launch returns.  The observables are
+    evaluated by the call that reaches the grid's end; it must hold the window's head rows, so it may not start inside the
+    window (ValueError).  A call that ends earlier returns None in place of every system's dict: take its checkpoint.  Series
+    entries before the call's first observation are NaN."""
+    who = "run_batched_exact_structure_mixed"
+    _refuse_resume(who, resume, mixed=True)
     from . import observables
     if reduce not in ("device", "rows"):
         raise ValueError("reduce must be 'device' or 'rows'")
     rows_wanted = reduce == "rows"
-    r, times_obs = _mixed_launch("run_batched_exact_structure_mixed", systems, T, obs_dt, groups, False, None, order,
-                                 structure=(k_max, start_fraction, rows_wanted, rows_wanted and return_series))
-    first = systems[0]
+    structure = (k_max, start_fraction, rows_wanted, rows_wanted and return_series)
+    first, ck = systems[0], None
+    if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
+        r, _, ck = _mixed_segments(who, systems, T, obs_dt, groups, False, None, order, structure=structure, resume=resume,
+                                            obs_range=obs_range, obs_per_launch=obs_per_launch)
+        times_obs = np.arange(0.0, T, obs_dt)
+        k0, k1 = r["obs_range"]
+        first.kernel_ms, first.bytes_back = r["kernel_ms"], r["bytes_back"]
+        if k1 < len(times_obs):                                # the window is not complete: nothing to evaluate yet
+            for s, ps in enumerate(systems):
+                ps.n_events = int(r["n_events"][s])
+            return ([None] * len(systems), ck) if return_checkpoint else [None] * len(systems)
+        if k0 > r["first_obs"]:
+            raise ValueError(f"{who}: this call starts at observation {k0}, inside the window that begins at {r['first_obs']}: the head rows of "
+                             "the window's earlier observations lie in an earlier call; cut the run before the window or use obs_per_launch")
+
+        def whole(a):                                          # rows of the whole grid: zeros before this call's first observation
+            return None if a is None else np.concatenate([np.zeros((a.shape[0], k0) + a.shape[2:], a.dtype), a], axis=1)
+        r = dict(r, head=whole(r["head"]), structure=whole(r["structure"]), scalars=whole(r["scalars"]), n_recorded=r["n_recorded"] + k0)
+    else:
+        r, times_obs = _mixed_launch(who, systems, T, obs_dt, groups, False, None, order, structure=structure)
     M, L = len(times_obs), first.L
     kk = L if k_max is None else min(int(k_max), L)
     first_obs = 0 if (rows_wanted and return_series) else int(start_fraction * M)
@@ -1039,7 +1372,7 @@ def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fracti
         ps.n_events = int(r["n_events"][s])
     first.kernel_ms = r["kernel_ms"]
     first.bytes_back = r["bytes_back"]
-    return out
+    return (out, ck) if return_checkpoint else out
 
 
 def run_batched_exact_structure(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_max=None, return_series=False, resume=None):
