@@ -15,7 +15,7 @@ SRCS = [SRC, os.path.join(HERE, "csrc", "pde_hip.hip"), os.path.join(HERE, "csrc
         os.path.join(HERE, "csrc", "gillespie_hip.hip"),
         os.path.join(HERE, "csrc", "gillespie_big_hip.hip")]   # stepper; PDE solver (both shapes); exact event loop
 HDR = os.path.join(ROOT, "include", "aps.h")
-HDRS = [HDR, os.path.join(ROOT, "include", "pde.h"), os.path.join(ROOT, "include", "pde_wide.h"), os.path.join(ROOT, "include", "pde_spectral.h"), os.path.join(ROOT, "include", "pde_sweep.h"), os.path.join(HERE, "csrc", "pde_sweep_fft.hpp"), os.path.join(HERE, "csrc", "pde_common.hpp"), os.path.join(HERE, "csrc", "pde_spectral.hpp"), os.path.join(HERE, "csrc", "aps_common.hpp"), os.path.join(HERE, "csrc", "tile_step.hpp"), os.path.join(HERE, "csrc", "tile_dense.hpp"), os.path.join(HERE, "csrc", "tile_loop.hpp"), os.path.join(HERE, "csrc", "ntt_conv.hpp"),
+HDRS = [HDR, os.path.join(ROOT, "include", "pde.h"), os.path.join(ROOT, "include", "pde_resume.h"),os.path.join(ROOT, "include", "pde_wide.h"), os.path.join(ROOT, "include", "pde_spectral.h"), os.path.join(ROOT, "include", "pde_sweep.h"), os.path.join(HERE, "csrc", "pde_sweep_fft.hpp"), os.path.join(HERE, "csrc", "pde_common.hpp"), os.path.join(HERE, "csrc", "pde_spectral.hpp"), os.path.join(HERE, "csrc", "aps_common.hpp"), os.path.join(HERE, "csrc", "tile_step.hpp"), os.path.join(HERE, "csrc", "tile_dense.hpp"), os.path.join(HERE, "csrc", "tile_loop.hpp"), os.path.join(HERE, "csrc", "ntt_conv.hpp"),
         os.path.join(HERE, "csrc", "dev_mem.hpp"), os.path.join(HERE, "csrc", "gillespie_common.hpp"),
         os.path.join(ROOT, "include", "gillespie.h"), os.path.join(ROOT, "include", "gillespie_many.h"),
         os.path.join(ROOT, "include", "gillespie_structure.h"), os.path.join(HERE, "csrc", "gillespie_structure.hpp"),

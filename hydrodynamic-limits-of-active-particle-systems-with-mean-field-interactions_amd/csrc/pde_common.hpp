@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "pde.h"
+#include "pde_resume.h"
 #include "dev_mem.hpp"                    // OneShot and the UP / WORK / OUT / DOWN of the staging
 
 namespace pde_common {
@@ -27,7 +28,48 @@ struct PdeIo {
     const double *beta, *rho_p0, *rho_m0, *tracer_x0; const int8_t *tracer_s0; const double *rand_u, *rand_n;
     double *rho_p, *rho_m, *m_series, *var_series, *v_eff_series, *D_eff_series, *snapshots, *m_snapshots, *fft_re, *fft_im, *tracer_x;
     int8_t *tracer_s; double *kernel_ms;
+    const pde_checkpoint *from; pde_checkpoint *to;   // the resumable entry points (include/pde_resume.h); null: a fresh start, no checkpoint left
 };
+
+// The steps and rows of one launch (include/pde_resume.h): the loop runs n = n_begin .. n_end in absolute step numbers and
+// records rows row0 .. n_end, n_rows of them, at launch-relative offsets; snap0 is the run's number of the launch's first
+// snapshot.  A fresh start is 0 .. nsteps, a resumed one (resume = 1) skips the recording part of iteration n_begin.
+struct PdeSpan { int n_begin, n_end, row0, n_rows, snap0, n_snap, resume; };
+
+// nullptr, or why no launch has these rows
+inline const char *pde_span(const pde_params *p, int32_t from_step, PdeSpan &sp) {
+    if (from_step < -1) return "from->step must be >= 0";
+    if (from_step >= 0 && p->nsteps < 1) return "a resumed launch needs nsteps >= 1";
+    if (p->nsteps < 0) return "nsteps >= 0 required";
+    if (p->snapshot_interval < 1) return "snapshot_interval must be >= 1";
+    if (from_step >= 0 && (long long)from_step + p->nsteps > INT32_MAX) return "from->step + nsteps exceeds INT32_MAX";
+    const int every = p->snapshot_interval;
+    sp.resume = from_step >= 0;
+    sp.n_begin = sp.resume ? from_step : 0;
+    sp.n_end = sp.n_begin + p->nsteps;
+    sp.row0 = sp.resume ? from_step + 1 : 0;
+    sp.n_rows = sp.n_end - sp.row0 + 1;
+    sp.snap0 = sp.resume ? from_step / every + 1 : 0;
+    sp.n_snap = sp.n_end / every - sp.snap0 + 1;
+    return nullptr;
+}
+
+// The checks of `from` and `to`; a resumed launch then starts from the checkpoint's arrays in place of the initial state.
+// nullptr, or the text of the complaint.
+inline const char *adopt_checkpoint(const pde_params *p, PdeIo &io, PdeSpan &sp) {
+    if (!p) return "null argument or n_systems < 1";
+    if (io.from && io.from->step < 0) return "from->step must be >= 0";
+    if (const char *why = pde_span(p, io.from ? io.from->step : -1, sp)) { if (io.from) return why; sp = PdeSpan{}; }   // a fresh start's own faults are check_args'
+    for (const pde_checkpoint *c : {io.from, (const pde_checkpoint *)io.to}) {
+        if (!c) continue;
+        if (!c->rho_p || !c->rho_m) return c == io.from ? "from: rho_p and rho_m are required" : "to: rho_p and rho_m are required";
+        if (p->n_tracers > 0 && (!c->tracer_x || !c->tracer_s || !c->hist))
+            return c == io.from ? "from: tracer_x, tracer_s and hist are required with n_tracers > 0" : "to: tracer_x, tracer_s and hist are required with n_tracers > 0";
+    }
+    if (io.from) { io.rho_p0 = io.from->rho_p; io.rho_m0 = io.from->rho_m; io.tracer_x0 = io.from->tracer_x; io.tracer_s0 = io.from->tracer_s; }
+    if (sp.n_snap == 0) io.snapshots = io.m_snapshots = nullptr;   // no snapshot row in this launch: the pointers are ignored
+    return nullptr;
+}
 
 // nullptr when the arguments of a solve are acceptable, else the text of the complaint
 inline const char *check_args(const pde_params *p, int32_t n_systems, const PdeIo &io) {
@@ -42,10 +84,10 @@ inline const char *check_args(const pde_params *p, int32_t n_systems, const PdeI
     return nullptr;
 }
 
-struct PdeExtents {        // systems, and systems times sites, recorded steps, tracers; snapshots per system
-    size_t S, SL, SN, ST; int n_snap;
-    PdeExtents(const pde_params *p, int32_t n)
-        : S((size_t)n), SL(S * p->L), SN(S * (p->nsteps + 1)), ST(S * p->n_tracers), n_snap(p->nsteps / p->snapshot_interval + 1) {}
+struct PdeExtents {        // systems, and systems times sites, recorded rows, tracers; snapshots per system; the launch's span
+    size_t S, SL, SN, ST; int n_snap; PdeSpan sp;
+    PdeExtents(const pde_params *p, int32_t n, const PdeSpan &span)
+        : S((size_t)n), SL(S * p->L), SN(S * span.n_rows), ST(S * p->n_tracers), n_snap(span.n_snap), sp(span) {}
 };
 
 struct Factor {            // (I - gamma dt Lap / dx^2) = L U, and the Sherman-Morrison data of the periodic corners
@@ -111,7 +153,7 @@ inline void twiddles(int L, std::vector<double> &twc, std::vector<double> &tws) 
 template <class Args>
 int pde_stage_inputs(OneShot &job, Args &a, const pde_params *p, const PdeExtents &x, const PdeIo &io, int ktaps, const std::vector<double> &ktab) {
     const size_t L = (size_t)p->L;
-    a.p = *p; a.dx = p->xlim / p->L; a.ktaps = ktaps; a.n_snap = x.n_snap;
+    a.p = *p; a.dx = p->xlim / p->L; a.ktaps = ktaps; a.n_snap = x.n_snap; a.span = x.sp;
     Factor fac;
     factorise(p, a.dx, fac);
     a.sm_coef = fac.sm_coef; a.sm_denom = fac.sm_denom;
@@ -131,7 +173,8 @@ int pde_stage_outputs(OneShot &job, Args &a, const pde_params *p, const PdeExten
     if (ntr) {
         UP(tracer_x0, io.tracer_x0, x.ST); UP(tracer_s0, io.tracer_s0, x.ST);
         if (io.rand_u) { UP(rand_u, io.rand_u, x.SN * ntr); UP(rand_n, io.rand_n, x.SN * ntr); }
-        WORK(hist, x.S * p->window * ntr); WORK(trx, x.ST); WORK(trs, x.ST);
+        if (io.from) UP(hist, io.from->hist, x.S * p->window * ntr); else WORK(hist, x.S * p->window * ntr);   // the ring goes on from the checkpoint's
+        WORK(trx, x.ST); WORK(trs, x.ST);
     }
     OUT(m_series, io.m_series, x.SN); OUT(var_series, io.var_series, x.SN);
     if (tracer_series) { OUT(v_eff, io.v_eff_series, x.SN); OUT(D_eff, io.D_eff_series, x.SN); }
@@ -146,6 +189,26 @@ int pde_fetch_outputs(OneShot &job, const Args &a, const pde_params *p, const Pd
     if (tracer_series) { DOWN(io.v_eff_series, v_eff, x.SN * 8); DOWN(io.D_eff_series, D_eff, x.SN * 8); }
     DOWN(io.snapshots, snapshots, x.S * x.n_snap * p->L * 8); DOWN(io.m_snapshots, m_snapshots, x.S * x.n_snap * p->L * 8);
     DOWN(io.fft_re, fft_re, x.SN * p->n_fft_modes * 8); DOWN(io.fft_im, fft_im, x.SN * p->n_fft_modes * 8);
+    return 0;
+}
+
+// The checkpoint at the launch's last row, from where the shape keeps its final state on the device (fields, working tracers).
+template <class Args>
+int pde_fetch_checkpoint(OneShot &job, const Args &a, const pde_params *p, const PdeExtents &x, const PdeIo &io,
+                         const double *rp, const double *rm) {
+    pde_checkpoint *to = io.to;
+    if (!to) return 0;
+    if (int rc = job.download(to->rho_p, rp, x.SL * 8, "checkpoint rho_p")) return rc;
+    if (int rc = job.download(to->rho_m, rm, x.SL * 8, "checkpoint rho_m")) return rc;
+    if (p->n_tracers > 0) {
+        const size_t ntr = (size_t)p->n_tracers, win = (size_t)p->window;
+        if (int rc = job.download(to->tracer_x, a.trx, x.ST * 8, "checkpoint tracer_x")) return rc;
+        if (int rc = job.download(to->tracer_s, a.trs, x.ST, "checkpoint tracer_s")) return rc;
+        if (int rc = job.download(to->hist, a.hist, x.S * win * ntr * 8, "checkpoint hist")) return rc;
+        for (size_t s = 0; s < x.S; ++s)                          // the slots no row has filled yet are written as 0
+            for (size_t slot = (size_t)x.sp.n_end + 1; slot < win; ++slot) std::fill_n(to->hist + (s * win + slot) * ntr, ntr, 0.0);
+    }
+    to->step = x.sp.n_end;
     return 0;
 }
 

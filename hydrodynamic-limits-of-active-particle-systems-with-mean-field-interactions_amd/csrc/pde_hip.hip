@@ -1,4 +1,6 @@
-// pde_hip.hip -- MI355X (gfx950) implementation of the C ABIs in include/pde.h and include/pde_sweep.h.
+// pde_hip.hip -- MI355X (gfx950) implementation of the C ABIs in include/pde.h and include/pde_sweep.h, and of their resumable
+// forms pder_solve / pdekr_solve in include/pde_resume.h (the same kernel; a resumed launch runs its RESUMED instantiation, whose loop
+// starts at a given absolute step).
 //
 // Replaces the time loop of the reference's IMEXPDE (IMEX_PDE_solver_class.py:236-290): one PERSISTENT workgroup
 // per system keeps rho_plus, rho_minus, the diffused fields and the magnetisation in LDS and runs all nsteps
@@ -41,7 +43,7 @@
 namespace {
 
 using namespace pde_common;
-std::string g_err, g_err_k;
+std::string g_err, g_err_k, g_err_r, g_err_kr;
 
 // The three forms of the kernel.  BATCH is pde_solve_batch: one kernel mode and one table of taps for the launch.  The two sweep
 // forms (pdek_solve) read mode, reach and taps per system; SWEEP_SPECTRAL evaluates mode 1 by the transform of pde_sweep_fft.hpp.
@@ -68,6 +70,7 @@ struct PdeArgs {
     const int *sys_mode, *sys_ktaps, *sys_log2;   // kernel mode, reach, log2 of the transform (0: none)
     const long long *sys_ktab;                    // where the system's taps begin in ktab
     const double2 *ctw;                           // twiddles of m = PDEK_MIN_LOG2 .., one table after another
+    PdeSpan span;                       // the absolute steps this launch runs and the rows it records (pde_common.hpp); read by the RESUMED kernels only
 };
 
 // x = A^{-1} d for both fields: d in (dp, dm), result overwrites them.
@@ -96,10 +99,12 @@ __device__ inline void diffuse2(const PdeArgs &a, double *dp, double *dm, double
     (void)red;
 }
 
-template <Form FORM>
+// RESUMED: the launch starts from a checkpoint (a.span).  A fresh start keeps an instantiation of its own, in which the span is the
+// constant 0 .. nsteps: with the span read at run time the BATCH form ran 2.8 % slower on the reference's beta sweep.
+template <Form FORM, bool RESUMED>
 __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
     extern __shared__ double lds[];
-    const int L = a.p.L, t = threadIdx.x, sys = blockIdx.x, ntr = a.p.n_tracers, nsteps = a.p.nsteps;
+    const int L = a.p.L, t = threadIdx.x, sys = blockIdx.x, ntr = a.p.n_tracers;
     // the five fields and the kernel taps: in LDS when they fit (L <= ~3000), else in this system's slab of global memory
     // (one workgroup = one CU: its L1 / the L2 serve it, workgroup barriers order the accesses); the scan scratch stays in LDS
     double *fields = a.work ? a.work + (size_t)sys * (size_t)a.work_stride : lds;
@@ -130,7 +135,12 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
         }
     }
     const double noise_amp = sqrt(2.0 * a.p.gamma * dt);
-    for (int n = 0; n <= nsteps; ++n) {
+    const int nsteps = a.p.nsteps, n_begin = RESUMED ? a.span.n_begin : 0, n_end = RESUMED ? a.span.n_end : nsteps;
+    const int row0 = RESUMED ? a.span.row0 : 0, n_rows = RESUMED ? a.span.n_rows : nsteps + 1, snap0 = RESUMED ? a.span.snap0 : 0;
+#define PDE_ROW ((size_t)sys * n_rows + (n - row0))             /* this system's row of iteration n in the launch's series */
+    for (int n = n_begin; n <= n_end; ++n) {
+        // a resumed launch starts behind the row of its checkpoint's step: the magnetisation only, step() needs it
+        const bool record = !RESUMED || n != n_begin;
         // ---- magnetisation of the current state (ref :156-168): used by the observables, the tracers and step()
         double m_global = 0.0;
         if (mode == 0) {
@@ -169,7 +179,7 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
         }
         __syncthreads();
         // ---- observables (ref :243-255)
-        {
+        if (record) {
             double sm_ = 0.0, st = 0.0;
             for (int i = t; i < L; i += NT) { sm_ += mf[i]; st += rp[i] + rm[i]; }
             sm_ = block_sum(sm_, red); st = block_sum(st, red);
@@ -178,8 +188,8 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
             for (int i = t; i < L; i += NT) { const double d = rp[i] + rm[i] - mean_t; sv += d * d; }
             sv = block_sum(sv, red);
             if (t == 0) {
-                if (a.m_series) a.m_series[(size_t)sys * (nsteps + 1) + n] = mode == 2 ? m_global : sm_ / L;
-                if (a.var_series) a.var_series[(size_t)sys * (nsteps + 1) + n] = sv / L;
+                if (a.m_series) a.m_series[PDE_ROW] = mode == 2 ? m_global : sm_ / L;
+                if (a.var_series) a.var_series[PDE_ROW] = sv / L;
             }
             if (a.fft_re)
                 for (int k = t; k < a.p.n_fft_modes; k += NT) {   // rfft(total)[k] / L = sum total_i (cos - i sin)(2 pi k i / L) / L
@@ -190,11 +200,11 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
                         re += v * a.twc[ph]; im -= v * a.tws[ph];
                         ph += k; if (ph >= L) ph -= L;
                     }
-                    a.fft_re[((size_t)sys * (nsteps + 1) + n) * a.p.n_fft_modes + k] = re / L;
-                    a.fft_im[((size_t)sys * (nsteps + 1) + n) * a.p.n_fft_modes + k] = im / L;
+                    a.fft_re[PDE_ROW * a.p.n_fft_modes + k] = re / L;
+                    a.fft_im[PDE_ROW * a.p.n_fft_modes + k] = im / L;
                 }
             if (n % a.p.snapshot_interval == 0) {
-                const size_t o = ((size_t)sys * a.n_snap + n / a.p.snapshot_interval) * L;
+                const size_t o = ((size_t)sys * a.n_snap + (n / a.p.snapshot_interval - snap0)) * L;
                 for (int i = t; i < L; i += NT) {
                     if (a.snapshots) a.snapshots[o + i] = rp[i] + rm[i];
                     if (a.m_snapshots) a.m_snapshots[o + i] = rp[i] - rm[i];
@@ -202,7 +212,7 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
             }
         }
         // ---- tracers (ref :257-287)
-        if (ntr > 0) {
+        if (record && ntr > 0) {
             double sdr = 0.0;
             const bool windowed = n >= a.p.window;
             double *hist = a.hist + (size_t)sys * a.p.window * ntr;
@@ -215,7 +225,7 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
                 int s = trs[i];
                 double u, g;
                 if (a.rand_u) {
-                    const size_t o = ((size_t)sys * (nsteps + 1) + n) * ntr + i;
+                    const size_t o = PDE_ROW * ntr + i;
                     u = a.rand_u[o]; g = a.rand_n[o];
                 } else {
                     uint32_t x[4];
@@ -239,16 +249,16 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
                 for (int i = t; i < ntr; i += NT) { const double d = trx[i] - old[i] - mean_dr; sv += d * d; }
                 sv = block_sum(sv, red) / ntr;
                 if (t == 0) {
-                    if (a.v_eff) a.v_eff[(size_t)sys * (nsteps + 1) + n] = mean_dr / (a.p.window * dt);
-                    if (a.D_eff) a.D_eff[(size_t)sys * (nsteps + 1) + n] = sv / (2 * a.p.window * dt);
+                    if (a.v_eff) a.v_eff[PDE_ROW] = mean_dr / (a.p.window * dt);
+                    if (a.D_eff) a.D_eff[PDE_ROW] = sv / (2 * a.p.window * dt);
                 }
             } else if (t == 0) {
                 const double nan = __longlong_as_double(0x7ff8000000000000ll);
-                if (a.v_eff) a.v_eff[(size_t)sys * (nsteps + 1) + n] = nan;
-                if (a.D_eff) a.D_eff[(size_t)sys * (nsteps + 1) + n] = nan;
+                if (a.v_eff) a.v_eff[PDE_ROW] = nan;
+                if (a.D_eff) a.D_eff[PDE_ROW] = nan;
             }
         }
-        if (n == nsteps) break;
+        if (n == n_end) break;
         // ---- step() (ref :190-233)
         for (int i = t; i < L; i += NT) { xp[i] = rp[i]; xm[i] = rm[i]; }
         __syncthreads();
@@ -288,6 +298,7 @@ __global__ __launch_bounds__(NT) void pde_kernel(const PdeArgs a) {
         for (int i = t; i < L; i += NT) { rp[i] *= sc; rm[i] *= sc; }
         __syncthreads();
     }
+#undef PDE_ROW
     for (int i = t; i < L; i += NT) {
         if (a.rho_p) a.rho_p[(size_t)sys * L + i] = rp[i];
         if (a.rho_m) a.rho_m[(size_t)sys * L + i] = rm[i];
@@ -350,13 +361,14 @@ int make_sweep_plan(const pde_params *p, int32_t n_systems, const double *kernel
     return PDE_OK;
 }
 
-// ---- host: the driver of both entry points.  sweep == nullptr: pde_solve_batch, one table of taps from p->kernel_sigma.
-int solve_impl(const char *who, std::string &err, const SweepPlan *sweep, const pde_params *p, int32_t n_systems, const PdeIo &io) {
+// ---- host: the driver of the entry points.  sweep == nullptr: pde_solve_batch / pder_solve, one table of taps from p->kernel_sigma.
+// `span`: the steps and rows of the launch; io.from / io.to: the checkpoints of the resumable forms.
+int solve_impl(const char *who, std::string &err, const SweepPlan *sweep, const pde_params *p, int32_t n_systems, const PdeIo &io, const PdeSpan &span) {
     OneShot job{who, err, false, PDE_ERR_NODEVICE, PDE_ERR_ARG, PDE_ERR_HIP};   // no zero-fill: the kernel writes every output in full
     if (int rc = job.select_device(p->device)) return rc;
 
     const int L = p->L;
-    const PdeExtents x(p, n_systems);
+    const PdeExtents x(p, n_systems, span);
     std::vector<double> plain;                                 // kernel taps (ref :84-93) of the one width; a sweep brings its systems' tables
     const int ktaps = sweep ? sweep->info.ktaps_max : kernel_taps(p, p->xlim / L, plain);
     PdeArgs a{};
@@ -373,7 +385,8 @@ int solve_impl(const char *who, std::string &err, const SweepPlan *sweep, const 
     }
     const bool tracer_series = true;                           // wherever the caller gave the pointer; without tracers nothing writes them: unspecified values
     if (int rc = pde_stage_outputs(job, a, p, x, io, tracer_series)) return rc;
-    OUT(rho_p, io.rho_p, x.SL); OUT(rho_m, io.rho_m, x.SL); OUT(tracer_x, io.tracer_x, x.ST); OUT(tracer_s, io.tracer_s, x.ST);
+    OUT(rho_p, io.rho_p ? io.rho_p : io.to ? io.to->rho_p : nullptr, x.SL); OUT(rho_m, io.rho_m ? io.rho_m : io.to ? io.to->rho_m : nullptr, x.SL);   // a checkpoint wants the fields too
+    OUT(tracer_x, io.tracer_x, x.ST); OUT(tracer_s, io.tracer_s, x.ST);
     size_t lds = base_lds_bytes(L, ktaps);
     if (sweep) lds = (size_t)sweep->info.lds_bytes;             // the plan has refused what does not fit
     else if (lds > 160 * 1024) {                               // beyond LDS: the fields live in global memory, the scans' scratch in LDS
@@ -381,7 +394,8 @@ int solve_impl(const char *who, std::string &err, const SweepPlan *sweep, const 
         WORK(work, x.S * (size_t)a.work_stride);
         lds = (size_t)((NT + 3) & ~3) * sizeof(double) + (size_t)2 * NT * sizeof(double4);
     }
-    void (*kernel)(const PdeArgs) = !sweep ? pde_kernel<BATCH> : sweep->info.conv_log2_max ? pde_kernel<SWEEP_SPECTRAL> : pde_kernel<SWEEP_DIRECT>;
+    void (*kernel)(const PdeArgs) = span.resume ? (!sweep ? pde_kernel<BATCH, true> : sweep->info.conv_log2_max ? pde_kernel<SWEEP_SPECTRAL, true> : pde_kernel<SWEEP_DIRECT, true>)
+                                                : (!sweep ? pde_kernel<BATCH, false> : sweep->info.conv_log2_max ? pde_kernel<SWEEP_SPECTRAL, false> : pde_kernel<SWEEP_DIRECT, false>);
     if (int rc = job.raise_lds_limit(reinterpret_cast<const void *>(kernel), lds)) return rc;
     if (int rc = job.create_events()) return rc;
     job.ev.start();
@@ -391,7 +405,29 @@ int solve_impl(const char *who, std::string &err, const SweepPlan *sweep, const 
     DOWN(io.rho_p, rho_p, x.SL * 8); DOWN(io.rho_m, rho_m, x.SL * 8);
     if (int rc = pde_fetch_outputs(job, a, p, x, io, tracer_series)) return rc;
     DOWN(io.tracer_x, tracer_x, x.ST * 8); DOWN(io.tracer_s, tracer_s, x.ST);
-    return PDE_OK;
+    return pde_fetch_checkpoint(job, a, p, x, io, a.rho_p, a.rho_m);
+}
+
+// The checks and the launch behind pde_solve_batch and pder_solve, behind pdek_solve and pdekr_solve: one body each, worded
+// by the entry's name.
+int batch_entry(const char *who, std::string &err, const pde_params *p, int32_t n_systems, PdeIo io) {
+    auto bad = [&](const char *m) { err = std::string(who) + ": " + m; return PDE_ERR_ARG; };
+    PdeSpan span;
+    if (const char *why = adopt_checkpoint(p, io, span)) return bad(why);
+    if (const char *why = check_args(p, n_systems, io)) return bad(why);
+    if (p->convolution != 0) return bad("convolution must be 0 here: the spectral convolution belongs to the wide shape (pdew_solve, include/pde_wide.h)");
+    return solve_impl(who, err, nullptr, p, n_systems, io, span);
+}
+
+int sweep_entry(const char *who, std::string &err, const pde_params *p, int32_t n_systems, const double *kernel_sigma, PdeIo io) {
+    auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return PDE_ERR_ARG; };
+    PdeSpan span;
+    if (const char *why = adopt_checkpoint(p, io, span)) return bad(why);
+    if (const char *why = check_args(p, n_systems, io)) return bad(why);
+    SweepPlan pl;
+    std::string why;
+    if (make_sweep_plan(p, n_systems, kernel_sigma, pl, why)) return bad(why);
+    return solve_impl(who, err, &pl, p, n_systems, io, span);
 }
 
 }  // namespace
@@ -407,10 +443,7 @@ int pde_solve_batch(const pde_params *p, int32_t n_systems, const double *beta, 
                     double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
     const PdeIo io{beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m, m_series, var_series, v_eff_series,
                    D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms};
-    auto bad = [&](const char *m) { g_err = std::string("pde_solve_batch: ") + m; return PDE_ERR_ARG; };
-    if (const char *why = check_args(p, n_systems, io)) return bad(why);
-    if (p->convolution != 0) return bad("convolution must be 0 here: the spectral convolution belongs to the wide shape (pdew_solve, include/pde_wide.h)");
-    return solve_impl("pde_solve_batch", g_err, nullptr, p, n_systems, io);
+    return batch_entry("pde_solve_batch", g_err, p, n_systems, io);
 }
 
 const char *pdek_last_error(void) { return g_err_k.c_str(); }
@@ -437,12 +470,43 @@ int pdek_solve(const pde_params *p, int32_t n_systems, const double *beta, const
                double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
     const PdeIo io{beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m, m_series, var_series, v_eff_series,
                    D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms};
-    auto bad = [&](const std::string &m) { g_err_k = "pdek_solve: " + m; return PDE_ERR_ARG; };
-    if (const char *why = check_args(p, n_systems, io)) return bad(why);
-    SweepPlan pl;
-    std::string why;
-    if (make_sweep_plan(p, n_systems, kernel_sigma, pl, why)) return bad(why);
-    return solve_impl("pdek_solve", g_err_k, &pl, p, n_systems, io);
+    return sweep_entry("pdek_solve", g_err_k, p, n_systems, kernel_sigma, io);
+}
+
+const char *pder_last_error(void) { return g_err_r.c_str(); }
+const char *pdekr_last_error(void) { return g_err_kr.c_str(); }
+
+int pder_extents(const pde_params *p, int32_t from_step, int32_t *first_row, int32_t *n_rows, int32_t *n_snap, int32_t *first_snap) {
+    auto bad = [&](const char *m) { g_err_r = std::string("pder_extents: ") + m; return PDE_ERR_ARG; };
+    if (!p) return bad("null argument");
+    PdeSpan sp;
+    if (const char *why = pde_span(p, from_step, sp)) return bad(from_step < -1 ? "from_step must be >= -1" : why);
+    if (first_row) *first_row = sp.row0;
+    if (n_rows) *n_rows = sp.n_rows;
+    if (n_snap) *n_snap = sp.n_snap;
+    if (first_snap) *first_snap = sp.snap0;
+    return PDE_OK;
+}
+
+int pder_solve(const pde_params *p, int32_t n_systems, const double *beta, const double *rho_p0, const double *rho_m0,
+               const double *tracer_x0, const int8_t *tracer_s0, const double *rand_u, const double *rand_n,
+               double *rho_p, double *rho_m, double *m_series, double *var_series, double *v_eff_series,
+               double *D_eff_series, double *snapshots, double *m_snapshots, double *fft_re, double *fft_im,
+               double *tracer_x, int8_t *tracer_s, double *kernel_ms, const pde_checkpoint *from, pde_checkpoint *to) {
+    const PdeIo io{beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m, m_series, var_series, v_eff_series,
+                   D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms, from, to};
+    return batch_entry("pder_solve", g_err_r, p, n_systems, io);
+}
+
+int pdekr_solve(const pde_params *p, int32_t n_systems, const double *beta, const double *kernel_sigma,
+                const double *rho_p0, const double *rho_m0, const double *tracer_x0, const int8_t *tracer_s0,
+                const double *rand_u, const double *rand_n,
+                double *rho_p, double *rho_m, double *m_series, double *var_series, double *v_eff_series,
+                double *D_eff_series, double *snapshots, double *m_snapshots, double *fft_re, double *fft_im,
+                double *tracer_x, int8_t *tracer_s, double *kernel_ms, const pde_checkpoint *from, pde_checkpoint *to) {
+    const PdeIo io{beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m, m_series, var_series, v_eff_series,
+                   D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms, from, to};
+    return sweep_entry("pdekr_solve", g_err_kr, p, n_systems, kernel_sigma, io);
 }
 
 }  // extern "C"

@@ -1,5 +1,8 @@
 // pde_wide_hip.hip -- MI355X (gfx950) implementation of the C ABI in include/pde_wide.h: the hydrodynamic-limit solver of
-// pde_hip.hip with ONE system spread over many workgroups.
+// pde_hip.hip with ONE system spread over many workgroups; and of its resumable form pdewr_solve (include/pde_resume.h).
+// A resumed launch takes the checkpoint's fields through the `init` form of pdew_renorm_fwd: the per-slab sums and forward
+// maps it forms from them are, operation for operation, those the fused form left when it stored these same values, so the
+// chain has the single launch's bits (for the same number of slabs).
 //
 // Same scheme and order of operations as pde_kernel (ref IMEX_PDE_solver_class.py:187-290): magnetisation -> observables ->
 // tracers -> implicit diffusion -> reaction / upwind advection / clip -> mass renormalisation, binary64 throughout.
@@ -48,7 +51,7 @@
 namespace {
 
 using namespace pde_common;
-std::string g_err, g_spec_err;
+std::string g_err, g_spec_err, g_err_r;
 
 #include "pde_spectral.hpp"
 
@@ -61,6 +64,7 @@ enum { P_ST = 0, P_SS, P_SMF, P_SV, P_M0, P_M1, NSLOT };   // per-slab partial s
 
 struct WArgs {
     pde_params p;
+    PdeSpan span;                       // the absolute steps this launch runs and the rows it records (pde_common.hpp)
     int G, q, r;                        // slab g: q + (g < r) sites from g * q + min(g, r)
     int n_snap, ktaps;
     int spectral;                       // the kernel_mode 1 convolution comes from the transforms of pde_spectral.hpp (sp)
@@ -354,8 +358,8 @@ __global__ __launch_bounds__(NT) void pdew_mag(const WArgs a, const int nstep) {
     }
     __syncthreads();
     double smf = 0.0, sv = 0.0;
-    const bool snap = nstep % a.p.snapshot_interval == 0;
-    const size_t so = ((size_t)sys * a.n_snap + nstep / a.p.snapshot_interval) * L;
+    const bool snap = nstep % a.p.snapshot_interval == 0 && nstep >= a.span.row0;   // a resumed launch records nothing of its checkpoint's step
+    const size_t so = ((size_t)sys * a.n_snap + (snap ? nstep / a.p.snapshot_interval - a.span.snap0 : 0)) * L;
     for (int i = a0 + t; i < a0 + n; i += NT) {
         const double vp = rp[i], vm = rm[i], d = vp + vm - mean_t;
         smf += mf[i]; sv += d * d;
@@ -387,7 +391,7 @@ __global__ __launch_bounds__(NT) void pdew_mag(const WArgs a, const int nstep) {
 
 // ---- tracers (ref :257-287), one thread per tracer
 __global__ __launch_bounds__(NT) void pdew_tracers(const WArgs a, const int nstep) {
-    const int L = a.p.L, sys = blockIdx.y, ntr = a.p.n_tracers, i = blockIdx.x * NT + threadIdx.x, nsteps = a.p.nsteps;
+    const int L = a.p.L, sys = blockIdx.y, ntr = a.p.n_tracers, i = blockIdx.x * NT + threadIdx.x;
     if (i >= ntr) return;
     const double *mf = a.mf + (size_t)sys * L;
     double *trx = a.trx + (size_t)sys * ntr, *hist = a.hist + (size_t)sys * a.p.window * ntr;
@@ -401,7 +405,7 @@ __global__ __launch_bounds__(NT) void pdew_tracers(const WArgs a, const int nste
     int s = trs[i];
     double u, gn;
     if (a.rand_u) {
-        const size_t o = ((size_t)sys * (nsteps + 1) + nstep) * ntr + i;
+        const size_t o = ((size_t)sys * a.span.n_rows + (nstep - a.span.row0)) * ntr + i;
         u = a.rand_u[o]; gn = a.rand_n[o];
     } else {
         tracer_noise(a.p.seed, nstep, i, sys, u, gn);
@@ -416,7 +420,8 @@ __global__ __launch_bounds__(NT) void pdew_tracers(const WArgs a, const int nste
 // ---- one workgroup per system: the series of this step from the partials, the tracers' window statistics
 __global__ __launch_bounds__(NT) void pdew_obs(const WArgs a, const int nstep) {
     __shared__ double red[NT / 64];
-    const int L = a.p.L, t = threadIdx.x, sys = blockIdx.y, G = a.G, ntr = a.p.n_tracers, ns = a.p.nsteps + 1;
+    const int L = a.p.L, t = threadIdx.x, sys = blockIdx.y, G = a.G, ntr = a.p.n_tracers;
+    const size_t row = (size_t)sys * a.span.n_rows + (nstep - a.span.row0);
     const double *part = a.part + (size_t)sys * NSLOT * G;
     if (a.m_series) {
         double m;
@@ -426,11 +431,11 @@ __global__ __launch_bounds__(NT) void pdew_obs(const WArgs a, const int nstep) {
         } else {
             m = combine(part + (size_t)P_SMF * G, G, red) / L;
         }
-        if (t == 0) a.m_series[(size_t)sys * ns + nstep] = m;
+        if (t == 0) a.m_series[row] = m;
     }
     if (a.var_series) {
         const double sv = combine(part + (size_t)P_SV * G, G, red);
-        if (t == 0) a.var_series[(size_t)sys * ns + nstep] = sv / L;
+        if (t == 0) a.var_series[row] = sv / L;
     }
     if (a.fft_re) {
         const int nf = a.p.n_fft_modes;
@@ -439,7 +444,7 @@ __global__ __launch_bounds__(NT) void pdew_obs(const WArgs a, const int nstep) {
             double s = 0.0;
             for (int g = 0; g < G; ++g) s += fpart[(size_t)e * G + g];
             double *out = (e & 1) ? a.fft_im : a.fft_re;
-            out[((size_t)sys * ns + nstep) * nf + (e >> 1)] = s / L;
+            out[row * nf + (e >> 1)] = s / L;
         }
     }
     if (ntr > 0 && (a.v_eff || a.D_eff)) {
@@ -454,13 +459,13 @@ __global__ __launch_bounds__(NT) void pdew_obs(const WArgs a, const int nstep) {
             for (int i = t; i < ntr; i += NT) { const double d = trx[i] - old[i] - mean_dr; sv += d * d; }
             sv = block_sum(sv, red) / ntr;
             if (t == 0) {
-                if (a.v_eff) a.v_eff[(size_t)sys * ns + nstep] = mean_dr / (a.p.window * dt);
-                if (a.D_eff) a.D_eff[(size_t)sys * ns + nstep] = sv / (2 * a.p.window * dt);
+                if (a.v_eff) a.v_eff[row] = mean_dr / (a.p.window * dt);
+                if (a.D_eff) a.D_eff[row] = sv / (2 * a.p.window * dt);
             }
         } else if (t == 0) {
             const double nan = __longlong_as_double(0x7ff8000000000000ll);
-            if (a.v_eff) a.v_eff[(size_t)sys * ns + nstep] = nan;
-            if (a.D_eff) a.D_eff[(size_t)sys * ns + nstep] = nan;
+            if (a.v_eff) a.v_eff[row] = nan;
+            if (a.D_eff) a.D_eff[row] = nan;
         }
     }
 }
@@ -508,6 +513,8 @@ const char *make_plan(const pde_params *p, int32_t n_systems, int32_t workgroups
     return nullptr;
 }
 
+int wide_entry(const char *who, std::string &err, const pde_params *p, int32_t n_systems, int32_t workgroups, PdeIo io);
+
 }  // namespace
 
 extern "C" {
@@ -548,17 +555,40 @@ int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const
                double *tracer_x, int8_t *tracer_s, double *kernel_ms) {
     const PdeIo io{beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m, m_series, var_series, v_eff_series,
                    D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms};
-    auto bad = [&](const char *m) { g_err = std::string("pdew_solve: ") + m; return PDE_ERR_ARG; };
+    return wide_entry("pdew_solve", g_err, p, n_systems, workgroups, io);
+}
+
+const char *pdewr_last_error(void) { return g_err_r.c_str(); }
+
+int pdewr_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const double *beta, const double *rho_p0,
+                const double *rho_m0, const double *tracer_x0, const int8_t *tracer_s0, const double *rand_u, const double *rand_n,
+                double *rho_p, double *rho_m, double *m_series, double *var_series, double *v_eff_series,
+                double *D_eff_series, double *snapshots, double *m_snapshots, double *fft_re, double *fft_im,
+                double *tracer_x, int8_t *tracer_s, double *kernel_ms, const pde_checkpoint *from, pde_checkpoint *to) {
+    const PdeIo io{beta, rho_p0, rho_m0, tracer_x0, tracer_s0, rand_u, rand_n, rho_p, rho_m, m_series, var_series, v_eff_series,
+                   D_eff_series, snapshots, m_snapshots, fft_re, fft_im, tracer_x, tracer_s, kernel_ms, from, to};
+    return wide_entry("pdewr_solve", g_err_r, p, n_systems, workgroups, io);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The checks and the launches behind pdew_solve and pdewr_solve, worded by the entry's name.
+int wide_entry(const char *who, std::string &g_err, const pde_params *p, int32_t n_systems, int32_t workgroups, PdeIo io) {
+    auto bad = [&](const char *m) { g_err = std::string(who) + ": " + m; return PDE_ERR_ARG; };
+    PdeSpan span;
+    if (const char *why = adopt_checkpoint(p, io, span)) return bad(why);
     if (const char *why = check_args(p, n_systems, io)) return bad(why);
     const int L = p->L, ntr = p->n_tracers;
     std::vector<double> ktab;
     const int ktaps = kernel_taps(p, p->xlim / L, ktab);
     Plan pl;
     if (const char *why = make_plan(p, n_systems, workgroups, ktaps, pl)) return bad(why);
-    OneShot job{"pdew_solve", g_err, false, PDE_ERR_NODEVICE, PDE_ERR_ARG, PDE_ERR_HIP};   // no zero-fill: the kernels write every buffer before it is read
+    OneShot job{who, g_err, false, PDE_ERR_NODEVICE, PDE_ERR_ARG, PDE_ERR_HIP};   // no zero-fill: the kernels write every buffer before it is read
     if (int rc = job.select_device(p->device)) return rc;
 
-    const PdeExtents x(p, n_systems);
+    const PdeExtents x(p, n_systems, span);
     const size_t S = x.S, SL = x.SL;
     const int G = pl.G;
     WArgs a{};
@@ -599,25 +629,27 @@ int pdew_solve(const pde_params *p, int32_t n_systems, int32_t workgroups, const
     job.ev.start();
     hipLaunchKernelGGL(pdew_renorm_fwd, grid, dim3(NT), 0, nullptr, a, 1);
     hipError_t err = hipGetLastError();
-    for (int n = 0; n <= p->nsteps && err == hipSuccess; ++n) {
+    for (int n = span.n_begin; err == hipSuccess; ++n) {        // absolute step numbers; the kernels make the rows launch-relative
+        const bool record = n >= span.row0;                        // a resumed launch starts behind the row of its checkpoint's step
         if (pl.spectral) pdes_convolve(a.sp, nz);
         hipLaunchKernelGGL(pdew_mag, grid, dim3(NT), mag_lds, nullptr, a, n);
-        if (ntr) hipLaunchKernelGGL(pdew_tracers, tgrid, dim3(NT), 0, nullptr, a, n);
-        if (want_obs) hipLaunchKernelGGL(pdew_obs, one, dim3(NT), 0, nullptr, a, n);
-        if (n < p->nsteps) {
+        if (ntr && record) hipLaunchKernelGGL(pdew_tracers, tgrid, dim3(NT), 0, nullptr, a, n);
+        if (want_obs && record) hipLaunchKernelGGL(pdew_obs, one, dim3(NT), 0, nullptr, a, n);
+        if (n < span.n_end) {
             hipLaunchKernelGGL(pdew_fwd_bwd, grid, dim3(NT), 0, nullptr, a);
             hipLaunchKernelGGL(pdew_bwd, grid, dim3(NT), 0, nullptr, a);
             hipLaunchKernelGGL(pdew_react, grid, dim3(NT), 0, nullptr, a);
             hipLaunchKernelGGL(pdew_renorm_fwd, grid, dim3(NT), 0, nullptr, a, 0);
         }
         err = hipGetLastError();
+        if (n == span.n_end) break;
     }
     job.ev.stop();
-    if (int rc = job.finish(err, "pdew_solve", io.kernel_ms)) return rc;
+    if (int rc = job.finish(err, who, io.kernel_ms)) return rc;
     DOWN(io.rho_p, rp, SL * 8); DOWN(io.rho_m, rm, SL * 8);         // the fields end in their work buffers
     if (int rc = pde_fetch_outputs(job, a, p, x, io, tracer_series)) return rc;
     if (ntr) { DOWN(io.tracer_x, trx, x.ST * 8); DOWN(io.tracer_s, trs, x.ST); }   // and the tracers in theirs
-    return PDE_OK;
+    return pde_fetch_checkpoint(job, a, p, x, io, a.rp, a.rm);
 }
 
-}  // extern "C"
+}  // namespace
