@@ -2009,6 +2009,9 @@ void ts_choose_geometry(aps_handle *h) {
     h->own_lo = h->ts_lo * h->ts_own;
     h->own_hi = std::min(L, h->ts_hi * h->ts_own);
     h->ts_reach = h->model.field_mode ? (h->tlen + 2 + h->ts_own - 1) / h->ts_own : 0;
+    // a torus whose last tile is ragged: across the seam `reach` tiles hold own - last sites fewer than whole tiles would, and the kernel
+    // sweeps the lists of every tile with a site in reach of its frame (tile_step.hpp: b0, nbk) -- the halo must carry them all
+    if (h->ts_reach && h->p.periodic && L % h->ts_own) h->ts_reach = (h->tlen + 2 + (h->ts_own - L % h->ts_own) + h->ts_own - 1) / h->ts_own;
     // steps per halo exchange: the ghost tiles a rank steps on top of its own cost next to nothing while the launch stays
     // within three workgroups per CU (one wave of workgroups: the step is latency bound there, 11 us at 256 tiles, 14.5 us
     // at 633), and at most a quarter more tiles otherwise

@@ -53,7 +53,17 @@ template <bool TAB_LDS> struct TsGeom { static constexpr int SB = TAB_LDS ? 4 : 
 __host__ __device__ inline int ts_table_pad(int RS, int own) { return 64 * RS + own + 2; }
 __host__ __device__ inline int ts_table_chunks(int tlen, int RS, int own, int wbytes) { return ((tlen + ts_table_pad(RS, own) + 1) * wbytes + 1023) / 1024; }   // 1 KB each
 constexpr int TS_WH = 8;                   // windowed sweep: bucket offsets per group (buckets tile - off and tile + off, off in [jH, jH + H))
-__host__ __device__ inline int ts_win_entries(int RS, int own) { return ((TS_WH + 1) * own + 64 * RS + 8 + 127) / 128 * 128; }
+// A window is staged in whole 1 KB chunks (stage_w: 256 entries of the 32-bit field) up to the one that holds its last entry, TS_WH own +
+// 64 RS (tiles shorter than their frame allows: (TS_WH - 1) own + 128 RS - 4 if that is more): a buffer must hold those chunks whole, or
+// the last one runs over into the other buffer while that one is being swept.  Only frames of one row need more than the first term for
+// that (640 entries against three chunks).  The 256 is the chunk of the 32-bit field applied to both: a binary64 chunk is 128 entries,
+// so its windows of one-row frames are 2 KB longer than they need be.
+__host__ __device__ inline int ts_win_entries(int RS, int own) {
+    const int span = (TS_WH + 1) * own + 64 * RS + 8;
+    const int last = TS_WH * own + 64 * RS > (TS_WH - 1) * own + 128 * RS - 4 ? TS_WH * own + 64 * RS : (TS_WH - 1) * own + 128 * RS - 4;
+    const int staged = (last / 256 + 1) * 256;
+    return ((span > staged ? span : staged) + 127) / 128 * 128;
+}
 constexpr int TS_SHCAP = 320;              // windowed sweep: capacity of a shared class list (a round adds at most 256 entries); per side: half
 constexpr int TS_SEG = 128;                // entries per deposit segment of a wave (four segments: P, M, F, image)
 struct TsLds { size_t seg, cells, props, occ, misc, plist, tab, field, total; int Q; bool cells_in_regs; };

@@ -519,7 +519,10 @@ def test_inlibrary_rccl_allgather_world1(capi, method):
 
 def test_table_too_large_for_lds_uses_global_table(capi, method):
     """sigma_g = 6000 -> 24001-entry table (188 KB) does not fit LDS: the kernels gather from the table in
-    global memory instead.  Same bit-exact bars."""
+    global memory instead.  Same bit-exact bars.  Which kernels that means depends on the formulation, and is asserted: `pairs`
+    and `lattice` gather from the global table; `tiles` between walls, with a table short of half the box, hands such a table to
+    the exact convolution (csrc/ntt_conv.hpp), NOT to the windowed sweep tile_step<BC, false, ...> -- that one is run, at every
+    frame height, by tests/test_gpu_sync_frames.py::test_windowed_table_at_every_frame."""
     par = params(L=60000, K=1, sigma=0.1)
     rng = np.random.default_rng(31)
     N = 3000
@@ -530,6 +533,9 @@ def test_table_too_large_for_lds_uses_global_table(capi, method):
     try:
         tab, q = h.table()
         assert len(tab) == 24001 and q == orc.q and np.array_equal(tab, orc.table)
+        assert h.ntt_info()["on"] == (method == "tiles"), (method, h.ntt_info())
+        if method == "tiles":
+            assert not h.tiles_info()["table_in_lds"]
         h.set_state(pos, spin)
         S, W, occ4 = h.pair_accumulate()
         S0, W0, occ0 = orc.pair_sums()
