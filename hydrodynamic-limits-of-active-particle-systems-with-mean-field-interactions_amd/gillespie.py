@@ -108,6 +108,9 @@ CAPTURE_COLUMNS = ("n", "n_bound", "binds", "unbinds", "exits", "occupied_sites"
 _I32, _DBL, _PTR, _MS = C.c_int32, C.c_double, C.c_void_p, C.POINTER(C.c_double)
 _PAR, _VAR, _CKP, _XCKP = C.POINTER(GilParams), C.POINTER(GilxVariants), C.POINTER(GilCheckpoint), C.POINTER(GilxCheckpoint)
 N_COMMON = 14       # n0, pos0, sigma0, bound0, uniforms; pos, sigma, flags, scalars, n_recorded, n_events, t_final, exits, n_exits
+CHECKPOINT_ARRAYS = (("pos", np.int32, 2), ("flags", np.uint8, 2), ("ref", np.int32, 2), ("t", np.float64, 1), ("n_events", np.int64, 1),
+                     ("next_obs", np.int32, 1))
+_WINDOW_ARRAYS = (("window", np.float64), ("n_window", np.int32), ("n_empty", np.int32))       # of a mixed structure run
 
 
 def _p(a):
@@ -124,17 +127,45 @@ def _stage_plain(c, **_):
     return [], [], [], {}
 
 
-def _stage_resumable(c, *, obs_first, **_):
-    """obs_first, the checkpoint to start from (NULL: a fresh start) and the one to fill, behind kernel_ms"""
+def _stage_checkpoints(c, obs_first, kk=None):
+    """The tail of a segment -- obs_first, the checkpoint to start from (NULL: a fresh start) and the one to fill -- and what it adds
+    to the dictionary: the latter's arrays and the first row of every system.  `kk=None`: a gil_checkpoint; otherwise a
+    gilx_checkpoint, with n_slots and, for kk > 0, the window sums of kk modes.  c.ck_in holds the six arrays of the caller's
+    checkpoint, c.ck_more what it has beyond them."""
+    more = {}
+    if kk is not None:
+        more = dict(n_slots=(np.int32, (c.S,)))
+        if kk > 0:
+            more.update({k: (dt, (c.S, kk, 3) if k == "window" else (c.S,)) for k, dt in _WINDOW_ARRAYS})
     ck_out = {k: np.zeros((c.S, c.ncap)[:nd], dt) for k, dt, nd in CHECKPOINT_ARRAYS}
-    c_in = None if c.ck_in is None else GilCheckpoint(**{k: _p(v).value for k, v in c.ck_in.items()})     # c.ck_in holds the arrays
-    c_out = GilCheckpoint(**{k: _p(v).value for k, v in ck_out.items()})                                  # the dictionary returned does
-    # first_row reads the checkpoint to start from only, which the library does not write (const in gillespie_resume.h)
-    first_row = np.zeros(c.S, np.int32) if c.ck_in is None else np.clip(c.ck_in["next_obs"] - int(obs_first), 0, None).astype(np.int32)
+    ck_out.update({k: np.zeros(shape, dt) for k, (dt, shape) in more.items()})
+    arrays, first_row = None, np.zeros(c.S, np.int32)
     if c.ck_in is not None:
-        first_row[c.ck_in["next_obs"] < int(obs_first)] = 0        # ended before this segment: n_recorded is 0 too
-    return [], [], [int(obs_first), None if c_in is None else C.byref(c_in), C.byref(c_out)], dict(
-        checkpoint=ck_out, first_row=first_row, obs_first=int(obs_first), n0=np.full(c.S, c.ncap, np.int32))   # any slot may be alive
+        arrays = dict(c.ck_in)
+        for k, (dt, shape) in more.items():
+            if c.ck_more.get(k) is None:
+                continue                                       # a missing array is the library's to refuse
+            arrays[k] = np.ascontiguousarray(c.ck_more[k], dtype=dt)
+            if arrays[k].shape != shape:
+                raise ValueError(f"checkpoint: {k} must have the shape {shape}")
+        c.keep.append(arrays)
+        # a system that ended before this segment starts at row 0, and its n_recorded is 0 too.  This reads the checkpoint to start
+        # from only, which the library does not write (const in gillespie_resume.h)
+        first_row = np.clip(c.ck_in["next_obs"] - int(obs_first), 0, None).astype(np.int32)
+
+    def struct(a):
+        base = GilCheckpoint(**{k: _p(a[k]).value for k, _, _ in CHECKPOINT_ARRAYS})
+        return base if kk is None else GilxCheckpoint(base=base, **{k: _p(a[k]).value for k in more if a.get(k) is not None})
+
+    c_in, c_out = None if arrays is None else struct(arrays), struct(ck_out)
+    n0 = np.full(c.S, c.ncap, np.int32) if kk is None else ck_out["n_slots"]     # a plain checkpoint: any slot may be alive
+    return [int(obs_first), None if c_in is None else C.byref(c_in), C.byref(c_out)], dict(checkpoint=ck_out, first_row=first_row,
+                                                                                          obs_first=int(obs_first), n0=n0)
+
+
+def _stage_resumable(c, *, obs_first, **_):
+    """obs_first, the checkpoint to start from and the one to fill, behind kernel_ms"""
+    return ([], [], *_stage_checkpoints(c, obs_first))
 
 
 def _stage_structure(c, *, k_max, first_obs, **_):
@@ -177,69 +208,37 @@ def _stage_mixed(c, *, mixed, **_):
     return [C.byref(desc)], [], [], {}
 
 
+def _stage_rows_and_head(c, k_max, first_obs, want_rows, sums):
+    """What gilxs_run and gilxsr_run share: k_max and first_obs behind the variants, the rows (`want_rows`) and the head behind the
+    common outputs; `sums` = the arrays of the window sums, which the two hand over differently."""
+    rows = np.zeros((c.S, c.M, 4 + 2 * max(int(k_max), 0))) if want_rows else None
+    head = np.zeros((c.S, c.M, 4))
+    back = c.results + [rows, head] + list(sums.values())
+    return ([int(k_max), int(first_obs)], [_p(rows), _p(head)],
+            dict(sums, structure=rows, head=head, bytes_back=int(sum(x.nbytes for x in back if x is not None))))
+
+
 def _stage_mixed_structure(c, *, mixed, k_max, first_obs, want_rows, **_):
+    """the window sums are three more outputs behind the head"""
     front = _stage_mixed(c, mixed=mixed)[0]
-    kk = max(int(k_max), 0)
-    rows = np.zeros((c.S, c.M, 4 + 2 * kk)) if want_rows else None
-    head, window = np.zeros((c.S, c.M, 4)), np.zeros((c.S, kk, 3))          # gilxs_run refuses k_max < 1
-    n_window, n_empty = np.zeros(c.S, np.int32), np.zeros(c.S, np.int32)
-    back = c.results + [rows, head, window, n_window, n_empty]
-    return (front + [int(k_max), int(first_obs)], [_p(rows), _p(head), _p(window), _p(n_window), _p(n_empty)], [],
-            dict(structure=rows, head=head, window=window, n_window=n_window, n_empty=n_empty,
-                 bytes_back=int(sum(x.nbytes for x in back if x is not None))))
-
-
-def _mixed_checkpoints(c, obs_first, kk):
-    """The gilx_checkpoint to start from (None: a fresh start) and the one to fill, with the dictionary of the latter's arrays
-    and the first row of every system; kk > 0: with the window sums of kk modes.  c.ck_more holds what the caller's checkpoint
-    has beyond the six arrays of c.ck_in."""
-    ck_out = {k: np.zeros((c.S, c.ncap)[:nd], dt) for k, dt, nd in CHECKPOINT_ARRAYS}
-    ck_out["n_slots"] = np.zeros(c.S, np.int32)
-    if kk > 0:
-        ck_out.update(window=np.zeros((c.S, kk, 3)), n_window=np.zeros(c.S, np.int32), n_empty=np.zeros(c.S, np.int32))
-
-    def struct(arrays):
-        more = {k: _p(arrays[k]).value for k in ("n_slots", "window", "n_window", "n_empty") if arrays.get(k) is not None}
-        return GilxCheckpoint(base=GilCheckpoint(**{k: _p(arrays[k]).value for k, _, _ in CHECKPOINT_ARRAYS}), **more)
-
-    c_in, first_row = None, np.zeros(c.S, np.int32)
-    if c.ck_in is not None:
-        more = {}
-        for k, dt, shape in (("n_slots", np.int32, (c.S,)), ("window", np.float64, (c.S, kk, 3)), ("n_window", np.int32, (c.S,)), ("n_empty", np.int32, (c.S,))):
-            if c.ck_more.get(k) is None or (kk == 0 and k != "n_slots"):
-                continue                                       # a missing array is the library's to refuse
-            more[k] = np.ascontiguousarray(c.ck_more[k], dtype=dt)
-            if more[k].shape != shape:
-                raise ValueError(f"checkpoint: {k} must have the shape {shape}")
-        arrays = dict(c.ck_in, **more)
-        c.keep.append(arrays)
-        c_in = struct(arrays)
-        first_row = np.clip(c.ck_in["next_obs"] - int(obs_first), 0, None).astype(np.int32)
-        first_row[c.ck_in["next_obs"] < int(obs_first)] = 0        # ended before this segment: n_recorded is 0 too
-    c_out = struct(ck_out)
-    c.keep.append((c_in, c_out))
-    return [int(obs_first), None if c_in is None else C.byref(c_in), C.byref(c_out)], ck_out, first_row
+    kk = max(int(k_max), 0)                                    # gilxs_run refuses k_max < 1
+    sums = {k: np.zeros((c.S, kk, 3) if k == "window" else c.S, dt) for k, dt in _WINDOW_ARRAYS}
+    numbers, behind, extra = _stage_rows_and_head(c, k_max, first_obs, want_rows, sums)
+    return front + numbers, behind + [_p(a) for a in sums.values()], [], extra
 
 
 def _stage_mixed_resumable(c, *, mixed, obs_first, **_):
     """the variants in front; obs_first, the checkpoint to start from and the one to fill behind kernel_ms"""
     front = _stage_mixed(c, mixed=mixed)[0]
-    tail, ck_out, first_row = _mixed_checkpoints(c, obs_first, 0)
-    return front, [], tail, dict(checkpoint=ck_out, first_row=first_row, obs_first=int(obs_first), n0=ck_out["n_slots"])
+    return (front, [], *_stage_checkpoints(c, obs_first, 0))
 
 
 def _stage_mixed_structure_resumable(c, *, mixed, k_max, first_obs, want_rows, obs_first, **_):
-    """_stage_mixed_structure where the window sums travel in the checkpoints: rows and head behind the common outputs"""
+    """_stage_mixed_structure where the window sums travel in the checkpoints"""
     front = _stage_mixed(c, mixed=mixed)[0]
-    kk = max(int(k_max), 0)
-    rows = np.zeros((c.S, c.M, 4 + 2 * kk)) if want_rows else None
-    head = np.zeros((c.S, c.M, 4))
-    tail, ck_out, first_row = _mixed_checkpoints(c, obs_first, kk)
-    back = c.results + [rows, head] + [ck_out.get(k) for k in ("window", "n_window", "n_empty")]
-    return (front + [int(k_max), int(first_obs)], [_p(rows), _p(head)], tail,
-            dict(structure=rows, head=head, window=ck_out.get("window"), n_window=ck_out.get("n_window"), n_empty=ck_out.get("n_empty"),
-                 checkpoint=ck_out, first_row=first_row, obs_first=int(obs_first), n0=ck_out["n_slots"],
-                 bytes_back=int(sum(x.nbytes for x in back if x is not None))))
+    tail, extra = _stage_checkpoints(c, obs_first, max(int(k_max), 0))
+    numbers, behind, more = _stage_rows_and_head(c, k_max, first_obs, want_rows, {k: extra["checkpoint"].get(k) for k, _ in _WINDOW_ARRAYS})
+    return front + numbers, behind, tail, dict(more, **extra)
 
 
 class _Entry:
@@ -371,10 +370,6 @@ def run_resumable_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active
     "first_row" (per system: the first row of this segment that is its own)."""
     kw = dict(locals())                                        # first statement: locals() are the keywords
     return _run_batch_entry("gilrm_run" if kw.pop("large") else "gilr_run", **kw)
-
-
-CHECKPOINT_ARRAYS = (("pos", np.int32, 2), ("flags", np.uint8, 2), ("ref", np.int32, 2), ("t", np.float64, 1), ("n_events", np.int64, 1),
-                     ("next_obs", np.int32, 1))
 
 
 def plan_many_large(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, want_states=True, want_scalars=True):
@@ -510,9 +505,7 @@ def run_mixed_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffus
     that a system can draw what it would draw in a `run_raw` launch of its own group.  `order`: the system each workgroup takes,
     a permutation (None: falling particle number).  Same dictionary as `run_raw`; the slots at and beyond a system's own particle
     number are zero in `pos`, `sigma` and `flags`."""
-    kw = dict(locals())
-    mixed = {k: kw.pop(k) for k in ("sigma_grids", "variant_of_system", "block_tables", "seeds", "streams", "order")}
-    return _run_batch_entry("gilx_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
+    return _run_mixed_entry("gilx_run", locals())              # first statement: locals() are the keywords
 
 
 def plan_mixed_many(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs, variant_of_system=None, order=None, want_states=True):
@@ -532,9 +525,7 @@ def run_mixed_many_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_d
     defaults of the keys are the large shape's: `seeds=None` is `seed` + s, `streams=None` is 0, so one variant with the defaults
     is `run_many_large_raw`.  Any L >= 2 is accepted; system s is, bit for bit, the `run_many_large_raw` system with its
     variant's range and blocking table under key `seeds[s]` (include/gillespie_mixed_many.h states the condition on n_cap)."""
-    kw = dict(locals())
-    mixed = {k: kw.pop(k) for k in ("sigma_grids", "variant_of_system", "block_tables", "seeds", "streams", "order")}
-    return _run_batch_entry("gilxm_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
+    return _run_mixed_entry("gilxm_run", locals())
 
 
 def plan_mixed_structure(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs, k_max, first_obs=0, variant_of_system=None,
@@ -564,9 +555,7 @@ def run_mixed_structure_raw(*, L, K, periodic, sigma_grids, variant_of_system, r
       `bytes_back`: the bytes of the output arrays the call copied back.
     One variant is the uniform batch.  `k_max=None`: all L modes (at most 4096)."""
     k_max = min(int(L), 4096) if k_max is None else int(k_max)
-    kw = dict(locals())
-    mixed = {k: kw.pop(k) for k in ("sigma_grids", "variant_of_system", "block_tables", "seeds", "streams", "order")}
-    return _run_batch_entry("gilxs_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
+    return _run_mixed_entry("gilxs_run", locals())
 
 
 def run_mixed_resumable_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
@@ -580,9 +569,7 @@ def run_mixed_resumable_raw(*, L, K, periodic, sigma_grids, variant_of_system, r
     "checkpoint" (the six arrays of `run_resumable_raw` and `n_slots`, every system's slot count of the run's start), or None for
     a fresh start from `states`.  The keys (`seeds`, `streams`) and the variants are the resuming launch's: pass the same for the
     same trajectory.  The result also has "checkpoint", "first_row", and "n0" = the slot counts."""
-    kw = dict(locals())
-    mixed = {k: kw.pop(k) for k in ("sigma_grids", "variant_of_system", "block_tables", "seeds", "streams", "order")}
-    return _run_batch_entry("gilxmr_run" if kw.pop("large") else "gilxr_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
+    return _run_mixed_entry("gilxmr_run" if large else "gilxr_run", locals())
 
 
 def run_mixed_structure_resumable_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs,
@@ -595,9 +582,15 @@ def run_mixed_structure_resumable_raw(*, L, K, periodic, sigma_grids, variant_of
     `n_empty`, which the segment continues; the dictionary's `window`, `n_window`, `n_empty` are those of the checkpoint it
     leaves (the sums over all segments so far), `head` and `structure` cover this segment's rows."""
     k_max = min(int(L), 4096) if k_max is None else int(k_max)
-    kw = dict(locals())
+    return _run_mixed_entry("gilxsr_run", locals())
+
+
+def _run_mixed_entry(entry, keywords):
+    """_run_batch_entry for the mixed raw functions: `keywords` = their locals(), of which the six of _mixed_descriptor travel as
+    `mixed`; a mixed launch has no range or blocking table of its own."""
+    kw = {k: v for k, v in keywords.items() if k != "large"}
     mixed = {k: kw.pop(k) for k in ("sigma_grids", "variant_of_system", "block_tables", "seeds", "streams", "order")}
-    return _run_batch_entry("gilxsr_run", sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
+    return _run_batch_entry(entry, sigma_grid=0.0, block_table=None, mixed=mixed, **kw)
 
 
 def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed,
@@ -609,18 +602,17 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     LDS), gilm_run (large systems), gils_run (either, with the structure sums: k_max, first_obs) and gilc_run (either, with the
     capture statistics: group_of_site, n_groups, c_bins, h_bins, h_dt, first_obs); gilp_run (either, with the ensemble profiles:
     n_bins, first_obs, want_field, group_of_system, n_groups, per_system); gilx_run (systems in LDS, a variant per system: `mixed`,
-    the keywords of _mixed_descriptor), gilxm_run (the same, large systems) and gilxs_run (the same with the structure sums: k_max, first_obs, want_rows); gilr_run and
-    gilrm_run (one segment of a run: obs_first, checkpoint); gilxr_run, gilxmr_run and gilxsr_run (one segment of a mixed run:
-    `mixed`, obs_first, and a checkpoint that also has n_slots and, for gilxsr_run, the window sums)."""
+    the keywords of _mixed_descriptor), gilxm_run (the same, large systems) and gilxs_run (the same with the structure sums: k_max,
+    first_obs, want_rows); gilr_run and gilrm_run (one segment of a run: obs_first, checkpoint); gilxr_run, gilxmr_run and
+    gilxsr_run (one segment of a mixed run: `mixed`, obs_first, and a checkpoint that also has n_slots and, for gilxsr_run, the
+    window sums)."""
     lib, row = _lib(), ENTRIES[entry]
     if row.header is not None and not hasattr(lib, entry):
         raise capi.ApsError(-1, f"the loaded library has no {entry} ({row.header})")
     call, last_error = getattr(lib, entry), getattr(lib, row.last_error)
     ck_in = None
     if checkpoint is not None:                                 # a resumed segment: the systems and their slots are the checkpoint's
-        ck_in = {k: np.ascontiguousarray(checkpoint[k], dtype=dt) for k, dt, _ in CHECKPOINT_ARRAYS}
-        if ck_in["pos"].ndim != 2 or any(ck_in[k].shape != ck_in["pos"].shape[:nd] for k, _, nd in CHECKPOINT_ARRAYS):
-            raise ValueError("checkpoint: pos, flags, ref must be [systems][slots], t, n_events, next_obs [systems]")
+        ck_in = _checkpoint_arrays(checkpoint, "checkpoint")
         if n_cap is not None and int(n_cap) != ck_in["pos"].shape[1]:
             raise ValueError("n_cap differs from the checkpoint's")
         n_cap = ck_in["pos"].shape[1]
@@ -761,18 +753,11 @@ def run_batched_exact(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var
     With none of the four keywords the run is one launch of the entry points that have no checkpoint."""
     who = "run_batched_exact"
     first, inits, seed = _open_batch(who, systems, resume=resume)
-    if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
-        r, times_obs, ck = _segmented_launches(who, systems, T, obs_dt, inits, seed, resume=resume, obs_range=obs_range,
-                                               obs_per_launch=obs_per_launch, uniforms=uniforms)
-        outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
-        first.kernel_ms = r["kernel_ms"]
-        return (outs, ck) if return_checkpoint else outs
-    times_obs = np.arange(0.0, T, obs_dt)
-    run = run_many_large_raw if _large_shape(first.L, max(len(p) for p, _ in inits)) else run_raw
-    r = run(**_model(first, systems, states=inits, times_obs=times_obs, T=T, seed=seed, uniforms=uniforms))
+    r, times_obs, ck = _launch(who, systems, T, obs_dt, inits, seed, uniforms=uniforms, resume=resume, obs_range=obs_range,
+                               return_checkpoint=return_checkpoint, obs_per_launch=obs_per_launch)
     outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
     first.kernel_ms = r["kernel_ms"]
-    return outs
+    return (outs, ck) if return_checkpoint else outs
 
 
 def _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local):
@@ -820,29 +805,19 @@ def run_batched_exact_statistics(systems, T=10.0, obs_dt=0.01, resume=None, obs_
     evaluates the concatenated sums, which are the single launch's."""
     who = "run_batched_exact_statistics"
     first, inits, seed = _open_batch(who, systems, resume=resume, no_exit=True)
-    if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
-        r, times_obs, ck = _segmented_launches(who, systems, T, obs_dt, inits, seed, resume=resume, obs_range=obs_range,
-                                               obs_per_launch=obs_per_launch, statistics=True)
-        if np.any(r["first_row"] > 0):
-            raise ValueError("run_batched_exact_statistics: the checkpoint's systems stand at different observations; "
-                             "the sums need a common first observation")
-        rows = _statistics_rows(systems, r, times_obs)
-        first.kernel_ms = r["kernel_ms"]
-        return (rows, ck) if return_checkpoint else rows
-    times_obs = np.arange(0.0, T, obs_dt)
-    kw, _ = _statistics_keywords(who, first, times_obs, [len(p) for p, _ in inits])
-    # the large-system kernel takes the same sums (gilm_run); no state array leaves the device either way
-    run = run_many_large_raw if _large_shape(first.L, max(len(p) for p, _ in inits)) else run_raw
-    r = run(**_model(first, systems, states=inits, times_obs=times_obs, T=T, seed=seed, **kw))
-    rows = _statistics_rows(systems, r, times_obs)
+    r, times_obs, ck = _launch(who, systems, T, obs_dt, inits, seed, statistics=True, resume=resume, obs_range=obs_range,
+                               return_checkpoint=return_checkpoint, obs_per_launch=obs_per_launch)
+    rows = _statistics_rows(who, systems, r, times_obs)
     first.kernel_ms = r["kernel_ms"]
-    return rows
+    return (rows, ck) if return_checkpoint else rows
 
 
-def _statistics_rows(systems, r, times_obs):
-    """The DeviceObservables rows from the scalar sums of the raw outputs `r`."""
+def _statistics_rows(who, systems, r, times_obs):
+    """The DeviceObservables rows from the scalar sums of the raw outputs `r` (of one launch, or of a chain: with `first_row`)."""
     from . import observables
     first = systems[0]
+    if np.any(r.get("first_row", 0) > 0):
+        raise ValueError(f"{who}: the checkpoint's systems stand at different observations; the sums need a common first observation")
     rows = []
     for s, ps in enumerate(systems):
         _require_recorded(r, s, len(times_obs))
@@ -865,10 +840,77 @@ def _refuse_resume(who, resume, mixed=False):
 
 
 CHECKPOINT_STREAMS = {"batch": "key = seed, stream = system index (gil_run_batch)", "large": "key = seed + system index, stream = 0 (gilm_run)"}
-_FINGERPRINT = ("L", "K", "periodic", "local_kernel_sigma", "anchor_mask", "n_systems", "n_cap", "seed", "streams", "obs_dt")
 
 
-class Checkpoint:
+def _anchor_mask(mask, L):
+    """An anchor mask as the checkpoints hold and compare it: uint8 [L], all zero for a system without anchors."""
+    return np.zeros(int(L), np.uint8) if mask is None else (np.asarray(mask).reshape(-1) != 0).astype(np.uint8)
+
+
+def _checkpoint_arrays(given, who):
+    """The six arrays of CHECKPOINT_ARRAYS out of the mapping `given`, converted; ValueError in the name of `who` unless their
+    shapes agree."""
+    a = {k: np.ascontiguousarray(given[k], dtype=dt) for k, dt, _ in CHECKPOINT_ARRAYS}
+    if a["pos"].ndim != 2 or any(a[k].shape != a["pos"].shape[:nd] for k, _, nd in CHECKPOINT_ARRAYS):
+        raise ValueError(f"{who}: pos, flags, ref must be [systems][slots], t, n_events, next_obs [systems]")
+    return a
+
+
+class _SavedState:
+    """What Checkpoint and MixedCheckpoint share: the six arrays, L and the anchor mask, and a fingerprint that `require` compares
+    and `save` / `load` carry.  A subclass states FINGERPRINT (the fields, in the order `require` names them), OPTIONAL (those a
+    checkpoint may lack), META (the scalars of the file's `meta`) and SAVED (its arrays in the file beyond `arrays()`)."""
+    FINGERPRINT = OPTIONAL = META = SAVED = ()
+
+    def _take(self, given, L, anchor_mask):
+        vars(self).update(_checkpoint_arrays(given, type(self).__name__))
+        self.L = int(L)
+        self.anchor_mask = _anchor_mask(anchor_mask, self.L)
+
+    n_systems = property(lambda self: self.pos.shape[0])
+    n_cap = property(lambda self: self.pos.shape[1])
+
+    def arrays(self):
+        """The dictionary of arrays `run_resumable_raw(checkpoint=...)` takes."""
+        return {k: getattr(self, k) for k, _, _ in CHECKPOINT_ARRAYS}
+
+    def fingerprint(self):
+        return {k: getattr(self, k) for k in self.FINGERPRINT}
+
+    def require(self, **expected):
+        """ValueError naming the first fingerprint field whose value differs from `expected[field]`."""
+        mine, name = self.fingerprint(), type(self).__name__
+        for k in self.FINGERPRINT + self.OPTIONAL:
+            if k not in expected:
+                continue
+            if k not in mine:
+                raise ValueError(f"{name}: the resuming run differs from the checkpoint in {k}: the checkpoint is of a run without structure sums")
+            want = expected[k]
+            if k == "anchor_mask":
+                same = np.array_equal(mine[k], _anchor_mask(want, self.L))
+            elif k == "seeds":
+                same = np.array_equal(mine[k], np.array([int(x) & (2 ** 64 - 1) for x in want], dtype=np.uint64))
+            elif isinstance(mine[k], np.ndarray):
+                same = np.array_equal(mine[k], np.asarray(want, dtype=mine[k].dtype))
+            else:
+                same = mine[k] == want
+            if not same:
+                shown = "" if isinstance(mine[k], np.ndarray) and mine[k].size > 16 else f": the checkpoint has {mine[k]!r}, the resuming run {want!r}"
+                raise ValueError(f"{name}: the resuming run differs from the checkpoint in {k}{shown}")
+
+    def save(self, path):
+        """One .npz without pickles: the arrays, the anchor mask and, as `meta`, the scalar fields."""
+        more = {k: getattr(self, k) for k in self.SAVED if getattr(self, k) is not None}
+        with open(path, "wb") as fh:
+            np.savez(fh, anchor_mask=self.anchor_mask, meta=np.array(json.dumps({k: getattr(self, k) for k in self.META})), **self.arrays(), **more)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(**{k: z[k] for k in z.files if k != "meta"}, **json.loads(str(z["meta"])))
+
+
+class Checkpoint(_SavedState):
     """The state of a batch of systems between two launches of the exact event loop (struct gil_checkpoint of
     include/gillespie_resume.h): per system and slot the site (`pos`), the flags (`flags`: GILR_PLUS | GILR_BOUND | GILR_ALIVE)
     and the origin of the displacement sums (`ref`, -1: none); per system the time after the last applied event (`t`; it may
@@ -882,54 +924,23 @@ class Checkpoint:
     constants and flip_rate_fn are deliberately NOT part of it: the systems passed on resume supply them, and other values than
     before mean the exact process with the parameter switched at the checkpoint's time."""
 
+    FINGERPRINT = ("L", "K", "periodic", "local_kernel_sigma", "anchor_mask", "n_systems", "n_cap", "seed", "streams", "obs_dt")
+    META = ("L", "K", "periodic", "local_kernel_sigma", "seed", "streams", "obs_dt")
+
     def __init__(self, *, pos, flags, ref, t, n_events, next_obs, L, K, periodic, local_kernel_sigma, anchor_mask, seed, streams, obs_dt):
-        for k, dt, nd in CHECKPOINT_ARRAYS:
-            setattr(self, k, np.ascontiguousarray(locals()[k], dtype=dt))
-        if self.pos.ndim != 2 or any(getattr(self, k).shape != self.pos.shape[:nd] for k, _, nd in CHECKPOINT_ARRAYS):
-            raise ValueError("Checkpoint: pos, flags, ref must be [systems][slots], t, n_events, next_obs [systems]")
+        self._take(locals(), L, anchor_mask)
         if streams not in CHECKPOINT_STREAMS:
             raise ValueError("Checkpoint: streams must be 'batch' or 'large'")
-        self.L, self.K, self.periodic, self.local_kernel_sigma = int(L), int(K), bool(periodic), float(local_kernel_sigma)
-        self.anchor_mask = np.zeros(self.L, np.uint8) if anchor_mask is None else (np.asarray(anchor_mask).reshape(-1) != 0).astype(np.uint8)
+        self.K, self.periodic, self.local_kernel_sigma = int(K), bool(periodic), float(local_kernel_sigma)
         self.seed, self.streams, self.obs_dt = int(seed), str(streams), float(obs_dt)
-
-    n_systems = property(lambda self: self.pos.shape[0])
-    n_cap = property(lambda self: self.pos.shape[1])
-
-    def arrays(self):
-        """The dictionary of arrays `run_resumable_raw(checkpoint=...)` takes."""
-        return {k: getattr(self, k) for k, _, _ in CHECKPOINT_ARRAYS}
-
-    def fingerprint(self):
-        return {k: getattr(self, k) for k in _FINGERPRINT}
-
-    def require(self, **expected):
-        """ValueError naming the first fingerprint field whose value differs from `expected[field]`."""
-        mine = self.fingerprint()
-        for k in _FINGERPRINT:
-            if k not in expected:
-                continue
-            same = np.array_equal(mine[k], np.asarray(expected[k]).reshape(-1) != 0) if k == "anchor_mask" else mine[k] == expected[k]
-            if not same:
-                shown = "" if k == "anchor_mask" else f": the checkpoint has {mine[k]!r}, the resuming run {expected[k]!r}"
-                raise ValueError(f"Checkpoint: the resuming run differs from the checkpoint in {k}{shown}")
-
-    def save(self, path):
-        """One .npz: the six arrays, the anchor mask and the scalar fields of the fingerprint."""
-        meta = {k: getattr(self, k) for k in _FINGERPRINT if k not in ("anchor_mask", "n_systems", "n_cap")}
-        with open(path, "wb") as fh:
-            np.savez(fh, anchor_mask=self.anchor_mask, meta=np.array(json.dumps(meta)), **self.arrays())
-
-    @classmethod
-    def load(cls, path):
-        with np.load(path, allow_pickle=False) as z:
-            return cls(anchor_mask=z["anchor_mask"], **{k: z[k] for k, _, _ in CHECKPOINT_ARRAYS}, **json.loads(str(z["meta"])))
 
 
 def _merge_segments(parts, k0):
-    """The raw outputs of a chain of segments as those of one launch over all their observations (row 0 = observation k0)."""
+    """The raw outputs of a chain of segments as those of one launch over all their observations (row 0 = observation k0).  Of a
+    mixed structure chain also `head` and `structure`, the bytes copied back, and the window sums: those of the last checkpoint."""
     last = parts[-1]
-    out = {k: (None if parts[0][k] is None else np.concatenate([r[k] for r in parts], axis=1)) for k in ("pos", "sigma", "flags", "scalars")}
+    out = {k: (None if parts[0][k] is None else np.concatenate([r[k] for r in parts], axis=1))
+           for k in ("pos", "sigma", "flags", "scalars", "head", "structure") if k in last}
     S, ncap = last["exits"].shape[:2]
     exits, n_exits = np.zeros((S, ncap, 3)), np.zeros(S, np.int32)
     for r in parts:                                            # the exit log of a segment holds that segment's exits
@@ -941,50 +952,73 @@ def _merge_segments(parts, k0):
     out.update(exits=exits, n_exits=n_exits, n_recorded=n_rec, first_row=np.minimum(parts[0]["first_row"], n_rec),
                n_events=last["n_events"], t_final=last["t_final"], n0=last["n0"], kernel_ms=float(sum(r["kernel_ms"] for r in parts)),
                checkpoint=last["checkpoint"], launches=len(parts))
+    out.update({k: last["checkpoint"][k] for k, _ in _WINDOW_ARRAYS if k in last["checkpoint"]})
+    if "bytes_back" in last:
+        out["bytes_back"] = int(sum(r["bytes_back"] for r in parts))
     return out
 
 
-def _segmented_launches(who, systems, T, obs_dt, inits, seed, *, resume, obs_range, obs_per_launch, uniforms=None, statistics=False):
-    """The observations `obs_range` of the run (T, obs_dt) of `systems`, from `resume` or from the fresh initial conditions `inits`
-    under the key `seed` (_open_batch), in launches of at most `obs_per_launch` observations (gilr_run / gilrm_run): (merged raw
-    outputs, their observation times, the Checkpoint at the end)."""
-    first = systems[0]
+def _chained(resume, obs_range, return_checkpoint, obs_per_launch):
+    """Any of the four keywords makes a run a chain of resumable launches; none: the one launch of an entry point without checkpoint."""
+    return resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None
+
+
+def _segment_chain(who, run_fn, T, obs_dt, inits, ck, obs_range, obs_per_launch, keywords):
+    """The observations `obs_range` of the run (T, obs_dt), from the arrays `ck` of a checkpoint (None: from the fresh initial states
+    `inits`), in launches of `run_fn` of at most `obs_per_launch` observations each.  `keywords(times_obs, n_obs)` makes the launch
+    keywords once the range (its times, the observations of the longest launch) is known; their `ref_obs` counts within the range
+    and is placed in the launch that holds it.  Returns (merged raw outputs with `obs_range`, the observation times)."""
     times_all = np.arange(0.0, T, obs_dt)
-    M, S = len(times_all), len(systems)
-    mask = np.zeros(first.L, np.uint8) if first.is_anchor_site is None else (np.asarray(first.is_anchor_site).reshape(-1) != 0).astype(np.uint8)
-    if resume is None:
-        large = _large_shape(first.L, max(len(p) for p, _ in inits))
-        ck, k_lo, n_live = None, 0, [len(p) for p, _ in inits]
-    else:
-        if not isinstance(resume, Checkpoint):
-            raise TypeError(f"{who}: resume must be a gillespie.Checkpoint")
-        resume.require(L=first.L, K=first.K, periodic=bool(first.periodic), local_kernel_sigma=float(first.local_kernel_sigma),
-                       anchor_mask=mask, n_systems=S, obs_dt=float(obs_dt), streams="large" if _large_shape(first.L, resume.n_cap) else "batch",
-                       **({} if first.seed is None else {"seed": int(first.seed)}))
-        seed, large, ck = resume.seed, resume.streams == "large", resume.arrays()
-        k_lo, n_live = int(resume.next_obs.min()), [int(((f & GILR_ALIVE) != 0).sum()) for f in resume.flags]
-    k0, k1 = (k_lo, M) if obs_range is None else (int(obs_range[0]), int(obs_range[1]))
+    M = len(times_all)
+    k0, k1 = (0 if ck is None else int(ck["next_obs"].min()), M) if obs_range is None else (int(obs_range[0]), int(obs_range[1]))
     if not 0 <= k0 < k1 <= M:
         raise ValueError(f"{who}: obs_range must be a non-empty range within the {M} observations of the run (got [{k0}, {k1}))")
-    if resume is None and k0 != 0:
+    if ck is None and k0 != 0:
         raise ValueError(f"{who}: a run without `resume` starts at observation 0")
     step = k1 - k0 if obs_per_launch is None else int(obs_per_launch)
     if step < 1:
         raise ValueError(f"{who}: obs_per_launch must be at least 1")
-    kw = _model(first, systems, T=T, seed=seed, uniforms=uniforms, large=large)
-    ref_abs = -1
-    if statistics:                                             # the keywords of run_batched_exact_statistics' launch
-        kw.update(_statistics_keywords(who, first, times_all[k0:k1], n_live)[0])
-        ref_abs = k0 + kw.pop("ref_obs")
+    kw = keywords(times_all[k0:k1], min(step, k1 - k0))
+    ref_abs = k0 + kw.pop("ref_obs") if "ref_obs" in kw else -1
     parts = []
     for a in range(k0, k1, step):
         b = min(a + step, k1)
-        r = run_resumable_raw(states=inits, times_obs=times_all[a:b], obs_first=a, checkpoint=ck, ref_obs=ref_abs - a if a <= ref_abs < b else -1, **kw)
-        ck = r["checkpoint"]
-        parts.append(r)
-    r = _merge_segments(parts, k0)
-    return r, times_all[k0:k1], Checkpoint(L=first.L, K=first.K, periodic=first.periodic, local_kernel_sigma=first.local_kernel_sigma,
-                                           anchor_mask=mask, seed=seed, streams="large" if large else "batch", obs_dt=obs_dt, **ck)
+        parts.append(run_fn(states=inits, times_obs=times_all[a:b], obs_first=a, checkpoint=ck, ref_obs=ref_abs - a if a <= ref_abs < b else -1, **kw))
+        ck = parts[-1]["checkpoint"]
+    return dict(_merge_segments(parts, k0), obs_range=(k0, k1)), times_all[k0:k1]
+
+
+def _launch(who, systems, T, obs_dt, inits, seed, *, uniforms=None, statistics=False, resume=None, obs_range=None, return_checkpoint=False,
+            obs_per_launch=None):
+    """The launch behind run_batched_exact and (`statistics`) run_batched_exact_statistics, from what _open_batch returned: one
+    launch of gil_run_batch / gilm_run or, with any of the four keywords, a chain of gilr_run / gilrm_run.  Returns (raw outputs,
+    their observation times, the Checkpoint at the end of a chain or None)."""
+    first = systems[0]
+
+    def keywords(times_obs, n_live, **more):                   # the statistics: those of run_batched_exact_statistics' launch
+        kw = _model(first, systems, T=T, seed=seed, uniforms=uniforms, **more)
+        return dict(kw, **_statistics_keywords(who, first, times_obs, n_live)[0]) if statistics else kw
+
+    if not _chained(resume, obs_range, return_checkpoint, obs_per_launch):
+        times_obs, n_live = np.arange(0.0, T, obs_dt), [len(p) for p, _ in inits]
+        # the large-system kernel takes the same sums (gilm_run); no state array leaves the device either way
+        run = run_many_large_raw if _large_shape(first.L, max(n_live)) else run_raw
+        return run(states=inits, times_obs=times_obs, **keywords(times_obs, n_live)), times_obs, None
+    mask = _anchor_mask(first.is_anchor_site, first.L)
+    if resume is None:
+        large, ck, n_live = _large_shape(first.L, max(len(p) for p, _ in inits)), None, [len(p) for p, _ in inits]
+    else:
+        if not isinstance(resume, Checkpoint):
+            raise TypeError(f"{who}: resume must be a gillespie.Checkpoint")
+        resume.require(L=first.L, K=first.K, periodic=bool(first.periodic), local_kernel_sigma=float(first.local_kernel_sigma),
+                       anchor_mask=mask, n_systems=len(systems), obs_dt=float(obs_dt), streams="large" if _large_shape(first.L, resume.n_cap) else "batch",
+                       **({} if first.seed is None else {"seed": int(first.seed)}))
+        seed, large, ck = resume.seed, resume.streams == "large", resume.arrays()
+        n_live = [int(((f & GILR_ALIVE) != 0).sum()) for f in resume.flags]
+    r, times_obs = _segment_chain(who, run_resumable_raw, T, obs_dt, inits, ck, obs_range, obs_per_launch,
+                                  lambda times_obs, n_obs: keywords(times_obs, n_live, large=large))
+    return r, times_obs, Checkpoint(L=first.L, K=first.K, periodic=first.periodic, local_kernel_sigma=first.local_kernel_sigma,
+                                    anchor_mask=mask, seed=seed, streams="large" if large else "batch", obs_dt=obs_dt, **r["checkpoint"])
 
 
 def mixed_variants(sigma_grids, block_tables=None):
@@ -1025,51 +1059,10 @@ def mixed_keys(systems, groups=None, large=False):
     return seeds, streams
 
 
-def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, order=None, structure=None, allow_large=False):
-    """The one launch behind run_batched_exact_mixed and run_batched_exact_statistics_mixed: checks, initial states, variants,
-    keys, gilx_run -- or, for a large shape with `allow_large`, gilxm_run with the large shape's keys.  `structure` = (k_max or
-    None, start_fraction, want_rows, all_observations): the launch behind run_batched_exact_structure_mixed instead, gilxs_run
-    without states (no large shape).  Returns (raw outputs, times_obs)."""
-    first, inits, _ = _open_batch(who, systems, skip=("local_kernel_sigma",), anchors="their anchor sites", flip=True, no_exit=statistics, seed=False)
-    n_cap = max(1, max(len(p) for p, _ in inits))
-    large = _large_shape(first.L, n_cap)
-    if large and not (allow_large and structure is None):
-        raise ValueError(f"{who}: L = {first.L}, N = {n_cap} is a large shape (beyond L = {GIL_MAX_L}, N = {GIL_MAX_N}); "
-                         "the large-system kernel takes no mixed batches")
-    seeds, streams = mixed_keys(systems, groups, large=large)
-    times_obs = np.arange(0.0, T, obs_dt)
-    kw, tables = {}, None
-    if statistics:                                             # every system is counted with the table of its own particle number
-        kw, tables = _statistics_keywords(who, first, times_obs, [len(p) for p, _ in inits], one_table=False)
-    sig, tabs, owner = mixed_variants([ps._sigma_grid for ps in systems], tables)
-    shape = dict(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems), n_cap=n_cap, n_obs=len(times_obs),
-                 variant_of_system=owner)
-    run_fn = run_mixed_many_raw if large else run_mixed_raw
-    if structure is not None:
-        k_max, start_fraction, want_rows, all_obs = structure
-        kk = first.L if k_max is None else min(int(k_max), first.L)
-        first_obs = 0 if all_obs else int(start_fraction * len(times_obs))
-        kw = dict(want_states=False, k_max=kk, first_obs=first_obs, want_rows=want_rows)
-        run_fn = run_mixed_structure_raw
-        plan = plan_mixed_structure(**shape, **kw)
-    else:
-        plan = (plan_mixed_many if large else plan_mixed)(**shape, want_states=not statistics)
-    if plan["lds_bytes"] > GILX_LDS_LIMIT:
-        raise ValueError(f"{who}: the launch needs {plan['lds_bytes']} bytes of LDS per system, over the limit of {GILX_LDS_LIMIT} bytes")
-    model = _model(first, systems, sigma_grids=sig, variant_of_system=owner, block_tables=tabs, states=inits, times_obs=times_obs, T=T,
-                   uniforms=uniforms, seeds=seeds, streams=streams, order=order, **kw)
-    del model["sigma_grid"]                                    # a mixed launch has a range per variant instead
-    r = run_fn(**model)
-    r["plan"] = plan
-    return r, times_obs
-
-
-_MIXED_FINGERPRINT = ("L", "K", "periodic", "anchor_mask", "n_systems", "n_cap", "obs_dt", "large", "sigma_grids", "seeds", "streams", "n_slots")
-_MIXED_WINDOW = (("window", np.float64), ("n_window", np.int32), ("n_empty", np.int32))
 _MIXED_PER_SYSTEM = (("n_slots", np.int32), ("seeds", np.uint64), ("streams", np.int32), ("sigma_grids", np.float64))
 
 
-class MixedCheckpoint:
+class MixedCheckpoint(_SavedState):
     """The state of a MIXED batch between two launches of the exact event loop (struct gilx_checkpoint of
     include/gillespie_mixed_resume.h): the six arrays of `Checkpoint` and, per system, the slot count of the run's start
     (`n_slots`: a mixed system groups its rate sums by it, dead slots included), the Philox key and stream (`seeds`, `streams`)
@@ -1083,21 +1076,22 @@ class MixedCheckpoint:
     part of it, as in `Checkpoint`: other values on resume are the exact process with the parameter switched at the
     checkpoint's time."""
 
+    FINGERPRINT = ("L", "K", "periodic", "anchor_mask", "n_systems", "n_cap", "obs_dt", "large", "sigma_grids", "seeds", "streams", "n_slots")
+    OPTIONAL = ("k_max", "first_obs")
+    META = ("L", "K", "periodic", "obs_dt", "large", "k_max", "first_obs")
+    SAVED = ("seeds", "streams", "sigma_grids", "block_tables")
+
     def __init__(self, *, pos, flags, ref, t, n_events, next_obs, n_slots, seeds, streams, sigma_grids, L, K, periodic, anchor_mask, obs_dt,
                  large=False, block_tables=None, k_max=None, first_obs=None, window=None, n_window=None, n_empty=None):
         given = locals()
-        for k, dt, nd in CHECKPOINT_ARRAYS:
-            setattr(self, k, np.ascontiguousarray(given[k], dtype=dt))
-        if self.pos.ndim != 2 or any(getattr(self, k).shape != self.pos.shape[:nd] for k, _, nd in CHECKPOINT_ARRAYS):
-            raise ValueError("MixedCheckpoint: pos, flags, ref must be [systems][slots], t, n_events, next_obs [systems]")
-        S = self.pos.shape[0]
+        self._take(given, L, anchor_mask)
+        S = self.n_systems
         for k, dt in _MIXED_PER_SYSTEM:
             a = [int(x) & (2 ** 64 - 1) for x in given[k]] if k == "seeds" else given[k]
             setattr(self, k, np.ascontiguousarray(a, dtype=dt))
             if getattr(self, k).shape != (S,):
                 raise ValueError(f"MixedCheckpoint: {k} must have one entry per system")
-        self.L, self.K, self.periodic, self.obs_dt, self.large = int(L), int(K), bool(periodic), float(obs_dt), bool(large)
-        self.anchor_mask = np.zeros(self.L, np.uint8) if anchor_mask is None else (np.asarray(anchor_mask).reshape(-1) != 0).astype(np.uint8)
+        self.K, self.periodic, self.obs_dt, self.large = int(K), bool(periodic), float(obs_dt), bool(large)
         self.block_tables = None if block_tables is None else np.ascontiguousarray(block_tables, dtype=np.uint8)
         if self.block_tables is not None and self.block_tables.shape != (S, self.K + 1, self.K + 1):
             raise ValueError("MixedCheckpoint: block_tables must be [systems][K + 1][K + 1]")
@@ -1108,146 +1102,110 @@ class MixedCheckpoint:
         else:
             if first_obs is None or window is None or n_window is None or n_empty is None:
                 raise ValueError("MixedCheckpoint: a structure run needs first_obs, window, n_window and n_empty")
-            for (k, dt), shape in zip(_MIXED_WINDOW, ((S, self.k_max, 3), (S,), (S,))):
+            for (k, dt), shape in zip(_WINDOW_ARRAYS, ((S, self.k_max, 3), (S,), (S,))):
                 setattr(self, k, np.ascontiguousarray(given[k], dtype=dt))
                 if getattr(self, k).shape != shape:
                     raise ValueError(f"MixedCheckpoint: {k} must have the shape {shape}")
 
-    n_systems = property(lambda self: self.pos.shape[0])
-    n_cap = property(lambda self: self.pos.shape[1])
     structure = property(lambda self: self.k_max is not None)
 
     def arrays(self):
         """The dictionary of arrays `run_mixed_resumable_raw(checkpoint=...)` takes (a structure run: with the window sums, as
         `run_mixed_structure_resumable_raw` takes it)."""
-        out = {k: getattr(self, k) for k, _, _ in CHECKPOINT_ARRAYS}
-        out["n_slots"] = self.n_slots
-        if self.structure:
-            out.update({k: getattr(self, k) for k, _ in _MIXED_WINDOW})
-        return out
+        more = ("n_slots",) + (tuple(k for k, _ in _WINDOW_ARRAYS) if self.structure else ())
+        return dict(super().arrays(), **{k: getattr(self, k) for k in more})
 
     def fingerprint(self):
-        return {k: getattr(self, k) for k in _MIXED_FINGERPRINT + (("k_max", "first_obs") if self.structure else ())}
-
-    def require(self, **expected):
-        """ValueError naming the first fingerprint field whose value differs from `expected[field]`."""
-        mine = self.fingerprint()
-        for k in _MIXED_FINGERPRINT + ("k_max", "first_obs"):
-            if k not in expected:
-                continue
-            if k not in mine:
-                raise ValueError(f"MixedCheckpoint: the resuming run differs from the checkpoint in {k}: the checkpoint is of a run without structure sums")
-            want = expected[k]
-            if k == "anchor_mask":
-                same = np.array_equal(mine[k], np.asarray(want).reshape(-1) != 0)
-            elif k == "seeds":
-                same = np.array_equal(mine[k], np.array([int(x) & (2 ** 64 - 1) for x in want], dtype=np.uint64))
-            elif isinstance(mine[k], np.ndarray):
-                same = np.array_equal(mine[k], np.asarray(want, dtype=mine[k].dtype))
-            else:
-                same = mine[k] == want
-            if not same:
-                shown = "" if isinstance(mine[k], np.ndarray) and mine[k].size > 16 else f": the checkpoint has {mine[k]!r}, the resuming run {want!r}"
-                raise ValueError(f"MixedCheckpoint: the resuming run differs from the checkpoint in {k}{shown}")
-
-    def save(self, path):
-        """One .npz: the arrays, the anchor mask and the scalar fields (no pickles)."""
-        meta = dict(L=self.L, K=self.K, periodic=self.periodic, obs_dt=self.obs_dt, large=self.large, k_max=self.k_max, first_obs=self.first_obs)
-        more = {k: getattr(self, k) for k, _ in _MIXED_PER_SYSTEM if k != "n_slots"}
-        if self.block_tables is not None:
-            more["block_tables"] = self.block_tables
-        with open(path, "wb") as fh:
-            np.savez(fh, anchor_mask=self.anchor_mask, meta=np.array(json.dumps(meta)), **self.arrays(), **more)
-
-    @classmethod
-    def load(cls, path):
-        with np.load(path, allow_pickle=False) as z:
-            return cls(**{k: z[k] for k in z.files if k != "meta"}, **json.loads(str(z["meta"])))
+        return dict(super().fingerprint(), **({k: getattr(self, k) for k in self.OPTIONAL} if self.structure else {}))
 
 
-def _mixed_segments(who, systems, T, obs_dt, groups, statistics, uniforms=None, order=None, structure=None, allow_large=False, *,
-                    resume, obs_range, obs_per_launch):
-    """_mixed_launch as a chain of segments (gilxr_run / gilxmr_run / gilxsr_run of include/gillespie_mixed_resume.h): the
-    observations `obs_range` of the run (T, obs_dt), from the MixedCheckpoint `resume` or from fresh initial states, in launches of
-    at most `obs_per_launch` observations.  Returns (merged raw outputs, their observation times, the MixedCheckpoint at the end).
-    A structure run's window is [first_obs, M) on the WHOLE grid of M observations; the merged `head` and `structure` cover the
-    range, `window`, `n_window`, `n_empty` are the last checkpoint's."""
-    first, inits, _ = _open_batch(who, systems, resume=resume, skip=("local_kernel_sigma",), anchors="their anchor sites", flip=True,
-                                  no_exit=statistics, seed=False)
-    times_all = np.arange(0.0, T, obs_dt)
-    M, S = len(times_all), len(systems)
-    mask = np.zeros(first.L, np.uint8) if first.is_anchor_site is None else (np.asarray(first.is_anchor_site).reshape(-1) != 0).astype(np.uint8)
-    sig_sys = np.array([float(ps._sigma_grid) for ps in systems])
-    kk = first_obs = None
-    if structure is not None:
-        k_max, start_fraction, want_rows, all_obs = structure
-        kk = first.L if k_max is None else min(int(k_max), first.L)
-        first_obs = 0 if all_obs else int(start_fraction * M)
-    if resume is None:
-        n_cap = max(1, max(len(p) for p, _ in inits))
-        large = _large_shape(first.L, n_cap)
+class _MixedBatch:
+    """A mixed batch, opened for one launch or for a chain of segments (`chained`; then `resume` may be a MixedCheckpoint): the
+    checks, the initial states (None on resume: no generator is consumed), then the slot counts and the shape, the refusal of a
+    large shape without `allow_large`, and the keys -- those of `mixed_keys` (the large shape's for a large shape), on resume the
+    checkpoint's, which must be what this batch would take where its systems state their seeds.  `structure` = (k_max or None,
+    start_fraction, want_rows, all_observations): the batch of run_batched_exact_structure_mixed, without states (no large shape)."""
+
+    def __init__(self, who, systems, T, obs_dt, groups, statistics, uniforms, order, structure, allow_large, resume, chained):
+        self.who, self.systems, self.T, self.statistics, self.uniforms, self.order, self.resume, self.chained = (
+            who, systems, T, statistics, uniforms, order, resume, chained)
+        first, self.inits, _ = _open_batch(who, systems, resume=resume, skip=("local_kernel_sigma",), anchors="their anchor sites", flip=True,
+                                           no_exit=statistics, seed=False)
+        self.first, self.mask = first, _anchor_mask(first.is_anchor_site, first.L)
+        self.sig_sys = np.array([float(ps._sigma_grid) for ps in systems])
+        self.k_max = self.first_obs = self.want_rows = self.tables = None
+        if structure is not None:                              # the window is [first_obs, M) on the WHOLE grid of M observations
+            k_max, start_fraction, self.want_rows, all_obs = structure
+            self.k_max = first.L if k_max is None else min(int(k_max), first.L)
+            self.first_obs = 0 if all_obs else int(start_fraction * len(np.arange(0.0, T, obs_dt)))
+        if resume is None:
+            self.n_live = [len(p) for p, _ in self.inits]
+            self.n_cap = max(1, max(self.n_live))
+            self.large = _large_shape(first.L, self.n_cap)
+        else:
+            more = {} if structure is None else dict(k_max=self.k_max, first_obs=self.first_obs)
+            resume.require(L=first.L, K=first.K, periodic=bool(first.periodic), anchor_mask=self.mask, n_systems=len(systems), obs_dt=float(obs_dt),
+                           sigma_grids=self.sig_sys, **more)
+            if structure is None and resume.structure:
+                raise ValueError(f"{who}: the checkpoint is of a structure run (it carries window sums); resume it with run_batched_exact_structure_mixed")
+            self.n_cap, self.large, self.n_live = resume.n_cap, resume.large, [int(n) for n in resume.n_slots]
+        if self.large and not (allow_large and structure is None):
+            raise ValueError(f"{who}: L = {first.L}, N = {self.n_cap} is a large shape (beyond L = {GIL_MAX_L}, N = {GIL_MAX_N}); "
+                             "the large-system kernel takes no mixed batches")
+        if resume is None:
+            self.seeds, self.streams = mixed_keys(systems, groups, large=self.large)
+        else:
+            if all(ps.seed is not None for ps in systems):     # the keys this batch would take: no generator is consumed
+                seeds, streams = mixed_keys(systems, groups, large=self.large)
+                resume.require(seeds=seeds, streams=streams)
+            self.seeds, self.streams = [int(x) for x in resume.seeds], resume.streams
+
+    def keywords(self, times_obs, n_obs):
+        """The keywords of a launch of at most `n_obs` of the observations `times_obs` (but states, times_obs and a segment's own):
+        the variants, where every system of a statistics run is counted with the blocking table of its own particle number (on
+        resume: the checkpoint's), and the model.  Notes the plan as `self.plan`; ValueError if it needs more LDS than there is."""
+        first, kw = self.first, {}
+        if self.statistics:
+            kw, self.tables = _statistics_keywords(self.who, first, times_obs, self.n_live, one_table=False)
+            if self.resume is not None and self.resume.block_tables is not None:
+                self.tables = list(self.resume.block_tables)
+        sig, tabs, owner = mixed_variants(self.sig_sys, self.tables)
+        shape = dict(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(self.systems), n_cap=self.n_cap, n_obs=n_obs,
+                     variant_of_system=owner)
+        if self.k_max is not None:                             # a segment's plan takes the window's start within the segment
+            kw = dict(want_states=False, k_max=self.k_max, first_obs=self.first_obs, want_rows=self.want_rows)
+            self.plan = plan_mixed_structure(**shape, **dict(kw, first_obs=min(self.first_obs, n_obs) if self.chained else self.first_obs))
+        else:
+            self.plan = (plan_mixed_many if self.large else plan_mixed)(**shape, want_states=not self.statistics)
+        if self.plan["lds_bytes"] > GILX_LDS_LIMIT:
+            raise ValueError(f"{self.who}: the launch needs {self.plan['lds_bytes']} bytes of LDS per system, over the limit of {GILX_LDS_LIMIT} bytes")
+        model = _model(first, self.systems, sigma_grids=sig, variant_of_system=owner, block_tables=tabs, T=self.T, uniforms=self.uniforms,
+                       seeds=self.seeds, streams=self.streams, order=self.order, n_cap=self.n_cap, **kw)
+        del model["sigma_grid"]                                # a mixed launch has a range per variant instead
+        return model
+
+
+def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, order=None, structure=None, allow_large=False, *, resume=None,
+                  obs_range=None, return_checkpoint=False, obs_per_launch=None):
+    """The launch behind the three mixed functions: one launch of gilx_run / gilxm_run / gilxs_run or, with any of the four keywords,
+    a chain of gilxr_run / gilxmr_run / gilxsr_run (include/gillespie_mixed_resume.h).  Returns (raw outputs with `plan`,
+    `obs_range`, `first_obs` and `k_max`, their observation times, the MixedCheckpoint at the end of a chain or None).  A structure
+    chain's `head` and `structure` cover the range, its `window`, `n_window`, `n_empty` are the last checkpoint's."""
+    chained = _chained(resume, obs_range, return_checkpoint, obs_per_launch)
+    b, ck = _MixedBatch(who, systems, T, obs_dt, groups, statistics, uniforms, order, structure, allow_large, resume, chained), None
+    if not chained:
+        times_obs = np.arange(0.0, T, obs_dt)
+        run_fn = run_mixed_structure_raw if structure is not None else run_mixed_many_raw if b.large else run_mixed_raw
+        r = dict(run_fn(states=b.inits, times_obs=times_obs, **b.keywords(times_obs, len(times_obs))), obs_range=(0, len(times_obs)))
     else:
-        more = {} if structure is None else dict(k_max=kk, first_obs=first_obs)
-        resume.require(L=first.L, K=first.K, periodic=bool(first.periodic), anchor_mask=mask, n_systems=S, obs_dt=float(obs_dt), sigma_grids=sig_sys, **more)
-        if structure is None and resume.structure:
-            raise ValueError(f"{who}: the checkpoint is of a structure run (it carries window sums); resume it with run_batched_exact_structure_mixed")
-        n_cap, large = resume.n_cap, resume.large
-    if large and not (allow_large and structure is None):
-        raise ValueError(f"{who}: L = {first.L}, N = {n_cap} is a large shape (beyond L = {GIL_MAX_L}, N = {GIL_MAX_N}); "
-                         "the large-system kernel takes no mixed batches")
-    if resume is None:
-        seeds, streams = mixed_keys(systems, groups, large=large)
-        ck, k_lo, n_live = None, 0, [len(p) for p, _ in inits]
-    else:
-        if all(ps.seed is not None for ps in systems):         # the keys this batch would take: no generator is consumed
-            seeds, streams = mixed_keys(systems, groups, large=large)
-            resume.require(seeds=seeds, streams=streams)
-        seeds, streams = [int(x) for x in resume.seeds], resume.streams
-        ck, k_lo, n_live = resume.arrays(), int(resume.next_obs.min()), [int(n) for n in resume.n_slots]
-    k0, k1 = (k_lo, M) if obs_range is None else (int(obs_range[0]), int(obs_range[1]))
-    if not 0 <= k0 < k1 <= M:
-        raise ValueError(f"{who}: obs_range must be a non-empty range within the {M} observations of the run (got [{k0}, {k1}))")
-    if resume is None and k0 != 0:
-        raise ValueError(f"{who}: a run without `resume` starts at observation 0")
-    step = k1 - k0 if obs_per_launch is None else int(obs_per_launch)
-    if step < 1:
-        raise ValueError(f"{who}: obs_per_launch must be at least 1")
-    kw, tables, ref_abs = {}, None, -1
-    if statistics:                                             # every system is counted with the table of its own particle number
-        kw, tables = _statistics_keywords(who, first, times_all[k0:k1], n_live, one_table=False)
-        if resume is not None and resume.block_tables is not None:
-            tables = list(resume.block_tables)
-        ref_abs = k0 + kw.pop("ref_obs")
-    sig, tabs, owner = mixed_variants(sig_sys, tables)
-    shape = dict(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=S, n_cap=n_cap, n_obs=min(step, k1 - k0), variant_of_system=owner)
-    if structure is not None:
-        kw = dict(want_states=False, k_max=kk, first_obs=first_obs, want_rows=want_rows)
-        run_fn = run_mixed_structure_resumable_raw
-        plan = plan_mixed_structure(**shape, **dict(kw, first_obs=min(first_obs, shape["n_obs"])))
-    else:
-        kw["large"] = large
-        run_fn = run_mixed_resumable_raw
-        plan = (plan_mixed_many if large else plan_mixed)(**shape, want_states=not statistics)
-    if plan["lds_bytes"] > GILX_LDS_LIMIT:
-        raise ValueError(f"{who}: the launch needs {plan['lds_bytes']} bytes of LDS per system, over the limit of {GILX_LDS_LIMIT} bytes")
-    model = _model(first, systems, sigma_grids=sig, variant_of_system=owner, block_tables=tabs, T=T, uniforms=uniforms, seeds=seeds, streams=streams,
-                   order=order, n_cap=n_cap, **kw)
-    del model["sigma_grid"]                                    # a mixed launch has a range per variant instead
-    parts = []
-    for a in range(k0, k1, step):
-        b = min(a + step, k1)
-        r = run_fn(states=inits, times_obs=times_all[a:b], obs_first=a, checkpoint=ck, ref_obs=ref_abs - a if a <= ref_abs < b else -1, **model)
-        ck = r["checkpoint"]
-        parts.append(r)
-    r = _merge_segments(parts, k0)
-    r.update(plan=plan, obs_range=(k0, k1))
-    if structure is not None:
-        r.update(head=np.concatenate([q["head"] for q in parts], axis=1), window=ck["window"], n_window=ck["n_window"], n_empty=ck["n_empty"],
-                 structure=np.concatenate([q["structure"] for q in parts], axis=1) if want_rows else None,
-                 bytes_back=int(sum(q["bytes_back"] for q in parts)), first_obs=first_obs)
-    return r, times_all[k0:k1], MixedCheckpoint(L=first.L, K=first.K, periodic=first.periodic, anchor_mask=mask, obs_dt=obs_dt, large=large,
-                                                seeds=seeds, streams=streams, sigma_grids=sig_sys, k_max=kk, first_obs=first_obs,
-                                                block_tables=None if tables is None else np.stack(tables), **ck)
+        run_fn, more = (run_mixed_resumable_raw, dict(large=b.large)) if structure is None else (run_mixed_structure_resumable_raw, {})
+        r, times_obs = _segment_chain(who, run_fn, T, obs_dt, b.inits, None if resume is None else resume.arrays(), obs_range, obs_per_launch,
+                                      lambda times_obs, n_obs: dict(b.keywords(times_obs, n_obs), **more))
+        ck = MixedCheckpoint(L=b.first.L, K=b.first.K, periodic=b.first.periodic, anchor_mask=b.mask, obs_dt=obs_dt, large=b.large, seeds=b.seeds,
+                             streams=b.streams, sigma_grids=b.sig_sys, k_max=b.k_max, first_obs=b.first_obs,
+                             block_tables=None if b.tables is None else np.stack(b.tables), **r["checkpoint"])
+    r.update(plan=b.plan, first_obs=b.first_obs, k_max=b.k_max)
+    return r, times_obs, ck
 
 
 def run_batched_exact_mixed(systems, T=10.0, obs_dt=0.01, record_fft=False, record_var=False, uniforms=None, want_m_local=True,
@@ -1269,16 +1227,11 @@ def run_batched_exact_mixed(systems, T=10.0, obs_dt=0.01, record_fft=False, reco
     checkpoint's.  With none of the four the run is the one launch it always was."""
     who = "run_batched_exact_mixed"
     _refuse_resume(who, resume, mixed=True)
-    if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
-        r, times_obs, ck = _mixed_segments(who, systems, T, obs_dt, groups, False, uniforms, order, allow_large=allow_large, resume=resume,
-                                           obs_range=obs_range, obs_per_launch=obs_per_launch)
-        outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
-        systems[0].kernel_ms = r["kernel_ms"]
-        return (outs, ck) if return_checkpoint else outs
-    r, times_obs = _mixed_launch("run_batched_exact_mixed", systems, T, obs_dt, groups, False, uniforms, order, allow_large=allow_large)
+    r, times_obs, ck = _mixed_launch(who, systems, T, obs_dt, groups, False, uniforms, order, allow_large=allow_large, resume=resume,
+                                     obs_range=obs_range, return_checkpoint=return_checkpoint, obs_per_launch=obs_per_launch)
     outs = _exact_outputs(systems, r, times_obs, record_fft, record_var, want_m_local)
     systems[0].kernel_ms = r["kernel_ms"]
-    return outs
+    return (outs, ck) if return_checkpoint else outs
 
 
 def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None, order=None, resume=None, allow_large=False,
@@ -1290,18 +1243,11 @@ def run_batched_exact_statistics_mixed(systems, T=10.0, obs_dt=0.01, groups=None
     blocking tables are the checkpoint's."""
     who = "run_batched_exact_statistics_mixed"
     _refuse_resume(who, resume, mixed=True)
-    if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
-        r, times_obs, ck = _mixed_segments(who, systems, T, obs_dt, groups, True, None, order, allow_large=allow_large, resume=resume,
-                                           obs_range=obs_range, obs_per_launch=obs_per_launch)
-        if np.any(r["first_row"] > 0):
-            raise ValueError(f"{who}: the checkpoint's systems stand at different observations; the sums need a common first observation")
-        rows = _statistics_rows(systems, r, times_obs)
-        systems[0].kernel_ms = r["kernel_ms"]
-        return (rows, ck) if return_checkpoint else rows
-    r, times_obs = _mixed_launch("run_batched_exact_statistics_mixed", systems, T, obs_dt, groups, True, None, order, allow_large=allow_large)
-    rows = _statistics_rows(systems, r, times_obs)
+    r, times_obs, ck = _mixed_launch(who, systems, T, obs_dt, groups, True, None, order, allow_large=allow_large, resume=resume,
+                                     obs_range=obs_range, return_checkpoint=return_checkpoint, obs_per_launch=obs_per_launch)
+    rows = _statistics_rows(who, systems, r, times_obs)
     systems[0].kernel_ms = r["kernel_ms"]
-    return rows
+    return (rows, ck) if return_checkpoint else rows
 
 
 def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_max=None, groups=None, order=None,
@@ -1324,41 +1270,46 @@ def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fracti
     entries before the call's first observation are NaN."""
     who = "run_batched_exact_structure_mixed"
     _refuse_resume(who, resume, mixed=True)
-    from . import observables
     if reduce not in ("device", "rows"):
         raise ValueError("reduce must be 'device' or 'rows'")
     rows_wanted = reduce == "rows"
-    structure = (k_max, start_fraction, rows_wanted, rows_wanted and return_series)
-    first, ck = systems[0], None
-    if resume is not None or obs_range is not None or return_checkpoint or obs_per_launch is not None:
-        r, _, ck = _mixed_segments(who, systems, T, obs_dt, groups, False, None, order, structure=structure, resume=resume,
-                                            obs_range=obs_range, obs_per_launch=obs_per_launch)
-        times_obs = np.arange(0.0, T, obs_dt)
-        k0, k1 = r["obs_range"]
-        first.kernel_ms, first.bytes_back = r["kernel_ms"], r["bytes_back"]
-        if k1 < len(times_obs):                                # the window is not complete: nothing to evaluate yet
-            for s, ps in enumerate(systems):
-                ps.n_events = int(r["n_events"][s])
-            return ([None] * len(systems), ck) if return_checkpoint else [None] * len(systems)
-        if k0 > r["first_obs"]:
-            raise ValueError(f"{who}: this call starts at observation {k0}, inside the window that begins at {r['first_obs']}: the head rows of "
-                             "the window's earlier observations lie in an earlier call; cut the run before the window or use obs_per_launch")
+    r, _, ck = _mixed_launch(who, systems, T, obs_dt, groups, False, None, order, (k_max, start_fraction, rows_wanted, rows_wanted and return_series),
+                             resume=resume, obs_range=obs_range, return_checkpoint=return_checkpoint, obs_per_launch=obs_per_launch)
 
+    def results():
+        return _structure_mixed_results(who, systems, r, np.arange(0.0, T, obs_dt), start_fraction, rows_wanted, return_series)
+
+    # a chain notes its times before it evaluates (it may refuse, or have nothing to evaluate yet), the one launch afterwards, as ever
+    out = None if ck is not None else results()
+    systems[0].kernel_ms, systems[0].bytes_back = r["kernel_ms"], r["bytes_back"]
+    if ck is not None:
+        out = results()
+    return (out, ck) if return_checkpoint else out
+
+
+def _structure_mixed_results(who, systems, r, times_obs, start_fraction, rows_wanted, return_series):
+    """The result dictionaries of run_batched_exact_structure_mixed from the raw outputs `r` of the observations r["obs_range"] of
+    the whole grid `times_obs`: None for every system where the range ends before the grid does (the window is not complete)."""
+    from . import observables
+    first, M, (k0, k1) = systems[0], len(times_obs), r["obs_range"]
+    if k1 < M:
+        for s, ps in enumerate(systems):
+            ps.n_events = int(r["n_events"][s])
+        return [None] * len(systems)
+    if k0 > r["first_obs"]:
+        raise ValueError(f"{who}: this call starts at observation {k0}, inside the window that begins at {r['first_obs']}: the head rows of "
+                         "the window's earlier observations lie in an earlier call; cut the run before the window or use obs_per_launch")
+    if k0 > 0:
         def whole(a):                                          # rows of the whole grid: zeros before this call's first observation
             return None if a is None else np.concatenate([np.zeros((a.shape[0], k0) + a.shape[2:], a.dtype), a], axis=1)
         r = dict(r, head=whole(r["head"]), structure=whole(r["structure"]), scalars=whole(r["scalars"]), n_recorded=r["n_recorded"] + k0)
-    else:
-        r, times_obs = _mixed_launch(who, systems, T, obs_dt, groups, False, None, order, structure=structure)
-    M, L = len(times_obs), first.L
-    kk = L if k_max is None else min(int(k_max), L)
-    first_obs = 0 if (rows_wanted and return_series) else int(start_fraction * M)
-    out = []
+    L, out = first.L, []
     for s, ps in enumerate(systems):
         _require_recorded(r, s, M)
         win = observables.DeviceStructureWindow(r["head"][s], r["window"][s], r["n_window"][s], r["n_empty"][s], L, first.dx, start_fraction)
         series = None
         if rows_wanted:
-            res, series = _reduce_structure_rows(r["structure"][s], M, L, first.dx, start_fraction, kk, first_obs, return_series)
+            res, series = _reduce_structure_rows(r["structure"][s], M, L, first.dx, start_fraction, r["k_max"], r["first_obs"], return_series)
         else:
             res = win.result()
         if return_series:
@@ -1370,9 +1321,7 @@ def run_batched_exact_structure_mixed(systems, T=10.0, obs_dt=0.01, start_fracti
                 res["fft_amp_series"] = np.array(series.amp)
         out.append(res)
         ps.n_events = int(r["n_events"][s])
-    first.kernel_ms = r["kernel_ms"]
-    first.bytes_back = r["bytes_back"]
-    return (out, ck) if return_checkpoint else out
+    return out
 
 
 def run_batched_exact_structure(systems, T=10.0, obs_dt=0.01, start_fraction=0.5, k_max=None, return_series=False, resume=None):

@@ -5,10 +5,12 @@ entry points and what it makes of what they return.
 the entry's name and the number of arguments, every scalar field of gil_params, every scalar argument and, for every pointer,
 either NULL or a CRC of the bytes it must point to; the extents are restated here from the headers (n_systems, n_cap, n_obs, L,
 K, flip_n, the variant count), and the bytes are read inside the stand-in after a gc.collect(): an array that nothing keeps alive
-until the C call returns shows as other bytes.  The arrays behind gilx_variants and gil_checkpoint are read the same way.  The
+until the C call returns shows as other bytes.  The arrays behind gilx_variants, gil_checkpoint and gilx_checkpoint (its six
+base arrays, n_slots and, with k_max > 0, the window sums) are read the same way.  The
 stand-in then fills the outputs from a generator seeded by the case's name with values a launch could return (n_recorded =
-n_obs, positions in [0, L), flags with the alive bit, next_obs at the segment's end, finite sums), so that the post-processing
-runs.  The plans go to the real library: they are host arithmetic.
+n_obs, positions in [0, L), flags with the alive bit, next_obs at the segment's end, finite sums; in a gilx_checkpoint n_slots
+as they came in, or n0 on a fresh start, a positive window, n_window = the window's observations up to the segment's end and
+n_empty = 0), so that the post-processing runs.  The plans go to the real library: they are host arithmetic.
 
 Recorded per case, and compared for equality (no tolerance; arrays by CRC of their bytes, so NaNs compare by bits): the calls,
 the returned structure or the exception's type and text, and per system n_events, kernel_ms, bytes_back and the state of
@@ -19,6 +21,11 @@ commit 9100240, the parent of the commit that added this file (there every entry
 opening and its C call out for itself), by this file's own
 
     python tests/test_exact_loop_python_contract_cpu.py --record      (run in a checkout of 9100240 that holds a copy of this file)
+
+The cases of the large mixed launch, of the mixed checkpoints and segment chains and of their raw functions (gilxm_run,
+gilxr_run, gilxmr_run, gilxsr_run, MixedCheckpoint, plan_mixed_many; NEWER below) were recorded the same way from commit
+5dbba22, where the mixed chain stood beside the mixed launch and the plain chain as a copy of both; every older entry came out
+of that recording byte for byte as 9100240 had given it.
 
 The case list is CASES below; the fixture holds nothing but names and recorded results (CRCs and texts).  Where a case asks
 for a number that the library refuses on the host before it looks for a device (n_bins = 0, k_max = 0, h_bins = 0), the
@@ -60,6 +67,8 @@ def crc_json(x):
 
 def digest(x):
     """A structure of dicts, lists, arrays and scalars as JSON: a CRC (with dtype and shape) per array, repr for scalars."""
+    if isinstance(x, gil.MixedCheckpoint):
+        return {"MixedCheckpoint": digest({**x.arrays(), **x.fingerprint(), "block_tables": x.block_tables})}
     if isinstance(x, gil.Checkpoint):
         return {"Checkpoint": digest({**x.arrays(), **x.fingerprint()})}
     if isinstance(x, dict):
@@ -83,6 +92,7 @@ VARIANT_POINTERS = {"sigma_grid": ("<f8", "V"), "block_table": ("|u1", "V*(K+1)*
                     "seed": ("<u8", "S"), "stream": ("<i4", "S"), "order": ("<i4", "S")}
 CHECKPOINT_POINTERS = {"pos": ("<i4", "S,N"), "flags": ("|u1", "S,N"), "ref": ("<i4", "S,N"), "t": ("<f8", "S"), "n_events": ("<i8", "S"),
                        "next_obs": ("<i4", "S")}
+MIXED_CHECKPOINT_POINTERS = {"n_slots": ("<i4", "S"), "window": ("<f8", "S,k_max,3"), "n_window": ("<i4", "S"), "n_empty": ("<i4", "S")}
 
 
 def _scalars(g, c, shape):
@@ -138,6 +148,7 @@ OUT = {"pos": ("<i4", "S,M,N", lambda g, c, s: g.integers(0, c["L"], s)),
 START = [("in", k) for k in ("n0", "pos0", "sigma0", "bound0", "uniforms")]
 RESULTS = [("out", k) for k in ("pos", "sigma", "flags", "scalars", "n_recorded", "n_events", "t_final", "exits", "n_exits")]
 RESUMABLE = ["par"] + START + RESULTS + ["ms", ("int", "obs_first"), "ck_in", "ck_out"]
+MIXED_RESUMABLE = ["par", "variants"] + START + RESULTS + ["ms", ("int", "obs_first"), "xck_in", "xck_out"]
 ENTRIES = {
     "gil_run_batch": ["par"] + START + RESULTS + ["ms"],
     "gilm_run": ["par"] + START + RESULTS + ["ms"],
@@ -151,12 +162,18 @@ ENTRIES = {
     "gilx_run": ["par", "variants"] + START + RESULTS + ["ms"],
     "gilxs_run": ["par", "variants", ("int", "k_max"), ("int", "first_obs")] + START + RESULTS
                  + [("out", k) for k in ("structure", "head", "window", "n_window", "n_empty")] + ["ms"],
+    "gilxm_run": ["par", "variants"] + START + RESULTS + ["ms"],
+    "gilxr_run": MIXED_RESUMABLE,
+    "gilxmr_run": MIXED_RESUMABLE,
+    "gilxsr_run": ["par", "variants", ("int", "k_max"), ("int", "first_obs")] + START + RESULTS + [("out", "structure"), ("out", "head")]
+                  + ["ms", ("int", "obs_first"), "xck_in", "xck_out"],
     "gil_run_large": ["par", ("int", "n0")] + [("in", "large_" + k) for k in ("pos0", "sigma0", "bound0", "uniforms")]
                      + [("out", k) for k in ("pos", "sigma", "flags", "n_recorded", "n_events", "t_final", "exits", "n_exits")] + ["ms"],
 }
 LAST_ERROR = {"gil_run_batch": "gil_last_error", "gil_run_large": "gil_large_last_error", "gilm_run": "gilm_last_error", "gils_run": "gils_last_error",
               "gilc_run": "gilc_last_error", "gilp_run": "gilp_last_error", "gilx_run": "gilx_last_error", "gilxs_run": "gilxs_last_error",
-              "gilr_run": "gilr_last_error", "gilrm_run": "gilr_last_error"}
+              "gilr_run": "gilr_last_error", "gilrm_run": "gilr_last_error", "gilxm_run": "gilxm_last_error", "gilxr_run": "gilxr_last_error",
+              "gilxmr_run": "gilxr_last_error", "gilxsr_run": "gilxr_last_error"}
 
 
 def _address(a):
@@ -189,13 +206,27 @@ def _struct(obj, pointers, ctx):
     return scalars, {f: _read(getattr(obj, f), *pointers[f], ctx) for f, t in obj._fields_ if t is C.c_void_p}
 
 
+def _values(address, dtype, n):
+    return np.frombuffer(C.string_at(address, n * np.dtype(dtype).itemsize), dtype=dtype).copy()
+
+
+def _mixed_checkpoint(obj, ctx):
+    """What a gilx_checkpoint to start from points to: the six base arrays, n_slots and, with k_max > 0, the window sums."""
+    rec = _struct(obj.base, CHECKPOINT_POINTERS, ctx)[1]
+    for k, (dtype, text) in MIXED_CHECKPOINT_POINTERS.items():
+        if k == "n_slots" or ctx.get("k_max", 0) > 0:
+            rec[k] = _read(getattr(obj, k), dtype, text, ctx)
+    return rec
+
+
 class StandIn:
     """What gillespie._lib() returns during a case.  `rc`: what every run returns (non-zero: nothing is filled); `short`: the
     observations every system but the first of a batch stays short of n_obs; `missing`: attributes the library does not have (an
-    older build); `ask_library`: every run, once noted, goes to the real library, which refuses it on the host."""
+    older build); `ask_library`: every run, once noted, goes to the real library, which refuses it on the host; `rc_after`: the
+    runs that succeed before `rc` sets in."""
 
-    def __init__(self, real, name, rc=0, short=0, missing=(), ask_library=False):
-        self.real, self.rc, self.short, self.missing, self.ask_library = real, rc, short, missing, ask_library
+    def __init__(self, real, name, rc=0, short=0, missing=(), ask_library=False, rc_after=0):
+        self.real, self.rc, self.short, self.missing, self.ask_library, self.rc_after = real, rc, short, missing, ask_library, rc_after
         self.rng = np.random.default_rng(zlib.crc32(name.encode()))
         self.calls = []
 
@@ -218,15 +249,18 @@ class StandIn:
         par = args[0]._obj
         ctx = dict(S=par.n_systems, N=par.n_cap, M=par.n_obs, L=par.L, K=par.K, E=par.max_events, F=par.flip_n, short=self.short)
         rec["par"], rec["par_pointers"] = _struct(par, PAR_POINTERS, ctx)
-        outs = []
+        outs, n_slots = [], None
         for what, a in zip(spec[1:], args[1:]):
             if what == "variants":
                 ctx["V"] = a._obj.n_variants
                 rec["variants"] = _struct(a._obj, VARIANT_POINTERS, ctx)
             elif what == "ck_in":
                 rec["ck_in"] = "NULL" if a is None else _struct(a._obj, CHECKPOINT_POINTERS, ctx)[1]
-            elif what == "ck_out":
-                outs.append(("ck_out", a._obj))
+            elif what == "xck_in":                             # the window sums are read where the header has them: with k_max > 0
+                rec["ck_in"] = "NULL" if a is None else _mixed_checkpoint(a._obj, ctx)
+                n_slots = n0 if a is None or not a._obj.n_slots else _values(a._obj.n_slots, "<i4", ctx["S"])
+            elif what in ("ck_out", "xck_out"):
+                outs.append((what, a._obj))
             elif what == "ms":
                 outs.append(("ms", a._obj))
             elif what[0] in ("int", "float"):
@@ -235,6 +269,8 @@ class StandIn:
                 rec["scalars"][what[1]] = repr(a)
             elif what[0] == "in":
                 rec["pointers"][what[1]] = _read(_address(a), *IN[what[1]], ctx)
+                if what[1] == "n0":
+                    n0 = _values(_address(a), "<i4", ctx["S"])
             else:
                 rec["pointers"][what[1]] = "NULL" if not _address(a) else "out"
                 outs.append((what[1], _address(a)))
@@ -243,17 +279,25 @@ class StandIn:
             rc = getattr(self.real, entry)(*args)
             assert rc != 0, f"{entry}: the library accepted what the case expects it to refuse"
             return rc
-        if self.rc:
+        if self.rc and len(self.calls) > self.rc_after:
             return self.rc
         for name, target in outs:
             if name == "ms":
                 target.value = float(self.rng.integers(1, 1000)) / 8.0
-            elif name == "ck_out":
+            elif name in ("ck_out", "xck_out"):
                 S, N, L = ctx["S"], ctx["N"], ctx["L"]
+                more, target = target, target.base if name == "xck_out" else target
                 fill = dict(pos=self.rng.integers(0, L, (S, N)), flags=4 | self.rng.integers(0, 4, (S, N)), ref=self.rng.integers(-1, L, (S, N)),
                             t=self.rng.random(S), n_events=self.rng.integers(100, 1000, S), next_obs=ctx["obs_first"] + ctx["M"] - _short(ctx))
                 for k, (dtype, text) in CHECKPOINT_POINTERS.items():
                     _write(getattr(target, k), fill[k], dtype, _shape(text, ctx))
+                if name == "xck_out":
+                    kk = max(ctx.get("k_max", 0), 0)
+                    fill = dict(n_slots=n_slots, window=self.rng.random((S, kk, 3)) + 0.5 if more.window else None, n_empty=np.zeros(S),
+                                n_window=np.full(S, max(ctx["obs_first"] + ctx["M"] - ctx.get("first_obs", 0), 0)))
+                    for k, (dtype, text) in MIXED_CHECKPOINT_POINTERS.items():
+                        if getattr(more, k):
+                            _write(getattr(more, k), fill[k], dtype, _shape(text, dict(ctx, k_max=kk)))
             elif target:
                 dtype, text, make = OUT[name]
                 shape = _shape(text, ctx)
@@ -594,13 +638,177 @@ PLANS = (("plan_many_large", gil.plan_many_large, dict(PLAN_LARGE, sigma_grid=3.
                                                                                         per_system=True)),
          ("plan_mixed", gil.plan_mixed, dict(PLAN, sigma_grids=[1.0, 3.0]), dict(variant_of_system=[0, 1, 1, 0], order=[3, 2, 1, 0], want_states=False)),
          ("plan_mixed_structure", gil.plan_mixed_structure, dict(PLAN, sigma_grids=[1.0, 3.0], k_max=16),
-          dict(first_obs=2, variant_of_system=[0, 1, 1, 0], order=[3, 2, 1, 0], want_states=False, want_rows=False)))
+          dict(first_obs=2, variant_of_system=[0, 1, 1, 0], order=[3, 2, 1, 0], want_states=False, want_rows=False)),
+         ("plan_mixed_many", gil.plan_mixed_many, dict(PLAN, sigma_grids=[1.0, 3.0]), dict(variant_of_system=[0, 1, 1, 0], order=[3, 2, 1, 0],
+                                                                                           want_states=False)))
 for tag, fn, kw, more in PLANS:
     case(f"{tag}-defaults", none, lambda s, fn=fn, kw=kw: fn(**kw))
     case(f"{tag}-every-keyword", none, lambda s, fn=fn, kw=dict(kw, **more): fn(**kw))
     case(f"{tag}-periodic-large-L", none, lambda s, fn=fn, kw=dict(kw, L=4100, periodic=True): fn(**kw))
     case(f"{tag}-refused", none, lambda s, fn=fn, kw=dict(kw, K=0): fn(**kw))
 case("plan_mixed-order-length", none, lambda s: gil.plan_mixed(**dict(PLAN, sigma_grids=[1.0], order=[0])))
+
+
+# ---- NEWER: the large mixed launch, MixedCheckpoint, the mixed segment chains, their raw functions and plan_mixed_many
+
+def mixed_checkpoint(next_obs=(2, 2, 2), make=with_sigmas(), N=20, structure=False, tables=False, **kw):
+    """A MixedCheckpoint that the systems of `make` (seed = 5, one group) can resume from; `kw` replaces constructor keywords."""
+    like = make()
+    S, first, g = len(like), like[0], np.random.default_rng(23)
+    large = gil._large_shape(first.L, N)
+    fields = dict(L=first.L, K=first.K, periodic=first.periodic, anchor_mask=first.is_anchor_site, obs_dt=DT, large=large,
+                  sigma_grids=[ps._sigma_grid for ps in like], seeds=[5 + s if large else 5 for s in range(S)],
+                  streams=[0 if large else s for s in range(S)], n_slots=[N] * S,
+                  pos=g.integers(0, first.L, (S, N)), flags=np.full((S, N), gil.GILR_ALIVE | gil.GILR_PLUS), ref=np.full((S, N), -1),
+                  t=g.random(S) * 0.01, n_events=g.integers(0, 50, S), next_obs=np.asarray(next_obs)[:S])
+    if tables:
+        fields["block_tables"] = g.integers(0, 2, (S, first.K + 1, first.K + 1))
+    if structure:
+        kk = first.L
+        fields.update(k_max=kk, first_obs=5, window=g.random((S, kk, 3)) + 0.5, n_window=[0] * S, n_empty=[0] * S)
+    fields.update(kw)
+    return gil.MixedCheckpoint(**fields)
+
+
+GOO = dict(groups=[0, 1, 0], order=[2, 1, 0])
+# one launch, large
+case("mixed-allow_large", large, lambda s: EM(s, allow_large=True, want_m_local=False, **RUN))
+case("statistics_mixed-allow_large", large, lambda s: ESM(s, allow_large=True, **RUN))
+case("mixed-allow_large-small-shape", with_sigmas(), lambda s: EM(s, allow_large=True, want_m_local=False, **RUN))
+case("statistics_mixed-allow_large-small-shape", with_sigmas(), lambda s: ESM(s, allow_large=True, **RUN))
+case("structure_mixed-large-resume", large, lambda s: ETM(s, resume=mixed_checkpoint(make=large, N=40, structure=True), **RUN))
+# segments
+case("mixed-two-segments", with_sigmas(), two_segments(EM, want_m_local=False))
+case("mixed-two-segments-seed-drawn", with_sigmas(seed=None), two_segments(EM, want_m_local=False))
+case("mixed-two-segments-groups-order-uniforms", with_sigmas(), two_segments(EM, want_m_local=False, uniforms=uniforms(3), **GOO))
+case("mixed-two-segments-allow_large", large, two_segments(EM, want_m_local=False, allow_large=True))
+case("statistics_mixed-two-segments", with_sigmas(two_densities), two_segments(ESM))
+case("statistics_mixed-two-segments-allow_large", large, two_segments(ESM, allow_large=True))
+for reduce in ("device", "rows"):
+    case(f"structure_mixed-cut-in-two-{reduce}", with_sigmas(), two_segments(ETM, reduce=reduce))
+# chains
+case("mixed-chain", with_sigmas(), lambda s: EM(s, obs_per_launch=3, want_m_local=False, **RUN))
+case("statistics_mixed-chain-checkpoint", with_sigmas(two_densities), lambda s: ESM(s, obs_per_launch=7, return_checkpoint=True, **RUN))
+case("structure_mixed-chain-rows-series", with_sigmas(), lambda s: ETM(s, obs_per_launch=4, reduce="rows", return_series=True, k_max=7, start_fraction=0.3,
+                                                                      **RUN))
+case("structure_mixed-chain-device-series-checkpoint", with_sigmas(seed=None), lambda s: ETM(s, obs_per_launch=3, return_series=True, return_checkpoint=True,
+                                                                                             groups=[0, 0, 1], **RUN))
+case("mixed-chain-short", with_sigmas(), lambda s: EM(s, obs_per_launch=3, want_m_local=False, **RUN), short=1)
+case("statistics_mixed-chain-short", with_sigmas(), lambda s: ESM(s, obs_per_launch=5, **RUN), short=1)
+case("structure_mixed-chain-short", with_sigmas(), lambda s: ETM(s, obs_per_launch=4, **RUN), short=1)
+# ranges
+case("mixed-obs_range", with_sigmas(), lambda s: EM(s, obs_range=(0, 6), want_m_local=False, **RUN))
+case("structure_mixed-obs_range-checkpoint", with_sigmas(), lambda s: ETM(s, obs_range=(0, 6), return_checkpoint=True, **RUN))
+case("structure_mixed-obs_range", with_sigmas(), lambda s: ETM(s, obs_range=(0, 6), **RUN))
+case("mixed-resume-given", with_sigmas(), lambda s: EM(s, resume=mixed_checkpoint((2, 3, 5)), want_m_local=False, **RUN))
+case("mixed-resume-range-chain", with_sigmas(), lambda s: EM(s, resume=mixed_checkpoint(), obs_range=(3, 9), obs_per_launch=4, return_checkpoint=True,
+                                                             want_m_local=False, **RUN))
+case("statistics_mixed-resume-tables", with_sigmas(), lambda s: ESM(s, resume=mixed_checkpoint(tables=True), return_checkpoint=True, **RUN))
+case("statistics_mixed-resume-range", with_sigmas(), lambda s: ESM(s, resume=mixed_checkpoint(), obs_range=(2, 8), **RUN))
+case("structure_mixed-resume-given", with_sigmas(), lambda s: ETM(s, resume=mixed_checkpoint(structure=True), return_series=True, **RUN))
+case("structure_mixed-resume-inside-window", with_sigmas(), lambda s: ETM(s, resume=mixed_checkpoint((7, 7, 7), structure=True), **RUN))
+case("statistics_mixed-resume-different-observations", with_sigmas(), lambda s: ESM(s, resume=mixed_checkpoint((2, 3, 3)), **RUN))
+# refusals before any launch
+case("mixed-resume-structure-checkpoint", with_sigmas(), lambda s: EM(s, resume=mixed_checkpoint(structure=True), **RUN))
+case("statistics_mixed-resume-structure-checkpoint", with_sigmas(), lambda s: ESM(s, resume=mixed_checkpoint(structure=True), **RUN))
+case("structure_mixed-resume-plain-mixed-checkpoint", with_sigmas(), lambda s: ETM(s, resume=mixed_checkpoint(), **RUN))
+case("structure_mixed-resume-plain-checkpoint", with_sigmas(), lambda s: ETM(s, resume=checkpoint(), **RUN))
+case("mixed-resume-arrays", with_sigmas(), lambda s: EM(s, resume=mixed_checkpoint().arrays(), **RUN))
+case("exact-resume-mixed-checkpoint", systems, lambda s: E(s, resume=mixed_checkpoint(make=systems), **RUN))
+case("statistics-resume-mixed-checkpoint", systems, lambda s: ES(s, resume=mixed_checkpoint(make=systems), **RUN))
+case("mixed-resume-other-L", with_sigmas(), lambda s: EM(s, resume=mixed_checkpoint(L=65), **RUN))
+case("mixed-resume-other-K", with_sigmas(), lambda s: EM(s, resume=mixed_checkpoint(K=2), **RUN))
+case("mixed-resume-other-periodic", with_sigmas(), lambda s: EM(s, resume=mixed_checkpoint(periodic=True), **RUN))
+case("mixed-resume-other-anchors", with_sigmas(**ANCHORS), lambda s: EM(s, resume=mixed_checkpoint(), **RUN))
+case("mixed-resume-other-systems", with_sigmas(n=2), lambda s: EM(s, resume=mixed_checkpoint(), **RUN))
+case("mixed-resume-other-obs_dt", with_sigmas(), lambda s: EM(s, resume=mixed_checkpoint(), T=T, obs_dt=0.01))
+case("mixed-resume-other-sigma_grids", systems, lambda s: EM(s, resume=mixed_checkpoint(), **RUN))
+case("mixed-resume-other-seeds", with_sigmas(), lambda s: EM(s, resume=mixed_checkpoint(seeds=[5, 6, 5]), **RUN))
+case("mixed-resume-other-seeds-seed-drawn", with_sigmas(seed=None), lambda s: EM(s, resume=mixed_checkpoint(seeds=[5, 6, 5]), want_m_local=False, **RUN))
+case("mixed-resume-other-streams", with_sigmas(), lambda s: EM(s, resume=mixed_checkpoint(), groups=[0, 1, 2], **RUN))
+case("mixed-resume-other-large-keys", large, lambda s: EM(s, resume=mixed_checkpoint(make=large, N=40, seeds=[5, 5]), allow_large=True, **RUN))
+case("structure_mixed-resume-other-k_max", with_sigmas(), lambda s: ETM(s, resume=mixed_checkpoint(structure=True), k_max=6, **RUN))
+case("structure_mixed-resume-other-first_obs", with_sigmas(), lambda s: ETM(s, resume=mixed_checkpoint(structure=True), start_fraction=0.4, **RUN))
+for tag, fn in (("mixed", EM), ("statistics_mixed", ESM), ("structure_mixed", ETM)):
+    case(f"{tag}-obs_range-empty", with_sigmas(), lambda s, fn=fn: fn(s, obs_range=(4, 4), **RUN))
+    case(f"{tag}-obs_range-beyond", with_sigmas(), lambda s, fn=fn: fn(s, obs_range=(0, 99), **RUN))
+    case(f"{tag}-obs_range-late-start", with_sigmas(), lambda s, fn=fn: fn(s, obs_range=(2, 5), **RUN))
+    case(f"{tag}-obs_per_launch-0", with_sigmas(), lambda s, fn=fn: fn(s, obs_per_launch=0, **RUN))
+    case(f"{tag}-chain-lds-limit", with_sigmas(), lds_limit(fn, obs_per_launch=3))
+    case(f"{tag}-chain-large", large, lambda s, fn=fn: fn(s, obs_per_launch=3, **RUN))
+    case(f"{tag}-chain-differ", altered("k_off", 0.3), lambda s, fn=fn: fn(s, obs_per_launch=3, **RUN))
+case("mixed-resume-large-not-allowed", large, lambda s: EM(s, resume=mixed_checkpoint(make=large, N=40), **RUN))
+case("statistics_mixed-chain-k_exit", lambda: systems(k_exit=0.5), lambda s: ESM(s, obs_per_launch=3, **RUN))
+# the library's side
+case("mixed-chain-refused-second", with_sigmas(), lambda s: EM(s, obs_per_launch=3, want_m_local=False, **RUN), rc=-1, rc_after=1)
+case("structure_mixed-chain-refused-second", with_sigmas(), lambda s: ETM(s, obs_per_launch=3, **RUN), rc=-5, rc_after=1)
+case("exact-chain-refused-second", systems, lambda s: E(s, obs_per_launch=3, want_m_local=False, **RUN), rc=-1, rc_after=1)
+case("mixed-chain-older-build", with_sigmas(), lambda s: EM(s, obs_per_launch=3, **RUN), missing=("gilxr_run",))
+case("mixed-chain-allow_large-older-build", large, lambda s: EM(s, obs_per_launch=3, allow_large=True, **RUN), missing=("gilxmr_run",))
+case("structure_mixed-chain-older-build", with_sigmas(), lambda s: ETM(s, obs_per_launch=3, **RUN), missing=("gilxsr_run",))
+case("mixed-allow_large-older-build", large, lambda s: EM(s, allow_large=True, **RUN), missing=("gilxm_run",))
+# MixedCheckpoint itself
+case("mixed_checkpoint", none, lambda s: mixed_checkpoint(tables=True))
+case("mixed_checkpoint-structure", none, lambda s: mixed_checkpoint(structure=True))
+case("mixed_checkpoint-shapes", none, lambda s: mixed_checkpoint(next_obs=(1, 2)))
+case("mixed_checkpoint-pos-1d", none, lambda s: mixed_checkpoint(pos=np.zeros(3)))
+for name in ("n_slots", "seeds", "streams", "sigma_grids"):
+    case(f"mixed_checkpoint-{name}-length", none, lambda s, name=name: mixed_checkpoint(**{name: [1, 2]}))
+case("mixed_checkpoint-structure-without-window", none, lambda s: mixed_checkpoint(structure=True, window=None))
+case("mixed_checkpoint-structure-without-first_obs", none, lambda s: mixed_checkpoint(structure=True, first_obs=None))
+case("mixed_checkpoint-window-shape", none, lambda s: mixed_checkpoint(structure=True, window=np.zeros((3, 5, 3))))
+case("mixed_checkpoint-n_window-shape", none, lambda s: mixed_checkpoint(structure=True, n_window=[0, 0]))
+case("mixed_checkpoint-block_tables-shape", none, lambda s: mixed_checkpoint(block_tables=np.zeros((3, 3, 3))))
+case("mixed_checkpoint-require-every-field", none, lambda s: mixed_checkpoint(structure=True).require(**mixed_checkpoint(structure=True).fingerprint()))
+for name, other in (("n_cap", 21), ("large", True), ("n_slots", [20, 19, 20]), ("streams", [0, 1, 1]), ("anchor_mask", np.arange(64) == 3)):
+    case(f"mixed_checkpoint-require-{name}", none, lambda s, name=name, other=other: mixed_checkpoint(structure=True).require(**{name: other}))
+case("checkpoint-require-every-field", none, lambda s: checkpoint().require(**checkpoint().fingerprint()))
+for name, other in (("K", 2), ("local_kernel_sigma", 0.01), ("n_cap", 21), ("anchor_mask", np.arange(64) == 3)):
+    case(f"checkpoint-require-{name}", none, lambda s, name=name, other=other: checkpoint().require(**{name: other}))
+# the raw functions and the plan
+NEWER_RAW = (("run_mixed_many_raw", gil.run_mixed_many_raw, MIXED), ("run_mixed_resumable_raw", gil.run_mixed_resumable_raw, MIXED),
+             ("run_mixed_resumable_raw-large", gil.run_mixed_resumable_raw, dict(MIXED, large=True)),
+             ("run_mixed_structure_resumable_raw", gil.run_mixed_structure_resumable_raw, MIXED))
+for tag, fn, extra in NEWER_RAW:
+    full = dict(FULL, block_tables=np.arange(18).reshape(2, 3, 3) % 2, seeds=[2 ** 64 + 3, -1], streams=[4, 0], order=[1, 0], **extra)
+    del full["block_table"]
+    if "structure" in tag:
+        full.update(k_max=3, first_obs=2, want_rows=False)
+    if "resumable" in tag:
+        full.update(obs_first=0)
+    case(f"{tag}-defaults", none, lambda s, fn=fn, kw=extra: fn(**raw(**kw)))
+    case(f"{tag}-every-keyword", none, lambda s, fn=fn, kw=full: fn(**raw(**kw)))
+    case(f"{tag}-uniforms", none, lambda s, fn=fn, kw=extra: fn(**raw(uniforms=uniforms(2, 5), max_events=3, **kw)))
+    case(f"{tag}-uniforms-shape", none, lambda s, fn=fn, kw=extra: fn(**raw(uniforms=uniforms(3, 5), **kw)))
+    case(f"{tag}-n_cap-small", none, lambda s, fn=fn, kw=extra: fn(**raw(n_cap=4, **kw)))
+    case(f"{tag}-empty-anchor-mask", none, lambda s, fn=fn, kw=extra: fn(**raw(anchor_mask=np.zeros(64, bool), betas=0.75, **kw)))
+    case(f"{tag}-refused", none, lambda s, fn=fn, kw=extra: fn(**raw(**kw)), rc=-4)
+    case(f"{tag}-no-variant_of_system", none, lambda s, fn=fn, kw=extra: fn(**raw(**dict(kw, variant_of_system=None))))
+    case(f"{tag}-block_tables-shape", none, lambda s, fn=fn, kw=extra: fn(**raw(**dict(kw, block_tables=np.zeros((2, 2, 2))))))
+CK_MIXED = dict(CK_RAW, n_slots=[5, 6])
+CK_WINDOW = dict(CK_MIXED, window=np.arange(24).reshape(2, 4, 3) + 0.5, n_window=[1, 0], n_empty=[0, 2])
+XR, XSR = gil.run_mixed_resumable_raw, gil.run_mixed_structure_resumable_raw
+case("run_mixed_resumable_raw-checkpoint", none, lambda s: XR(**raw(checkpoint=CK_MIXED, obs_first=2, states=None, **MIXED)))
+case("run_mixed_resumable_raw-checkpoint-large-n_cap", none, lambda s: XR(**raw(checkpoint=CK_MIXED, obs_first=3, states=None, n_cap=6, large=True, **MIXED)))
+case("run_mixed_resumable_raw-checkpoint-with-window", none, lambda s: XR(**raw(checkpoint=CK_WINDOW, obs_first=2, states=None, **MIXED)))
+case("run_mixed_structure_resumable_raw-checkpoint", none, lambda s: XSR(**raw(checkpoint=CK_WINDOW, obs_first=2, states=None, k_max=4, first_obs=3, **MIXED)))
+case("run_mixed_structure_resumable_raw-checkpoint-no-rows", none, lambda s: XSR(**raw(checkpoint=CK_WINDOW, obs_first=4, states=None, k_max=4, first_obs=3,
+                                                                                        want_rows=False, want_states=False, **MIXED)))
+case("run_mixed_structure_resumable_raw-checkpoint-no-window", none, lambda s: XSR(**raw(checkpoint=CK_MIXED, obs_first=2, states=None, k_max=4, **MIXED)))
+case("run_mixed_structure_resumable_raw-checkpoint-window-shape", none,
+     lambda s: XSR(**raw(checkpoint=dict(CK_WINDOW, window=np.zeros((2, 3, 3))), states=None, k_max=4, **MIXED)))
+case("run_mixed_structure_resumable_raw-checkpoint-n_empty-shape", none,
+     lambda s: XSR(**raw(checkpoint=dict(CK_WINDOW, n_empty=[0]), states=None, k_max=4, **MIXED)))
+case("run_mixed_structure_resumable_raw-k_max-0", none, lambda s: XSR(**raw(k_max=0, **MIXED)), ask_library=True)
+for tag, fn, more in (("run_mixed_resumable_raw", XR, {}), ("run_mixed_structure_resumable_raw", XSR, dict(k_max=4))):
+    case(f"{tag}-checkpoint-other-n_cap", none, lambda s, fn=fn, more=more: fn(**raw(checkpoint=CK_WINDOW, states=None, n_cap=7, **more, **MIXED)))
+    case(f"{tag}-checkpoint-shapes", none, lambda s, fn=fn, more=more: fn(**raw(checkpoint=dict(CK_WINDOW, t=[0.25]), states=None, **more, **MIXED)))
+    case(f"{tag}-checkpoint-n_slots-shape", none, lambda s, fn=fn, more=more: fn(**raw(checkpoint=dict(CK_WINDOW, n_slots=[5]), states=None, **more, **MIXED)))
+    case(f"{tag}-checkpoint-no-n_slots", none, lambda s, fn=fn, more=more: fn(**raw(checkpoint=CK_RAW, states=None, **more, **MIXED)))
+    case(f"{tag}-older-build", none, lambda s, fn=fn, more=more: fn(**raw(**more, **MIXED)), missing=("gilxr_run", "gilxsr_run"))
+case("run_mixed_resumable_raw-large-older-build", none, lambda s: XR(**raw(large=True, **MIXED)), missing=("gilxmr_run",))
+case("run_mixed_many_raw-older-build", none, lambda s: gil.run_mixed_many_raw(**raw(**MIXED)), missing=("gilxm_run",))
+case("plan_mixed_many-order-length", none, lambda s: gil.plan_mixed_many(**dict(PLAN, sigma_grids=[1.0], order=[0])))
 
 assert len({name for name, _, _, _ in CASES}) == len(CASES), "case names must be unique"
 
