@@ -1,5 +1,5 @@
 // gillespie_big_hip.hip -- gil_run_large of include/gillespie.h, gilm_run of include/gillespie_many.h, gilxm_run of
-// include/gillespie_mixed_many.h and the large shape of gils_run, gilc_run, gilp_run, gilrm_run and gilxmr_run: the reference's
+// include/gillespie_mixed_many.h and the large shape of gils_run, gilc_run, gilp_run, gilrm_run, gilxmr_run and gilxp_run: the reference's
 // exact event loop (PARTICLE_solver_CLASS.py:511-538) for systems far too large for a workgroup's LDS (the BASELINE size:
 // N = 1e5 particles on L = 2e5 sites, where the reference manages 0.8 events/s because it recomputes the whole
 // field and all N rates before every event).  One kernel and one host driver serve both entry points: a batch is a grid
@@ -247,6 +247,7 @@ __global__ __launch_bounds__(256) void big_field_init_mixed(const GilxBigArgs a0
 }
 
 struct GilxrBigArgs : GilxBigArgs { GilrArgs rs; };         // arguments of the resumable mixed instantiation
+struct GilxpBigArgs : GilxBigArgs { GilpArgs pf; };         // arguments of the mixed profile instantiation (gilxp_run's large shape)
 
 // From a checkpoint in a mixed launch: big_field_init_live with the system's own table, length and field mode
 __global__ __launch_bounds__(256) void big_field_init_live_mixed(const GilxBigArgs a0) {
@@ -267,6 +268,7 @@ template <> struct BigKernelArgs<GilKind::Profile> { using type = GilpBigArgs; }
 template <> struct BigKernelArgs<GilKind::Resume> { using type = GilrBigArgs; };
 template <> struct BigKernelArgs<GilKind::Mixed> { using type = GilxBigArgs; };
 template <> struct BigKernelArgs<GilKind::MixedResume> { using type = GilxrBigArgs; };
+template <> struct BigKernelArgs<GilKind::MixedProfile> { using type = GilxpBigArgs; };
 
 // V = the variant, a compile-time property, so that each kernel is the code it was before the others existed:
 //   Structure  also reduce the structure sums at an observation (gillespie_structure.hpp);
@@ -283,11 +285,14 @@ template <> struct BigKernelArgs<GilKind::MixedResume> { using type = GilxrBigAr
 //   MixedResume  a resumable mixed launch (include/gillespie_mixed_resume.h): Mixed with the start and end of Resume.  The
 //              checkpoint's rows are the system's (RS_ROW), not the workgroup's; gilxm_select is applied before anything is read.
 //              The rate sums are grouped by blocks of the launch's n_cap, so the slot count does not enter here.
+//   MixedProfile  the ensemble profiles of a mixed launch (include/gillespie_mixed_profile.h): Mixed with the observation pass of
+//              Profile.  The group table, members and the per-system rows are indexed by the SYSTEM (mx_sys), the field mode is the
+//              one gilxm_select wrote, and the slots lie behind ctl[] of the launch's layout (tab_region).
 template <GilKind V>
 __global__ __launch_bounds__(BT) void gil_big_kernel(const typename BigKernelArgs<V>::type a0) {
-    constexpr bool ST = V == GilKind::Structure, CP = V == GilKind::Capture, PF = V == GilKind::Profile;
+    constexpr bool ST = V == GilKind::Structure, CP = V == GilKind::Capture, PF = V == GilKind::Profile || V == GilKind::MixedProfile;
     constexpr bool RS = V == GilKind::Resume || V == GilKind::MixedResume;
-    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedResume;
+    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedResume || V == GilKind::MixedProfile;
     extern __shared__ double lds[];
     BigArgs a = a0;
     uint32_t stream = 0u;                                      // Philox counter word 2: the system's own with MX
@@ -397,7 +402,7 @@ __global__ __launch_bounds__(BT) void gil_big_kernel(const typename BigKernelArg
             if (k >= a0.pf.first_obs) {
                 double mg = 0.0;                               // global-mean mode: the one value of every site (ref :219-221)
                 if (!M.field_mode && gsum_n > 0) { mg = (double)gsum_s / (double)gsum_n; mg = mg > 1.0 ? 1.0 : (mg < -1.0 ? -1.0 : mg); }
-                gilp_record<BT>(a0.pf, ctl + 32, (size_t)blockIdx.x, k, nobs, L, N, a.pos, a.flg, a.W, a.S, M.field_mode != 0, mg);
+                gilp_record<BT>(a0.pf, ctl + 32, MX ? (size_t)mx_sys : (size_t)blockIdx.x, k, nobs, L, N, a.pos, a.flg, a.W, a.S, M.field_mode != 0, mg);
             }
         }
     };
@@ -851,6 +856,7 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
     GilxrBigArgs c{};                                           // the mixed launch's arguments: a's own and the variants (and, resumable,
     static_cast<BigArgs &>(c) = a;                              //   the checkpoint: GilxBigArgs is its base)
     c.rs = b.rs;
+    GilxpBigArgs d{};                                           // the mixed profile launch's: the mixed launch's own and the profile's (below)
     if (mx) {
         c.tab_region = xinfo.max_tlen_lds >= 0 ? ((xinfo.max_tlen_lds + 2) & ~1) : 0;
         c.mx.has_block = mx->block_table ? 1 : 0;
@@ -859,6 +865,7 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
         if ((rc = job.upload(&c.mx.variants, tb.var.data(), tb.var.size(), "variants"))) return rc;
         if ((rc = job.upload(&c.mx.seed, seed.data(), (size_t)S, "seed"))) return rc;
         if ((rc = job.upload(&c.mx.stream, stream.data(), (size_t)S, "stream"))) return rc;
+        static_cast<GilxBigArgs &>(d) = c; d.pf = a.pf;
     }
     const dim3 field_grid((unsigned)((L + 255) / 256), (unsigned)S);   // W, S of the start state: before the timed window
     if (rs && mx) hipLaunchKernelGGL(big_field_init_live_mixed, field_grid, dim3(256), 0, nullptr, static_cast<const GilxBigArgs &>(c));
@@ -867,6 +874,7 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
     else hipLaunchKernelGGL(big_field_init, field_grid, dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
     rc = ex.structure_obs ? big_launch<GilKind::Structure>(job, S, lds, a)
          : cap            ? big_launch<GilKind::Capture>(job, S, lds, a)
+         : mx && prof     ? big_launch<GilKind::MixedProfile>(job, S, lds, d)
          : prof           ? big_launch<GilKind::Profile>(job, S, lds, a)
          : mx && rs       ? big_launch<GilKind::MixedResume>(job, S, lds, c)
          : mx             ? big_launch<GilKind::Mixed>(job, S, lds, c)
@@ -887,6 +895,17 @@ int gil_large_plan(const char *who, std::string &err, const gil_params *p, int32
     if (int rc = big_plan(who, err, p, false, false, &info, nullptr)) return rc;
     *lds_bytes = info.lds_bytes + extra_lds;
     *work_bytes = (int64_t)p->n_systems * info.work_bytes_per_system;
+    if (*lds_bytes > 160 * 1024) { err = std::string(who) + ": LDS budget exceeded"; return GIL_ERR_ARG; }
+    return GIL_OK;
+}
+
+int gil_large_mixed_plan(const char *who, std::string &err, const gil_params *p, const gilx_variants *v, bool want_states, int32_t extra_lds,
+                         int32_t *lds_bytes, int64_t *work_bytes, int32_t *max_tlen, int64_t *table_doubles) {
+    gilxm_plan_info info{}; GilxTables tb;
+    if (int rc = gilxm_decide(who, err, p, v, want_states, true, info, tb)) return rc;
+    *lds_bytes = info.lds_bytes + extra_lds;
+    *work_bytes = (int64_t)p->n_systems * info.work_bytes_per_system;
+    *max_tlen = info.max_tlen; *table_doubles = info.table_doubles;
     if (*lds_bytes > 160 * 1024) { err = std::string(who) + ": LDS budget exceeded"; return GIL_ERR_ARG; }
     return GIL_OK;
 }

@@ -36,7 +36,8 @@ struct GilIo {
 // What one entry point adds, at most one of: gils_run's rows (k_max modes, from observation first_obs on), gilc_run's call,
 // gilp_run's, the start state of gilr_run / gilrm_run (checked by gilr_prepare; it comes back as the end state), gilxs_run's call,
 // gilxm_run's variants (the large shape's mixed launch).  The resumable mixed launches (include/gillespie_mixed_resume.h) have
-// `rs` (checked by gilxr_prepare) next to `xs` or `mx`.
+// `rs` (checked by gilxr_prepare) next to `xs` or `mx`; gilxp_run (include/gillespie_mixed_profile.h) has `prof` in a mixed launch
+// (large shape: next to `mx`).
 struct GilExtras {
     int k_max = 0, first_obs = 0; double *structure_obs = nullptr;
     const GilcCall *cap = nullptr; const GilpCall *prof = nullptr; GilrCall *rs = nullptr; const GilxsCall *xs = nullptr;
@@ -45,7 +46,7 @@ struct GilExtras {
 
 // One enumerator per kernel variant that exists; a kernel family maps each of its own to an argument struct (GilKernelArgs in
 // gillespie_hip.hip, BigKernelArgs in gillespie_big_hip.hip), so a combination nobody wrote cannot be instantiated.
-enum class GilKind { Plain, Structure, Capture, Profile, Mixed, MixedStructure, Resume, MixedResume, MixedStructureResume };
+enum class GilKind { Plain, Structure, Capture, Profile, Mixed, MixedStructure, Resume, MixedResume, MixedStructureResume, MixedProfile };
 
 namespace {
 
@@ -246,3 +247,8 @@ __attribute__((visibility("hidden"))) int gil_large_plan(const char *who, std::s
                                                          int32_t *lds_bytes, int64_t *work_bytes);
 __attribute__((visibility("hidden"))) int gil_large_run(const char *who, std::string &err, const gil_params *p, const GilIo &io,
                                                         const GilExtras &ex);
+// gil_large_plan for a mixed launch (gilxm_plan's checks and numbers, by host arithmetic): also the longest table's length and the
+// doubles of all tables
+__attribute__((visibility("hidden"))) int gil_large_mixed_plan(const char *who, std::string &err, const gil_params *p, const gilx_variants *v,
+                                                               bool want_states, int32_t extra_lds, int32_t *lds_bytes, int64_t *work_bytes,
+                                                               int32_t *max_tlen, int64_t *table_doubles);

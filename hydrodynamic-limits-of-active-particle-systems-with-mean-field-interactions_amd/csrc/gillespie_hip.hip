@@ -31,6 +31,7 @@
 #include "gillespie_profile.h"
 #include "gillespie_mixed.h"
 #include "gillespie_mixed_structure.h"
+#include "gillespie_mixed_profile.h"
 #include "gillespie_resume.h"
 #include "gillespie_mixed_resume.h"
 #include "aps_common.hpp"
@@ -82,6 +83,8 @@ struct GilxsBatchArgs : GilxBatchArgs { GilsArgs st; GilwArgs wn; };   // argume
 struct GilrBatchArgs : GilArgs { GilrArgs rs; };            // arguments of the resumable instantiations (gilr_run's)
 struct GilxrBatchArgs : GilxBatchArgs { GilrArgs rs; };     // arguments of the resumable mixed instantiations (gilxr_run's)
 struct GilxsrBatchArgs : GilxsBatchArgs { GilrArgs rs; };   // arguments of the resumable mixed structure instantiations (gilxsr_run's)
+struct GilxpBatchArgs : GilxBatchArgs { GilpArgs pf; };     // arguments of the mixed profile instantiations (gilxp_run's)
+struct GilxDriverArgs : GilxsrBatchArgs { GilpArgs pf; };   // mixed_run's one struct: what every mixed launch takes is in it
 
 // the argument struct of each variant of the batch kernel
 template <GilKind V> struct GilKernelArgs;
@@ -94,6 +97,7 @@ template <> struct GilKernelArgs<GilKind::MixedStructure> { using type = GilxsBa
 template <> struct GilKernelArgs<GilKind::Resume> { using type = GilrBatchArgs; };
 template <> struct GilKernelArgs<GilKind::MixedResume> { using type = GilxrBatchArgs; };
 template <> struct GilKernelArgs<GilKind::MixedStructureResume> { using type = GilxsrBatchArgs; };
+template <> struct GilKernelArgs<GilKind::MixedProfile> { using type = GilxpBatchArgs; };
 
 // the structure sums' slots: behind the loop's own LDS (which ends with the plus-occupancy bytes), at the next multiple of 8
 __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L) {
@@ -118,12 +122,15 @@ __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L)
 //                   those of the run's start, and the loops ask the flags; the end state beyond these slots is written as
 //                   empty.  With the structure sums, st.first_obs counts within the launch's slice (the host subtracts the
 //                   slice's first index), and the window's accumulators and counts start from the checkpoint's.
+//   MixedProfile    the ensemble profiles of a mixed launch (include/gillespie_mixed_profile.h): Mixed with the observation pass of
+//                   Profile over the system's own slots (those beyond were never loaded) and with the system's own field mode;
+//                   the profile slots lie behind the launch's layout, which a.tlen = the longest table fixes.
 template <int NT, GilKind V>
 __global__ __launch_bounds__(NT) void gil_kernel(const typename GilKernelArgs<V>::type a) {
     constexpr bool XR = V == GilKind::MixedResume || V == GilKind::MixedStructureResume;   // MX and RS together
     constexpr bool ST = V == GilKind::Structure || V == GilKind::MixedStructure || V == GilKind::MixedStructureResume;
-    constexpr bool CP = V == GilKind::Capture, PF = V == GilKind::Profile;
-    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedStructure || XR, RS = V == GilKind::Resume || XR;
+    constexpr bool CP = V == GilKind::Capture, PF = V == GilKind::Profile || V == GilKind::MixedProfile;
+    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedStructure || V == GilKind::MixedProfile || XR, RS = V == GilKind::Resume || XR;
     extern __shared__ double lds[];
     const Model &M = a.m;
     const GilxView vw = gilx_view<MX, NT>(a);                  // empty without MX
@@ -276,8 +283,8 @@ __global__ __launch_bounds__(NT) void gil_kernel(const typename GilKernelArgs<V>
         if constexpr (PF) {
             if (k >= a.pf.first_obs) {
                 double mg = 0.0;                               // global-mean mode: the one value of every site (ref :219-221)
-                if (!M.field_mode && gsum_n > 0) { mg = (double)gsum_s / (double)gsum_n; mg = mg > 1.0 ? 1.0 : (mg < -1.0 ? -1.0 : mg); }
-                gilp_record<NT>(a.pf, gils_slots(lds, occp, L), (size_t)sys, k, nobs, L, ncap, pos, flg, W, S, M.field_mode != 0, mg);
+                if (!GX_FIELD && gsum_n > 0) { mg = (double)gsum_s / (double)gsum_n; mg = mg > 1.0 ? 1.0 : (mg < -1.0 ? -1.0 : mg); }
+                gilp_record<NT>(a.pf, gils_slots(lds, occp, L), (size_t)sys, k, nobs, L, GX_SLOTS, pos, flg, W, S, GX_FIELD != 0, mg);
             }
         }
     };
@@ -751,21 +758,27 @@ int gilc_decide(const char *who, const gil_params *p, const GilcCall &c, bool st
 std::string g_gilp_err;
 
 // the checks gilp_plan and gilp_run share, and the shape: 0 with `info` filled, or GIL_ERR_ARG with the text in g_gilp_err
-int gilp_decide(const char *who, const gil_params *p, const GilpCall &c, bool states, gilp_plan_info &info) {
-    auto bad = [&](const std::string &m) { g_gilp_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
-    if (const char *why = gil_check_plan_params(p)) return bad(why);
+// what gilp_decide and gilxp_decide refuse of a profile call on its own numbers: empty, or the text of the complaint
+std::string gilp_check_call(const gil_params *p, const GilpCall &c) {
     const int max_bins = std::min(p->L, GILP_MAX_BINS);
-    if (c.n_bins < 1 || c.n_bins > max_bins) return bad("n_bins = " + std::to_string(c.n_bins) + " is outside [1, min(L, GILP_MAX_BINS) = " + std::to_string(max_bins) + "]");
-    if (c.n_groups < 1 || c.n_groups > GILP_MAX_GROUPS) return bad("n_groups = " + std::to_string(c.n_groups) + " is outside [1, " + std::to_string(GILP_MAX_GROUPS) + "]");
-    if (c.first_obs < 0 || c.first_obs > p->n_obs) return bad("first_obs = " + std::to_string(c.first_obs) + " is outside [0, n_obs = " + std::to_string(p->n_obs) + "]");
-    if (c.want_field != 0 && c.want_field != 1) return bad("want_field = " + std::to_string(c.want_field) + " is neither 0 nor 1");
+    if (c.n_bins < 1 || c.n_bins > max_bins) return "n_bins = " + std::to_string(c.n_bins) + " is outside [1, min(L, GILP_MAX_BINS) = " + std::to_string(max_bins) + "]";
+    if (c.n_groups < 1 || c.n_groups > GILP_MAX_GROUPS) return "n_groups = " + std::to_string(c.n_groups) + " is outside [1, " + std::to_string(GILP_MAX_GROUPS) + "]";
+    if (c.first_obs < 0 || c.first_obs > p->n_obs) return "first_obs = " + std::to_string(c.first_obs) + " is outside [0, n_obs = " + std::to_string(p->n_obs) + "]";
+    if (c.want_field != 0 && c.want_field != 1) return "want_field = " + std::to_string(c.want_field) + " is neither 0 nor 1";
     if (c.want_field && (int64_t)p->L * p->n_systems >= (1ll << 31))
-        return bad("want_field with L * n_systems = " + std::to_string((int64_t)p->L * p->n_systems) + " >= 2^31: the fixed-point field sum could overflow 64 bits");
+        return "want_field with L * n_systems = " + std::to_string((int64_t)p->L * p->n_systems) + " >= 2^31: the fixed-point field sum could overflow 64 bits";
     if (c.group_of_system)
         for (int s = 0; s < p->n_systems; ++s) {
             const int g = c.group_of_system[s];
-            if (g < 0 || g >= c.n_groups) return bad("group id " + std::to_string(g) + " of system " + std::to_string(s) + " is outside [0, n_groups = " + std::to_string(c.n_groups) + ")");
+            if (g < 0 || g >= c.n_groups) return "group id " + std::to_string(g) + " of system " + std::to_string(s) + " is outside [0, n_groups = " + std::to_string(c.n_groups) + ")";
         }
+    return "";
+}
+
+int gilp_decide(const char *who, const gil_params *p, const GilpCall &c, bool states, gilp_plan_info &info) {
+    auto bad = [&](const std::string &m) { g_gilp_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    if (const char *why = gil_check_plan_params(p)) return bad(why);
+    { const std::string why = gilp_check_call(p, c); if (!why.empty()) return bad(why); }
     const size_t prof_lds = gilp_lds_bytes(c.n_bins, c.want_field != 0);
     GilShape sh;
     if (int rc = gil_choose_shape(who, g_gilp_err, p, false, nullptr, prof_lds, (int32_t)prof_lds, sh)) return rc;
@@ -835,15 +848,60 @@ int gilxs_decide(const char *who, std::string &err, const gil_params *p, const g
     return gil_refuse_plan_bytes(who, err, info.work_bytes, info.output_bytes);
 }
 
-// gilx_run's driver, and with ex.xs gilxs_run's: the variant tables, the launch order, the seeds and streams and the window
-// outputs are its own, the rest is the staging path batch_run takes.  With ex.rs (gilxr_run, gilxsr_run) the launch is a segment:
+std::string g_gilxp_err;
+
+// the checks gilxp_plan and gilxp_run share, and the shape: 0 with `info` filled, or GIL_ERR_ARG with the text in g_gilxp_err.
+// The mixed launch's refusals first (gilx_decide's where the batch shape takes the launch, else gilxm_decide's), then
+// gilp_decide's.  The shape rule is gilp_run's with the longest table of the batch: the batch shape where gilx_run takes the
+// launch and the profile slots fit the 160 KB behind it, else the large shape.
+int gilxp_decide(const char *who, const gil_params *p, const gilx_variants *v, const GilpCall &c, bool states, gilxp_plan_info &info) {
+    auto bad = [&](const std::string &m) { g_gilxp_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    gilx_plan_info xi{}; GilxTables tb;
+    bool batch = p->L <= GIL_MAX_L && p->n_cap <= GIL_MAX_N && gilx_decide(who, p, v, states, xi, tb, g_gilxp_err) == GIL_OK;
+    int32_t large_lds = 0, large_tlen = 0; int64_t large_work = 0, large_doubles = 0;
+    bool planned_large = false;
+    auto plan_large = [&]() {                                  // the profile slots enter once the call's numbers are checked
+        planned_large = true;
+        return gil_large_mixed_plan(who, g_gilxp_err, p, v, states, 0, &large_lds, &large_work, &large_tlen, &large_doubles);
+    };
+    if (!batch) if (int rc = plan_large()) return rc;
+    { const std::string why = gilp_check_call(p, c); if (!why.empty()) return bad(why); }
+    const size_t prof_lds = gilp_lds_bytes(c.n_bins, c.want_field != 0);
+    int NT = 0; size_t lds = 0;
+    if (batch) {
+        batch_shape(p->L, p->n_cap, tb.max_tlen, false, NT, lds, nullptr, nullptr, prof_lds);
+        batch = lds <= 160 * 1024;
+    }
+    if (!batch && !planned_large) if (int rc = plan_large()) return rc;
+    info = gilxp_plan_info{};
+    info.bin_width = (p->L + c.n_bins - 1) / c.n_bins;
+    info.n_bins_used = (p->L + info.bin_width - 1) / info.bin_width;
+    info.output_bytes = gilp_output_bytes(p, c.n_groups, c.n_bins, states, c.profile_obs != nullptr);
+    info.work_bytes = (int64_t)p->n_systems * 4;
+    if (batch) {
+        info.shape = GILS_SHAPE_BATCH; info.threads = NT; info.lds_bytes = (int32_t)lds; info.max_tlen = tb.max_tlen;
+        info.table_doubles = (int64_t)tb.table.size();
+    } else {
+        info.shape = GILS_SHAPE_LARGE; info.threads = 1024; info.lds_bytes = large_lds + (int32_t)prof_lds; info.max_tlen = large_tlen;
+        info.table_doubles = large_doubles; info.work_bytes += large_work;
+        if (info.lds_bytes > 160 * 1024)
+            return bad("the launch needs " + std::to_string(info.lds_bytes) + " bytes of LDS per system with the profile slots (n_bins = " +
+                       std::to_string(c.n_bins) + "), more than the " + std::to_string(160 * 1024) + " bytes (160 KB) of a workgroup");
+    }
+    return gil_refuse_plan_bytes(who, g_gilxp_err, info.work_bytes, info.output_bytes);
+}
+
+// gilx_run's driver, with ex.xs gilxs_run's and with ex.prof gilxp_run's (batch shape; gilxp_decide has accepted the call): the
+// variant tables, the launch order, the seeds and streams and the window outputs are its own, the rest is the staging path
+// batch_run takes.  With ex.rs (gilxr_run, gilxsr_run) the launch is a segment:
 // the start state, the slot counts and the window sums so far are the checkpoint's (gilxr_prepare has checked them), no start
 // state is read from io, and xs->first_obs counts within the slice.
 int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, const GilExtras &ex) {
     const GilxsCall *xs = ex.xs;
+    const GilpCall *prof = ex.prof;
     GilrCall *rs = ex.rs;
-    const char *who = rs ? (xs ? "gilxsr_run" : "gilxr_run") : xs ? "gilxs_run" : "gilx_run";
-    std::string &err = rs ? g_gilxr_err : xs ? g_gilxs_err : g_gilx_err;
+    const char *who = rs ? (xs ? "gilxsr_run" : "gilxr_run") : xs ? "gilxs_run" : prof ? "gilxp_run" : "gilx_run";
+    std::string &err = rs ? g_gilxr_err : xs ? g_gilxs_err : prof ? g_gilxp_err : g_gilx_err;
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilx_plan_info info; GilxTables tb;
     gilxs_plan_info sinfo{};
@@ -852,6 +910,11 @@ int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, cons
         info = gilx_plan_info{};
         info.threads = sinfo.threads; info.lds_bytes = sinfo.lds_bytes;
     } else if (int rc = gilx_decide(who, p, v, io.states(), info, tb, err)) return rc;
+    if (prof) {                                                // the profile slots behind the launch's layout: gilxp_plan's lds_bytes
+        int nt = 0; size_t with_slots = 0;
+        batch_shape(p->L, p->n_cap, tb.max_tlen, false, nt, with_slots, nullptr, nullptr, gilp_lds_bytes(prof->n_bins, prof->want_field != 0));
+        info.lds_bytes = (int32_t)with_slots;
+    }
     const int S = p->n_systems, V = v->n_variants, NT = info.threads;
     if (!rs) { const std::string why = gil_check_start(p, io, nullptr); if (!why.empty()) return bad(why); }
     if (const char *why = gil_check_flip_table(p)) return bad(why);
@@ -863,7 +926,8 @@ int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, cons
     OneShot job{who, err, true, GIL_ERR_NODEVICE, GIL_ERR_ARG, GIL_ERR_HIP};   // zero-fill: slots beyond n0 and rows never reached stay zero
     if (int rc = job.select_device(p->device)) return rc;
     if (xs) if (int rc = gil_refuse_device_bytes(job, sinfo.work_bytes, sinfo.output_bytes)) return rc;
-    GilxsrBatchArgs a{};                                        // the driver's one struct: every mixed launch's arguments are a base of it
+    if (prof) if (int rc = gil_refuse_device_bytes(job, (int64_t)S * 4, gilp_output_bytes(p, prof->n_groups, prof->n_bins, io.states(), prof->profile_obs != nullptr))) return rc;
+    GilxDriverArgs a{};                                         // the driver's one struct: every mixed launch's arguments are in it
     a.p = *p; a.p.sigma_grid = 0.0; a.p.block_table = nullptr;
     a.tlen = tb.max_tlen; a.chunk = (p->n_cap + NT - 1) / NT;    // the layout's table length; the kernel takes every system's own chunk
     a.m = gil_model(p);
@@ -883,14 +947,18 @@ int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, cons
         if (carried) { UP(wn.window, rs->xfrom->window, (size_t)S * 3 * xs->k_max); UP(wn.n_window, rs->xfrom->n_window, (size_t)S); UP(wn.n_empty, rs->xfrom->n_empty, (size_t)S); }
         else { WORK(wn.window, (size_t)S * 3 * xs->k_max); WORK(wn.n_window, (size_t)S); WORK(wn.n_empty, (size_t)S); }
     }
+    if (prof) if (int rc = gil_stage_profile(job, a, p, *prof)) return rc;   // sums and members are zero-filled
     if (int rc = job.create_events()) return rc;
     GilxrBatchArgs b{};                                         // gilxr_run's arguments: the mixed launch's own and the checkpoint
     static_cast<GilxBatchArgs &>(b) = a; b.rs = a.rs;
-    if (int rc = rs ? (xs ? gil_launch<GilKind::MixedStructureResume>(job, NT, S, lds, a) : gil_launch<GilKind::MixedResume>(job, NT, S, lds, b))
+    GilxpBatchArgs d{};                                         // gilxp_run's: the mixed launch's own and the profile's
+    static_cast<GilxBatchArgs &>(d) = a; d.pf = a.pf;
+    if (int rc = prof ? gil_launch<GilKind::MixedProfile>(job, NT, S, lds, d) : rs ? (xs ? gil_launch<GilKind::MixedStructureResume>(job, NT, S, lds, a) : gil_launch<GilKind::MixedResume>(job, NT, S, lds, b))
                     : (xs ? gil_launch<GilKind::MixedStructure>(job, NT, S, lds, a) : gil_launch<GilKind::Mixed>(job, NT, S, lds, a))) return rc;
     if (int rc = job.finish(hipGetLastError(), "gil_kernel (mixed)", io.kernel_ms)) return rc;
     if (int rc = gil_fetch_common(job, a, p, io)) return rc;
     if (rs) if (int rc = gil_fetch_checkpoint(job, *rs, p, a.rs.pos_out, a.rs.ref_out, a.rs.flg_out)) return rc;
+    if (prof) if (int rc = gil_fetch_profile(job, a, p, *prof)) return rc;
     if (xs) {
         if (int rc = gil_fetch_structure(job, a, p, xs->structure_obs)) return rc;
         if (int rc = job.download(xs->head_obs, a.wn.head, SO * 4 * 8, "head_obs")) return rc;
@@ -1013,6 +1081,38 @@ int gilxs_run(const gil_params *p, const gilx_variants *v, int32_t k_max, int32_
     const GilxsCall xs{k_max, first_obs, structure_obs, head_obs, window, n_window, n_empty};
     GilExtras ex; ex.xs = &xs;
     return mixed_run(p, v, io, ex);
+}
+
+const char *gilxp_last_error(void) { return g_gilxp_err.c_str(); }
+
+int gilxp_plan(const gil_params *p, const gilx_variants *v, int32_t n_bins, int32_t n_groups, int32_t first_obs, int32_t want_field,
+               int32_t want_states, int32_t want_per_system, gilxp_plan_info *out) {
+    if (!p || !v || !out) { g_gilxp_err = "gilxp_plan: null argument"; return GIL_ERR_ARG; }
+    int32_t some = 0;                                          // a plan has no buffers: only whether the per-system rows are wanted
+    const GilpCall c{nullptr, n_groups, n_bins, first_obs, want_field, nullptr, nullptr, want_per_system ? &some : nullptr};
+    gilxp_plan_info info;
+    if (int rc = gilxp_decide("gilxp_plan", p, v, c, want_states != 0, info)) return rc;
+    *out = info;
+    return GIL_OK;
+}
+
+int gilxp_run(const gil_params *p, const gilx_variants *v, int32_t n_bins, int32_t first_obs, int32_t want_field,
+              const int32_t *group_of_system, int32_t n_groups,
+              const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0, const double *uniforms,
+              int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
+              int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, int64_t *ensemble_sums, int32_t *members,
+              int32_t *profile_obs, double *kernel_ms) {
+    if (!p || !v || !n0 || !pos0 || !sigma0 || !p->beta || !p->times_obs || !v->variant_of_system || !ensemble_sums || !members) {
+        g_gilxp_err = "gilxp_run: null argument"; return GIL_ERR_ARG;
+    }
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    const GilpCall c{group_of_system, n_groups, n_bins, first_obs, want_field, ensemble_sums, members, profile_obs};
+    gilxp_plan_info info;
+    if (int rc = gilxp_decide("gilxp_run", p, v, c, io.states(), info)) return rc;
+    GilExtras ex; ex.prof = &c;
+    if (info.shape == GILS_SHAPE_BATCH) return mixed_run(p, v, io, ex);
+    ex.mx = v;
+    return gil_large_run("gilxp_run", g_gilxp_err, p, io, ex);
 }
 
 const char *gilp_last_error(void) { return g_gilp_err.c_str(); }

@@ -11,7 +11,9 @@ N > 2048, include/gillespie_mixed_many.h).  `sweep_betas_for_structures` / `swee
 taken on the GPU; `sweep_sigmas_for_structures` is that study over the interaction range, all (sigma, beta, run) systems in one mixed
 launch with the window reduction on the device (include/gillespie_mixed_structure.h).  `capture_study` is the anchor-capture study (PARTICLE_solver_CLASS.py:766-976) as an ensemble in one launch.
 `profile_sweep` gives the ensemble density and field profiles per beta (the means over runs of rho_plus_list, rho_minus_list,
-m_local_list, PARTICLE_solver_CLASS.py:205-213), all (beta, run) pairs in one launch and summed over the runs on the GPU."""
+m_local_list, PARTICLE_solver_CLASS.py:205-213), all (beta, run) pairs in one launch and summed over the runs on the GPU;
+`profile_sweep_over_sigmas` and `profile_sweep_over_densities` are that study over the interaction range and over the particle
+number, all systems in ONE mixed launch of either shape (include/gillespie_mixed_profile.h)."""
 from __future__ import annotations
 
 import warnings
@@ -430,3 +432,64 @@ def profile_sweep(beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwar
         rows = [observables.profile_observables([o for o, g in zip(outs, owner) if g == bi], n_bins, want_field, dx=systems[0].dx)
                 for bi in range(len(beta_values))]
     return {beta: rows[bi] for bi, beta in enumerate(beta_values)}
+
+
+def _profile_sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_kwargs, n_bins, rng_seeds, want_field, allow_large):
+    """The profile sweeps of `cases` = [(ps_kwargs, init_kwargs)] as ONE mixed launch (gillespie.run_batched_exact_profiles_mixed):
+    the systems are built in the order of the host loop over the cases, the ensemble group is (case, beta) and every case is a
+    group of `mixed_keys`, so each case draws what its own `profile_sweep` launch draws.  Returns [case][beta index] results."""
+    from . import gillespie
+    run_kwargs = dict(run_kwargs or {})
+    unknown = set(run_kwargs) - {"T", "obs_dt"}
+    if unknown:
+        raise ValueError(f"run_kwargs may hold T and obs_dt; got {sorted(unknown)}")
+    for ps_kwargs, _ in cases:
+        if _is_stepper(ps_kwargs, None):
+            raise ValueError(f"{who} needs the exact dynamics; the fixed-dt stepper has no mixed launch")
+    systems, group, key_group, B = [], [], [], len(beta_values)
+    for ci, (ps_kwargs, init_kwargs) in enumerate(cases):
+        for bi, beta in enumerate(beta_values):
+            for r in range(n_runs_per_beta):
+                rng = None if rng_seeds is None else np.random.default_rng(int(rng_seeds[bi][r]))
+                systems.append(ParticleSystem(beta=beta, rng=rng, **ps_kwargs, **init_kwargs))
+                group.append(ci * B + bi)
+                key_group.append(ci)
+    rows = gillespie.run_batched_exact_profiles_mixed(systems, n_bins=n_bins, groups=group, key_groups=key_group, want_field=want_field,
+                                                      allow_large=allow_large, **run_kwargs)
+    return [rows[ci * B:(ci + 1) * B] for ci in range(len(cases))]
+
+
+def profile_sweep_over_sigmas(sigma_values, beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwargs, n_bins, rng_seeds=None,
+                              want_field=False, one_launch=True, allow_large=False):
+    """`profile_sweep` for every interaction range `local_kernel_sigma` of `sigma_values`: {sigma: {beta: profiles}}, the particle
+    side of the comparison with pde.sweep_over_kernel_sigmas (the ensemble means of PARTICLE_solver_CLASS.py:205-213, :517-536
+    per width).  `one_launch=True`: all (sigma, beta, run) systems in ONE mixed launch that adds every run's bin counts to the sums
+    of its (sigma, beta) group (gillespie.run_batched_exact_profiles_mixed, include/gillespie_mixed_profile.h), with the draws and
+    hence the numbers of the loop over sigma.  `one_launch=False` is that host loop, one `profile_sweep` launch per sigma.
+    `allow_large=True` (with one_launch): a launch the library plans as a large shape (L > 4096, N > 2048, or profile slots that
+    do not fit beside the loop) runs on the large-system kernel instead of a ValueError; its numbers equal the host loop's where
+    every sigma's own launch is a large shape too, which is always so when L > 4096.  Exact dynamics only."""
+    kws = [dict(ps_kwargs or {}, local_kernel_sigma=float(sigma)) for sigma in sigma_values]
+    if one_launch:
+        rows = _profile_sweeps_in_one_launch("profile_sweep_over_sigmas", [(kw, dict(init_kwargs or {})) for kw in kws], beta_values,
+                                             n_runs_per_beta, run_kwargs, n_bins, rng_seeds, want_field, allow_large)
+        return {sigma: dict(zip(beta_values, rows[si])) for si, sigma in enumerate(sigma_values)}
+    return {sigma: profile_sweep(beta_values, n_runs_per_beta, kw, init_kwargs, run_kwargs, n_bins, rng_seeds, want_field)
+            for sigma, kw in zip(sigma_values, kws)}
+
+
+def profile_sweep_over_densities(n_part_values, beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwargs, n_bins, rng_seeds=None,
+                                 want_field=False, one_launch=True, allow_large=False):
+    """`profile_sweep` for every particle number of `n_part_values` (the density N / L, the route to the hydrodynamic limit):
+    {N: {beta: profiles}}.  `one_launch`, `allow_large`: as in profile_sweep_over_sigmas, the group being (N, beta) and every N a
+    group of `mixed_keys`; here a sweep straddles the limit when L <= 4096 and only some particle numbers exceed 2048."""
+    for n_part in n_part_values:
+        if float(n_part) != int(n_part):
+            raise ValueError("particle numbers must be integral")
+    iks = [dict(init_kwargs or {}, N=int(n_part)) for n_part in n_part_values]
+    if one_launch:
+        rows = _profile_sweeps_in_one_launch("profile_sweep_over_densities", [(dict(ps_kwargs or {}), ik) for ik in iks], beta_values,
+                                             n_runs_per_beta, run_kwargs, n_bins, rng_seeds, want_field, allow_large)
+        return {int(n_part): dict(zip(beta_values, rows[ni])) for ni, n_part in enumerate(n_part_values)}
+    return {int(n_part): profile_sweep(beta_values, n_runs_per_beta, ps_kwargs, ik, run_kwargs, n_bins, rng_seeds, want_field)
+            for n_part, ik in zip(n_part_values, iks)}

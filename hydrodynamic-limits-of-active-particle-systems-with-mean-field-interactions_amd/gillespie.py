@@ -10,7 +10,8 @@ the interaction range or in the blocking threshold of their particle number shar
 (`run_batched_exact_mixed`, `run_batched_exact_statistics_mixed`, include/gillespie_mixed.h; with `allow_large=True` also systems
 beyond one workgroup's LDS, include/gillespie_mixed_many.h); the structure observables of such a batch come from sums the
 mixed launch takes and reduces over the window on the device (`run_batched_exact_structure_mixed`,
-include/gillespie_mixed_structure.h).  A run may be cut into segments and resumed bit for bit (`Checkpoint`,
+include/gillespie_mixed_structure.h), and its ensemble profiles from sums the mixed launch adds per group, in either shape
+(`run_batched_exact_profiles_mixed`, include/gillespie_mixed_profile.h).  A run may be cut into segments and resumed bit for bit (`Checkpoint`,
 include/gillespie_resume.h), a mixed batch too (`MixedCheckpoint`, include/gillespie_mixed_resume.h).
 
 Differences to the reference: randomness is Philox4x32-10 keyed by `seed` (the reference consumes a NumPy Generator), so
@@ -82,6 +83,13 @@ class GilxmPlanInfo(C.Structure):
     """struct gilxm_plan_info of include/gillespie_mixed_many.h, field for field."""
     _fields_ = [("n_systems", C.c_int32), ("n_blocks", C.c_int32), ("max_tlen", C.c_int32), ("max_tlen_lds", C.c_int32),
                 ("n_global", C.c_int32), ("lds_bytes", C.c_int32), ("table_doubles", C.c_int64), ("work_bytes_per_system", C.c_int64),
+                ("output_bytes", C.c_int64)]
+
+
+class GilxpPlanInfo(C.Structure):
+    """struct gilxp_plan_info of include/gillespie_mixed_profile.h, field for field."""
+    _fields_ = [("shape", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32), ("max_tlen", C.c_int32),
+                ("bin_width", C.c_int32), ("n_bins_used", C.c_int32), ("table_doubles", C.c_int64), ("work_bytes", C.c_int64),
                 ("output_bytes", C.c_int64)]
 
 
@@ -208,6 +216,14 @@ def _stage_mixed(c, *, mixed, **_):
     return [C.byref(desc)], [], [], {}
 
 
+def _stage_mixed_profiles(c, *, mixed, n_bins, first_obs, want_field, group_of_system, n_groups, per_system, **_):
+    """the variants in front of gilp_run's five numbers; its three outputs behind the common ones"""
+    front = _stage_mixed(c, mixed=mixed)[0]
+    numbers, behind, tail, extra = _stage_profiles(c, n_bins=n_bins, first_obs=first_obs, want_field=want_field, group_of_system=group_of_system,
+                                                   n_groups=n_groups, per_system=per_system)
+    return front + numbers, behind, tail, extra
+
+
 def _stage_rows_and_head(c, k_max, first_obs, want_rows, sums):
     """What gilxs_run and gilxsr_run share: k_max and first_obs behind the variants, the rows (`want_rows`) and the head behind the
     common outputs; `sums` = the arrays of the window sums, which the two hand over differently."""
@@ -263,6 +279,8 @@ ENTRIES = {
     "gilx_run": _Entry("gilx_last_error", _stage_mixed, [_VAR]),   # a variant per system
     "gilxs_run": _Entry("gilxs_last_error", _stage_mixed_structure, [_VAR, _I32, _I32], [_PTR] * 5),
     "gilxm_run": _Entry("gilxm_last_error", _stage_mixed, [_VAR], header="include/gillespie_mixed_many.h"),   # the same, large systems
+    "gilxp_run": _Entry("gilxp_last_error", _stage_mixed_profiles, [_VAR, _I32, _I32, _I32, _PTR, _I32], [_PTR] * 3,
+                        header="include/gillespie_mixed_profile.h", finish=_profile_bins),   # a variant per system and the profiles, either shape
     # one segment of a mixed run: systems in LDS, large systems, systems in LDS with the structure sums
     "gilxr_run": _Entry("gilxr_last_error", _stage_mixed_resumable, [_VAR], tail=[_I32, _XCKP, _XCKP], header="include/gillespie_mixed_resume.h"),
     "gilxmr_run": _Entry("gilxr_last_error", _stage_mixed_resumable, [_VAR], tail=[_I32, _XCKP, _XCKP], header="include/gillespie_mixed_resume.h"),
@@ -278,6 +296,7 @@ PLANS = {
     "gilx_plan": ("gilx_last_error", [_VAR, _I32], GilxPlanInfo),
     "gilxs_plan": ("gilxs_last_error", [_VAR, _I32, _I32, _I32, _I32], capi.GilxsPlanInfo),
     "gilxm_plan": ("gilxm_last_error", [_VAR, _I32], GilxmPlanInfo),
+    "gilxp_plan": ("gilxp_last_error", [_VAR] + [_I32] * 6, GilxpPlanInfo),
 }
 # an older build named by APS_LIB (a timing yardstick) may lack any entry point but these
 EVERY_BUILD = ("gil_run_batch", "gil_run_large", "gilm_run", "gilm_plan", "gils_run", "gils_plan")
@@ -528,6 +547,33 @@ def run_mixed_many_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_d
     return _run_mixed_entry("gilxm_run", locals())
 
 
+def plan_mixed_profiles(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs, n_bins, n_groups=1, first_obs=0, want_field=False,
+                        variant_of_system=None, order=None, want_states=True, per_system=False):
+    """gilxp_plan: what a mixed launch with the ensemble profiles (`run_mixed_profiles_raw`) would use -- the shape (0: systems in
+    LDS, gilx_run's kernel; 1: large systems, gilxm_run's), threads per system, LDS of a workgroup (the mixed launch's for the
+    longest table plus the profile slots), that table's length, the bin width and the bins that hold sites, the doubles of all
+    tables, work and output bytes -- by host arithmetic; no device needed.  Refuses what the run would refuse on these numbers."""
+    return _plan("gilxp_plan", dict(L=L, K=K, periodic=periodic, n_systems=n_systems, n_cap=n_cap, n_obs=n_obs),
+                 [int(n_bins), int(n_groups), int(first_obs), int(want_field), int(bool(want_states)), int(bool(per_system))],
+                 dict(sigma_grids=sigma_grids, variant_of_system=variant_of_system, order=order))
+
+
+def run_mixed_profiles_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
+                           minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
+                           anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
+                           block_tables=None, device=0, flip_table=None, seeds=None, streams=None, order=None, n_cap=None, n_bins=None,
+                           first_obs=0, want_field=False, group_of_system=None, n_groups=None, per_system=False):
+    """`run_mixed_raw` with the bin counts of `run_profiles_raw` summed over the systems of a group in the same launch, every
+    system with its own variant's field (gilxp_run of include/gillespie_mixed_profile.h).  The library picks the kernel as
+    `plan_mixed_profiles` tells: `run_mixed_raw`'s or `run_mixed_many_raw`'s, and the defaults of `seeds` and `streams` are that
+    shape's.  A group may hold systems of different variants.  The dictionary of `run_mixed_raw` plus `ensemble_sums`, `members`,
+    `profile_obs` (when `per_system`), `bin_width` and `n_bins_used` of `run_profiles_raw`."""
+    n_bins = min(int(L), GILP_MAX_BINS) if n_bins is None else int(n_bins)
+    if n_groups is None:
+        n_groups = 1 if group_of_system is None else int(max(0, np.max(group_of_system))) + 1
+    return _run_mixed_entry("gilxp_run", locals())
+
+
 def plan_mixed_structure(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs, k_max, first_obs=0, variant_of_system=None,
                          order=None, want_states=True, want_rows=True):
     """gilxs_plan: what a mixed launch with the structure sums (`run_mixed_structure_raw`) would use -- threads per system, LDS of
@@ -602,8 +648,9 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     LDS), gilm_run (large systems), gils_run (either, with the structure sums: k_max, first_obs) and gilc_run (either, with the
     capture statistics: group_of_site, n_groups, c_bins, h_bins, h_dt, first_obs); gilp_run (either, with the ensemble profiles:
     n_bins, first_obs, want_field, group_of_system, n_groups, per_system); gilx_run (systems in LDS, a variant per system: `mixed`,
-    the keywords of _mixed_descriptor), gilxm_run (the same, large systems) and gilxs_run (the same with the structure sums: k_max,
-    first_obs, want_rows); gilr_run and gilrm_run (one segment of a run: obs_first, checkpoint); gilxr_run, gilxmr_run and
+    the keywords of _mixed_descriptor), gilxm_run (the same, large systems), gilxs_run (the same with the structure sums: k_max,
+    first_obs, want_rows) and gilxp_run (`mixed` with gilp_run's keywords, either shape); gilr_run and gilrm_run (one segment of a
+    run: obs_first, checkpoint); gilxr_run, gilxmr_run and
     gilxsr_run (one segment of a mixed run: `mixed`, obs_first, and a checkpoint that also has n_slots and, for gilxsr_run, the
     window sums)."""
     lib, row = _lib(), ENTRIES[entry]
@@ -1124,9 +1171,11 @@ class _MixedBatch:
     checks, the initial states (None on resume: no generator is consumed), then the slot counts and the shape, the refusal of a
     large shape without `allow_large`, and the keys -- those of `mixed_keys` (the large shape's for a large shape), on resume the
     checkpoint's, which must be what this batch would take where its systems state their seeds.  `structure` = (k_max or None,
-    start_fraction, want_rows, all_observations): the batch of run_batched_exact_structure_mixed, without states (no large shape)."""
+    start_fraction, want_rows, all_observations): the batch of run_batched_exact_structure_mixed, without states (no large shape).
+    `profiles` = the profile keywords of run_mixed_profiles_raw: the batch of run_batched_exact_profiles_mixed, without states; its
+    shape is the plan's (`plan_mixed_profiles`), asked before the keys are formed."""
 
-    def __init__(self, who, systems, T, obs_dt, groups, statistics, uniforms, order, structure, allow_large, resume, chained):
+    def __init__(self, who, systems, T, obs_dt, groups, statistics, uniforms, order, structure, allow_large, resume, chained, profiles=None):
         self.who, self.systems, self.T, self.statistics, self.uniforms, self.order, self.resume, self.chained = (
             who, systems, T, statistics, uniforms, order, resume, chained)
         first, self.inits, _ = _open_batch(who, systems, resume=resume, skip=("local_kernel_sigma",), anchors="their anchor sites", flip=True,
@@ -1134,6 +1183,7 @@ class _MixedBatch:
         self.first, self.mask = first, _anchor_mask(first.is_anchor_site, first.L)
         self.sig_sys = np.array([float(ps._sigma_grid) for ps in systems])
         self.k_max = self.first_obs = self.want_rows = self.tables = None
+        self.profiles = None if profiles is None else dict(profiles, want_states=False)
         if structure is not None:                              # the window is [first_obs, M) on the WHOLE grid of M observations
             k_max, start_fraction, self.want_rows, all_obs = structure
             self.k_max = first.L if k_max is None else min(int(k_max), first.L)
@@ -1142,6 +1192,12 @@ class _MixedBatch:
             self.n_live = [len(p) for p, _ in self.inits]
             self.n_cap = max(1, max(self.n_live))
             self.large = _large_shape(first.L, self.n_cap)
+            if self.profiles is not None:                      # the profile slots may push a batch-shape launch to the large shape
+                sig, _, owner = mixed_variants(self.sig_sys)
+                self.plan = plan_mixed_profiles(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems),
+                                                n_cap=self.n_cap, n_obs=len(np.arange(0.0, T, obs_dt)), variant_of_system=owner, order=order,
+                                                **{k: v for k, v in self.profiles.items() if k != "group_of_system"})
+                self.large = self.plan["shape"] == 1
         else:
             more = {} if structure is None else dict(k_max=self.k_max, first_obs=self.first_obs)
             resume.require(L=first.L, K=first.K, periodic=bool(first.periodic), anchor_mask=self.mask, n_systems=len(systems), obs_dt=float(obs_dt),
@@ -1172,7 +1228,9 @@ class _MixedBatch:
         sig, tabs, owner = mixed_variants(self.sig_sys, self.tables)
         shape = dict(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(self.systems), n_cap=self.n_cap, n_obs=n_obs,
                      variant_of_system=owner)
-        if self.k_max is not None:                             # a segment's plan takes the window's start within the segment
+        if self.profiles is not None:                          # the plan was asked when the batch was opened
+            kw = dict(self.profiles)
+        elif self.k_max is not None:                           # a segment's plan takes the window's start within the segment
             kw = dict(want_states=False, k_max=self.k_max, first_obs=self.first_obs, want_rows=self.want_rows)
             self.plan = plan_mixed_structure(**shape, **dict(kw, first_obs=min(self.first_obs, n_obs) if self.chained else self.first_obs))
         else:
@@ -1186,16 +1244,18 @@ class _MixedBatch:
 
 
 def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, order=None, structure=None, allow_large=False, *, resume=None,
-                  obs_range=None, return_checkpoint=False, obs_per_launch=None):
-    """The launch behind the three mixed functions: one launch of gilx_run / gilxm_run / gilxs_run or, with any of the four keywords,
+                  obs_range=None, return_checkpoint=False, obs_per_launch=None, profiles=None):
+    """The launch behind the four mixed functions: one launch of gilx_run / gilxm_run / gilxs_run / gilxp_run (`profiles`: the profile
+    keywords of run_mixed_profiles_raw) or, with any of the four keywords,
     a chain of gilxr_run / gilxmr_run / gilxsr_run (include/gillespie_mixed_resume.h).  Returns (raw outputs with `plan`,
     `obs_range`, `first_obs` and `k_max`, their observation times, the MixedCheckpoint at the end of a chain or None).  A structure
     chain's `head` and `structure` cover the range, its `window`, `n_window`, `n_empty` are the last checkpoint's."""
     chained = _chained(resume, obs_range, return_checkpoint, obs_per_launch)
-    b, ck = _MixedBatch(who, systems, T, obs_dt, groups, statistics, uniforms, order, structure, allow_large, resume, chained), None
+    b, ck = _MixedBatch(who, systems, T, obs_dt, groups, statistics, uniforms, order, structure, allow_large, resume, chained, profiles), None
     if not chained:
         times_obs = np.arange(0.0, T, obs_dt)
-        run_fn = run_mixed_structure_raw if structure is not None else run_mixed_many_raw if b.large else run_mixed_raw
+        run_fn = (run_mixed_structure_raw if structure is not None else run_mixed_profiles_raw if profiles is not None
+                  else run_mixed_many_raw if b.large else run_mixed_raw)
         r = dict(run_fn(states=b.inits, times_obs=times_obs, **b.keywords(times_obs, len(times_obs))), obs_range=(0, len(times_obs)))
     else:
         run_fn, more = (run_mixed_resumable_raw, dict(large=b.large)) if structure is None else (run_mixed_structure_resumable_raw, {})
@@ -1403,6 +1463,43 @@ def run_batched_exact_profiles(systems, T=10.0, obs_dt=0.01, n_bins=None, groups
     for g in range(n_groups):
         mine = np.flatnonzero(owner == g)
         prof = observables.DeviceProfiles(times_obs, L, first.dx, n_bins, r["ensemble_sums"][g], r["members"][g],
+                                          n_particles=[int(r["n0"][s]) for s in mine], k_exit=first.k_exit, want_field=want_field,
+                                          first_obs=first_obs).result()
+        if per_system:
+            prof["profile_obs"] = r["profile_obs"][mine]
+        out.append(prof)
+    for s, ps in enumerate(systems):
+        ps.n_events = int(r["n_events"][s])
+    first.kernel_ms = r["kernel_ms"]
+    return out
+
+
+def run_batched_exact_profiles_mixed(systems, T=10.0, obs_dt=0.01, n_bins=None, groups=None, key_groups=None, order=None, first_obs=0,
+                                     want_field=False, per_system=False, uniforms=None, allow_large=False, resume=None):
+    """`run_batched_exact_profiles` for systems that may ALSO differ in `local_kernel_sigma` (and, like there, in beta, state and
+    particle number): one mixed launch that adds every system's bin counts to its group's sums (include/gillespie_mixed_profile.h).
+    The other attributes, the anchor sites and the flip table must agree, as in run_batched_exact_mixed.  `groups[s]` is the
+    ensemble group system s adds to (None: one group); a group may hold systems of different ranges, but its members must start
+    with the same particle number.  `key_groups[s]` is the group of `mixed_keys`: the launch of the host loop whose numbers the
+    system draws (None: one launch); `order` as in run_batched_exact_mixed.  Returns one dict per ensemble group, in the order of
+    the group ids (observables.DeviceProfiles.result); `per_system=True` adds `profile_obs`.
+    The shape is the library's (`plan_mixed_profiles`): the kernel of systems in LDS where L <= 4096, N <= 2048 and the profile
+    slots fit beside the loop, else the large-system kernel, which needs `allow_large=True` (ValueError otherwise) and takes the
+    large shape's keys (`mixed_keys(..., large=True)`).  Profiles have no resumable form: `resume` is refused."""
+    who = "run_batched_exact_profiles_mixed"
+    _refuse_resume(who, resume)
+    from . import observables
+    first = systems[0]
+    n_bins = min(first.L, GILP_MAX_BINS) if n_bins is None else int(n_bins)
+    owner = np.zeros(len(systems), np.int32) if groups is None else np.asarray(groups, dtype=np.int32)
+    n_groups = int(owner.max()) + 1 if owner.size else 1
+    r, times_obs, _ = _mixed_launch(who, systems, T, obs_dt, key_groups, False, uniforms, order, allow_large=allow_large,
+                                    profiles=dict(n_bins=n_bins, first_obs=first_obs, want_field=want_field, group_of_system=owner,
+                                                  n_groups=n_groups, per_system=per_system))
+    out = []
+    for g in range(n_groups):
+        mine = np.flatnonzero(owner == g)
+        prof = observables.DeviceProfiles(times_obs, first.L, first.dx, n_bins, r["ensemble_sums"][g], r["members"][g],
                                           n_particles=[int(r["n0"][s]) for s in mine], k_exit=first.k_exit, want_field=want_field,
                                           first_obs=first_obs).result()
         if per_system:
