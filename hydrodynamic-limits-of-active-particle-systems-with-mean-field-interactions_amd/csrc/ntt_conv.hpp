@@ -56,19 +56,23 @@ inline uint32_t ntt_powmod(uint32_t b, unsigned long long e, uint32_t P) {
 // floor(x / P - 2^-10): never above the true quotient (floor: also for negative x), at most one below it for every product that
 // occurs here (|a| < 2^39, b < 2^32, P > 2^30.7: quotient below 2^40.3, three roundings of 2^-53 relative + the dropped low part
 // l / P < 2^-13 -> error below 2^-11 < 2^-10), so a remainder lies in [0, 2 P) without any correction step.
+// tests/ntt_lazy_arith.hip holds ntt_mul, ntt_red and a 128-point column of ntt_reg_levels to this contract on the host, against
+// 128-bit integers, at the inputs where the estimate is tightest (true remainders within 64 of 0 or of P at the top of the range).
+// Measured head room: that family still passes for |a| < 2^41 and first fails (negative results) below 2^42 -- two butterfly levels
+// beyond the contract, which stays 2^39 / 2^40.
 constexpr double NTT_BIAS = 0.0009765625;                        // 2^-10
 struct NttMod { double P, Pinv; };                               // the prime as a double and its reciprocal (rounded)
 // a * b mod P, lazy: |a| < 2^39, 0 <= b < 2^32 -> [0, 2 P).  Exact: a b = h + l with l from fma; h - q P is a small integer (fma again).
-__device__ __forceinline__ double ntt_mul(const double a, const double b, const NttMod md) {
+__host__ __device__ __forceinline__ double ntt_mul(const double a, const double b, const NttMod md) {
     const double h = a * b, l = fma(a, b, -h);
     const double q = floor(fma(h, md.Pinv, -NTT_BIAS));
     return fma(-q, md.P, h) + l;
 }
-__device__ __forceinline__ double ntt_red(const double v, const NttMod md) {   // v an integer, |v| < 2^40 -> [0, 2 P), congruent
+__host__ __device__ __forceinline__ double ntt_red(const double v, const NttMod md) {   // v an integer, |v| < 2^40 -> [0, 2 P), congruent
     const double q = floor(fma(v, md.Pinv, -NTT_BIAS));
     return fma(-q, md.P, v);
 }
-__device__ __forceinline__ uint32_t ntt_canon(const uint32_t v, const uint32_t P) { return v >= P ? v - P : v; }     // [0, 2 P) -> [0, P)
+__host__ __device__ __forceinline__ uint32_t ntt_canon(const uint32_t v, const uint32_t P) { return v >= P ? v - P : v; }     // [0, 2 P) -> [0, P)
 
 struct NttPrime {                          // the tables of one prime (device pointers)
     uint32_t P;
@@ -98,7 +102,7 @@ struct NttPlan {
 // N0: n is known to be zero (the second pass): the pairs with j = 0 need no product; otherwise every pair multiplies (w_R^0 = 1
 // for the rare n = j = 0: a branch per butterfly would cost more than the product)
 template <int B, bool N0>
-__device__ __forceinline__ void ntt_reg_levels(double (&x)[1 << B], const double *__restrict__ wtab, const int n, const int lo_shift, const int s0, const NttMod md) {
+__host__ __device__ __forceinline__ void ntt_reg_levels(double (&x)[1 << B], const double *__restrict__ wtab, const int n, const int lo_shift, const int s0, const NttMod md) {
     // a level at most doubles the magnitude of its values (sums and differences; a product is back in [0, 2 P))
 #pragma unroll
     for (int s = 0; s < B; ++s) {

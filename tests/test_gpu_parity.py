@@ -986,17 +986,20 @@ def test_fp32_windowed_sweep_dense_buckets(capi, periodic):
 
 
 @pytest.mark.parametrize("fp32", [True, False], ids=["i32", "f64"])
-@pytest.mark.parametrize("sigma,L,fused", [(0.02, 90000, "1"), (0.02, 90000, "0"), (0.004, 16000, "1"), (0.1, 120000, "1")],
-                         ids=["m17", "m17_five_launches", "m14_two_sweeps", "m18_beyond_lds"])
-def test_fp32_field_update_by_exact_convolution(capi, sigma, L, fused, fp32):
+@pytest.mark.parametrize("sigma,L,fused,log2_m", [(0.02, 90000, "1", (17, 17)), (0.02, 90000, "0", (17, 17)), (0.004, 16000, "1", (15, 15)),
+                                                  (0.1, 120000, "1", (18, 18))],
+                         ids=["m17", "m17_five_launches", "m15_short_table", "m18_beyond_lds"])
+def test_fp32_field_update_by_exact_convolution(capi, sigma, L, fused, log2_m, fp32):
     """csrc/ntt_conv.hpp: the step's deposits -> W, S of all sites by ONE number-theoretic convolution (mod 15 * 2^27 + 1, length
     2^m >= L + 2 reach, wall images entered as mirrored deposits) instead of the sweep -- exact integers, so state after every
     block and {W, S, occupancy} on ALL sites must equal the oracle's (which knows nothing of transforms) bit for bit.  Forced by
-    APS_NTT=1 for tables that fit LDS (the first two cases: transforms of three and of two sweeps); the third is beyond LDS and
-    takes the convolution by itself.  From m = 15 on the three middle launches are one (ntt_mid: a 128 x 128 slab per workgroup);
-    APS_NTT_FUSED=0 keeps the five launches, which m = 14 always takes.  Dense clusters at both walls and inside, K = 3, a thin
-    background.  f64: the binary64 field (integers below 2^51 in units of its 2^-q) by the same transform modulo two primes, put
-    together by the last sweep (Chinese remainder) -- from m = 15 on (the binary64 table of the second case is longer: m = 15)."""
+    APS_NTT=1 for tables that fit LDS (the first three cases); the last is beyond LDS and takes the convolution by itself.  From
+    m = 15 on the three middle launches are one (ntt_mid: a 128 x 128 slab per workgroup); APS_NTT_FUSED=0 keeps the five launches.
+    log2_m: the transform every case runs, (32-bit field, binary64 field) -- the short table of the third case gives 16000 + 2 * 256 =
+    16512 words, one slab past 2^14, so it runs m = 15 like any other; the transform of two sweeps (m = 14) and every other size
+    are cases of tests/ntt_cases.py.  Dense clusters at both walls and inside, K = 3, a thin background.  f64: the binary64 field
+    (integers below 2^51 in units of its 2^-q) by the same transform modulo two primes, put together by the last sweep (Chinese
+    remainder)."""
     par = params(L=L, K=3, sigma=sigma, rate_diffusion=3.0)
     rng = np.random.default_rng(2)
     sites = np.concatenate([rng.integers(L // 4, L // 4 + 1500, 2500), rng.integers(0, L, 1500), np.arange(L - 300, L), np.arange(0, 200)])
@@ -1015,7 +1018,8 @@ def test_fp32_field_update_by_exact_convolution(capi, sigma, L, fused, fp32):
     try:
         info = h.ntt_info()
         assert info["on"] and (1 << info["log2_m"]) >= L + 2 * (len(h.table()[0]) - 1), info
-        assert info["launches"] == (3 if fused == "1" and info["log2_m"] >= 15 else 5 if info["log2_m"] >= 15 else 3), info
+        assert info["log2_m"] == log2_m[0 if fp32 else 1] and info["blocks"] == 1, info
+        assert info["launches"] == (3 if fused == "1" else 5), info
         h.set_state(pos, spin)
         check_lattice(h, orc)
         for block, n in enumerate((1, 2, 37)):               # single steps and graph replay
