@@ -25,7 +25,8 @@ HDRS = [HDR, os.path.join(ROOT, "include", "pde.h"), os.path.join(ROOT, "include
         os.path.join(ROOT, "include", "gillespie_mixed_structure.h"), os.path.join(HERE, "csrc", "gillespie_window.hpp"),
         os.path.join(ROOT, "include", "gillespie_mixed_many.h"),
         os.path.join(ROOT, "include", "gillespie_resume.h"), os.path.join(HERE, "csrc", "gillespie_resume.hpp"),
-        os.path.join(ROOT, "include", "gillespie_mixed_resume.h"), os.path.join(ROOT, "include", "gillespie_mixed_profile.h")]
+        os.path.join(ROOT, "include", "gillespie_mixed_resume.h"), os.path.join(ROOT, "include", "gillespie_mixed_profile.h"),
+        os.path.join(ROOT, "include", "gillespie_profile_resume.h")]
 LIB = os.path.join(HERE, "libaps_hip.so")
 ARCH = "gfx950"
 

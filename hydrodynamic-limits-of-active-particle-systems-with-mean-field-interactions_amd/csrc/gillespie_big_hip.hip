@@ -1,5 +1,5 @@
 // gillespie_big_hip.hip -- gil_run_large of include/gillespie.h, gilm_run of include/gillespie_many.h, gilxm_run of
-// include/gillespie_mixed_many.h and the large shape of gils_run, gilc_run, gilp_run, gilrm_run, gilxmr_run and gilxp_run: the reference's
+// include/gillespie_mixed_many.h and the large shape of gils_run, gilc_run, gilp_run, gilrm_run, gilxmr_run, gilxp_run, gilpr_run and gilxpr_run: the reference's
 // exact event loop (PARTICLE_solver_CLASS.py:511-538) for systems far too large for a workgroup's LDS (the BASELINE size:
 // N = 1e5 particles on L = 2e5 sites, where the reference manages 0.8 events/s because it recomputes the whole
 // field and all N rates before every event).  One kernel and one host driver serve both entry points: a batch is a grid
@@ -248,6 +248,8 @@ __global__ __launch_bounds__(256) void big_field_init_mixed(const GilxBigArgs a0
 
 struct GilxrBigArgs : GilxBigArgs { GilrArgs rs; };         // arguments of the resumable mixed instantiation
 struct GilxpBigArgs : GilxBigArgs { GilpArgs pf; };         // arguments of the mixed profile instantiation (gilxp_run's large shape)
+struct GilprBigArgs : GilrBigArgs { GilpArgs pf; };         // arguments of the resumable profile instantiation (gilpr_run's large shape)
+struct GilxprBigArgs : GilxrBigArgs { GilpArgs pf; };       // arguments of the resumable mixed profile instantiation (gilxpr_run's)
 
 // From a checkpoint in a mixed launch: big_field_init_live with the system's own table, length and field mode
 __global__ __launch_bounds__(256) void big_field_init_live_mixed(const GilxBigArgs a0) {
@@ -269,6 +271,8 @@ template <> struct BigKernelArgs<GilKind::Resume> { using type = GilrBigArgs; };
 template <> struct BigKernelArgs<GilKind::Mixed> { using type = GilxBigArgs; };
 template <> struct BigKernelArgs<GilKind::MixedResume> { using type = GilxrBigArgs; };
 template <> struct BigKernelArgs<GilKind::MixedProfile> { using type = GilxpBigArgs; };
+template <> struct BigKernelArgs<GilKind::ProfileResume> { using type = GilprBigArgs; };
+template <> struct BigKernelArgs<GilKind::MixedProfileResume> { using type = GilxprBigArgs; };
 
 // V = the variant, a compile-time property, so that each kernel is the code it was before the others existed:
 //   Structure  also reduce the structure sums at an observation (gillespie_structure.hpp);
@@ -288,11 +292,16 @@ template <> struct BigKernelArgs<GilKind::MixedProfile> { using type = GilxpBigA
 //   MixedProfile  the ensemble profiles of a mixed launch (include/gillespie_mixed_profile.h): Mixed with the observation pass of
 //              Profile.  The group table, members and the per-system rows are indexed by the SYSTEM (mx_sys), the field mode is the
 //              one gilxm_select wrote, and the slots lie behind ctl[] of the launch's layout (tab_region).
+//   ProfileResume, MixedProfileResume  a resumable profile launch (include/gillespie_profile_resume.h): the start and end of
+//              Resume / MixedResume with the observation pass of Profile / MixedProfile over all N slots (it asks the flags).  The
+//              observations a resumed start records before its first event go through the same pass, with the checkpoint's state
+//              and the global mean rebuilt from its live flags; pf.first_obs and the group rows count within the launch's slice.
 template <GilKind V>
 __global__ __launch_bounds__(BT) void gil_big_kernel(const typename BigKernelArgs<V>::type a0) {
-    constexpr bool ST = V == GilKind::Structure, CP = V == GilKind::Capture, PF = V == GilKind::Profile || V == GilKind::MixedProfile;
-    constexpr bool RS = V == GilKind::Resume || V == GilKind::MixedResume;
-    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedResume || V == GilKind::MixedProfile;
+    constexpr bool ST = V == GilKind::Structure, CP = V == GilKind::Capture;
+    constexpr bool PF = V == GilKind::Profile || V == GilKind::MixedProfile || V == GilKind::ProfileResume || V == GilKind::MixedProfileResume;
+    constexpr bool RS = V == GilKind::Resume || V == GilKind::MixedResume || V == GilKind::ProfileResume || V == GilKind::MixedProfileResume;
+    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedResume || V == GilKind::MixedProfile || V == GilKind::MixedProfileResume;
     extern __shared__ double lds[];
     BigArgs a = a0;
     uint32_t stream = 0u;                                      // Philox counter word 2: the system's own with MX
@@ -845,17 +854,17 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
     WORK(pos, SN); WORK(occ, SL); WORK(occp, SL); WORK(slot, SL * p->K); WORK(work, SN); WORK(ref, SN);
     WORK(flg, SN); WORK(rate, SN); WORK(bsum, (size_t)S * a.nblk); WORK(W, SL); WORK(S, SL);
     const size_t lds = (size_t)info.lds_bytes;
-    GilrBigArgs b{};                                            // the resumable launch's arguments: a's own and the checkpoint
+    GilprBigArgs b{};                                           // the resumable launches' arguments: a's own, the checkpoint and (gilpr_run) the profile's
     int rc = ex.structure_obs ? gil_stage_structure(job, a, p, ex.k_max, ex.first_obs, true, false)
              : cap            ? gil_stage_capture(job, a, p, *cap, true)
-             : prof           ? gil_stage_profile(job, a, p, *prof)
-             : rs             ? gil_stage_checkpoint(job, b.rs, p, *rs, false) : 0;
+             : prof           ? gil_stage_profile(job, a, p, *prof) : 0;
     if (rc) return rc;
+    if (rs && (rc = gil_stage_checkpoint(job, b.rs, p, *rs, false))) return rc;
     if ((rc = job.create_events())) return rc;
-    static_cast<BigArgs &>(b) = a;
-    GilxrBigArgs c{};                                           // the mixed launch's arguments: a's own and the variants (and, resumable,
-    static_cast<BigArgs &>(c) = a;                              //   the checkpoint: GilxBigArgs is its base)
-    c.rs = b.rs;
+    static_cast<BigArgs &>(b) = a; b.pf = a.pf;
+    GilxprBigArgs c{};                                          // the mixed launch's arguments: a's own and the variants (and, resumable,
+    static_cast<BigArgs &>(c) = a;                              //   the checkpoint: GilxBigArgs is its base; gilxpr_run: the profile's too)
+    c.rs = b.rs; c.pf = a.pf;
     GilxpBigArgs d{};                                           // the mixed profile launch's: the mixed launch's own and the profile's (below)
     if (mx) {
         c.tab_region = xinfo.max_tlen_lds >= 0 ? ((xinfo.max_tlen_lds + 2) & ~1) : 0;
@@ -874,7 +883,9 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
     else hipLaunchKernelGGL(big_field_init, field_grid, dim3(256), 0, nullptr, static_cast<const BigArgs &>(a));
     rc = ex.structure_obs ? big_launch<GilKind::Structure>(job, S, lds, a)
          : cap            ? big_launch<GilKind::Capture>(job, S, lds, a)
+         : mx && prof && rs ? big_launch<GilKind::MixedProfileResume>(job, S, lds, c)
          : mx && prof     ? big_launch<GilKind::MixedProfile>(job, S, lds, d)
+         : prof && rs     ? big_launch<GilKind::ProfileResume>(job, S, lds, b)
          : prof           ? big_launch<GilKind::Profile>(job, S, lds, a)
          : mx && rs       ? big_launch<GilKind::MixedResume>(job, S, lds, c)
          : mx             ? big_launch<GilKind::Mixed>(job, S, lds, c)
@@ -885,7 +896,7 @@ int gil_large_run(const char *who, std::string &err, const gil_params *p, const 
     if (ex.structure_obs) rc = gil_fetch_structure(job, a, p, ex.structure_obs);
     else if (cap) rc = gil_fetch_capture(job, a, p, *cap);
     else if (prof) rc = gil_fetch_profile(job, a, p, *prof);
-    else if (rs) rc = gil_fetch_checkpoint(job, *rs, p, a.pos, a.ref, a.flg);
+    if (!rc && rs) rc = gil_fetch_checkpoint(job, *rs, p, a.pos, a.ref, a.flg);
     return rc ? rc : GIL_OK;
 }
 

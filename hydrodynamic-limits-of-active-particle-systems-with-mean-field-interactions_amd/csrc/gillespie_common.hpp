@@ -37,7 +37,8 @@ struct GilIo {
 // gilp_run's, the start state of gilr_run / gilrm_run (checked by gilr_prepare; it comes back as the end state), gilxs_run's call,
 // gilxm_run's variants (the large shape's mixed launch).  The resumable mixed launches (include/gillespie_mixed_resume.h) have
 // `rs` (checked by gilxr_prepare) next to `xs` or `mx`; gilxp_run (include/gillespie_mixed_profile.h) has `prof` in a mixed launch
-// (large shape: next to `mx`).
+// (large shape: next to `mx`).  The resumable profile launches (include/gillespie_profile_resume.h) have `prof` next to `rs`, the
+// mixed one in a mixed launch; prof->first_obs then counts within the segment's slice.
 struct GilExtras {
     int k_max = 0, first_obs = 0; double *structure_obs = nullptr;
     const GilcCall *cap = nullptr; const GilpCall *prof = nullptr; GilrCall *rs = nullptr; const GilxsCall *xs = nullptr;
@@ -46,7 +47,8 @@ struct GilExtras {
 
 // One enumerator per kernel variant that exists; a kernel family maps each of its own to an argument struct (GilKernelArgs in
 // gillespie_hip.hip, BigKernelArgs in gillespie_big_hip.hip), so a combination nobody wrote cannot be instantiated.
-enum class GilKind { Plain, Structure, Capture, Profile, Mixed, MixedStructure, Resume, MixedResume, MixedStructureResume, MixedProfile };
+enum class GilKind { Plain, Structure, Capture, Profile, Mixed, MixedStructure, Resume, MixedResume, MixedStructureResume, MixedProfile,
+                     ProfileResume, MixedProfileResume };
 
 namespace {
 

@@ -14,7 +14,8 @@
 //   E  t += tau; states / scalar sums of the observation times that were crossed go to HBM (ref :517-536)
 // Randomness: Philox4x32-10 keyed by the seed, counter (event index, system) -- or numbers supplied by the caller.
 // Host side: every extern "C" run function fills a GilIo and a GilExtras (gillespie_common.hpp) and calls batch_run, mixed_run or,
-// for the large shape, gil_large_run of gillespie_big_hip.hip (the resumable ones through gilr_drive / gilxr_drive); the drivers stage and fetch through the helpers of
+// for the large shape, gil_large_run of gillespie_big_hip.hip (the resumable ones, the profile segments of
+// include/gillespie_profile_resume.h among them, through gilr_drive / gilxr_drive); the drivers stage and fetch through the helpers of
 // gillespie_common.hpp, and gil_launch<V> is the one place that names a kernel instantiation.
 
 #include <hip/hip_runtime.h>
@@ -34,6 +35,7 @@
 #include "gillespie_mixed_profile.h"
 #include "gillespie_resume.h"
 #include "gillespie_mixed_resume.h"
+#include "gillespie_profile_resume.h"
 #include "aps_common.hpp"
 #include "gillespie_common.hpp"           // the call record, the variant tags, the staging path of the drivers
 #include "gillespie_structure.hpp"        // the structure sums of an observation (structure instantiations only)
@@ -85,6 +87,8 @@ struct GilxrBatchArgs : GilxBatchArgs { GilrArgs rs; };     // arguments of the 
 struct GilxsrBatchArgs : GilxsBatchArgs { GilrArgs rs; };   // arguments of the resumable mixed structure instantiations (gilxsr_run's)
 struct GilxpBatchArgs : GilxBatchArgs { GilpArgs pf; };     // arguments of the mixed profile instantiations (gilxp_run's)
 struct GilxDriverArgs : GilxsrBatchArgs { GilpArgs pf; };   // mixed_run's one struct: what every mixed launch takes is in it
+struct GilprBatchArgs : GilrBatchArgs { GilpArgs pf; };     // arguments of the resumable profile instantiations (gilpr_run's)
+struct GilxprBatchArgs : GilxrBatchArgs { GilpArgs pf; };   // arguments of the resumable mixed profile instantiations (gilxpr_run's)
 
 // the argument struct of each variant of the batch kernel
 template <GilKind V> struct GilKernelArgs;
@@ -98,6 +102,8 @@ template <> struct GilKernelArgs<GilKind::Resume> { using type = GilrBatchArgs; 
 template <> struct GilKernelArgs<GilKind::MixedResume> { using type = GilxrBatchArgs; };
 template <> struct GilKernelArgs<GilKind::MixedStructureResume> { using type = GilxsrBatchArgs; };
 template <> struct GilKernelArgs<GilKind::MixedProfile> { using type = GilxpBatchArgs; };
+template <> struct GilKernelArgs<GilKind::ProfileResume> { using type = GilprBatchArgs; };
+template <> struct GilKernelArgs<GilKind::MixedProfileResume> { using type = GilxprBatchArgs; };
 
 // the structure sums' slots: behind the loop's own LDS (which ends with the plus-occupancy bytes), at the next multiple of 8
 __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L) {
@@ -125,12 +131,18 @@ __device__ __forceinline__ double *gils_slots(double *lds, uint8_t *occp, int L)
 //   MixedProfile    the ensemble profiles of a mixed launch (include/gillespie_mixed_profile.h): Mixed with the observation pass of
 //                   Profile over the system's own slots (those beyond were never loaded) and with the system's own field mode;
 //                   the profile slots lie behind the launch's layout, which a.tlen = the longest table fixes.
+//   ProfileResume, MixedProfileResume  a resumable profile launch (include/gillespie_profile_resume.h): the start and end of
+//                   Resume / MixedResume with the observation pass of Profile / MixedProfile.  The observations a resumed start
+//                   records before its first event go through the same pass, with the checkpoint's state and the global mean
+//                   rebuilt from its live flags; pf.first_obs and the group rows count within the launch's slice (nobs rows).
 template <int NT, GilKind V>
 __global__ __launch_bounds__(NT) void gil_kernel(const typename GilKernelArgs<V>::type a) {
-    constexpr bool XR = V == GilKind::MixedResume || V == GilKind::MixedStructureResume;   // MX and RS together
+    constexpr bool XR = V == GilKind::MixedResume || V == GilKind::MixedStructureResume || V == GilKind::MixedProfileResume;   // MX and RS together
     constexpr bool ST = V == GilKind::Structure || V == GilKind::MixedStructure || V == GilKind::MixedStructureResume;
-    constexpr bool CP = V == GilKind::Capture, PF = V == GilKind::Profile || V == GilKind::MixedProfile;
-    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedStructure || V == GilKind::MixedProfile || XR, RS = V == GilKind::Resume || XR;
+    constexpr bool CP = V == GilKind::Capture;
+    constexpr bool PF = V == GilKind::Profile || V == GilKind::MixedProfile || V == GilKind::ProfileResume || V == GilKind::MixedProfileResume;
+    constexpr bool MX = V == GilKind::Mixed || V == GilKind::MixedStructure || V == GilKind::MixedProfile || XR;
+    constexpr bool RS = V == GilKind::Resume || V == GilKind::ProfileResume || XR;
     extern __shared__ double lds[];
     const Model &M = a.m;
     const GilxView vw = gilx_view<MX, NT>(a);                  // empty without MX
@@ -631,16 +643,17 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const GilI
     a.m = gil_model(p);
     if (int rc = gil_stage_common(job, a, p, io, table, (size_t)S * ncap, true, p->block_table, (size_t)(p->K + 1) * (p->K + 1))) return rc;
     if (lds > 160 * 1024) return bad("system does not fit the 160 KB of LDS");
-    GilrBatchArgs b{};                                          // the resumable launch's arguments: a's own and the checkpoint
+    GilprBatchArgs b{};                                         // the resumable launches' arguments: a's own, the checkpoint and (gilpr_run) the profile's
     int rc = ex.structure_obs ? gil_stage_structure(job, a, p, ex.k_max, ex.first_obs, true, phase_in_lds)
              : cap            ? gil_stage_capture(job, a, p, *cap, false)
-             : prof           ? gil_stage_profile(job, a, p, *prof)
-             : ex.rs          ? gil_stage_checkpoint(job, b.rs, p, *ex.rs, true) : 0;
+             : prof           ? gil_stage_profile(job, a, p, *prof) : 0;
     if (rc) return rc;
+    if (ex.rs && (rc = gil_stage_checkpoint(job, b.rs, p, *ex.rs, true))) return rc;
     if ((rc = job.create_events())) return rc;
-    static_cast<GilArgs &>(b) = a;
+    static_cast<GilArgs &>(b) = a; b.pf = a.pf;
     rc = ex.structure_obs ? gil_launch<GilKind::Structure>(job, NT, S, lds, a)
          : cap            ? gil_launch<GilKind::Capture>(job, NT, S, lds, a)
+         : prof && ex.rs  ? gil_launch<GilKind::ProfileResume>(job, NT, S, lds, b)
          : prof           ? gil_launch<GilKind::Profile>(job, NT, S, lds, a)
          : ex.rs          ? gil_launch<GilKind::Resume>(job, NT, S, lds, b) : gil_launch<GilKind::Plain>(job, NT, S, lds, a);
     if (rc) return rc;
@@ -649,24 +662,41 @@ int batch_run(const char *who, std::string &err, const gil_params *p, const GilI
     if (ex.structure_obs) rc = gil_fetch_structure(job, a, p, ex.structure_obs);
     else if (cap) rc = gil_fetch_capture(job, a, p, *cap);
     else if (prof) rc = gil_fetch_profile(job, a, p, *prof);
-    else if (ex.rs) rc = gil_fetch_checkpoint(job, *ex.rs, p, b.rs.pos_out, b.rs.ref_out, b.rs.flg_out);
+    if (!rc && ex.rs) rc = gil_fetch_checkpoint(job, *ex.rs, p, b.rs.pos_out, b.rs.ref_out, b.rs.flg_out);
     return rc ? rc : GIL_OK;
 }
 
-std::string g_gilr_err;
+std::string g_gilr_err, g_gilpr_err;
 
-// gilr_run and gilrm_run: the start state is checked and laid out here, the launch is the shape's own driver
+// defined with the profile plans below
+int gilp_decide(const char *who, const gil_params *p, const GilpCall &c, bool states, gilp_plan_info &info, std::string *err, bool byte_limit);
+int gilp_slice(std::string &err, const char *who, const GilpCall &run, int32_t obs_first, int32_t n_obs, GilpCall &slice);
+
+// gilr_run and gilrm_run: the start state is checked and laid out here, the launch is the shape's own driver.  With `prof`
+// (gilpr_run of include/gillespie_profile_resume.h; its first_obs is ABSOLUTE, errors go to g_gilpr_err) the launch also takes the
+// profiles of the slice and the shape is gilp_run's, whatever `large` says: the profile call's refusals, then the segment's, then
+// the plan's byte limit.
 int gilr_drive(bool large, const char *who, const gil_params *p, const GilIo &io, int32_t obs_first, const gil_checkpoint *from,
-               gil_checkpoint *to) {
-    auto bad = [&](const std::string &m) { g_gilr_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
-    if (!p || !p->beta || !p->times_obs || (!from && (!io.n0 || !io.pos0 || !io.sigma0))) return bad("null argument");
+               gil_checkpoint *to, const GilpCall *prof = nullptr) {
+    std::string &err = prof ? g_gilpr_err : g_gilr_err;
+    auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    if (!p || !p->beta || !p->times_obs || (!from && (!io.n0 || !io.pos0 || !io.sigma0)) || (prof && (!prof->ensemble_sums || !prof->members)))
+        return bad("null argument");
     if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0 || p->L < 2 || p->K < 1) return bad("bad n_systems / n_cap / n_obs / max_events / L / K");
     if (large && p->n_systems > GILM_MAX_SYSTEMS) return bad("n_systems must be in [1, GILM_MAX_SYSTEMS]");
     const size_t S = (size_t)p->n_systems;
+    GilpCall slice{};                                          // the profiles start at row first_obs - obs_first of this slice, within [0, n_obs]
+    gilp_plan_info pinfo{};
+    if (prof) {
+        if (int rc = gilp_slice(err, who, *prof, obs_first, p->n_obs, slice)) return rc;
+        if (int rc = gilp_decide(who, p, slice, io.states(), pinfo, &err, false)) return rc;
+        large = pinfo.shape == GILS_SHAPE_LARGE;
+    }
     if (!from) { const std::string why = gil_check_start(p, io, "n0 outside [0, n_cap]"); if (!why.empty()) return bad(why); }
     GilrCall call;
     const std::string why = gilr_prepare(p, io.n0, io.pos0, io.sigma0, io.bound0, obs_first, from, to, call);
     if (!why.empty()) return bad(why);
+    if (prof) if (int rc = gil_refuse_plan_bytes(who, err, pinfo.work_bytes, pinfo.output_bytes)) return rc;
     std::vector<int32_t> nrec(S, 0);                           // the checkpoint needs these three whether or not the caller wants them
     std::vector<int64_t> nev(S, 0);
     std::vector<double> tfin(S, 0.0);
@@ -674,7 +704,8 @@ int gilr_drive(bool large, const char *who, const gil_params *p, const GilIo &io
     run.n0 = run.pos0 = nullptr; run.sigma0 = nullptr; run.bound0 = nullptr;
     run.n_recorded = nrec.data(); run.n_events = nev.data(); run.t_final = tfin.data();
     GilExtras ex; ex.rs = &call;
-    if (int rc = large ? gil_large_run(who, g_gilr_err, p, run, ex) : batch_run(who, g_gilr_err, p, run, ex)) return rc;
+    if (prof) ex.prof = &slice;
+    if (int rc = large ? gil_large_run(who, err, p, run, ex) : batch_run(who, err, p, run, ex)) return rc;
     gilr_finish(p, call, nrec.data(), nev.data(), tfin.data());
     for (size_t s = 0; s < S; ++s) {
         if (io.n_recorded) io.n_recorded[s] = nrec[s];
@@ -775,20 +806,36 @@ std::string gilp_check_call(const gil_params *p, const GilpCall &c) {
     return "";
 }
 
-int gilp_decide(const char *who, const gil_params *p, const GilpCall &c, bool states, gilp_plan_info &info) {
-    auto bad = [&](const std::string &m) { g_gilp_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+// `err`: where the text goes (null: g_gilp_err); byte_limit false: the caller asks gil_refuse_plan_bytes itself, after checks of
+// its own (a segment's)
+int gilp_decide(const char *who, const gil_params *p, const GilpCall &c, bool states, gilp_plan_info &info, std::string *err = nullptr,
+                bool byte_limit = true) {
+    std::string &text = err ? *err : g_gilp_err;
+    auto bad = [&](const std::string &m) { text = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     if (const char *why = gil_check_plan_params(p)) return bad(why);
     { const std::string why = gilp_check_call(p, c); if (!why.empty()) return bad(why); }
     const size_t prof_lds = gilp_lds_bytes(c.n_bins, c.want_field != 0);
     GilShape sh;
-    if (int rc = gil_choose_shape(who, g_gilp_err, p, false, nullptr, prof_lds, (int32_t)prof_lds, sh)) return rc;
+    if (int rc = gil_choose_shape(who, text, p, false, nullptr, prof_lds, (int32_t)prof_lds, sh)) return rc;
     info = gilp_plan_info{};
     info.bin_width = (p->L + c.n_bins - 1) / c.n_bins;
     info.n_bins_used = (p->L + info.bin_width - 1) / info.bin_width;
     info.output_bytes = gilp_output_bytes(p, c.n_groups, c.n_bins, states, c.profile_obs != nullptr);
     info.shape = sh.shape; info.threads = sh.threads; info.lds_bytes = sh.lds_bytes;
     info.work_bytes = sh.large_work + (int64_t)p->n_systems * 4;
-    return gil_refuse_plan_bytes(who, g_gilp_err, info.work_bytes, info.output_bytes);
+    return byte_limit ? gil_refuse_plan_bytes(who, text, info.work_bytes, info.output_bytes) : GIL_OK;
+}
+
+// The profile call of one segment (include/gillespie_profile_resume.h) from the run's: first_obs is absolute there and counts
+// within the slice here, clamp(first_obs - obs_first, 0, n_obs).  0, or GIL_ERR_ARG with the text in `err`.
+int gilp_slice(std::string &err, const char *who, const GilpCall &run, int32_t obs_first, int32_t n_obs, GilpCall &slice) {
+    if (run.first_obs < 0) {
+        err = std::string(who) + ": first_obs = " + std::to_string(run.first_obs) + " must not be negative: it is an index on the run's observation grid";
+        return GIL_ERR_ARG;
+    }
+    slice = run;
+    slice.first_obs = (int)std::min<int64_t>(std::max<int64_t>((int64_t)run.first_obs - obs_first, 0), std::max(n_obs, 0));
+    return GIL_OK;
 }
 
 std::string g_gilx_err;
@@ -854,15 +901,18 @@ std::string g_gilxp_err;
 // The mixed launch's refusals first (gilx_decide's where the batch shape takes the launch, else gilxm_decide's), then
 // gilp_decide's.  The shape rule is gilp_run's with the longest table of the batch: the batch shape where gilx_run takes the
 // launch and the profile slots fit the 160 KB behind it, else the large shape.
-int gilxp_decide(const char *who, const gil_params *p, const gilx_variants *v, const GilpCall &c, bool states, gilxp_plan_info &info) {
-    auto bad = [&](const std::string &m) { g_gilxp_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+// `err`, byte_limit: as in gilp_decide.
+int gilxp_decide(const char *who, const gil_params *p, const gilx_variants *v, const GilpCall &c, bool states, gilxp_plan_info &info,
+                 std::string *err = nullptr, bool byte_limit = true) {
+    std::string &text = err ? *err : g_gilxp_err;
+    auto bad = [&](const std::string &m) { text = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilx_plan_info xi{}; GilxTables tb;
-    bool batch = p->L <= GIL_MAX_L && p->n_cap <= GIL_MAX_N && gilx_decide(who, p, v, states, xi, tb, g_gilxp_err) == GIL_OK;
+    bool batch = p->L <= GIL_MAX_L && p->n_cap <= GIL_MAX_N && gilx_decide(who, p, v, states, xi, tb, text) == GIL_OK;
     int32_t large_lds = 0, large_tlen = 0; int64_t large_work = 0, large_doubles = 0;
     bool planned_large = false;
     auto plan_large = [&]() {                                  // the profile slots enter once the call's numbers are checked
         planned_large = true;
-        return gil_large_mixed_plan(who, g_gilxp_err, p, v, states, 0, &large_lds, &large_work, &large_tlen, &large_doubles);
+        return gil_large_mixed_plan(who, text, p, v, states, 0, &large_lds, &large_work, &large_tlen, &large_doubles);
     };
     if (!batch) if (int rc = plan_large()) return rc;
     { const std::string why = gilp_check_call(p, c); if (!why.empty()) return bad(why); }
@@ -888,20 +938,20 @@ int gilxp_decide(const char *who, const gil_params *p, const gilx_variants *v, c
             return bad("the launch needs " + std::to_string(info.lds_bytes) + " bytes of LDS per system with the profile slots (n_bins = " +
                        std::to_string(c.n_bins) + "), more than the " + std::to_string(160 * 1024) + " bytes (160 KB) of a workgroup");
     }
-    return gil_refuse_plan_bytes(who, g_gilxp_err, info.work_bytes, info.output_bytes);
+    return byte_limit ? gil_refuse_plan_bytes(who, text, info.work_bytes, info.output_bytes) : GIL_OK;
 }
 
 // gilx_run's driver, with ex.xs gilxs_run's and with ex.prof gilxp_run's (batch shape; gilxp_decide has accepted the call): the
 // variant tables, the launch order, the seeds and streams and the window outputs are its own, the rest is the staging path
-// batch_run takes.  With ex.rs (gilxr_run, gilxsr_run) the launch is a segment:
+// batch_run takes.  With ex.rs (gilxr_run, gilxsr_run; with ex.prof as well gilxpr_run, whose first_obs counts within the slice) the launch is a segment:
 // the start state, the slot counts and the window sums so far are the checkpoint's (gilxr_prepare has checked them), no start
 // state is read from io, and xs->first_obs counts within the slice.
 int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, const GilExtras &ex) {
     const GilxsCall *xs = ex.xs;
     const GilpCall *prof = ex.prof;
     GilrCall *rs = ex.rs;
-    const char *who = rs ? (xs ? "gilxsr_run" : "gilxr_run") : xs ? "gilxs_run" : prof ? "gilxp_run" : "gilx_run";
-    std::string &err = rs ? g_gilxr_err : xs ? g_gilxs_err : prof ? g_gilxp_err : g_gilx_err;
+    const char *who = rs ? (xs ? "gilxsr_run" : prof ? "gilxpr_run" : "gilxr_run") : xs ? "gilxs_run" : prof ? "gilxp_run" : "gilx_run";
+    std::string &err = rs ? (prof ? g_gilpr_err : g_gilxr_err) : xs ? g_gilxs_err : prof ? g_gilxp_err : g_gilx_err;
     auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
     gilx_plan_info info; GilxTables tb;
     gilxs_plan_info sinfo{};
@@ -953,7 +1003,9 @@ int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, cons
     static_cast<GilxBatchArgs &>(b) = a; b.rs = a.rs;
     GilxpBatchArgs d{};                                         // gilxp_run's: the mixed launch's own and the profile's
     static_cast<GilxBatchArgs &>(d) = a; d.pf = a.pf;
-    if (int rc = prof ? gil_launch<GilKind::MixedProfile>(job, NT, S, lds, d) : rs ? (xs ? gil_launch<GilKind::MixedStructureResume>(job, NT, S, lds, a) : gil_launch<GilKind::MixedResume>(job, NT, S, lds, b))
+    GilxprBatchArgs e{};                                        // gilxpr_run's: gilxr_run's and the profile's
+    static_cast<GilxrBatchArgs &>(e) = b; e.pf = a.pf;
+    if (int rc = prof && rs ? gil_launch<GilKind::MixedProfileResume>(job, NT, S, lds, e) : prof ? gil_launch<GilKind::MixedProfile>(job, NT, S, lds, d) : rs ? (xs ? gil_launch<GilKind::MixedStructureResume>(job, NT, S, lds, a) : gil_launch<GilKind::MixedResume>(job, NT, S, lds, b))
                     : (xs ? gil_launch<GilKind::MixedStructure>(job, NT, S, lds, a) : gil_launch<GilKind::Mixed>(job, NT, S, lds, a))) return rc;
     if (int rc = job.finish(hipGetLastError(), "gil_kernel (mixed)", io.kernel_ms)) return rc;
     if (int rc = gil_fetch_common(job, a, p, io)) return rc;
@@ -971,18 +1023,35 @@ int mixed_run(const gil_params *p, const gilx_variants *v, const GilIo &io, cons
 
 // gilxr_run, gilxmr_run (large) and gilxsr_run (xs: k_max, the ABSOLUTE first_obs, structure_obs, head_obs; its window outputs are
 // filled in here): the start state is checked and laid out here (gilxr_prepare), the launch is the shape's own mixed driver
+// With `prof` (gilxpr_run of include/gillespie_profile_resume.h; its first_obs is ABSOLUTE, errors go to g_gilpr_err) the launch
+// also takes the profiles of the slice and the shape is the mixed profile plan's, whatever `large` says: the mixed launch's
+// refusals, then the profile call's, then the segment's, then the plan's byte limit.
 int gilxr_drive(bool large, const char *who, const gil_params *p, const gilx_variants *v, const GilIo &io, const GilxsCall *xs,
-                int32_t obs_first, const gilx_checkpoint *from, gilx_checkpoint *to) {
-    auto bad = [&](const std::string &m) { g_gilxr_err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
-    if (!p || !v || !p->beta || !p->times_obs || !v->variant_of_system || (!from && (!io.n0 || !io.pos0 || !io.sigma0)) || (xs && !xs->head_obs))
+                int32_t obs_first, const gilx_checkpoint *from, gilx_checkpoint *to, const GilpCall *prof = nullptr) {
+    std::string &err = prof ? g_gilpr_err : g_gilxr_err;
+    auto bad = [&](const std::string &m) { err = std::string(who) + ": " + m; return GIL_ERR_ARG; };
+    if (!p || !v || !p->beta || !p->times_obs || !v->variant_of_system || (!from && (!io.n0 || !io.pos0 || !io.sigma0)) || (xs && !xs->head_obs) ||
+        (prof && (!prof->ensemble_sums || !prof->members)))
         return bad("null argument");
     if (p->n_systems < 1 || p->n_cap < 1 || p->n_obs < 1 || p->max_events < 0 || p->L < 2 || p->K < 1) return bad("bad n_systems / n_cap / n_obs / max_events / L / K");
     const size_t S = (size_t)p->n_systems;
     if (xs && xs->first_obs < 0) return bad("first_obs = " + std::to_string(xs->first_obs) + " must not be negative: it is an index on the run's observation grid");
+    GilpCall pslice{};                                         // the profiles start at row first_obs - obs_first of this slice, within [0, n_obs]
+    gilxp_plan_info pinfo{};
+    if (prof) {
+        if (int rc = gilp_slice(err, who, *prof, obs_first, p->n_obs, pslice)) return rc;
+        if (int rc = gilxp_decide(who, p, v, pslice, io.states(), pinfo, &err, false)) return rc;
+        large = pinfo.shape == GILS_SHAPE_LARGE;
+        for (const gilx_checkpoint *c : {from, (const gilx_checkpoint *)to})
+            if (c && (c->window || c->n_window || c->n_empty))
+                return bad(std::string("the checkpoint `") + (c == from ? "from" : "to") + "` has " + (c->window ? "window" : c->n_window ? "n_window" : "n_empty") +
+                           " set: a profile launch carries no window sums, the three must be NULL");
+    }
     if (!from) { const std::string why = gil_check_start(p, io, nullptr); if (!why.empty()) return bad(why); }
     GilrCall call;
     const std::string why = gilxr_prepare(p, xs ? xs->k_max : 0, io.n0, io.pos0, io.sigma0, io.bound0, obs_first, from, to, call);
     if (!why.empty()) return bad(why);
+    if (prof) if (int rc = gil_refuse_plan_bytes(who, err, pinfo.work_bytes, pinfo.output_bytes)) return rc;
     std::vector<int32_t> nrec(S, 0);                           // the checkpoint needs these three whether or not the caller wants them
     std::vector<int64_t> nev(S, 0);
     std::vector<double> tfin(S, 0.0);
@@ -997,8 +1066,9 @@ int gilxr_drive(bool large, const char *who, const gil_params *p, const gilx_var
         slice.window = to ? to->window : nullptr; slice.n_window = to ? to->n_window : nullptr; slice.n_empty = to ? to->n_empty : nullptr;
         ex.xs = &slice;
     }
+    if (prof) ex.prof = &pslice;
     if (large) ex.mx = v;
-    if (int rc = large ? gil_large_run(who, g_gilxr_err, p, run, ex) : mixed_run(p, v, run, ex)) return rc;
+    if (int rc = large ? gil_large_run(who, err, p, run, ex) : mixed_run(p, v, run, ex)) return rc;
     gilxr_finish(p, call, nrec.data(), nev.data(), tfin.data());
     for (size_t s = 0; s < S; ++s) {
         if (io.n_recorded) io.n_recorded[s] = nrec[s];
@@ -1140,6 +1210,29 @@ int gilp_run(const gil_params *p, int32_t n_bins, int32_t first_obs, int32_t wan
     if (int rc = gilp_decide("gilp_run", p, c, io.states(), info)) return rc;
     GilExtras ex; ex.prof = &c;
     return info.shape == GILS_SHAPE_BATCH ? batch_run("gilp_run", g_gilp_err, p, io, ex) : gil_large_run("gilp_run", g_gilp_err, p, io, ex);
+}
+
+const char *gilpr_last_error(void) { return g_gilpr_err.c_str(); }
+
+int gilpr_run(const gil_params *p, int32_t n_bins, int32_t first_obs, int32_t want_field, const int32_t *group_of_system, int32_t n_groups,
+              const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0, const double *uniforms,
+              int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
+              int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, int64_t *ensemble_sums, int32_t *members,
+              int32_t *profile_obs, double *kernel_ms, int32_t obs_first, const gil_checkpoint *from, gil_checkpoint *to) {
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    const GilpCall c{group_of_system, n_groups, n_bins, first_obs, want_field, ensemble_sums, members, profile_obs};
+    return gilr_drive(false, "gilpr_run", p, io, obs_first, from, to, &c);
+}
+
+int gilxpr_run(const gil_params *p, const gilx_variants *v, int32_t n_bins, int32_t first_obs, int32_t want_field,
+               const int32_t *group_of_system, int32_t n_groups,
+               const int32_t *n0, const int32_t *pos0, const int8_t *sigma0, const uint8_t *bound0, const double *uniforms,
+               int32_t *pos_obs, int8_t *sigma_obs, uint8_t *flags_obs, int64_t *scalars_obs, int32_t *n_recorded,
+               int64_t *n_events, double *t_final, double *exits, int32_t *n_exits, int64_t *ensemble_sums, int32_t *members,
+               int32_t *profile_obs, double *kernel_ms, int32_t obs_first, const gilx_checkpoint *from, gilx_checkpoint *to) {
+    const GilIo io{n0, pos0, sigma0, bound0, uniforms, pos_obs, sigma_obs, flags_obs, scalars_obs, n_recorded, n_events, t_final, exits, n_exits, kernel_ms};
+    const GilpCall c{group_of_system, n_groups, n_bins, first_obs, want_field, ensemble_sums, members, profile_obs};
+    return gilxr_drive(false, "gilxpr_run", p, v, io, nullptr, obs_first, from, to, &c);
 }
 
 const char *gilc_last_error(void) { return g_gilc_err.c_str(); }

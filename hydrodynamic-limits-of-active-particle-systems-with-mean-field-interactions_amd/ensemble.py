@@ -404,7 +404,7 @@ def capture_study(ps_kwargs, init_kwargs, n_runs, run_kwargs, rng_seeds=None, on
 
 
 def profile_sweep(beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwargs, n_bins, rng_seeds=None, want_field=False,
-                  on_device=True):
+                  on_device=True, obs_per_launch=None, resume=None, return_checkpoint=False):
     """Space-time profiles per beta under the exact dynamics: {beta: observables.DeviceProfiles.result()} -- per observation and
     bin the mean and standard error over the runs of the plus, minus, total and signed counts, the reference's densities
     `rho_plus`, `rho_minus`, `rho_total` (count / (N bin_sites dx)) and, with `want_field`, the mean field `field_mean`.  All
@@ -413,9 +413,15 @@ def profile_sweep(beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwar
 
     on_device=True (gillespie.run_batched_exact_profiles): the event loop adds every run's bin counts to its beta's sums, and
     [betas][observations][7][n_bins] integers leave the GPU.  on_device=False (gillespie.run_batched_exact +
-    observables.profile_observables): the same keys from the full state outputs, a bincount per run and observation on the host."""
+    observables.profile_observables): the same keys from the full state outputs, a bincount per run and observation on the host.
+    `obs_per_launch=n`, `resume=ProfileCheckpoint`, `return_checkpoint=True` (on_device only): the one launch as a chain of launches
+    of at most n observations, started from a checkpoint of the same sweep, and returning (results, checkpoint)
+    (gillespie.run_batched_exact_profiles, include/gillespie_profile_resume.h); the numbers are the one launch's, bit for bit."""
     from . import gillespie
     ps_kwargs, init_kwargs, run_kwargs = dict(ps_kwargs or {}), dict(init_kwargs or {}), dict(run_kwargs or {})
+    chain = _chain_keywords("profile_sweep", True, _is_stepper(ps_kwargs, None), obs_per_launch, resume, return_checkpoint)
+    if chain and not on_device:
+        raise ValueError("profile_sweep: the chain keywords need on_device=True; the host route has no checkpointed profile launch")
     unknown = set(run_kwargs) - {"T", "obs_dt"}
     if unknown:
         raise ValueError(f"run_kwargs may hold T and obs_dt; got {sorted(unknown)}")
@@ -426,20 +432,24 @@ def profile_sweep(beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwar
             systems.append(ParticleSystem(beta=beta, rng=rng, **ps_kwargs, **init_kwargs))
             owner.append(bi)
     if on_device:
-        rows = gillespie.run_batched_exact_profiles(systems, n_bins=n_bins, groups=owner, want_field=want_field, **run_kwargs)
+        rows = gillespie.run_batched_exact_profiles(systems, n_bins=n_bins, groups=owner, want_field=want_field, **run_kwargs, **chain)
+        if return_checkpoint:
+            rows, ck = rows
     else:
         outs = gillespie.run_batched_exact(systems, want_m_local=want_field, **run_kwargs)
         rows = [observables.profile_observables([o for o, g in zip(outs, owner) if g == bi], n_bins, want_field, dx=systems[0].dx)
                 for bi in range(len(beta_values))]
-    return {beta: rows[bi] for bi, beta in enumerate(beta_values)}
+    res = {beta: rows[bi] for bi, beta in enumerate(beta_values)}
+    return (res, ck) if return_checkpoint else res
 
 
-def _profile_sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_kwargs, n_bins, rng_seeds, want_field, allow_large):
+def _profile_sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_kwargs, n_bins, rng_seeds, want_field, allow_large, chain=None):
     """The profile sweeps of `cases` = [(ps_kwargs, init_kwargs)] as ONE mixed launch (gillespie.run_batched_exact_profiles_mixed):
     the systems are built in the order of the host loop over the cases, the ensemble group is (case, beta) and every case is a
-    group of `mixed_keys`, so each case draws what its own `profile_sweep` launch draws.  Returns [case][beta index] results."""
+    group of `mixed_keys`, so each case draws what its own `profile_sweep` launch draws.  Returns [case][beta index] results.
+    `chain` (_chain_keywords): the launch in segments; with its return_checkpoint the result is (the list, the MixedProfileCheckpoint)."""
     from . import gillespie
-    run_kwargs = dict(run_kwargs or {})
+    run_kwargs, chain = dict(run_kwargs or {}), dict(chain or {})
     unknown = set(run_kwargs) - {"T", "obs_dt"}
     if unknown:
         raise ValueError(f"run_kwargs may hold T and obs_dt; got {sorted(unknown)}")
@@ -455,12 +465,16 @@ def _profile_sweeps_in_one_launch(who, cases, beta_values, n_runs_per_beta, run_
                 group.append(ci * B + bi)
                 key_group.append(ci)
     rows = gillespie.run_batched_exact_profiles_mixed(systems, n_bins=n_bins, groups=group, key_groups=key_group, want_field=want_field,
-                                                      allow_large=allow_large, **run_kwargs)
-    return [rows[ci * B:(ci + 1) * B] for ci in range(len(cases))]
+                                                      allow_large=allow_large, **run_kwargs, **chain)
+    ck = None
+    if chain.get("return_checkpoint"):
+        rows, ck = rows
+    per_case = [rows[ci * B:(ci + 1) * B] for ci in range(len(cases))]
+    return (per_case, ck) if chain.get("return_checkpoint") else per_case
 
 
 def profile_sweep_over_sigmas(sigma_values, beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwargs, n_bins, rng_seeds=None,
-                              want_field=False, one_launch=True, allow_large=False):
+                              want_field=False, one_launch=True, allow_large=False, obs_per_launch=None, resume=None, return_checkpoint=False):
     """`profile_sweep` for every interaction range `local_kernel_sigma` of `sigma_values`: {sigma: {beta: profiles}}, the particle
     side of the comparison with pde.sweep_over_kernel_sigmas (the ensemble means of PARTICLE_solver_CLASS.py:205-213, :517-536
     per width).  `one_launch=True`: all (sigma, beta, run) systems in ONE mixed launch that adds every run's bin counts to the sums
@@ -468,28 +482,41 @@ def profile_sweep_over_sigmas(sigma_values, beta_values, n_runs_per_beta, ps_kwa
     hence the numbers of the loop over sigma.  `one_launch=False` is that host loop, one `profile_sweep` launch per sigma.
     `allow_large=True` (with one_launch): a launch the library plans as a large shape (L > 4096, N > 2048, or profile slots that
     do not fit beside the loop) runs on the large-system kernel instead of a ValueError; its numbers equal the host loop's where
-    every sigma's own launch is a large shape too, which is always so when L > 4096.  Exact dynamics only."""
+    every sigma's own launch is a large shape too, which is always so when L > 4096.  Exact dynamics only.
+    `obs_per_launch=n`, `resume=MixedProfileCheckpoint`, `return_checkpoint=True` (with one_launch): the one launch as a chain of
+    launches of at most n observations, started from a checkpoint of the same sweep, and returning (results, checkpoint)
+    (gillespie.run_batched_exact_profiles_mixed); the numbers are the one launch's, bit for bit.  ValueError without one_launch."""
     kws = [dict(ps_kwargs or {}, local_kernel_sigma=float(sigma)) for sigma in sigma_values]
+    chain = _chain_keywords("profile_sweep_over_sigmas", one_launch, _is_stepper(ps_kwargs, None), obs_per_launch, resume, return_checkpoint)
     if one_launch:
         rows = _profile_sweeps_in_one_launch("profile_sweep_over_sigmas", [(kw, dict(init_kwargs or {})) for kw in kws], beta_values,
-                                             n_runs_per_beta, run_kwargs, n_bins, rng_seeds, want_field, allow_large)
-        return {sigma: dict(zip(beta_values, rows[si])) for si, sigma in enumerate(sigma_values)}
+                                             n_runs_per_beta, run_kwargs, n_bins, rng_seeds, want_field, allow_large, chain)
+        if return_checkpoint:
+            rows, ck = rows
+        res = {sigma: dict(zip(beta_values, rows[si])) for si, sigma in enumerate(sigma_values)}
+        return (res, ck) if return_checkpoint else res
     return {sigma: profile_sweep(beta_values, n_runs_per_beta, kw, init_kwargs, run_kwargs, n_bins, rng_seeds, want_field)
             for sigma, kw in zip(sigma_values, kws)}
 
 
 def profile_sweep_over_densities(n_part_values, beta_values, n_runs_per_beta, ps_kwargs, init_kwargs, run_kwargs, n_bins, rng_seeds=None,
-                                 want_field=False, one_launch=True, allow_large=False):
+                                 want_field=False, one_launch=True, allow_large=False, obs_per_launch=None, resume=None,
+                                 return_checkpoint=False):
     """`profile_sweep` for every particle number of `n_part_values` (the density N / L, the route to the hydrodynamic limit):
     {N: {beta: profiles}}.  `one_launch`, `allow_large`: as in profile_sweep_over_sigmas, the group being (N, beta) and every N a
-    group of `mixed_keys`; here a sweep straddles the limit when L <= 4096 and only some particle numbers exceed 2048."""
+    group of `mixed_keys`; here a sweep straddles the limit when L <= 4096 and only some particle numbers exceed 2048.
+    `obs_per_launch`, `resume`, `return_checkpoint` (with one_launch): as in profile_sweep_over_sigmas."""
     for n_part in n_part_values:
         if float(n_part) != int(n_part):
             raise ValueError("particle numbers must be integral")
     iks = [dict(init_kwargs or {}, N=int(n_part)) for n_part in n_part_values]
+    chain = _chain_keywords("profile_sweep_over_densities", one_launch, _is_stepper(ps_kwargs, None), obs_per_launch, resume, return_checkpoint)
     if one_launch:
         rows = _profile_sweeps_in_one_launch("profile_sweep_over_densities", [(dict(ps_kwargs or {}), ik) for ik in iks], beta_values,
-                                             n_runs_per_beta, run_kwargs, n_bins, rng_seeds, want_field, allow_large)
-        return {int(n_part): dict(zip(beta_values, rows[ni])) for ni, n_part in enumerate(n_part_values)}
+                                             n_runs_per_beta, run_kwargs, n_bins, rng_seeds, want_field, allow_large, chain)
+        if return_checkpoint:
+            rows, ck = rows
+        res = {int(n_part): dict(zip(beta_values, rows[ni])) for ni, n_part in enumerate(n_part_values)}
+        return (res, ck) if return_checkpoint else res
     return {int(n_part): profile_sweep(beta_values, n_runs_per_beta, ps_kwargs, ik, run_kwargs, n_bins, rng_seeds, want_field)
             for n_part, ik in zip(n_part_values, iks)}

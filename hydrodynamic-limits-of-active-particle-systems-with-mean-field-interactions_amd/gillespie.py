@@ -257,6 +257,20 @@ def _stage_mixed_structure_resumable(c, *, mixed, k_max, first_obs, want_rows, o
     return front + numbers, behind, tail, dict(more, **extra)
 
 
+def _stage_profiles_resumable(c, *, obs_first, **profile):
+    """_stage_profiles (first_obs ABSOLUTE on the run's grid) with a segment's tail and a gil_checkpoint"""
+    numbers, behind, _, extra = _stage_profiles(c, **profile)
+    tail, more = _stage_checkpoints(c, obs_first)
+    return numbers, behind, tail, dict(extra, **more)
+
+
+def _stage_mixed_profiles_resumable(c, *, obs_first, **profile):
+    """_stage_mixed_profiles likewise, with a gilx_checkpoint that has n_slots and no window sums"""
+    front, behind, _, extra = _stage_mixed_profiles(c, **profile)
+    tail, more = _stage_checkpoints(c, obs_first, 0)
+    return front, behind, tail, dict(extra, **more)
+
+
 class _Entry:
     """last_error; the C types in `front` of the common pointers, `behind` them and, after kernel_ms, in the `tail`; `stage`;
     `header`: named by the error of a call that finds the entry point missing in the loaded library; `finish`: like `stage`, what a
@@ -286,6 +300,11 @@ ENTRIES = {
     "gilxmr_run": _Entry("gilxr_last_error", _stage_mixed_resumable, [_VAR], tail=[_I32, _XCKP, _XCKP], header="include/gillespie_mixed_resume.h"),
     "gilxsr_run": _Entry("gilxr_last_error", _stage_mixed_structure_resumable, [_VAR, _I32, _I32], [_PTR] * 2, [_I32, _XCKP, _XCKP],
                          header="include/gillespie_mixed_resume.h"),
+    # one segment of a profile run, unmixed and mixed, either shape (the library picks it as for the one launch)
+    "gilpr_run": _Entry("gilpr_last_error", _stage_profiles_resumable, [_I32, _I32, _I32, _PTR, _I32], [_PTR] * 3, [_I32, _CKP, _CKP],
+                        header="include/gillespie_profile_resume.h", finish=_profile_bins),
+    "gilxpr_run": _Entry("gilpr_last_error", _stage_mixed_profiles_resumable, [_VAR, _I32, _I32, _I32, _PTR, _I32], [_PTR] * 3,
+                         [_I32, _XCKP, _XCKP], header="include/gillespie_profile_resume.h", finish=_profile_bins),
 }
 # the plans: name -> (last_error, the C types between gil_params and the info structure, the info structure)
 PLANS = {
@@ -476,6 +495,25 @@ def plan_profiles(*, L, K, periodic, sigma_grid, n_systems, n_cap, n_obs, n_bins
                  [int(n_bins), int(n_groups), int(first_obs), int(want_field), int(bool(want_states)), int(bool(per_system))])
 
 
+def run_profiles_resumable_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, betas, states, times_obs, T, seed=0,
+                               minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0, k_exit=0.0,
+                               anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1, front_lo=None,
+                               block_table=None, device=0, flip_table=None, n_bins=None, first_obs=0, want_field=False,
+                               group_of_system=None, n_groups=None, per_system=False, n_cap=None, obs_first=0, checkpoint=None):
+    """`run_profiles_raw` as one SEGMENT of a run (gilpr_run of include/gillespie_profile_resume.h), with the slices and the
+    checkpoint of `run_resumable_raw`: `times_obs` holds the absolute times of the observations obs_first, obs_first + 1, ...;
+    `checkpoint` is the dictionary a previous segment returned under "checkpoint", or None for a fresh start from `states`.
+    `first_obs` is an ABSOLUTE index on the run's grid; `n_bins`, `want_field`, the groups and `per_system` are the run's in every
+    segment.  The library picks the kernel as for `run_profiles_raw` (`plan_profiles`, which does not depend on the number of
+    observations), so every segment has the same shape and keys.  `ensemble_sums`, `members` and `profile_obs` cover this
+    segment's rows; laid one after the other along the observation axis they are the one launch's.  The result also has
+    "checkpoint" and "first_row"."""
+    n_bins = min(int(L), GILP_MAX_BINS) if n_bins is None else int(n_bins)
+    if n_groups is None:
+        n_groups = 1 if group_of_system is None else int(max(0, np.max(group_of_system))) + 1
+    return _run_batch_entry("gilpr_run", **locals())
+
+
 def _mixed_descriptor(S, K, sigma_grids, variant_of_system, block_tables=None, seeds=None, streams=None, order=None):
     """struct gilx_variants for S systems, and the arrays it points to (keep them alive for the call)."""
     sg = np.ascontiguousarray(sigma_grids, dtype=np.float64).reshape(-1)
@@ -574,6 +612,22 @@ def run_mixed_profiles_raw(*, L, K, periodic, sigma_grids, variant_of_system, ra
     return _run_mixed_entry("gilxp_run", locals())
 
 
+def run_mixed_profiles_resumable_raw(*, L, K, periodic, sigma_grids, variant_of_system, rate_diffusion, rate_active, betas, states, times_obs,
+                                     T, seed=0, minus_anchor=True, immobilize=True, suppress_flip=True, crowding=False, k_on=0.0, k_off=0.0,
+                                     k_exit=0.0, anchor_mask=None, uniforms=None, max_events=None, want_states=True, x_wall=0, ref_obs=-1,
+                                     front_lo=None, block_tables=None, device=0, flip_table=None, seeds=None, streams=None, order=None,
+                                     n_cap=None, n_bins=None, first_obs=0, want_field=False, group_of_system=None, n_groups=None,
+                                     per_system=False, obs_first=0, checkpoint=None):
+    """`run_mixed_profiles_raw` as one SEGMENT of a run (gilxpr_run of include/gillespie_profile_resume.h), with the slices and the
+    checkpoint of `run_mixed_resumable_raw` (the six arrays and `n_slots`; no window sums).  `first_obs` is an ABSOLUTE index on
+    the run's grid.  The library picks the kernel as `plan_mixed_profiles` tells, for every segment alike; the keys (`seeds`,
+    `streams`) and the variants are the resuming launch's.  The three profile arrays cover this segment's rows."""
+    n_bins = min(int(L), GILP_MAX_BINS) if n_bins is None else int(n_bins)
+    if n_groups is None:
+        n_groups = 1 if group_of_system is None else int(max(0, np.max(group_of_system))) + 1
+    return _run_mixed_entry("gilxpr_run", locals())
+
+
 def plan_mixed_structure(*, L, K, periodic, sigma_grids, n_systems, n_cap, n_obs, k_max, first_obs=0, variant_of_system=None,
                          order=None, want_states=True, want_rows=True):
     """gilxs_plan: what a mixed launch with the structure sums (`run_mixed_structure_raw`) would use -- threads per system, LDS of
@@ -652,7 +706,8 @@ def _run_batch_entry(entry, *, L, K, periodic, sigma_grid, rate_diffusion, rate_
     first_obs, want_rows) and gilxp_run (`mixed` with gilp_run's keywords, either shape); gilr_run and gilrm_run (one segment of a
     run: obs_first, checkpoint); gilxr_run, gilxmr_run and
     gilxsr_run (one segment of a mixed run: `mixed`, obs_first, and a checkpoint that also has n_slots and, for gilxsr_run, the
-    window sums)."""
+    window sums); gilpr_run and gilxpr_run (one segment of a profile run: gilp_run's / gilxp_run's keywords with first_obs absolute,
+    obs_first, and the checkpoint of gilr_run / gilxr_run)."""
     lib, row = _lib(), ENTRIES[entry]
     if row.header is not None and not hasattr(lib, entry):
         raise capi.ApsError(-1, f"the loaded library has no {entry} ({row.header})")
@@ -877,11 +932,14 @@ def _statistics_rows(who, systems, r, times_obs):
     return rows
 
 
-def _refuse_resume(who, resume, mixed=False):
+def _refuse_resume(who, resume, mixed=False, own=None):
     """The structure, capture, profile and mixed launches carry sums of their own across a run (window sums, bind times, group
     rows) or values per system (slot counts, keys), which a Checkpoint does not hold: they cannot start from one.  `mixed`: the
-    mixed launches resume from a MixedCheckpoint, which is not refused here."""
-    if resume is not None and not (mixed and isinstance(resume, MixedCheckpoint)):
+    mixed launches resume from a MixedCheckpoint, which is not refused here.  `own`: the profile functions resume from the class
+    of their own alone (ProfileCheckpoint, MixedProfileCheckpoint), whose fingerprint holds what keeps the rows of a chain together."""
+    if own is not None and isinstance(resume, own):
+        return
+    if resume is not None and not (own is None and mixed and isinstance(resume, MixedCheckpoint)):
         raise ValueError(f"{who} cannot resume from a checkpoint: its launch carries sums across the run that a Checkpoint does not hold "
                          "(include/gillespie_resume.h); run_batched_exact and run_batched_exact_statistics can")
 
@@ -982,12 +1040,42 @@ class Checkpoint(_SavedState):
         self.seed, self.streams, self.obs_dt = int(seed), str(streams), float(obs_dt)
 
 
+_PROFILE_FIELDS = ("n_bins", "want_field", "first_obs", "groups", "per_system")
+
+
+def _take_profile_fields(self, n_bins, want_field, first_obs, groups, per_system):
+    """What the two profile checkpoints add to their base: the numbers that must not change between the segments of a profile
+    chain, because their rows would no longer belong together."""
+    self.n_bins, self.want_field, self.first_obs, self.per_system = int(n_bins), bool(want_field), int(first_obs), bool(per_system)
+    self.groups = np.ascontiguousarray(groups, dtype=np.int32)
+    if self.groups.shape != (self.n_systems,):
+        raise ValueError(f"{type(self).__name__}: groups must have one entry per system")
+
+
+class ProfileCheckpoint(Checkpoint):
+    """The state of a batch between two launches of a PROFILE run (include/gillespie_profile_resume.h): the arrays and the
+    fingerprint of `Checkpoint` -- a row of the profile sums belongs to one observation, so the loop state is all a cut hands over
+    -- and, in the fingerprint as well, `n_bins`, `want_field`, `first_obs` (absolute on the run's grid), `groups` [systems] and
+    `per_system`.  `streams` is the shape the PROFILE plan gives (`plan_profiles`): it can be "large" for a batch-sized system
+    whose profile slots do not fit beside the loop, which is why a plain Checkpoint, made elsewhere, is not taken over."""
+
+    FINGERPRINT = Checkpoint.FINGERPRINT + _PROFILE_FIELDS
+    META = Checkpoint.META + ("n_bins", "want_field", "first_obs", "per_system")
+    SAVED = ("groups",)
+
+    def __init__(self, *, n_bins, want_field, first_obs, groups, per_system, **checkpoint):
+        super().__init__(**checkpoint)
+        _take_profile_fields(self, n_bins, want_field, first_obs, groups, per_system)
+
+
 def _merge_segments(parts, k0):
     """The raw outputs of a chain of segments as those of one launch over all their observations (row 0 = observation k0).  Of a
-    mixed structure chain also `head` and `structure`, the bytes copied back, and the window sums: those of the last checkpoint."""
+    mixed structure chain also `head` and `structure`, the bytes copied back, and the window sums: those of the last checkpoint.
+    Of a profile chain also `ensemble_sums`, `members` and `profile_obs`, whose second axis is the observation's too."""
     last = parts[-1]
     out = {k: (None if parts[0][k] is None else np.concatenate([r[k] for r in parts], axis=1))
-           for k in ("pos", "sigma", "flags", "scalars", "head", "structure") if k in last}
+           for k in ("pos", "sigma", "flags", "scalars", "head", "structure", "ensemble_sums", "members", "profile_obs") if k in last}
+    out.update({k: last[k] for k in ("bin_width", "n_bins_used") if k in last})
     S, ncap = last["exits"].shape[:2]
     exits, n_exits = np.zeros((S, ncap, 3)), np.zeros(S, np.int32)
     for r in parts:                                            # the exit log of a segment holds that segment's exits
@@ -1166,6 +1254,22 @@ class MixedCheckpoint(_SavedState):
         return dict(super().fingerprint(), **({k: getattr(self, k) for k in self.OPTIONAL} if self.structure else {}))
 
 
+class MixedProfileCheckpoint(MixedCheckpoint):
+    """`ProfileCheckpoint` for a MIXED batch (gilxpr_run of include/gillespie_profile_resume.h): the arrays and the fingerprint of
+    `MixedCheckpoint` without window sums, and `n_bins`, `want_field`, `first_obs` (absolute), `groups` (the ensemble groups) and
+    `per_system`, in the fingerprint as well.  `large` is the shape the profile plan gives (`plan_mixed_profiles`)."""
+
+    FINGERPRINT = MixedCheckpoint.FINGERPRINT + _PROFILE_FIELDS
+    META = MixedCheckpoint.META + ("n_bins", "want_field", "per_system")
+    SAVED = MixedCheckpoint.SAVED + ("groups",)
+
+    def __init__(self, *, n_bins, want_field, first_obs, groups, per_system, **checkpoint):
+        if checkpoint.get("k_max") is not None:
+            raise ValueError("MixedProfileCheckpoint: a profile run carries no window sums (k_max must be None)")
+        super().__init__(**checkpoint)
+        _take_profile_fields(self, n_bins, want_field, first_obs, groups, per_system)
+
+
 class _MixedBatch:
     """A mixed batch, opened for one launch or for a chain of segments (`chained`; then `resume` may be a MixedCheckpoint): the
     checks, the initial states (None on resume: no generator is consumed), then the slot counts and the shape, the refusal of a
@@ -1173,7 +1277,8 @@ class _MixedBatch:
     checkpoint's, which must be what this batch would take where its systems state their seeds.  `structure` = (k_max or None,
     start_fraction, want_rows, all_observations): the batch of run_batched_exact_structure_mixed, without states (no large shape).
     `profiles` = the profile keywords of run_mixed_profiles_raw: the batch of run_batched_exact_profiles_mixed, without states; its
-    shape is the plan's (`plan_mixed_profiles`), asked before the keys are formed."""
+    shape is the plan's (`plan_mixed_profiles`), asked before the keys are formed; on resume (a MixedProfileCheckpoint) the plan's
+    shape and the profile numbers must be the checkpoint's."""
 
     def __init__(self, who, systems, T, obs_dt, groups, statistics, uniforms, order, structure, allow_large, resume, chained, profiles=None):
         self.who, self.systems, self.T, self.statistics, self.uniforms, self.order, self.resume, self.chained = (
@@ -1192,19 +1297,26 @@ class _MixedBatch:
             self.n_live = [len(p) for p, _ in self.inits]
             self.n_cap = max(1, max(self.n_live))
             self.large = _large_shape(first.L, self.n_cap)
-            if self.profiles is not None:                      # the profile slots may push a batch-shape launch to the large shape
-                sig, _, owner = mixed_variants(self.sig_sys)
-                self.plan = plan_mixed_profiles(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems),
-                                                n_cap=self.n_cap, n_obs=len(np.arange(0.0, T, obs_dt)), variant_of_system=owner, order=order,
-                                                **{k: v for k, v in self.profiles.items() if k != "group_of_system"})
-                self.large = self.plan["shape"] == 1
         else:
             more = {} if structure is None else dict(k_max=self.k_max, first_obs=self.first_obs)
+            if self.profiles is not None:                      # what keeps the rows of a profile chain together
+                more = dict(n_bins=self.profiles["n_bins"], want_field=bool(self.profiles["want_field"]), first_obs=int(self.profiles["first_obs"]),
+                            groups=self.profiles["group_of_system"], per_system=bool(self.profiles["per_system"]))
             resume.require(L=first.L, K=first.K, periodic=bool(first.periodic), anchor_mask=self.mask, n_systems=len(systems), obs_dt=float(obs_dt),
                            sigma_grids=self.sig_sys, **more)
             if structure is None and resume.structure:
                 raise ValueError(f"{who}: the checkpoint is of a structure run (it carries window sums); resume it with run_batched_exact_structure_mixed")
             self.n_cap, self.large, self.n_live = resume.n_cap, resume.large, [int(n) for n in resume.n_slots]
+        if self.profiles is not None:                          # the profile slots may push a batch-shape launch to the large shape
+            sig, _, owner = mixed_variants(self.sig_sys)
+            numbers = {k: v for k, v in self.profiles.items() if k != "group_of_system"}
+            if chained:                                        # a segment's first_obs is the library's to place; the shape does not depend on it
+                numbers["first_obs"] = 0
+            self.plan = plan_mixed_profiles(L=first.L, K=first.K, periodic=first.periodic, sigma_grids=sig, n_systems=len(systems),
+                                            n_cap=self.n_cap, n_obs=len(np.arange(0.0, T, obs_dt)), variant_of_system=owner, order=order, **numbers)
+            if resume is not None:
+                resume.require(large=self.plan["shape"] == 1)
+            self.large = self.plan["shape"] == 1
         if self.large and not (allow_large and structure is None):
             raise ValueError(f"{who}: L = {first.L}, N = {self.n_cap} is a large shape (beyond L = {GIL_MAX_L}, N = {GIL_MAX_N}); "
                              "the large-system kernel takes no mixed batches")
@@ -1247,7 +1359,8 @@ def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, or
                   obs_range=None, return_checkpoint=False, obs_per_launch=None, profiles=None):
     """The launch behind the four mixed functions: one launch of gilx_run / gilxm_run / gilxs_run / gilxp_run (`profiles`: the profile
     keywords of run_mixed_profiles_raw) or, with any of the four keywords,
-    a chain of gilxr_run / gilxmr_run / gilxsr_run (include/gillespie_mixed_resume.h).  Returns (raw outputs with `plan`,
+    a chain of gilxr_run / gilxmr_run / gilxsr_run (include/gillespie_mixed_resume.h) or, with `profiles`, of gilxpr_run
+    (include/gillespie_profile_resume.h; the checkpoint is then a MixedProfileCheckpoint).  Returns (raw outputs with `plan`,
     `obs_range`, `first_obs` and `k_max`, their observation times, the MixedCheckpoint at the end of a chain or None).  A structure
     chain's `head` and `structure` cover the range, its `window`, `n_window`, `n_empty` are the last checkpoint's."""
     chained = _chained(resume, obs_range, return_checkpoint, obs_per_launch)
@@ -1258,12 +1371,17 @@ def _mixed_launch(who, systems, T, obs_dt, groups, statistics, uniforms=None, or
                   else run_mixed_many_raw if b.large else run_mixed_raw)
         r = dict(run_fn(states=b.inits, times_obs=times_obs, **b.keywords(times_obs, len(times_obs))), obs_range=(0, len(times_obs)))
     else:
-        run_fn, more = (run_mixed_resumable_raw, dict(large=b.large)) if structure is None else (run_mixed_structure_resumable_raw, {})
+        run_fn, more = ((run_mixed_profiles_resumable_raw, {}) if profiles is not None else (run_mixed_resumable_raw, dict(large=b.large))
+                        if structure is None else (run_mixed_structure_resumable_raw, {}))
         r, times_obs = _segment_chain(who, run_fn, T, obs_dt, b.inits, None if resume is None else resume.arrays(), obs_range, obs_per_launch,
                                       lambda times_obs, n_obs: dict(b.keywords(times_obs, n_obs), **more))
-        ck = MixedCheckpoint(L=b.first.L, K=b.first.K, periodic=b.first.periodic, anchor_mask=b.mask, obs_dt=obs_dt, large=b.large, seeds=b.seeds,
-                             streams=b.streams, sigma_grids=b.sig_sys, k_max=b.k_max, first_obs=b.first_obs,
-                             block_tables=None if b.tables is None else np.stack(b.tables), **r["checkpoint"])
+        common = dict(L=b.first.L, K=b.first.K, periodic=b.first.periodic, anchor_mask=b.mask, obs_dt=obs_dt, large=b.large, seeds=b.seeds,
+                      streams=b.streams, sigma_grids=b.sig_sys, **r["checkpoint"])
+        if profiles is not None:
+            ck = MixedProfileCheckpoint(n_bins=profiles["n_bins"], want_field=profiles["want_field"], first_obs=profiles["first_obs"],
+                                        groups=profiles["group_of_system"], per_system=profiles["per_system"], **common)
+        else:
+            ck = MixedCheckpoint(k_max=b.k_max, first_obs=b.first_obs, block_tables=None if b.tables is None else np.stack(b.tables), **common)
     r.update(plan=b.plan, first_obs=b.first_obs, k_max=b.k_max)
     return r, times_obs, ck
 
@@ -1441,30 +1559,78 @@ def run_batched_exact_capture(systems, T=10.0, obs_dt=0.01, c_bins=16, h_bins=40
 
 
 def run_batched_exact_profiles(systems, T=10.0, obs_dt=0.01, n_bins=None, groups=None, first_obs=0, want_field=False,
-                               per_system=False, uniforms=None, resume=None):
+                               per_system=False, uniforms=None, resume=None, obs_range=None, return_checkpoint=False, obs_per_launch=None):
     """The ensemble profiles <rho+(x, t)>, <rho-(x, t)> and <m(x, t)> of many ParticleSystem objects under the exact dynamics
     (the means over runs of the reference's rho_plus_list, rho_minus_list, m_local_list, PARTICLE_solver_CLASS.py:205-213,
     :517-536), coarse-grained to `n_bins` bins of sites and summed over the runs of a group inside the event loop: no state array
     leaves the GPU, and what does is [groups][observations][7][n_bins].  `groups[s]` is the group system s adds to (None: one
     group).  Returns one dict per group, in the order of the group ids (observables.DeviceProfiles.result); `per_system=True`
-    adds each member's own counts as `profile_obs` [members][observations][3][n_bins] (single-run heat maps at n_bins = L)."""
-    _refuse_resume("run_batched_exact_profiles", resume)
-    from . import observables
-    first, inits, seed = _open_batch("run_batched_exact_profiles", systems)
-    times_obs = np.arange(0.0, T, obs_dt)
+    adds each member's own counts as `profile_obs` [members][observations][3][n_bins] (single-run heat maps at n_bins = L).
+    `resume` (a ProfileCheckpoint; any other checkpoint is refused), `obs_range`, `return_checkpoint`, `obs_per_launch`: as in
+    run_batched_exact, through the resumable profile launches (include/gillespie_profile_resume.h).  A row of the sums belongs to
+    one observation, so the rows of a chain are the one launch's, bit for bit, and the result over `obs_range=(k0, k1)` is that of
+    those observations; `first_obs` stays an index on the whole grid.  `n_bins`, `want_field`, `first_obs`, `groups` and
+    `per_system` must be the checkpoint's.  With none of the four the run is the one launch it always was."""
+    who = "run_batched_exact_profiles"
+    _refuse_resume(who, resume, own=ProfileCheckpoint)
+    first, inits, seed = _open_batch(who, systems, resume=resume)
     L = first.L
     n_bins = min(L, GILP_MAX_BINS) if n_bins is None else int(n_bins)
     owner = np.zeros(len(systems), np.int32) if groups is None else np.asarray(groups, dtype=np.int32)
     n_groups = int(owner.max()) + 1 if owner.size else 1
-    r = run_profiles_raw(**_model(first, systems, states=inits, times_obs=times_obs, T=T, seed=seed, uniforms=uniforms, want_states=False,
-                                  n_bins=n_bins, first_obs=first_obs, want_field=want_field, group_of_system=owner, n_groups=n_groups,
-                                  per_system=per_system))
+    prof = dict(n_bins=n_bins, first_obs=first_obs, want_field=want_field, group_of_system=owner, n_groups=n_groups, per_system=per_system)
+    ck = None
+    if not _chained(resume, obs_range, return_checkpoint, obs_per_launch):
+        times_obs = np.arange(0.0, T, obs_dt)
+        r = run_profiles_raw(**_model(first, systems, states=inits, times_obs=times_obs, T=T, seed=seed, uniforms=uniforms, want_states=False, **prof))
+    else:
+        r, times_obs, ck = _profile_chain(who, systems, T, obs_dt, inits, seed, uniforms, prof, resume, obs_range, obs_per_launch)
+    out = _profile_results(systems, r, times_obs, owner, n_groups, n_bins, want_field, first_obs, per_system)
+    return (out, ck) if return_checkpoint else out
+
+
+def _profile_chain(who, systems, T, obs_dt, inits, seed, uniforms, prof, resume, obs_range, obs_per_launch):
+    """The chain of gilpr_run launches behind run_batched_exact_profiles: (merged raw outputs with `n0` = the live particles of the
+    start state, their observation times, the ProfileCheckpoint at the end).  The plan is asked first: its shape says which key
+    convention the run has (`streams`), and a checkpoint of the other shape is refused by name."""
+    first = systems[0]
+    mask = _anchor_mask(first.is_anchor_site, first.L)
+    if resume is None:
+        n_live, ck = [len(p) for p, _ in inits], None
+        n_cap = max(1, max(n_live))
+    else:
+        n_live, ck, n_cap = [int(((f & GILR_ALIVE) != 0).sum()) for f in resume.flags], resume.arrays(), resume.n_cap
+    plan = plan_profiles(L=first.L, K=first.K, periodic=first.periodic, sigma_grid=first._sigma_grid, n_systems=len(systems), n_cap=n_cap,
+                         n_obs=1, n_bins=prof["n_bins"], n_groups=prof["n_groups"], want_field=prof["want_field"], want_states=False,
+                         per_system=prof["per_system"])       # the shape does not depend on the observations
+    streams = "large" if plan["shape"] == 1 else "batch"
+    if resume is not None:
+        resume.require(L=first.L, K=first.K, periodic=bool(first.periodic), local_kernel_sigma=float(first.local_kernel_sigma), anchor_mask=mask,
+                       n_systems=len(systems), obs_dt=float(obs_dt), streams=streams, n_bins=prof["n_bins"], want_field=bool(prof["want_field"]),
+                       first_obs=int(prof["first_obs"]), groups=prof["group_of_system"], per_system=bool(prof["per_system"]),
+                       **({} if first.seed is None else {"seed": int(first.seed)}))
+        seed = resume.seed
+    r, times_obs = _segment_chain(who, run_profiles_resumable_raw, T, obs_dt, inits, ck, obs_range, obs_per_launch,
+                                  lambda times_obs, n_obs: _model(first, systems, T=T, seed=seed, uniforms=uniforms, want_states=False, **prof))
+    r.update(plan=plan, n0=np.array(n_live, np.int32))
+    return r, times_obs, ProfileCheckpoint(L=first.L, K=first.K, periodic=first.periodic, local_kernel_sigma=first.local_kernel_sigma,
+                                           anchor_mask=mask, seed=seed, streams=streams, obs_dt=obs_dt, n_bins=prof["n_bins"],
+                                           want_field=prof["want_field"], first_obs=prof["first_obs"], groups=prof["group_of_system"],
+                                           per_system=prof["per_system"], **r["checkpoint"])
+
+
+def _profile_results(systems, r, times_obs, owner, n_groups, n_bins, want_field, first_obs, per_system):
+    """One observables.DeviceProfiles.result per group from the raw outputs `r` of a profile launch, or of a chain over
+    r["obs_range"] of the grid (`first_obs` is then placed within the range); notes the event counts and the kernel time."""
+    from . import observables
+    first = systems[0]
+    first_row = max(int(first_obs) - r["obs_range"][0], 0) if "obs_range" in r else first_obs
     out = []
     for g in range(n_groups):
         mine = np.flatnonzero(owner == g)
-        prof = observables.DeviceProfiles(times_obs, L, first.dx, n_bins, r["ensemble_sums"][g], r["members"][g],
+        prof = observables.DeviceProfiles(times_obs, first.L, first.dx, n_bins, r["ensemble_sums"][g], r["members"][g],
                                           n_particles=[int(r["n0"][s]) for s in mine], k_exit=first.k_exit, want_field=want_field,
-                                          first_obs=first_obs).result()
+                                          first_obs=first_row).result()
         if per_system:
             prof["profile_obs"] = r["profile_obs"][mine]
         out.append(prof)
@@ -1475,7 +1641,8 @@ def run_batched_exact_profiles(systems, T=10.0, obs_dt=0.01, n_bins=None, groups
 
 
 def run_batched_exact_profiles_mixed(systems, T=10.0, obs_dt=0.01, n_bins=None, groups=None, key_groups=None, order=None, first_obs=0,
-                                     want_field=False, per_system=False, uniforms=None, allow_large=False, resume=None):
+                                     want_field=False, per_system=False, uniforms=None, allow_large=False, resume=None, obs_range=None,
+                                     return_checkpoint=False, obs_per_launch=None):
     """`run_batched_exact_profiles` for systems that may ALSO differ in `local_kernel_sigma` (and, like there, in beta, state and
     particle number): one mixed launch that adds every system's bin counts to its group's sums (include/gillespie_mixed_profile.h).
     The other attributes, the anchor sites and the flip table must agree, as in run_batched_exact_mixed.  `groups[s]` is the
@@ -1485,30 +1652,23 @@ def run_batched_exact_profiles_mixed(systems, T=10.0, obs_dt=0.01, n_bins=None, 
     the group ids (observables.DeviceProfiles.result); `per_system=True` adds `profile_obs`.
     The shape is the library's (`plan_mixed_profiles`): the kernel of systems in LDS where L <= 4096, N <= 2048 and the profile
     slots fit beside the loop, else the large-system kernel, which needs `allow_large=True` (ValueError otherwise) and takes the
-    large shape's keys (`mixed_keys(..., large=True)`).  Profiles have no resumable form: `resume` is refused."""
+    large shape's keys (`mixed_keys(..., large=True)`).
+    `resume` (a MixedProfileCheckpoint; any other checkpoint is refused), `obs_range`, `return_checkpoint`, `obs_per_launch`: as in
+    run_batched_exact_profiles, through gilxpr_run (include/gillespie_profile_resume.h).  The shape of every segment is the
+    plan's, so a checkpoint carries it (`large`) and `allow_large` keeps its meaning; the keys and slot counts are the
+    checkpoint's.  With none of the four the run is the one launch it always was."""
     who = "run_batched_exact_profiles_mixed"
-    _refuse_resume(who, resume)
-    from . import observables
+    _refuse_resume(who, resume, own=MixedProfileCheckpoint)
     first = systems[0]
     n_bins = min(first.L, GILP_MAX_BINS) if n_bins is None else int(n_bins)
     owner = np.zeros(len(systems), np.int32) if groups is None else np.asarray(groups, dtype=np.int32)
     n_groups = int(owner.max()) + 1 if owner.size else 1
-    r, times_obs, _ = _mixed_launch(who, systems, T, obs_dt, key_groups, False, uniforms, order, allow_large=allow_large,
-                                    profiles=dict(n_bins=n_bins, first_obs=first_obs, want_field=want_field, group_of_system=owner,
-                                                  n_groups=n_groups, per_system=per_system))
-    out = []
-    for g in range(n_groups):
-        mine = np.flatnonzero(owner == g)
-        prof = observables.DeviceProfiles(times_obs, first.L, first.dx, n_bins, r["ensemble_sums"][g], r["members"][g],
-                                          n_particles=[int(r["n0"][s]) for s in mine], k_exit=first.k_exit, want_field=want_field,
-                                          first_obs=first_obs).result()
-        if per_system:
-            prof["profile_obs"] = r["profile_obs"][mine]
-        out.append(prof)
-    for s, ps in enumerate(systems):
-        ps.n_events = int(r["n_events"][s])
-    first.kernel_ms = r["kernel_ms"]
-    return out
+    r, times_obs, ck = _mixed_launch(who, systems, T, obs_dt, key_groups, False, uniforms, order, allow_large=allow_large, resume=resume,
+                                     obs_range=obs_range, return_checkpoint=return_checkpoint, obs_per_launch=obs_per_launch,
+                                     profiles=dict(n_bins=n_bins, first_obs=first_obs, want_field=want_field, group_of_system=owner,
+                                                   n_groups=n_groups, per_system=per_system))
+    out = _profile_results(systems, r, times_obs, owner, n_groups, n_bins, want_field, first_obs, per_system)
+    return (out, ck) if return_checkpoint else out
 
 
 def run_large_raw(*, L, K, periodic, sigma_grid, rate_diffusion, rate_active, beta, state, times_obs, T, seed=0,

@@ -3,8 +3,9 @@
  *
  * Same dynamics, parameters (gil_params, reused unchanged), buffers and error codes as include/gillespie.h.  gilr_run is
  * gil_run_batch (systems in one workgroup's LDS), gilrm_run is gilm_run of include/gillespie_many.h (large systems), each
- * with two more arguments: the checkpoint the launch starts from and the checkpoint it leaves.  The structure, capture and
- * profile entry points carry sums of their own across a run and cannot be resumed.  The mixed entry points (gilx_run,
+ * with two more arguments: the checkpoint the launch starts from and the checkpoint it leaves.  The structure and capture
+ * entry points carry sums of their own across a run and cannot be resumed; the profile entry points, whose rows belong to one
+ * observation each, have their segments in include/gillespie_profile_resume.h.  The mixed entry points (gilx_run,
  * gilxm_run, gilxs_run) need more than gil_checkpoint holds -- a slot count per system and, with the structure sums, the window
  * accumulators: their segments are gilxr_run, gilxmr_run and gilxsr_run of include/gillespie_mixed_resume.h, under these rules.
  *
